@@ -14,14 +14,26 @@ window's marker-scaled pose tail and absolute chain (SURVEY.md §8e;
 main_sharded).
 value = (B x steps x ranks) / max-over-ranks wall time.
 
-Also reported:
-  roofline      the dominant kernel group's algorithmic bytes / its HIP-event
-                time on the library's stream, against 8 TB/s HBM
+A plain run sets up, warms up, times one run of exactly K steps and prints the
+result line (value, ms_per_step, and the dominant stage's roofline from the
+HIP events of those same steps: algorithmic bytes / HIP-event time on the
+library's stream, against 8 TB/s HBM).
+
+--dump-outputs DIR writes what the last timed step handed back (the retired
+batch's pair records field by field, its relative and absolute poses) as
+DIR/<name>.npy; the inputs are seeded, so two builds run with the same
+arguments can be compared array for array.
+
+--full adds everything that takes runs of its own:
+  runs          5 timed runs of K steps each (value = the median run)
   cpu_baseline  the oracle (C++ restatement of the OpenCV path, -O3
                 -march=native) over bounded samples of the same stream on all
                 host threads (value) and on one core (rank 0, N=1)
+  pose checks   the device records against the oracle, bit for bit
+  legs          reference-equivalent, host-fed, rank-0 world-8 tail, the other
+                BASELINE configs, the drop-in surface
 
-Run: python bench.py --gpus N --steps K --warmup W
+Run: python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 """
 from __future__ import annotations
 
@@ -35,6 +47,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+T_START = time.perf_counter()  # the result line's `wall_s` counts from here
 # HIP maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (4 by default); streams that
 # share a queue run in order, so the copy stream of the host-fed leg queued behind a library stream's
 # kernels (host-fed 45.0 K -> 58.1 K frames/s with 8; the device-resident run is unchanged,
@@ -112,14 +125,48 @@ def parse():
     ap.add_argument("--leg-runs", type=int, default=3, help="timed runs of a config leg (value = the median)")
     ap.add_argument("--leg-pose-pairs", type=int, default=64,
                     help="pairs of a config leg's pose check against the oracle in the same semantics")
-    ap.add_argument("--runs", type=int, default=5,
-                    help="timed runs of exactly --steps steps each; value = the median run (BASELINE.md §3: "
-                         "median of 5 runs), every run's rate reported under `runs`")
+    ap.add_argument("--runs", type=int, default=None,
+                    help="timed runs of exactly --steps steps each; value = the median run, every run's rate "
+                         "reported under `runs`.  Default: 1, so --steps is the number of timed steps; with --full "
+                         "5 (BASELINE.md §3: median of 5 runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run, everything else the benchmark measures or checks: the CPU "
+                         "baseline, the pose checks against the oracle, the reference-equivalent, host-fed, "
+                         "rank-0 tail, config and drop-in legs (each still governed by its own option), and 5 "
+                         "timed runs instead of 1.  Without it none of them runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned (the retired batch's pair "
+                         "records field by field, T_rel, T_abs) as DIR/<name>.npy, float64")
     ap.add_argument("--pose-check-per-rank", type=int, default=6,
                     help="N > 1: pairs at the start of every rank's run of the gathered window checked against "
                          "the oracle (0 = skip)")
     ap.add_argument("--spawn-check", action="store_true", help=argparse.SUPPRESS)  # tests/test_bench_launch.py
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.runs is None:
+        args.runs = 5 if args.full else 1
+    if not args.full:
+        # a plain run: the headline figure only; whatever takes runs of its own waits for --full
+        args.cpu_seconds = args.dropin_seconds = 0.0
+        args.no_ref_equivalent = args.no_host_fed = True
+        args.tail_world = args.pose_check_32 = args.pose_check_per_rank = 0
+        args.config_legs = "none"
+    return args
+
+
+# pair-record fields a caller reads (pad0 is padding, `reserved` the pose tail's own scratch)
+DUMP_RECORD_FIELDS = ("R", "t", "E", "n_kp_prev", "n_kp_cur", "n_matches", "n_inliers", "n_good", "ransac_iters",
+                      "status", "n_models", "n_hypotheses")
+
+
+def dump_outputs(path, recs, T_rel, T_abs):
+    """--dump-outputs: the last timed step's outputs as float64 .npy files (about 1.5 MB at the
+    default batch: a record's fields and two 4x4 poses per pair)."""
+    os.makedirs(path, exist_ok=True)
+    for name in DUMP_RECORD_FIELDS:
+        np.save(os.path.join(path, f"records_{name}.npy"), np.ascontiguousarray(recs[name], dtype=np.float64))
+    for name, a in (("T_rel", T_rel), ("T_abs", T_abs)):
+        if a is not None:
+            np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def free_port():
@@ -225,6 +272,14 @@ def runs_summary(per_run_s, units_per_run):
                  "note": "value = the median run; each run times exactly `steps` steps (BASELINE.md §3)"}
 
 
+def render_frames(scene, first, last, chunk=8):
+    """Frames first .. last-1 of the scene as one uint8 [n, H, W] tensor, rendered `chunk` at a time
+    (SceneStream.render_batch: the same bytes as one frame at a time, a chunk's temporaries small
+    enough to stay in cache)."""
+    import torch
+    return torch.cat([scene.render_batch(range(a, min(a + chunk, last))) for a in range(first, last, chunk)])
+
+
 def stage_bytes(w, h, nfeatures, n_matches):
     """Algorithmic HBM bytes per frame for each kernel group."""
     from droplet_visual_odometry_amd.plan import level_sizes
@@ -281,8 +336,10 @@ def main():
     if world > 1 or args.sharded:
         return main_sharded(args, world, rank, local_rank, backend, dev, scene)
     pool_n = args.pool or (2 * B + 1)
-    pool = torch.stack([scene.render(i) for i in range(pool_n)]).contiguous()
+    t_import = time.perf_counter()
+    pool = render_frames(scene, 0, pool_n)
     torch.cuda.synchronize()
+    t_render = time.perf_counter()
 
     ctx = Context(local_rank)
     S = max(1, args.streams)
@@ -311,6 +368,7 @@ def main():
 
     sync_all = pipe.sync
     prime = max(args.warmup, pipe.prime_steps)  # the pipeline is full: every timed step retires one batch
+    t_setup = time.perf_counter()
     for i in range(prime):
         step(i)
     sync_all()
@@ -320,6 +378,11 @@ def main():
     torch.cuda.synchronize()
     t_origin = time.perf_counter()
     per_run = timed_runs(args, step, sync_all, prime)
+    if args.dump_outputs:
+        # the batch the last timed step retired, before the drain below retires the ones behind it
+        (r, pairs), k = pipe.last, pipe.last_k
+        dump_outputs(args.dump_outputs, FrameStream.records_numpy(r, pairs), T_rel[k][:pairs].cpu().numpy(),
+                     T_abs[k][:pairs].cpu().numpy())
     n_run = len(per_run)
     for i, t_a, t_b, t_c in host_log:
         print(f"host step {i}: submit enqueued at {1e3 * (t_a - t_origin):8.2f} ms, took {1e3 * (t_b - t_a):6.2f} ms",
@@ -441,6 +504,9 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(ms_per_step, 3),
+        "wall_s": {"import": round(t_import - T_START, 2), "render_pool": round(t_render - t_import, 2),
+                   "streams": round(t_setup - t_render, 2), "warmup": round(t_origin - t_setup, 2),
+                   "timed": round(sum(per_run), 2), "total": round(time.perf_counter() - T_START, 2)},
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -501,6 +567,7 @@ class Pipeline:
         self.gseq = 0
         self.last = None      # (records, pairs) of the last retired batch
         self.last_s0 = None   # its first frame in the pool
+        self.last_k = None    # the stream it ran on (its poses are in T_rel[k], T_abs[k])
         self.prime_steps = len(fss) * (self.D - 1)
         self.on_retire = None  # optional hook(k, records, pairs, s0) instead of the pose tail
 
@@ -521,7 +588,7 @@ class Pipeline:
             c = self.corners
             self.fss[k].pose_tail_batch(r, pairs, c[s0:s0 + pairs], c[s0 + 1:s0 + pairs + 1], self.L, self.T_rel[k],
                                         self.T_abs[k])
-        self.last, self.last_s0 = (r, pairs), s0
+        self.last, self.last_s0, self.last_k = (r, pairs), s0, k
 
     def drain(self):
         # every stream's remaining rounds, then the pose tails in submission order (one carry)
@@ -881,7 +948,7 @@ def config_leg(args, ctx, dev, name):
     t_leg = time.perf_counter()
     scene = SceneStream(W, H, device=str(dev))
     pool_n = 2 * B + 1
-    pool = torch.stack([scene.render(i) for i in range(pool_n)]).contiguous()
+    pool = render_frames(scene, 0, pool_n)
     corners = torch.tensor(np.stack([scene.marker_corners(i) for i in range(pool_n)]), dtype=torch.float64,
                            device=dev)
     fss = [FrameStream(W, H, scene.K, nfeatures=N, max_frames=B + 1, max_iters=it, ctx=ctx, opencv=c["opencv"])
@@ -986,7 +1053,7 @@ def main_sharded(args, world, rank, local_rank, backend, dev, scene):
     n_windows = 2
     wins = [ddist.shard_window(WP, world, rank, j * WP) for j in range(n_windows)]
     # each rank renders only the frames of its own runs (no scatter)
-    pools = [torch.stack([scene.render(g) for g in range(f0, f1)]).contiguous() for (_, _, f0, f1) in wins]
+    pools = [render_frames(scene, f0, f1) for (_, _, f0, f1) in wins]
     corners = [torch.tensor(np.stack([scene.marker_corners(g) for g in range(f0, f1)]), dtype=torch.float64,
                             device=dev) for (_, _, f0, f1) in wins]
     torch.cuda.synchronize()
@@ -995,9 +1062,13 @@ def main_sharded(args, world, rank, local_rank, backend, dev, scene):
     S = run.S
     torch.cuda.synchronize()
 
+    last_out = []  # (records, T_rel, T_abs future) of the last window a step retired (rank 0: --dump-outputs)
+
     def step(i):
         j = i % n_windows
-        run.step(pools[j], corners[j][:-1], corners[j][1:], wait_torch=False)  # frames resident
+        outs = run.step(pools[j], corners[j][:-1], corners[j][1:], wait_torch=False)  # frames resident
+        if outs:
+            last_out[:] = [outs[-1]]
 
     sync_all = run.sync
     prime = max(args.warmup, run.prime_steps)  # the pipeline is full: every timed step retires one window
@@ -1009,6 +1080,11 @@ def main_sharded(args, world, rank, local_rank, backend, dev, scene):
             f.set_profiling(True)
     per_run = timed_runs(args, step, sync_all, prime, dist=dist,
                          device=torch.device("cpu") if run.host_gather else dev)
+    if args.dump_outputs and rank == 0 and last_out:
+        r, T_rel, T_abs = last_out[0]
+        dump_outputs(args.dump_outputs, r.cpu().numpy().view(PAIR_RECORD_DTYPE),
+                     T_rel.cpu().numpy() if T_rel is not None else None,
+                     np.asarray(T_abs.result()) if T_abs is not None else None)
     value, runs = runs_summary(per_run, WP * args.steps)
     elapsed = WP * args.steps / value
     stage_ms, calls = {}, 0

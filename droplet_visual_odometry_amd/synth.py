@@ -130,24 +130,33 @@ class SceneStream:
 
     def render(self, idx: int) -> torch.Tensor:
         """Frame `idx` as uint8 [H, W] on self.device."""
+        return self.render_batch([idx])[0]
+
+    def render_batch(self, idxs) -> torch.Tensor:
+        """Frames `idxs` as uint8 [n, H, W] on self.device.  The ray cast is elementwise per pixel,
+        so its steps run once over the whole batch (on a GPU a frame alone costs some 600 small
+        launches); what is not elementwise, the ray-direction product and the seeded noise, stays
+        one call per frame.  A frame's bytes therefore do not depend on the batch it is rendered in
+        (tests/test_synth_batch.py)."""
         dev = torch.device(self.device)
         w, h = self.width, self.height
+        n = len(idxs)
         fx, fy, cx, cy = self.K[0, 0], self.K[1, 1], self.K[0, 2], self.K[1, 2]
-        R, C = camera_pose(idx)
-        Rt = torch.tensor(R.T, dtype=torch.float32, device=dev)   # camera -> world
-        Cw = torch.tensor(C, dtype=torch.float32, device=dev)
+        poses = [camera_pose(i) for i in idxs]
+        Cw = torch.tensor(np.stack([C for _, C in poses]), dtype=torch.float32, device=dev)  # [n, 3]
+        Cw1 = Cw.view(n, 1, 1, 3)
         v, u = torch.meshgrid(torch.arange(h, device=dev, dtype=torch.float32),
                               torch.arange(w, device=dev, dtype=torch.float32), indexing="ij")
         dc = torch.stack([(u - cx) / fx, (v - cy) / fy, torch.ones_like(u)], -1)
-        d = dc @ Rt.T                                                # world ray directions
-        inf = torch.full_like(u, float("inf"))
-        best_t = inf.clone()
-        sid = torch.zeros_like(u, dtype=torch.int32)
+        # world ray directions, [n, H, W, 3]: one [H, W, 3] x [3, 3] product per frame (Rt = camera -> world)
+        d = torch.stack([dc @ torch.tensor(R.T, dtype=torch.float32, device=dev).T for R, _ in poses])
+        best_t = torch.full((n, h, w), float("inf"), dtype=torch.float32, device=dev)
+        sid = torch.zeros((n, h, w), dtype=torch.int32, device=dev)
 
         def plane(axis, value, surface):
             nonlocal best_t, sid
             den = d[..., axis]
-            tt = (value - Cw[axis]) / torch.where(den.abs() > 1e-9, den, torch.full_like(den, 1e-9))
+            tt = (value - Cw[:, axis].view(n, 1, 1)) / torch.where(den.abs() > 1e-9, den, torch.full_like(den, 1e-9))
             ok = (tt > 1e-4) & (tt < best_t)
             best_t = torch.where(ok, tt, best_t)
             sid = torch.where(ok, torch.full_like(sid, surface), sid)
@@ -158,18 +167,18 @@ class SceneStream:
         plane(0, -ROOM, 4)
         plane(1, ROOM, 5)
         plane(1, -ROOM, 6)
+        safe = torch.where(d.abs() > 1e-9, d, torch.full_like(d, 1e-9))
         for bi, (bx, by, bz, hx, hy, hz) in enumerate(BOXES):
             lo = torch.tensor([bx - hx, by - hy, bz - hz], device=dev)
             hi = torch.tensor([bx + hx, by + hy, bz + hz], device=dev)
-            safe = torch.where(d.abs() > 1e-9, d, torch.full_like(d, 1e-9))
-            t0 = (lo - Cw) / safe
-            t1 = (hi - Cw) / safe
+            t0 = (lo - Cw1) / safe
+            t1 = (hi - Cw1) / safe
             tmin = torch.minimum(t0, t1).amax(-1)
             tmax = torch.maximum(t0, t1).amin(-1)
             ok = (tmax >= tmin) & (tmin > 1e-4) & (tmin < best_t)
             best_t = torch.where(ok, tmin, best_t)
             sid = torch.where(ok, torch.full_like(sid, 10 + bi), sid)
-        P = Cw + d * best_t.unsqueeze(-1)
+        P = Cw1 + d * best_t.unsqueeze(-1)
         X, Y, Z = P[..., 0], P[..., 1], P[..., 2]
         # surface parametrisation (s, t) and a per-orientation shade
         ax = (X.abs() > ROOM - 1e-3) | ((sid >= 10) & self._face_is(P, sid, 0))
@@ -180,8 +189,9 @@ class SceneStream:
         tex = _texture(s + 0.37 * sid, t - 0.21 * sid, sid)
         img = 25.0 + 215.0 * tex * shade
         img = img * (0.85 + 0.15 * torch.cos(0.9 * s + 0.6 * t))
-        gen = torch.Generator(device=dev).manual_seed(1000 + idx)
-        img = img + self.noise_sigma * torch.randn(img.shape, generator=gen, device=dev)
+        noise = torch.stack([torch.randn((h, w), generator=torch.Generator(device=dev).manual_seed(1000 + i), device=dev)
+                             for i in idxs])
+        img = img + self.noise_sigma * noise
         return img.clamp(0, 255).round().to(torch.uint8)
 
     @staticmethod

@@ -13,4 +13,4 @@ timeout -k 10 400 rocprofv3 --kernel-trace --stats -d /tmp/st_$tag -o run --outp
 python3 "$root/tools/summarize_profile.py" $(find /tmp/st_$tag -name '*kernel_stats.csv') "$out/${tag}_kernel_stats.csv" > "$out/${tag}_kernel_stats.txt"
 rm -rf /tmp/st_$tag
 cd "$root"
-timeout -k 10 400 python3 -u bench.py > "$out/${tag}_bench_default.json" 2> "$out/${tag}_bench_default.err"
+timeout -k 10 400 python3 -u bench.py --full > "$out/${tag}_bench_default.json" 2> "$out/${tag}_bench_default.err"
