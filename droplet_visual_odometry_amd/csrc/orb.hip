@@ -702,15 +702,6 @@ __device__ __forceinline__ int fast_score16_pk(const uint8_t* p, int stride, int
     return max((int)acc.x, (int)acc.y) - 1;
 }
 
-__device__ __forceinline__ bool has_run9(uint32_t m) {
-    uint32_t m2 = m | (m << 16);
-    uint32_t a = m2 & (m2 >> 1);  // runs >= 2
-    a = a & (a >> 2);             // >= 4
-    a = a & (a >> 4);             // >= 8
-    a = a & (m2 >> 8);            // >= 9
-    return (a & 0xFFFFu) != 0;
-}
-
 __device__ __forceinline__ int block_excl_scan(int v, int& total, int* lds) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
     // inclusive scan within the wave
@@ -747,20 +738,24 @@ __device__ __forceinline__ uint32_t byte_at(uint32_t lo, uint32_t hi, int k) {  
 // NMS neighbourhood, score rows [r0-1, r1] x score columns [xs-1, xs+125): the
 // first tile computes all kBandRows+2 score rows, later tiles the kBandRows new ones and carry
 // the two above (and the corners of the last one, an output row of the next
-// tile, in a small list).  Per tile, each wave runs compass -> segment test ->
-// score on its own rows with its own LDS list segment (no workgroup barrier
-// in between: at ~6% candidates a wave's list is about one 64-lane round, as
-// the concatenated list's share per wave was), then workgroup barriers
-// separate NMS (which reads neighbours' scores) and the output:
+// tile, in a small list).  Per tile, each wave runs compass -> score on its
+// own rows with its own LDS list segment (no workgroup barrier in between: at
+// ~6% candidates a wave's list is about one 64-lane round, as the
+// concatenated list's share per wave was), then workgroup barriers separate
+// NMS (which reads neighbours' scores) and the output:
 //   compass  every pixel: a run of 9 on the 16-circle contains two adjacent
 //            compass pixels (0,4 / 4,8 / 8,12 / 12,0) that are both brighter
 //            or both darker: min(max(c0,c8), max(c4,c12)) > v+t, or the dual;
 //            a lane tests the 4 pixels of one LDS word from 5 word reads
 //            (centre row -1/0/+1 words, rows -3/+3), byte-permuted into packed
 //            u16 pairs and compared with saturating v_pk ops;
-//   segment  survivors (~6%): the 16 circle compares packed into bright/dark
-//            masks with v_alignbit (sign bit shifted in), run-of-9 test;
-//   score    corners (~1%): cornerScore<16> into the LDS score plane;
+//   score    survivors (~6%): cornerScore<16>.  The score classifies: it is
+//            max(thr, A, B) - 1 (A, B the best arc-of-9 minima of v - c and
+//            c - v), so a FAST-9 corner scores >= thr and any other pixel
+//            thr - 1; corners (~1%) store their score byte to the LDS score
+//            plane and are compacted into the wave's corner list.  A separate
+//            run-of-9 test before it read the same 17 bytes and only ever
+//            paid when a wave's rows held no corner at all;
 //   NMS      per corner: strict 3x3 maximum -> keep bit of its row;
 //   output   keeps per tile row in column order, (offset << 16 | count) per
 //            row; select_fast_kernel restores raster order across tiles.
@@ -776,7 +771,7 @@ __device__ __forceinline__ uint32_t byte_at(uint32_t lo, uint32_t hi, int k) {  
 constexpr int kFtLW = 144;                      // LDS row stride of the image and score planes
 constexpr int kFtRows = kBandRows + 8;          // staged image rows per tile: [r0-4, r0+kBandRows+4)
 static_assert(kFastTW == 124 && (kBorder - 7) % 4 == 0, "FAST tiles: score columns = LDS words 1..32");
-// per-wave list capacities: compass, row pairs wid, wid+4, .. of 64 lanes x 4 px; segment test, the
+// per-wave list capacities: compass, row pairs wid, wid+4, .. of 64 lanes x 4 px; score, the
 // concatenated candidates of the tile (<= (kBandRows + 2) x 126) in 64-lane rounds of the 4 waves
 constexpr int kFtSegCand = ((kBandRows + 3) / 2 + 3) / 4 * 256;
 constexpr int kFtWordCand = kFtSegCand / 4;  // compass word entries per wave (64 lanes x iterations)
@@ -922,7 +917,7 @@ __global__ __launch_bounds__(kFastNT, DVO_FAST_WAVES_PER_EU) void fast_strip_ker
                 pf[k] = q < kFtNewW ? (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsrc, voff[k], bx + ynew * sp, 0) : 0u;
             }
         }
-        // ---- compass, segment test and score, each wave on its own rows, no workgroup barrier in
+        // ---- compass and score, each wave on its own rows, no workgroup barrier in
         // between: the window is in LDS, a wave's candidates and corners are its own list segment and
         // its scores land on its own score pixels.  Four score pixels per lane: lane -> LDS word
         // 1 + (lane & 31) of score row sr_lo + 2 (wid + 4 t) + (lane >> 5), t = 0, 1, ...
@@ -991,37 +986,24 @@ __global__ __launch_bounds__(kFastNT, DVO_FAST_WAVES_PER_EU) void fast_strip_ker
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            // segment test over the wave's candidates in 64-lane rounds; its j-th corner overwrites its
-            // j-th read entry (already consumed: j <= the entries read so far)
+            // cornerScore of the wave's candidates in 64-lane rounds.  The score decides: it is
+            // max(thr, A, B) - 1 with A (B) the largest minimum of v - c (c - v) over the 16 arcs of
+            // 9, and a pixel is a FAST-9 corner at thr exactly when A > thr or B > thr, so a corner
+            // scores >= thr and everything else thr - 1 (tests/test_fast_score_classifies.py).  A
+            // corner stores its score byte (the others leave the plane at 0) and the wave's j-th
+            // corner overwrites its j-th read entry (already consumed: j <= the entries read so far)
             for (int e0 = 0; e0 < n; e0 += 64) {
                 const int e = e0 + lane;
-                bool is_corner = false;
-                int a = 0;
+                int a = 0, s = -1;
                 if (e < n) {
                     a = cand[seg_off + e];
-                    const uint8_t* p = img + a;
-                    const int v = p[0];
-                    const uint32_t hi = (uint32_t)(v + thr), lo = (uint32_t)(v - thr);
-                    uint32_t br = 0, dk = 0;
-#pragma unroll
-                    for (int k = 0; k < 16; ++k) {
-                        const uint32_t cv = p[kCdy[k] * kFtLW + kCdx[k]];
-                        br = __builtin_amdgcn_alignbit(br, hi - cv, 31);  // bit <- (cv > v + thr)
-                        dk = __builtin_amdgcn_alignbit(dk, cv - lo, 31);  // bit <- (cv < v - thr)
-                    }
-                    is_corner = has_run9(br) || has_run9(dk);
+                    s = fast_score16_pk(img + a, kFtLW, thr);
                 }
+                const bool is_corner = s >= thr;
+                if (is_corner) sc[a - 3 * kFtLW] = (uint8_t)s;
                 const unsigned long long bal = __ballot(is_corner);
                 cand[is_corner ? seg_off + ncw + (int)lane_prefix(bal) : spare_i] = (uint16_t)a;
                 ncw += __popcll(bal);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            // scores of the wave's corners into the score plane
-            for (int e = lane; e < ncw; e += 64) {
-                const int a = cand[seg_off + e];
-                sc[a - 3 * kFtLW] = (uint8_t)fast_score16_pk(img + a, kFtLW, thr);
             }
             if (lane == 0) ncorner[wid] = ncw;
         }
