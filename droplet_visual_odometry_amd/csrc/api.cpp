@@ -778,6 +778,11 @@ int dvo_stream_create(dvo_ctx* ctx, const dvo_stream_config* cfg, dvo_stream** o
         return fail(ctx, DVO_EINVAL, "frame size out of range (8..4095)");
     if (cfg->max_frames < 1) return fail(ctx, DVO_EINVAL, "max_frames < 1");
     if (cfg->cross_check < 0 || cfg->cross_check > 2) return fail(ctx, DVO_EINVAL, "cross_check must be 0, 1 or 2");
+    if (!(cfg->prob > 0 && cfg->prob < 1)) return fail(ctx, DVO_EINVAL, "prob must be in (0, 1)");
+    if (!(cfg->threshold > 0) || !std::isfinite(cfg->threshold))
+        return fail(ctx, DVO_EINVAL, "threshold must be finite and > 0");
+    if (cfg->max_iters < 1) return fail(ctx, DVO_EINVAL, "max_iters must be >= 1");
+    if (!std::isfinite(cfg->dist_thresh)) return fail(ctx, DVO_EINVAL, "dist_thresh must be finite");
     HIP_TRY(hipSetDevice(ctx->device));
     auto s = std::make_unique<dvo_stream>();
     s->ctx = ctx;
@@ -1772,6 +1777,8 @@ int dvo_find_essential_mat(dvo_ctx* ctx, const double* p1, const double* p2, int
     *e_rows = 0;
     if (m < 0 || (m > 0 && (!p1 || !p2))) return fail(ctx, DVO_EINVAL, "bad point arrays");
     if (!(prob > 0 && prob < 1)) return fail(ctx, DVO_EINVAL, "prob must be in (0, 1)");
+    if (!(threshold > 0) || !std::isfinite(threshold)) return fail(ctx, DVO_EINVAL, "threshold must be finite and > 0");
+    if (max_iters < 1) return fail(ctx, DVO_EINVAL, "max_iters must be >= 1");
     if (m < 5) return fail(ctx, DVO_EFEWPTS, "fewer than 5 correspondences");
     HIP_TRY(hipSetDevice(ctx->device));
     void *dpts, *dn, *dmod, *dE, *dinfo, *dmask, *dnmod, *dcnt, *dsub, *drs, *drec, *doff, *dctl, *dlist, *daoff, *dsoff;
@@ -1840,6 +1847,7 @@ int dvo_recover_pose(dvo_ctx* ctx, const double* E, int e_rows, const double* p1
     if (!ctx || !E || !K || !R || !t || !good) return DVO_EINVAL;
     if (e_rows != 3) return fail(ctx, DVO_EINVAL, "recoverPose: E must be 3x3 (decomposeEssentialMat reshape)");
     if (m < 0 || (m > 0 && (!p1 || !p2))) return fail(ctx, DVO_EINVAL, "bad point arrays");
+    if (!std::isfinite(dist_thresh)) return fail(ctx, DVO_EINVAL, "distanceThresh must be finite");
     HIP_TRY(hipSetDevice(ctx->device));
     void *dpts, *dn, *dE, *dinfo, *dRt, *dgood, *dpick, *dpm, *dmin = nullptr;
     int rc;

@@ -143,13 +143,16 @@ int dvo_surf_detect_and_compute(dvo_ctx* ctx, const uint8_t* img, int w, int h, 
 /* Replaces cv::findEssentialMat(points1, points2, K, RANSAC, prob, threshold,
  * maxIters) — visual_odometry_v3.py:297-300.  p1/p2: m x 2 doubles (pixel
  * coords, the float32 KeyPoint_convert output widened).  E receives 3 rows
- * (or 3*k rows when m == 5, as OpenCV); cap 90 doubles.  mask: m bytes 0/1. */
+ * (or 3*k rows when m == 5, as OpenCV); cap 90 doubles.  mask: m bytes 0/1.
+ * prob outside (0, 1), threshold non-finite or <= 0, max_iters < 1 -> DVO_EINVAL. */
 int dvo_find_essential_mat(dvo_ctx* ctx, const double* p1, const double* p2, int m, const double* K, double prob,
                            double threshold, int max_iters, double* E, int* e_rows, uint8_t* mask);
 
 /* Replaces cv::recoverPose(E, points1, points2, K, distanceThresh=50, mask) —
  * visual_odometry_v3.py:303-306.  R row-major 3x3, t unit 3-vector,
- * mask_out m bytes 0/255, *good = cheirality count (the Python retval). */
+ * mask_out m bytes 0/255 (with mask_in: mask_in & that, byte for byte, as
+ * OpenCV's bitwise_and), *good = cheirality count (the Python retval).  A
+ * non-finite dist_thresh -> DVO_EINVAL. */
 int dvo_recover_pose(dvo_ctx* ctx, const double* E, int e_rows, const double* p1, const double* p2, int m,
                      const double* K, double dist_thresh, const uint8_t* mask_in, double* R, double* t,
                      uint8_t* mask_out, int* good);
@@ -212,6 +215,8 @@ typedef struct {
     double reserved[6];
 } dvo_pair_record;
 
+/* prob, threshold, max_iters and dist_thresh are checked as in dvo_find_essential_mat /
+ * dvo_recover_pose (DVO_EINVAL). */
 int dvo_stream_create(dvo_ctx* ctx, const dvo_stream_config* cfg, dvo_stream** out);
 void dvo_stream_destroy(dvo_stream* s);
 /* d_frames: device pointer, frame i at d_frames + i*frame_stride, rows `stride`

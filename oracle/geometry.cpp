@@ -795,9 +795,10 @@ int ora_recover_pose(const double* E, const double* p1, const double* p2, int m,
             double z = Pr[0] * q0 + Pr[1] * q1 + Pr[2] * q2 + Pr[3] * q3;
             ok = (z > 0) && ok;
             ok = (z < dist_thresh) && ok;
-            if (mask_in && !mask_in[i]) ok = false;
-            masks[(size_t)c * m + i] = ok ? 255 : 0;
-            good[c] += ok;
+            uint8_t mv = ok ? 255 : 0;
+            if (mask_in) mv &= mask_in[i];  // bitwise_and(mask, mask_c, mask_c): the caller's byte values stay
+            masks[(size_t)c * m + i] = mv;
+            good[c] += mv != 0;  // countNonZero(mask_c)
         }
     }
     int pick;

@@ -340,25 +340,30 @@ def keypoints_to_points(kps):
     return np.stack([kps["x"], kps["y"]], axis=1).astype(np.float32)
 
 
-def pair_pose(img_prev, img_cur, K, nfeatures=500, max_iters=1000, kp_prev=None, semantics=OCV4):
+def pair_pose(img_prev, img_cur, K, nfeatures=500, max_iters=1000, kp_prev=None, semantics=OCV4, prob=0.999,
+              threshold=1.0, dist_thresh=50.0, cross_check=None):
     """The full per-pair hot path (v3:384-408 minus the host pose tail) on the CPU.
     semantics OCV32: OpenCV 3.2's ORB pyramid / retainBest and BFMatcher
-    cross check (mode 2)."""
+    cross check (mode 2).  prob / threshold / dist_thresh / cross_check: the
+    dvo_stream_config fields of the same names (defaults: the reference's calls;
+    cross_check None = the semantics' own mode)."""
     if kp_prev is None:
         kp_prev = detect_and_compute(img_prev, nfeatures, semantics)
     kp1, d1 = kp_prev
     kp2, d2 = detect_and_compute(img_cur, nfeatures, semantics)
-    q, t, d = bf_match(d1, d2, 2 if semantics == OCV32 else 1)
+    if cross_check is None:
+        cross_check = 2 if semantics == OCV32 else 1
+    q, t, d = bf_match(d1, d2, cross_check)
     order = np.argsort(d, kind="stable")  # sorted(matches, key=distance), v3:221
     q, t = q[order], t[order]
     p1 = keypoints_to_points(kp1[q]).astype(np.float64)
     p2 = keypoints_to_points(kp2[t]).astype(np.float64)
-    E, mask, iters = find_essential(p1, p2, K, max_iters=max_iters)
+    E, mask, iters = find_essential(p1, p2, K, prob=prob, threshold=threshold, max_iters=max_iters)
     out = dict(kp_prev=kp1, kp_cur=kp2, desc_cur=d2, q=q, t=t, p1=p1, p2=p2, E=E, mask=mask, iters=iters)
     if E is None or E.shape[0] != 3:
         out.update(R=None, t_unit=None, good=0)
         return out
-    good, R, tv, _ = recover_pose(E, p1, p2, K)
+    good, R, tv, _ = recover_pose(E, p1, p2, K, dist_thresh=dist_thresh)
     out.update(R=R, t_unit=tv, good=good)
     return out
 

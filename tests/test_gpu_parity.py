@@ -99,6 +99,7 @@ def test_essential_and_pose(gpu_ctx, oracle_mod, frames_640):
         assert good == ref["good"]
         np.testing.assert_array_equal(R, ref["R"])
         np.testing.assert_array_equal(t, ref["t_unit"])
+        np.testing.assert_array_equal(pm.ravel(), oracle_mod.recover_pose(ref["E"], ref["p1"], ref["p2"], K)[3])
 
 
 def test_stream_end_to_end_640(gpu_ctx, oracle_mod, frames_640):
