@@ -7,14 +7,12 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <string>
-#include <type_traits>
 #include <vector>
 
+#include "device_mem.h"
 #include "dvo_internal.h"
 
 using namespace dvo;
@@ -26,14 +24,14 @@ struct SiftPlanDev {  // per-size device buffers of dvo_sift_detect_and_compute
     int tap_off[6] = {0}, tap_n[6] = {0};
     uint8_t* img = nullptr;
     int pitch = 0;
-    std::vector<void*> allocs;
+    DeviceAllocs mem;
 };
 
 struct SurfPlanDev {  // per-size device buffers of dvo_surf_detect_and_compute
     int w = 0, h = 0;
     SurfArgs a{};
     uint8_t* img = nullptr;
-    std::vector<void*> allocs;
+    DeviceAllocs mem;
 };
 
 struct dvo_ctx {
@@ -42,21 +40,17 @@ struct dvo_ctx {
     std::string err;
     SiftPlanDev sift;
     SurfPlanDev surf;
-    // grow-only scratch for the per-call entry points
-    std::vector<std::pair<void*, size_t>> scratch;
+    CallSlots call;  // grow-only device and pinned buffers of the per-call entry points (CallMem)
     dvo_stream* call_stream = nullptr;  // cached plan for detectAndCompute
     int call_w = 0, call_h = 0, call_nf = 0;
-    // grow-only pinned host staging of the synchronous per-call entry points
-    uint8_t* pin = nullptr;
-    size_t pin_cap = 0;
 };
 
 struct dvo_stream {
     dvo_ctx* ctx = nullptr;
     dvo_stream_config cfg{};
     Plan plan{};
-    Buffers buf{};
-    std::vector<void*> allocs;
+    Buffers buf{};  // pts, nmatch, hdr stay null here: params_of fills them from a pair set's view
+    DeviceAllocs mem;
     uint8_t* d_frames = nullptr;  // per-call upload slab (max_frames images)
     double* d_carry = nullptr;    // pose tail carry: P_prev (12) | T_abs_prev (16)
     hipEvent_t carry_ev = nullptr;  // recorded after every pose tail on this carry
@@ -89,8 +83,8 @@ struct dvo_stream {
         dvo_pair_record* rec = nullptr;  // the caller's records of the batch
     };
     PairSet sets[kMaxSets];
-    int nsets = 0;  // pair sets allocated: 1 until the first submit, then kRansacRounds (alloc_sets)
-    std::vector<void*> set_allocs;  // their buffers (also in allocs)
+    // their arrays: 1 set until the first submit, then kRansacRounds; pairs.all.g is the stream's GeomArgs
+    PairSets pairs;
     int next_set = 0;  // the set the next submit fills (sets are taken in ring order)
     int last_set = 0;  // the set of the last submitted batch (get_matches)
     int retired = 0;   // batches retired by the last submit / drain / process call
@@ -104,6 +98,14 @@ struct dvo_stream {
     std::vector<std::vector<hipEvent_t>> ev_free;
     double stage_ms[DVO_NSTAGES] = {0};
     int prof_calls = 0;
+
+    ~dvo_stream() {  // the members free the device memory
+        for (auto* pool : {&ev_pending, &ev_free})
+            for (auto& e : *pool)
+                for (auto x : e) hipEventDestroy(x);
+        if (carry_ev) hipEventDestroy(carry_ev);
+        if (own_hs) hipStreamDestroy(hs);
+    }
 };
 
 namespace {
@@ -123,6 +125,8 @@ int fail(dvo_ctx* ctx, int code, const std::string& msg) {
 }
 
 int cv_round_f(float v) { return (int)lrintf(v); }
+
+void set_camera(GeomArgs& g, const double* K) { g.fx = K[0], g.fy = K[4], g.cx = K[2], g.cy = K[5]; }
 
 // orb.cpp computeKeyPoints: features per level (float arithmetic as OpenCV).
 void features_per_level(int nfeatures, int nlevels, int* out) {
@@ -311,81 +315,19 @@ int check_orb_params(dvo_ctx* ctx, const dvo_orb_params* o) {
 template <class T>
 int dalloc(dvo_stream* s, T** p, size_t n) {
     dvo_ctx* ctx = s->ctx;
-    void* q = nullptr;
-    HIP_TRY(hipMalloc(&q, n * sizeof(T) + 256));
-    s->allocs.push_back(q);
-    *p = reinterpret_cast<T*>(q);
+    HIP_TRY(s->mem.alloc(p, n * sizeof(T) + 256));
     return DVO_OK;
 }
 
-// grow-only per-context scratch slot
-// One synchronous per-call operation's host traffic through pinned memory: inputs are
-// packed into the staging area and sent with asynchronous copies on the call's
-// stream, outputs come back the same way, and the caller synchronises once (a
-// pageable hipMemcpy is a blocking staged copy each: ~10-20 us apiece).
-struct Staging {
-    uint8_t* base = nullptr;
-    size_t off = 0, cap = 0;
-    hipStream_t s = nullptr;
-    static size_t round(size_t n) { return (n + 63) & ~(size_t)63; }
-    uint8_t* take(size_t n) {  // the next n staged bytes (64-byte aligned)
-        uint8_t* h = base + off;
-        off += round(n);
-        if (off > cap) {  // a caller sized its staging() request wrong: never write past the area
-            std::fprintf(stderr, "dvo: staging overflow (%zu > %zu)\n", off, cap);
-            std::abort();
-        }
-        return h;
-    }
-    hipError_t send(void* dev, const uint8_t* h, size_t n) {  // host -> device of staged bytes
-        return n ? hipMemcpyAsync(dev, h, n, hipMemcpyHostToDevice, s) : hipSuccess;
-    }
-    hipError_t put(void* dev, const void* src, size_t n) {
-        uint8_t* h = take(n);
-        if (n) std::memcpy(h, src, n);
-        return send(dev, h, n);
-    }
-    hipError_t get(const void* dev, size_t n, uint8_t** h) {  // device -> host, valid after synchronising
-        *h = take(n);
-        return n ? hipMemcpyAsync(*h, dev, n, hipMemcpyDeviceToHost, s) : hipSuccess;
-    }
-};
-
-static int staging(dvo_ctx* ctx, size_t bytes, hipStream_t s, Staging* st) {
-    if (ctx->pin_cap < bytes) {
-        if (ctx->pin) HIP_TRY(hipHostFree(ctx->pin));
-        ctx->pin = nullptr;
-        ctx->pin_cap = 0;
-        const size_t nb = bytes < (1u << 20) ? (1u << 20) : bytes + bytes / 4;
-        HIP_TRY(hipHostMalloc((void**)&ctx->pin, nb, hipHostMallocDefault));
-        ctx->pin_cap = nb;
-    }
-    st->base = ctx->pin;
-    st->off = 0;
-    st->cap = ctx->pin_cap;
-    st->s = s;
-    return DVO_OK;
-}
-
-int scratch(dvo_ctx* ctx, int slot, size_t bytes, void** out) {
-    if ((int)ctx->scratch.size() <= slot) ctx->scratch.resize(slot + 1, {nullptr, 0});
-    auto& e = ctx->scratch[slot];
-    if (e.second < bytes) {
-        if (e.first) HIP_TRY(hipFree(e.first));
-        e.first = nullptr;
-        e.second = 0;
-        size_t nb = bytes < 4096 ? 4096 : bytes + bytes / 4;
-        HIP_TRY(hipMalloc(&e.first, nb));
-        e.second = nb;
-    }
-    *out = e.first;
-    return DVO_OK;
-}
-
-StreamParams params_of(dvo_stream* s, const uint8_t* frames, int nframes, int64_t frame_stride, int pitch) {
+// The parameter block of a batch whose match stage writes pair set `set`.
+StreamParams params_of(dvo_stream* s, const uint8_t* frames, int nframes, int64_t frame_stride, int pitch, int set = 0) {
     StreamParams P{};
     P.plan = s->plan;
     P.buf = s->buf;
+    const PairArrays v = s->pairs.view(set);
+    P.buf.pts = v.pts;
+    P.buf.nmatch = v.nmatch;
+    P.buf.hdr = v.hdr;
     P.frames = frames;
     P.frame_stride = frame_stride;
     P.in_pitch = pitch;
@@ -394,112 +336,17 @@ StreamParams params_of(dvo_stream* s, const uint8_t* frames, int nframes, int64_
     return P;
 }
 
-GeomArgs stream_geom(dvo_stream* s) {
-    GeomArgs g{};
-    const dvo_stream_config& c = s->cfg;
-    g.pts_f = s->buf.pts;
-    g.m_arr = s->buf.nmatch;
-    g.pts_stride = s->plan.kp_cap;
-    g.fx = c.K[0];
-    g.fy = c.K[4];
-    g.cx = c.K[2];
-    g.cy = c.K[5];
-    g.prob = c.prob;
-    g.threshold = c.threshold;
-    g.max_iters = c.max_iters;
-    g.dist_thresh = c.dist_thresh;
-    g.npts = s->buf.npts;
-    g.models = s->buf.models;
-    g.nmod = s->buf.nmod;
-    g.cnt = s->buf.rcnt;
-    g.subsets = s->buf.subsets;
-    g.rs = s->buf.rs;
-    g.fprec = s->buf.fprec;
-    g.dk_off = s->buf.dk_off;
-    g.a_off = s->buf.a_off;
-    g.s_off = s->buf.s_off;
-    g.dk_ctl = s->buf.dk_ctl;
-    g.hyp_cap = c.max_iters > 1 ? c.max_iters : 1;
-    g.dk_list = s->buf.dk_list;
-    g.dk_list_cap = std::max<int64_t>(round_items_bound(s->cfg.max_frames, g.hyp_cap), g.hyp_cap);
-    g.E = s->buf.E;
-    g.info = s->buf.info;
-    g.Rt = s->buf.Rt;
-    g.good = s->buf.good;
-    g.pose_P = s->buf.pose_P;
-    g.pose_cnt = s->buf.pose_cnt;
-    return g;
-}
-
-// Set k's view of the per-pair geometry arrays (pairs [k F, (k + 1) F) of the stream's sets).
-GeomArgs geom_set(const GeomArgs& g, int k, int F, int64_t hc) {
-    GeomArgs o = g;
-    const int64_t p0 = (int64_t)k * F;
-    o.pts_f = g.pts_f + p0 * g.pts_stride * 4;
-    o.m_arr = g.m_arr + p0;
-    o.npts = g.npts + p0 * g.pts_stride * 4;
-    o.models = g.models + p0 * hc * 90;
-    o.nmod = g.nmod + p0 * hc;
-    o.cnt = g.cnt + p0 * hc * 10;
-    o.subsets = g.subsets + p0 * hc * 5;
-    o.rs = g.rs + p0;
-    o.E = g.E + p0 * 90;
-    o.info = g.info + p0 * 4;
-    o.Rt = g.Rt + p0 * 12;
-    o.good = g.good + p0;
-    o.pose_P = g.pose_P + p0 * 72;
-    o.pose_cnt = g.pose_cnt + p0 * 5;
-    return o;
-}
-
 // Row pitch of the internal frame slab (word-aligned rows for the byte kernels).
 int frame_pitch(const dvo_stream* s) { return (s->cfg.width + 15) & ~15; }
 
-// The per-pair geometry, one copy per pair set.  A stream starts with one set: the
-// drained calls (dvo_stream_process, _process_pairs, _pair) run a batch's rounds back to back
-// in it.  The first dvo_stream_submit / _submit_pairs grows it to kRansacRounds sets (the
-// pipeline depth); no set is occupied then, since every drained call retires what it started.
-// At 1280x720, N 2000, maxIters 1000 a set costs about 0.9 MB per pair (models 720 KB of it).
-int alloc_sets(dvo_stream* s, int nsets) {
+size_t hyp_cap(const dvo_stream* s) { return (size_t)(s->cfg.max_iters > 1 ? s->cfg.max_iters : 1); }
+
+// At least `want` pair sets (PairSets::ensure).  After a failure the stream has none, and the
+// next call that needs one allocates it.
+int ensure_sets(dvo_stream* s, int want) {
     dvo_ctx* ctx = s->ctx;
-    Buffers& b = s->buf;
-    if (!s->set_allocs.empty()) {
-        HIP_TRY(hipStreamSynchronize(s->hs));
-        for (void* q : s->set_allocs) {
-            hipFree(q);
-            s->allocs.erase(std::find(s->allocs.begin(), s->allocs.end(), q));
-        }
-        s->set_allocs.clear();
-    }
-    const size_t first = s->allocs.size();
-    const size_t SF = (size_t)nsets * s->cfg.max_frames;
-    const int cap = s->plan.kp_cap;
-    const size_t hc = (size_t)(s->cfg.max_iters > 1 ? s->cfg.max_iters : 1);
-    int rc = DVO_OK;
-    auto take = [&](auto*& ptr, size_t n) {
-        if (!rc) rc = dalloc(s, &ptr, n);
-    };
-    take(b.nmatch, SF);
-    take(b.pts, SF * cap * 4);
-    take(b.npts, SF * cap * 4);
-    take(b.models, SF * hc * 90);
-    take(b.nmod, SF * hc);
-    take(b.rcnt, SF * hc * 10);
-    take(b.subsets, SF * hc * 5);
-    take(b.rs, SF);
-    take(b.hdr, SF);
-    take(b.dk_off, SF + 1);
-    take(b.a_off, SF + 1);
-    take(b.s_off, SF + 1);
-    take(b.E, SF * 90);
-    take(b.info, SF * 4);
-    take(b.Rt, SF * 12);
-    take(b.good, SF);
-    take(b.pose_P, SF * 72);
-    take(b.pose_cnt, SF * 5);
-    s->set_allocs.assign(s->allocs.begin() + first, s->allocs.end());
-    s->nsets = rc ? 0 : nsets;
-    return rc;
+    HIP_TRY(s->pairs.ensure(want, s->cfg.max_frames, s->plan.kp_cap, hyp_cap(s)));
+    return DVO_OK;
 }
 
 int stream_alloc(dvo_stream* s) {
@@ -529,13 +376,26 @@ int stream_alloc(dvo_stream* s) {
     A(b.mq, (size_t)F * cap);
     A(b.mt, (size_t)F * cap);
     A(b.md, (size_t)F * cap);
-    const size_t hc = (size_t)(s->cfg.max_iters > 1 ? s->cfg.max_iters : 1);
-    if ((rc = alloc_sets(s, 1))) return rc;
+    const size_t hc = hyp_cap(s);
+    // the stream's GeomArgs: configuration and the round-local arrays here, once; the per-pair
+    // pointers are PairSets::ensure's
+    const dvo_stream_config& c = s->cfg;
+    GeomArgs& g = s->pairs.all.g;
+    g.pts_stride = cap;
+    set_camera(g, c.K);
+    g.prob = c.prob;
+    g.threshold = c.threshold;
+    g.max_iters = c.max_iters;
+    g.dist_thresh = c.dist_thresh;
+    g.hyp_cap = (int)hc;
+    g.dk_list_cap = std::max<int64_t>(round_items_bound(F, (int)hc), (int64_t)hc);
+    s->pairs.stream = s->hs;
+    if ((rc = ensure_sets(s, 1))) return rc;
     // five-point records and parked Durand-Kerner lists of one merged round (a bound over any
     // number of sets: one set at each round)
-    A(b.fprec, (size_t)std::max<int64_t>(round_blocks_bound(F, (int)hc), (int64_t)(hc + 63) / 64) * 128 * 64);
-    A(b.dk_ctl, (size_t)2 + kDkMaxPasses);
-    A(b.dk_list, (size_t)(kDkMaxPasses - 1) * std::max<int64_t>(round_items_bound(F, (int)hc), (int64_t)hc));
+    A(g.fprec, (size_t)std::max<int64_t>(round_blocks_bound(F, (int)hc), (int64_t)(hc + 63) / 64) * 128 * 64);
+    A(g.dk_ctl, (size_t)2 + kDkMaxPasses);
+    A(g.dk_list, (size_t)(kDkMaxPasses - 1) * g.dk_list_cap);
     A(b.status, (size_t)F);
     A(s->d_frames, (size_t)F * frame_pitch(s) * s->cfg.height);
     A(s->d_carry, (size_t)28);
@@ -604,11 +464,11 @@ int collect_events(dvo_stream* s) {
 int merged_round(dvo_stream* s) {
     dvo_ctx* ctx = s->ctx;
     RoundSpec sp{};
-    sp.nsets = s->nsets;
+    sp.nsets = s->pairs.nsets;
     sp.F = s->cfg.max_frames;
     bool any = false;
     for (int r = 0; r < kRansacRounds; ++r) sp.bound[r] = kRansacBounds[r];  // indexed by round
-    for (int k = 0; k < s->nsets; ++k) {
+    for (int k = 0; k < s->pairs.nsets; ++k) {
         auto& st = s->sets[k];
         const bool run = st.used && st.round < kRansacRounds;
         sp.round[k] = run ? st.round : -1;
@@ -616,7 +476,7 @@ int merged_round(dvo_stream* s) {
         any |= run;
     }
     if (!any) return DVO_OK;
-    HIP_TRY(launch_ransac_round(stream_geom(s), sp, s->hs));
+    HIP_TRY(launch_ransac_round(s->pairs.all.g, sp, s->hs));
     for (auto& st : s->sets)
         if (st.used && st.round < kRansacRounds) ++st.round;
     return DVO_OK;
@@ -625,14 +485,13 @@ int merged_round(dvo_stream* s) {
 // Retire the sets whose last round has run, oldest first: E, recoverPose, the records.
 int retire_sets(dvo_stream* s) {
     dvo_ctx* ctx = s->ctx;
-    const int F = s->cfg.max_frames;
-    const GeomArgs g = stream_geom(s);
     // ring order from the oldest set (the one after the newest)
     for (int j = 1; j <= kRansacRounds; ++j) {
         const int k = (s->last_set + j) % kRansacRounds;
         auto& st = s->sets[k];
         if (!st.used || st.round < kRansacRounds) continue;
-        HIP_TRY(launch_retire(geom_set(g, k, F, g.hyp_cap), st.pairs, s->buf.hdr + (size_t)k * F, st.rec, s->hs));
+        const PairArrays v = s->pairs.view(k);
+        HIP_TRY(launch_retire(v.g, st.pairs, v.hdr, st.rec, s->hs));
         s->retired_rec[s->retired] = st.rec;
         s->retired_pairs[s->retired] = st.pairs;
         ++s->retired;
@@ -656,14 +515,17 @@ bool sets_pending(const dvo_stream* s) {
 int run_stream(dvo_stream* s, const uint8_t* d_frames, int n, int64_t fstride, int pitch, dvo_pair_record* d_rec,
                bool detect_only, int pair_step = 1, bool drain = true) {
     dvo_ctx* ctx = s->ctx;
-    if (!detect_only && !drain && s->nsets < kRansacRounds) {  // the first pipelined submit: grow the sets
+    const int want = drain ? 1 : kRansacRounds;
+    if (!detect_only && s->pairs.nsets < want) {
+        // the first pipelined submit grows the sets; a drained call after a failed grow allocates one
         // (before params_of: the parameter block carries the buffer pointers)
         if (sets_pending(s)) return fail(ctx, DVO_EINVAL, "pair sets occupied at the first submit");
-        int rc = alloc_sets(s, kRansacRounds);
+        s->next_set = s->last_set = s->last_sub_pairs = 0;  // the last batch's matches go with the old sets
+        int rc = ensure_sets(s, want);
         if (rc) return rc;
-        s->next_set = 0;
     }
-    StreamParams P = params_of(s, d_frames, n, fstride, pitch);
+    const int k = s->next_set;
+    StreamParams P = params_of(s, d_frames, n, fstride, pitch, k);
     P.pair_step = pair_step;
     const int pairs = detect_only ? 0 : stream_pairs(P);
     hipEvent_t* ev = nullptr;
@@ -674,8 +536,6 @@ int run_stream(dvo_stream* s, const uint8_t* d_frames, int n, int64_t fstride, i
     }
     s->retired = 0;
     s->last_has_pairs = false;  // set again when a batch retires: the pose tail reads its records
-    const int F = s->cfg.max_frames;
-    const int k = s->next_set;
     if (pairs >= 1 && s->sets[k].used) {  // the ring is full (cannot happen in lockstep): finish its oldest
         int rc;
         while (s->sets[k].used && s->sets[k].round < kRansacRounds)
@@ -693,16 +553,13 @@ int run_stream(dvo_stream* s, const uint8_t* d_frames, int n, int64_t fstride, i
     if (detect_only) return DVO_OK;
     if (pairs >= 1) {
         // match into set k (its KeyPoint_convert points and counts), the frame-side record values
-        StreamParams Pk = P;
-        Pk.buf.pts += (size_t)k * F * s->plan.kp_cap * 4;
-        Pk.buf.nmatch += (size_t)k * F;
-        HIP_TRY(launch_match(Pk, s->cfg.cross_check, s->hs, ev));
-        HIP_TRY(launch_pair_header(P, s->buf.hdr + (size_t)k * F, s->hs));
-        const GeomArgs g = stream_geom(s);
-        HIP_TRY(launch_geometry_args(geom_set(g, k, F, g.hyp_cap), pairs, kStageNormalize, s->hs));
+        HIP_TRY(launch_match(P, s->cfg.cross_check, s->hs, ev));
+        HIP_TRY(launch_pair_header(P, P.buf.hdr, s->hs));
+        HIP_TRY(launch_geometry_args(s->pairs.view(k).g, pairs, kStageNormalize, s->hs));
         s->sets[k] = dvo_stream::PairSet{true, 0, pairs, d_rec};
         s->last_set = k;
-        s->next_set = (k + 1) % s->nsets;
+        // nsets >= 1 here: every path that matches has passed ensure_sets above
+        s->next_set = (k + 1) % s->pairs.nsets;
     }
     if (pairs < 1 && !drain) return DVO_OK;
     int rc;
@@ -757,12 +614,7 @@ int dvo_ctx_create(dvo_ctx** out, int device) {
 void dvo_ctx_destroy(dvo_ctx* ctx) {
     if (!ctx) return;
     hipSetDevice(ctx->device);
-    for (void* p : ctx->sift.allocs) hipFree(p);
-    for (void* p : ctx->surf.allocs) hipFree(p);
     if (ctx->call_stream) dvo_stream_destroy(ctx->call_stream);
-    for (auto& e : ctx->scratch)
-        if (e.first) hipFree(e.first);
-    if (ctx->pin) hipHostFree(ctx->pin);
     if (ctx->stream) hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -793,10 +645,8 @@ int dvo_stream_create(dvo_ctx* ctx, const dvo_stream_config* cfg, dvo_stream** o
         return fail(ctx, DVO_EHIP, "hipStreamCreate failed");
     s->own_hs = true;
     s->carry_owner = s.get();
-    if (hipEventCreateWithFlags(&s->carry_ev, hipEventDisableTiming) != hipSuccess) {
-        hipStreamDestroy(s->hs);
+    if (hipEventCreateWithFlags(&s->carry_ev, hipEventDisableTiming) != hipSuccess)
         return fail(ctx, DVO_EHIP, "hipEventCreate failed");
-    }
     rc = stream_alloc(s.get());
     if (!rc) {
         const std::vector<int32_t> coefs = resize_coefs(s->plan), coefs32 = resize_coefs_32(s->plan);
@@ -805,12 +655,7 @@ int dvo_stream_create(dvo_ctx* ctx, const dvo_stream_config* cfg, dvo_stream** o
                 hipSuccess)
             rc = fail(ctx, DVO_EHIP, "coefficient upload failed");
     }
-    if (rc) {
-        for (void* p : s->allocs) hipFree(p);
-        hipEventDestroy(s->carry_ev);
-        hipStreamDestroy(s->hs);
-        return rc;
-    }
+    if (rc) return rc;
     *out = s.release();
     return DVO_OK;
 }
@@ -819,12 +664,6 @@ void dvo_stream_destroy(dvo_stream* s) {
     if (!s) return;
     hipSetDevice(s->ctx->device);
     hipStreamSynchronize(s->hs);
-    for (void* p : s->allocs) hipFree(p);
-    for (auto* pool : {&s->ev_pending, &s->ev_free})
-        for (auto& e : *pool)
-            for (auto x : e) hipEventDestroy(x);
-    hipEventDestroy(s->carry_ev);
-    if (s->own_hs) hipStreamDestroy(s->hs);
     delete s;
 }
 
@@ -1071,15 +910,15 @@ int dvo_stream_pair(dvo_stream* s, const uint8_t* prev_img, const uint8_t* cur_i
             (!s->fc_n && (rc = dalloc(s, &s->fc_n, 2))) || (rc = dalloc(s, &s->pair_rec, 1)))
             return rc;
     }
-    Staging st;
-    const size_t img_bytes = (size_t)w * h;
-    int rc = staging(ctx, Staging::round(sizeof(dvo_pair_record)) + (reuse_prev ? 1 : 2) * Staging::round(img_bytes),
-                     s->hs, &st);
+    int rc = ensure_sets(s, 1);  // set 0 takes the pair
     if (rc) return rc;
+    CallMem mem(ctx->call, s->hs);
+    const size_t img_bytes = (size_t)w * h;
     const int pw = frame_pitch(s);
-    // host frames go through the pinned staging area: one host copy, one asynchronous DMA each
+    // host frames go through pinned buffers: one host copy, one asynchronous DMA each
     auto upload = [&](uint8_t* dst, const uint8_t* img) -> hipError_t {
-        uint8_t* hp = st.take(img_bytes);
+        uint8_t* hp = mem.host(img_bytes);
+        if (!hp) return mem.error();
         if (stride == w) {
             std::memcpy(hp, img, img_bytes);
         } else {
@@ -1090,7 +929,7 @@ int dvo_stream_pair(dvo_stream* s, const uint8_t* prev_img, const uint8_t* cur_i
     const int64_t fst = (int64_t)pw * h;
     const Buffers& b = s->buf;
     // after the first upload, an error drains the stream before returning: its DMAs read the
-    // context's pinned staging area, which the next staging user rewrites (or frees to grow it)
+    // context's pinned buffers, which the next per-call entry point rewrites (or frees to grow them)
     auto body = [&]() -> int {
     // the feature arrays of frame 0, frame 1 and the cache (the last current frame's), in 4-byte words
     FeatSlots fsl{};
@@ -1123,9 +962,9 @@ int dvo_stream_pair(dvo_stream* s, const uint8_t* prev_img, const uint8_t* cur_i
     int tsplit = 1;
     while (tsplit < 16 && nqb * tsplit * 2 <= 256 && nst >= tsplit * 8) tsplit *= 2;
     HIP_TRY(launch_match(P, s->cfg.cross_check, s->hs, nullptr, tsplit));
-    HIP_TRY(launch_geometry(P, stream_geom(s), s->pair_rec, s->hs, nullptr, true));
+    HIP_TRY(launch_geometry(P, s->pairs.all.g, s->pair_rec, s->hs, nullptr, true));
     uint8_t* hr = nullptr;
-    HIP_TRY(st.get(s->pair_rec, sizeof(dvo_pair_record), &hr));
+    HIP_TRY(mem.get(s->pair_rec, sizeof(dvo_pair_record), &hr));
     HIP_TRY(hipStreamSynchronize(s->hs));
     std::memcpy(rec_out, hr, sizeof(dvo_pair_record));
     return DVO_OK;
@@ -1184,8 +1023,7 @@ int dvo_stream_get_matches(dvo_stream* s, int pair, dvo_dmatch* out, int cap, in
     if (pair < 0 || pair >= s->last_sub_pairs) return fail(ctx, DVO_EINVAL, "pair out of range");
     HIP_TRY(hipStreamSynchronize(s->hs));
     int nm = 0;
-    HIP_TRY(hipMemcpy(&nm, s->buf.nmatch + (size_t)s->last_set * s->cfg.max_frames + pair, sizeof(int),
-                      hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&nm, s->pairs.view(s->last_set).nmatch + pair, sizeof(int), hipMemcpyDeviceToHost));
     *m = nm;
     if (nm > cap) return fail(ctx, DVO_ECAP, "caller capacity too small");
     std::vector<int32_t> q(nm), t(nm);
@@ -1266,19 +1104,16 @@ int dvo_orb_detect_and_compute(dvo_ctx* ctx, const dvo_orb_params* params, const
     dvo_stream* s = ctx->call_stream;
     const int pw = frame_pitch(s);
     const size_t kc = (size_t)s->plan.kp_cap;
-    Staging st;
-    if ((rc = staging(ctx, 2 * Staging::round(4) + Staging::round(kc * sizeof(dvo_keypoint)) + Staging::round(kc * 32),
-                      s->hs, &st)))
-        return rc;
+    CallMem mem(ctx->call, s->hs);
     HIP_TRY(hipMemcpy2DAsync(s->d_frames, pw, img, stride, w, h, hipMemcpyHostToDevice, s->hs));
     rc = run_stream(s, s->d_frames, 1, (int64_t)pw * h, pw, nullptr, true);
     if (rc) return rc;
     // dvo_stream_get_features of frame 0, with every list copied back at once (capacity-sized)
     uint8_t *hn, *hst, *hk = nullptr, *hd = nullptr;
-    HIP_TRY(st.get(s->buf.nkp, sizeof(int), &hn));
-    HIP_TRY(st.get(s->buf.status, sizeof(int), &hst));
-    if (kps) HIP_TRY(st.get(s->buf.kps, kc * sizeof(dvo_keypoint), &hk));
-    if (desc) HIP_TRY(st.get(s->buf.desc, kc * 32, &hd));
+    HIP_TRY(mem.get(s->buf.nkp, sizeof(int), &hn));
+    HIP_TRY(mem.get(s->buf.status, sizeof(int), &hst));
+    if (kps) HIP_TRY(mem.get(s->buf.kps, kc * sizeof(dvo_keypoint), &hk));
+    if (desc) HIP_TRY(mem.get(s->buf.desc, kc * 32, &hd));
     HIP_TRY(hipStreamSynchronize(s->hs));
     int nk = 0, stt = 0;
     std::memcpy(&nk, hn, sizeof(int));
@@ -1303,24 +1138,19 @@ int dvo_bf_match_hamming(dvo_ctx* ctx, const uint8_t* dq, int nq, const uint8_t*
     if (nq == 0 || nt == 0) return DVO_OK;  // BFMatcher returns no matches
     if (!dq || !dt || !out) return fail(ctx, DVO_EINVAL, "null buffer");
     HIP_TRY(hipSetDevice(ctx->device));
-    void *bq, *bt, *bnn, *bout, *bm;
-    int rc;
-    if ((rc = scratch(ctx, 0, (size_t)nq * 32, &bq)) || (rc = scratch(ctx, 1, (size_t)nt * 32, &bt)) ||
-        (rc = scratch(ctx, 2, match_pair_work_size(nq, nt), &bnn)) ||
-        (rc = scratch(ctx, 3, (size_t)nq * sizeof(dvo_dmatch), &bout)) ||
-        (rc = scratch(ctx, 4, 64, &bm)))
-        return rc;
-    Staging st;
-    if ((rc = staging(ctx, Staging::round((size_t)nq * 32) + Staging::round((size_t)nt * 32) + Staging::round(64) +
-                               Staging::round((size_t)nq * sizeof(dvo_dmatch)), ctx->stream, &st)))
-        return rc;
-    HIP_TRY(st.put(bq, dq, (size_t)nq * 32));
-    HIP_TRY(st.put(bt, dt, (size_t)nt * 32));
-    HIP_TRY(launch_match_pair((const uint8_t*)bq, nq, (const uint8_t*)bt, nt, cross_check, bnn, (dvo_dmatch*)bout,
-                              (int*)bm, ctx->stream));
+    CallMem mem(ctx->call, ctx->stream);
+    uint8_t* bq = mem.dev<uint8_t>((size_t)nq * 32);
+    uint8_t* bt = mem.dev<uint8_t>((size_t)nt * 32);
+    uint8_t* bnn = mem.dev<uint8_t>(match_pair_work_size(nq, nt));
+    dvo_dmatch* bout = mem.dev<dvo_dmatch>(nq);
+    int* bm = mem.dev<int>(16);
+    HIP_TRY(mem.error());
+    HIP_TRY(mem.put(bq, dq, (size_t)nq * 32));
+    HIP_TRY(mem.put(bt, dt, (size_t)nt * 32));
+    HIP_TRY(launch_match_pair(bq, nq, bt, nt, cross_check, bnn, bout, bm, ctx->stream));
     uint8_t *hm, *hout;
-    HIP_TRY(st.get(bm, sizeof(int), &hm));
-    HIP_TRY(st.get(bout, (size_t)nq * sizeof(dvo_dmatch), &hout));  // at most one match per query
+    HIP_TRY(mem.get(bm, sizeof(int), &hm));
+    HIP_TRY(mem.get(bout, (size_t)nq * sizeof(dvo_dmatch), &hout));  // at most one match per query
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     int m = 0;
     std::memcpy(&m, hm, sizeof(int));
@@ -1352,17 +1182,18 @@ int dvo_bf_knn_float(dvo_ctx* ctx, const float* dq, int nq, const float* dt, int
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
     const int ranges = knn_ranges(nq, nt, cus);
     const size_t out_n = (size_t)nq * k, part_n = ranges > 1 ? (size_t)ranges * nq * k : 1;
-    void *bq, *bt, *bd, *bi, *bpd, *bpi, *bb;
-    int rc;
-    if ((rc = scratch(ctx, 27, (size_t)nq * dim * 4, &bq)) || (rc = scratch(ctx, 28, (size_t)nt * dim * 4, &bt)) ||
-        (rc = scratch(ctx, 29, out_n * 4, &bd)) || (rc = scratch(ctx, 30, out_n * 4, &bi)) ||
-        (rc = scratch(ctx, 31, part_n * 4, &bpd)) || (rc = scratch(ctx, 32, part_n * 4, &bpi)) ||
-        (rc = scratch(ctx, 33, knn_bytes_size(nq, nt, dim), &bb)))
-        return rc;
+    CallMem mem(ctx->call, ctx->stream);
+    float* bq = mem.dev<float>((size_t)nq * dim);
+    float* bt = mem.dev<float>((size_t)nt * dim);
+    float* bd = mem.dev<float>(out_n);
+    int32_t* bi = mem.dev<int32_t>(out_n);
+    float* bpd = mem.dev<float>(part_n);
+    int32_t* bpi = mem.dev<int32_t>(part_n);
+    uint8_t* bb = mem.dev<uint8_t>(knn_bytes_size(nq, nt, dim));
+    HIP_TRY(mem.error());
     HIP_TRY(hipMemcpyAsync(bq, dq, (size_t)nq * dim * 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(bt, dt, (size_t)nt * dim * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(launch_knn_float((const float*)bq, nq, (const float*)bt, nt, dim, k, norm, ranges, bb, (float*)bpd, (int32_t*)bpi,
-                             (float*)bd, (int32_t*)bi, ctx->stream));
+    HIP_TRY(launch_knn_float(bq, nq, bt, nt, dim, k, norm, ranges, bb, bpd, bpi, bd, bi, ctx->stream));
     HIP_TRY(hipMemcpyAsync(dist, bd, out_n * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipMemcpyAsync(train_idx, bi, out_n * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1406,28 +1237,29 @@ int dvo_flann_knn(dvo_ctx* ctx, const float* dq, int nq, const float* dt, int nt
     HIP_TRY(hipSetDevice(ctx->device));
     const int n = nt, draws = 2 * n - 1, nodes_per_tree = 2 * n - 1;
     constexpr int kChunks = 64;
-    void *bq, *bt, *bR, *bcs, *bcnt, *boff, *bfill, *blist, *bind, *bind2, *bxv, *bsl, *bsr, *bnodes, *bopen, *blev,
-        *bidx, *bdist, *bflag, *bredo;
-    int rc;
-    if ((rc = scratch(ctx, 40, (size_t)nq * dim * 4, &bq)) || (rc = scratch(ctx, 41, (size_t)nt * dim * 4, &bt)) ||
-        (rc = scratch(ctx, 42, (size_t)draws * 4, &bR)) || (rc = scratch(ctx, 43, (size_t)trees * kChunks * 8, &bcs)) ||
-        (rc = scratch(ctx, 44, (size_t)n * 4, &bcnt)) || (rc = scratch(ctx, 45, (size_t)(n + 1) * 4, &boff)) ||
-        (rc = scratch(ctx, 46, (size_t)n * 4, &bfill)) || (rc = scratch(ctx, 47, (size_t)n * 4, &blist)) ||
-        (rc = scratch(ctx, 48, (size_t)n * 4, &bind)) || (rc = scratch(ctx, 49, (size_t)n * 4, &bind2)) ||
-        (rc = scratch(ctx, 50, (size_t)n * 4, &bxv)) || (rc = scratch(ctx, 51, (size_t)n * 4, &bsl)) ||
-        (rc = scratch(ctx, 52, (size_t)n * 4, &bsr)) ||
-        (rc = scratch(ctx, 53, (size_t)trees * nodes_per_tree * 16, &bnodes)) ||
-        (rc = scratch(ctx, 54, (size_t)2 * n * 16, &bopen)) || (rc = scratch(ctx, 55, (size_t)(n + 2) * 4, &blev)) ||
-        (rc = scratch(ctx, 56, (size_t)nq * k * 4, &bidx)) || (rc = scratch(ctx, 57, (size_t)nq * k * 4, &bdist)) ||
-        (rc = scratch(ctx, 58, (size_t)nq * 4, &bflag)) || (rc = scratch(ctx, 59, (size_t)(nq + 1) * 4, &bredo)))
-        return rc;
     hipStream_t s = ctx->stream;
-    Staging st;
-    if ((rc = staging(ctx, Staging::round((size_t)nq * dim * 4) + Staging::round((size_t)nt * dim * 4) +
-                               Staging::round((size_t)trees * kChunks * 8) + 2 * Staging::round((size_t)nq * k * 4) +
-                               2 * Staging::round(4),
-                      s, &st)))
-        return rc;
+    CallMem mem(ctx->call, s);
+    float* bq = mem.dev<float>((size_t)nq * dim);
+    float* bt = mem.dev<float>((size_t)nt * dim);
+    uint32_t* bR = mem.dev<uint32_t>(draws);
+    uint64_t* bcs = mem.dev<uint64_t>((size_t)trees * kChunks);
+    int* bcnt = mem.dev<int>(n);
+    int* boff = mem.dev<int>(n + 1);
+    int* bfill = mem.dev<int>(n);
+    int* blist = mem.dev<int>(n);
+    int* ind = mem.dev<int>(n);
+    int* ind2 = mem.dev<int>(n);
+    float* bxv = mem.dev<float>(n);
+    int* bsl = mem.dev<int>(n);
+    int* bsr = mem.dev<int>(n);
+    int4* bnodes = mem.dev<int4>((size_t)trees * nodes_per_tree);
+    int4* bopen = mem.dev<int4>((size_t)2 * n);
+    int* blev = mem.dev<int>(n + 2);
+    int32_t* bidx = mem.dev<int32_t>((size_t)nq * k);
+    float* bdist = mem.dev<float>((size_t)nq * k);
+    int32_t* bflag = mem.dev<int32_t>(nq);
+    int32_t* bredo = mem.dev<int32_t>(nq + 1);
+    HIP_TRY(mem.error());
     // the multiply-with-carry state at the start of every draw chunk of every tree (tree t's draws
     // begin t (2n - 1) steps after the call's state)
     std::vector<uint64_t> cs((size_t)trees * kChunks);
@@ -1435,26 +1267,24 @@ int dvo_flann_knn(dvo_ctx* ctx, const float* dq, int nq, const float* dt, int nt
         for (int c = 0; c < kChunks; ++c)
             cs[(size_t)t * kChunks + c] =
                 therng_jump(*rng_state, (uint64_t)t * draws + (uint64_t)((int64_t)draws * c / kChunks));
-    HIP_TRY(st.put(bq, dq, (size_t)nq * dim * 4));
-    HIP_TRY(st.put(bt, dt, (size_t)nt * dim * 4));
-    HIP_TRY(st.put(bcs, cs.data(), cs.size() * 8));
+    HIP_TRY(mem.put(bq, dq, (size_t)nq * dim * 4));
+    HIP_TRY(mem.put(bt, dt, (size_t)nt * dim * 4));
+    HIP_TRY(mem.put(bcs, cs.data(), cs.size() * 8));
     // ind = 0..n-1 once; every tree shuffles the previous tree's final order (KDTreeIndex::buildIndex)
     {
         std::vector<int32_t> iota(n);
         for (int i = 0; i < n; ++i) iota[i] = i;
-        HIP_TRY(hipMemcpyAsync(bind, iota.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(ind, iota.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
         HIP_TRY(hipStreamSynchronize(s));  // the pageable copy must finish before iota goes out of scope
     }
-    int* ind = (int*)bind;
-    int* ind2 = (int*)bind2;
-    int32_t* hcnt = reinterpret_cast<int32_t*>(st.take(4));
+    int32_t* hcnt = reinterpret_cast<int32_t*>(mem.host(4));
+    int32_t* hredo = reinterpret_cast<int32_t*>(mem.host(4));
+    HIP_TRY(mem.error());
     for (int t = 0; t < trees; ++t) {
-        HIP_TRY(launch_flann_draws((const uint64_t*)bcs + (size_t)t * kChunks, kChunks, draws, (uint32_t*)bR, s));
-        HIP_TRY(launch_flann_shuffle((const uint32_t*)bR, n, (int*)bcnt, (int*)boff, (int*)bfill, (int*)blist, ind, ind2,
-                                     s));
+        HIP_TRY(launch_flann_draws(bcs + (size_t)t * kChunks, kChunks, draws, bR, s));
+        HIP_TRY(launch_flann_shuffle(bR, n, bcnt, boff, bfill, blist, ind, ind2, s));
         std::swap(ind, ind2);
-        FlannBuildArgs a{(const float*)bt, n, dim, ind, (float*)bxv, (int*)bsl, (int*)bsr, (const uint32_t*)bR,
-                         (int4*)bnodes + (size_t)t * nodes_per_tree, (int4*)bopen, (int4*)bopen + n, (int*)blev};
+        FlannBuildArgs a{bt, n, dim, ind, bxv, bsl, bsr, bR, bnodes + (size_t)t * nodes_per_tree, bopen, bopen + n, blev};
         HIP_TRY(hipMemsetAsync(blev, 0, (size_t)(n + 2) * 4, s));
         HIP_TRY(launch_flann_root(a, s));
         // level-synchronous divideTree: a level has at most min(2^d, n / 2) open nodes; levels go in
@@ -1462,29 +1292,29 @@ int dvo_flann_knn(dvo_ctx* ctx, const float* dq, int nq, const float* dt, int nt
         for (int d = 0; d < n; d += 8) {
             for (int e = d; e < d + 8 && e < n; ++e)
                 HIP_TRY(launch_flann_level(a, e, (int)std::min<int64_t>(int64_t(1) << std::min(e, 20), n / 2 + 1), s));
-            HIP_TRY(hipMemcpyAsync(hcnt, (int*)blev + std::min(d + 8, n + 1), 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(hcnt, blev + std::min(d + 8, n + 1), 4, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
             if (*hcnt == 0) break;
         }
     }
-    FlannSearchArgs sa{(const float*)bq, (const float*)bt, (const int4*)bnodes, nq, n, dim, k, trees, checks,
-                       (int32_t*)bidx, (float*)bdist, (int32_t*)bflag};
+    FlannSearchArgs sa{bq, bt, bnodes, nq, n, dim, k, trees, checks, bidx, bdist, bflag};
     HIP_TRY(launch_flann_search(sa, s));
-    HIP_TRY(launch_flann_redo_list((const int32_t*)bflag, nq, (int32_t*)bredo + 1, (int32_t*)bredo, s));
-    int32_t* hredo = reinterpret_cast<int32_t*>(st.take(4));
+    HIP_TRY(launch_flann_redo_list(bflag, nq, bredo + 1, bredo, s));
     HIP_TRY(hipMemcpyAsync(hredo, bredo, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    for (int done = 0; done < *hredo;) {  // queries whose heap outgrew LDS, with the heap in global memory
+    // queries whose heap outgrew LDS, with the heap in global memory: batches of at most 256
+    const size_t heap_n = (size_t)std::min(*hredo, 256) * n;
+    float* bhd = mem.dev<float>(heap_n);
+    int32_t* bhn = mem.dev<int32_t>(heap_n);
+    HIP_TRY(mem.error());
+    for (int done = 0; done < *hredo;) {
         const int batch = std::min(*hredo - done, 256);
-        void *bhd, *bhn;
-        if ((rc = scratch(ctx, 60, (size_t)batch * n * 4, &bhd)) || (rc = scratch(ctx, 61, (size_t)batch * n * 4, &bhn)))
-            return rc;
-        HIP_TRY(launch_flann_search_global(sa, (const int32_t*)bredo + 1 + done, batch, (float*)bhd, (int32_t*)bhn, s));
+        HIP_TRY(launch_flann_search_global(sa, bredo + 1 + done, batch, bhd, bhn, s));
         done += batch;
     }
     uint8_t *hi, *hd;
-    HIP_TRY(st.get(bidx, (size_t)nq * k * 4, &hi));
-    HIP_TRY(st.get(bdist, (size_t)nq * k * 4, &hd));
+    HIP_TRY(mem.get(bidx, (size_t)nq * k * 4, &hi));
+    HIP_TRY(mem.get(bdist, (size_t)nq * k * 4, &hd));
     HIP_TRY(hipStreamSynchronize(s));
     std::memcpy(train_idx, hi, (size_t)nq * k * 4);
     std::memcpy(dist, hd, (size_t)nq * k * 4);
@@ -1512,7 +1342,6 @@ std::vector<float> sift_gauss_taps(double sigma) {
 int sift_plan(dvo_ctx* ctx, int w, int h) {
     SiftPlanDev& P = ctx->sift;
     if (P.w == w && P.h == h) return DVO_OK;
-    for (void* p : P.allocs) hipFree(p);
     P = SiftPlanDev{};
     SiftArgs& A = P.a;
     const int W = 2 * w, H = 2 * h;  // firstOctave = -1
@@ -1552,13 +1381,7 @@ int sift_plan(dvo_ctx* ctx, int w, int h) {
         taps.insert(taps.end(), t.begin(), t.end());
     }
     P.pitch = (w + 255) & ~255;
-    auto A_ = [&](auto*& p, size_t bytes) {
-        void* q = nullptr;
-        if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return false;
-        P.allocs.push_back(q);
-        p = static_cast<std::remove_reference_t<decltype(p)>>(q);
-        return true;
-    };
+    auto A_ = [&](auto*& p, size_t bytes) { return P.mem.alloc(&p, bytes ? bytes : 16) == hipSuccess; };
     int order_n = 1;
     while (order_n < A.kp_cap) order_n <<= 1;
     int* counters = nullptr;
@@ -1567,7 +1390,6 @@ int sift_plan(dvo_ctx* ctx, int w, int h) {
         !A_(A.order, (size_t)order_n * 4) || !A_(A.kps, (size_t)A.kp_cap * sizeof(dvo_keypoint)) ||
         !A_(A.desc, (size_t)A.kp_cap * 128 * 4) || !A_(counters, 64) || !A_(P.taps, taps.size() * 4) ||
         !A_(P.img, (size_t)P.pitch * h)) {
-        for (void* p : P.allocs) hipFree(p);
         P = SiftPlanDev{};
         return fail(ctx, DVO_EHIP, "SIFT buffers: hipMalloc failed");
     }
@@ -1616,7 +1438,6 @@ void surf_haar(const int src[][5], SurfHaar* dst, int n, int old_size, int new_s
 int surf_plan(dvo_ctx* ctx, int w, int h) {
     SurfPlanDev& P = ctx->surf;
     if (P.w == w && P.h == h) return DVO_OK;
-    for (void* p : P.allocs) hipFree(p);
     P = SurfPlanDev{};
     SurfArgs& A = P.a;
     A.w = w;
@@ -1658,13 +1479,7 @@ int surf_plan(dvo_ctx* ctx, int w, int h) {
     A.kp_cap = std::max(4096, (w * h) / 64);
     int order_n = 1;
     while (order_n < A.kp_cap) order_n <<= 1;
-    auto A_ = [&](auto*& p, size_t bytes) {
-        void* q = nullptr;
-        if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return false;
-        P.allocs.push_back(q);
-        p = static_cast<std::remove_reference_t<decltype(p)>>(q);
-        return true;
-    };
+    auto A_ = [&](auto*& p, size_t bytes) { return P.mem.alloc(&p, bytes ? bytes : 16) == hipSuccess; };
     int* counters = nullptr;
     SurfHaar* d_haar = nullptr;
     int8_t* d_apt = nullptr;
@@ -1675,7 +1490,6 @@ int surf_plan(dvo_ctx* ctx, int w, int h) {
         !A_(A.out, (size_t)A.kp_cap * sizeof(dvo_keypoint)) || !A_(A.desc, (size_t)A.kp_cap * 64 * 4) ||
         !A_(counters, 64) || !A_(d_haar, haar.size() * sizeof(SurfHaar)) || !A_(d_apt, apt.size()) ||
         !A_(d_aptw, aptw.size() * 4) || !A_(P.img, (size_t)A.pitch * h)) {
-        for (void* p : P.allocs) hipFree(p);
         P = SurfPlanDev{};
         return fail(ctx, DVO_EHIP, "SURF buffers: hipMalloc failed");
     }
@@ -1757,17 +1571,19 @@ int dvo_sift_detect_and_compute(dvo_ctx* ctx, const uint8_t* img, int w, int h, 
     return DVO_OK;
 }
 
-static int upload_points(dvo_ctx* ctx, Staging& st, const double* p1, const double* p2, int m, void** dpts) {
-    int rc = scratch(ctx, 5, (size_t)(m > 0 ? m : 1) * 32, dpts);
-    if (rc) return rc;
-    double* h = reinterpret_cast<double*>(st.take((size_t)m * 32));
+// The correspondences as the geometry kernels read them: [m][4] (x1, y1, x2, y2), on the device.
+static int upload_points(dvo_ctx* ctx, CallMem& mem, const double* p1, const double* p2, int m, const double** dpts) {
+    double* d = mem.dev<double>((size_t)m * 4);
+    double* h = reinterpret_cast<double*>(mem.host((size_t)m * 32));
+    HIP_TRY(mem.error());
     for (int i = 0; i < m; ++i) {
         h[4 * i] = p1[2 * i];
         h[4 * i + 1] = p1[2 * i + 1];
         h[4 * i + 2] = p2[2 * i];
         h[4 * i + 3] = p2[2 * i + 1];
     }
-    HIP_TRY(st.send(*dpts, reinterpret_cast<const uint8_t*>(h), (size_t)m * 32));
+    HIP_TRY(mem.send(d, reinterpret_cast<const uint8_t*>(h), (size_t)m * 32));
+    *dpts = d;
     return DVO_OK;
 }
 
@@ -1781,56 +1597,39 @@ int dvo_find_essential_mat(dvo_ctx* ctx, const double* p1, const double* p2, int
     if (max_iters < 1) return fail(ctx, DVO_EINVAL, "max_iters must be >= 1");
     if (m < 5) return fail(ctx, DVO_EFEWPTS, "fewer than 5 correspondences");
     HIP_TRY(hipSetDevice(ctx->device));
-    void *dpts, *dn, *dmod, *dE, *dinfo, *dmask, *dnmod, *dcnt, *dsub, *drs, *drec, *doff, *dctl, *dlist, *daoff, *dsoff;
-    int rc;
     const size_t hc = (size_t)(max_iters > 1 ? max_iters : 1);
-    Staging st;
-    if ((rc = staging(ctx, Staging::round((size_t)m * 32) + Staging::round(16) + Staging::round(90 * 8) +
-                               Staging::round((size_t)m), ctx->stream, &st)))
-        return rc;
-    if ((rc = scratch(ctx, 6, (size_t)m * 32, &dn)) ||
-        (rc = scratch(ctx, 7, hc * 90 * 8, &dmod)) || (rc = scratch(ctx, 8, 90 * 8, &dE)) ||
-        (rc = scratch(ctx, 9, 16, &dinfo)) || (rc = scratch(ctx, 10, (size_t)m, &dmask)) ||
-        (rc = scratch(ctx, 16, hc * 4, &dnmod)) || (rc = scratch(ctx, 17, hc * 40, &dcnt)) ||
-        (rc = scratch(ctx, 18, hc * 20, &dsub)) || (rc = scratch(ctx, 19, sizeof(RansacState), &drs)) ||
-        (rc = scratch(ctx, 21, ((hc + 63) / 64) * 128 * 64 * 8, &drec)) || (rc = scratch(ctx, 22, 8, &doff)) ||
-        (rc = scratch(ctx, 23, 4 * (2 + kDkMaxPasses), &dctl)) || (rc = scratch(ctx, 24, hc * 8, &dlist)) ||
-        (rc = scratch(ctx, 62, 8, &daoff)) || (rc = scratch(ctx, 63, 8, &dsoff)) ||
-        (rc = upload_points(ctx, st, p1, p2, m, &dpts)))
-        return rc;
+    CallMem mem(ctx->call, ctx->stream);
     GeomArgs g{};
-    g.pts_d = (const double*)dpts;
     g.m_const = m;
     g.pts_stride = m;
-    g.fx = K[0];
-    g.fy = K[4];
-    g.cx = K[2];
-    g.cy = K[5];
+    set_camera(g, K);
     g.prob = prob;
     g.threshold = threshold;
     g.max_iters = max_iters;
-    g.npts = (double*)dn;
-    g.models = (double*)dmod;
-    g.nmod = (int32_t*)dnmod;
-    g.cnt = (int32_t*)dcnt;
-    g.subsets = (int32_t*)dsub;
-    g.rs = (RansacState*)drs;
-    g.fprec = (double*)drec;
-    g.dk_off = (int32_t*)doff;
-    g.a_off = (int32_t*)daoff;
-    g.s_off = (int32_t*)dsoff;
-    g.dk_ctl = (int32_t*)dctl;
-    g.dk_list = (int32_t*)dlist;
+    g.npts = mem.dev<double>((size_t)m * 4);
+    g.models = mem.dev<double>(hc * 90);
+    g.E = mem.dev<double>(90);
+    g.info = mem.dev<int32_t>(4);
+    g.mask = mem.dev<uint8_t>(m);
+    g.nmod = mem.dev<int32_t>(hc);
+    g.cnt = mem.dev<int32_t>(hc * 10);
+    g.subsets = mem.dev<int32_t>(hc * 5);
+    g.rs = mem.dev<RansacState>(1);
+    g.fprec = mem.dev<double>(((hc + 63) / 64) * 128 * 64);
+    g.dk_off = mem.dev<int32_t>(2);
+    g.a_off = mem.dev<int32_t>(2);
+    g.s_off = mem.dev<int32_t>(2);
+    g.dk_ctl = mem.dev<int32_t>(2 + kDkMaxPasses);
+    g.dk_list = mem.dev<int32_t>(hc * 2);
     g.dk_list_cap = (int64_t)hc;
     g.hyp_cap = (int)hc;
-    g.E = (double*)dE;
-    g.info = (int32_t*)dinfo;
-    g.mask = (uint8_t*)dmask;
+    int rc = upload_points(ctx, mem, p1, p2, m, &g.pts_d);
+    if (rc) return rc;
     HIP_TRY(launch_geometry_args(g, 1, kStageNormalize | kStageRansac | kStageOneRound, ctx->stream));
     uint8_t *hinfo, *hE, *hmask = nullptr;
-    HIP_TRY(st.get(dinfo, 16, &hinfo));
-    HIP_TRY(st.get(dE, 90 * 8, &hE));  // every row the kernel may write (<= 10 models)
-    if (mask) HIP_TRY(st.get(dmask, (size_t)m, &hmask));
+    HIP_TRY(mem.get(g.info, 16, &hinfo));
+    HIP_TRY(mem.get(g.E, 90 * 8, &hE));  // every row the kernel may write (<= 10 models)
+    if (mask) HIP_TRY(mem.get(g.mask, (size_t)m, &hmask));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     int info[4];
     std::memcpy(info, hinfo, sizeof(info));
@@ -1849,52 +1648,36 @@ int dvo_recover_pose(dvo_ctx* ctx, const double* E, int e_rows, const double* p1
     if (m < 0 || (m > 0 && (!p1 || !p2))) return fail(ctx, DVO_EINVAL, "bad point arrays");
     if (!std::isfinite(dist_thresh)) return fail(ctx, DVO_EINVAL, "distanceThresh must be finite");
     HIP_TRY(hipSetDevice(ctx->device));
-    void *dpts, *dn, *dE, *dinfo, *dRt, *dgood, *dpick, *dpm, *dmin = nullptr;
-    int rc;
     const int mm = m > 0 ? m : 1;
-    Staging st;
-    if ((rc = staging(ctx, Staging::round((size_t)m * 32) + Staging::round((size_t)m) + 2 * Staging::round(96) +
-                               Staging::round(16) * 3 + Staging::round((size_t)m * 4), ctx->stream, &st)))
-        return rc;
-    if ((rc = scratch(ctx, 6, (size_t)mm * 32, &dn)) ||
-        (rc = scratch(ctx, 8, 90 * 8, &dE)) || (rc = scratch(ctx, 9, 16, &dinfo)) ||
-        (rc = scratch(ctx, 11, 12 * 8, &dRt)) || (rc = scratch(ctx, 12, 8, &dgood)) ||
-        (rc = scratch(ctx, 13, 8, &dpick)) || (rc = scratch(ctx, 14, (size_t)mm * 4, &dpm)))
-        return rc;
-    if (mask_in && (rc = scratch(ctx, 15, (size_t)mm, &dmin))) return rc;
-    void *dpP, *dpc;
-    if ((rc = scratch(ctx, 25, 72 * sizeof(double), &dpP)) || (rc = scratch(ctx, 26, 5 * sizeof(int32_t), &dpc)) ||
-        (rc = upload_points(ctx, st, p1, p2, m, &dpts)))
-        return rc;
-    if (mask_in) HIP_TRY(st.put(dmin, mask_in, (size_t)m));
-    const int info[4] = {3, 0, 0, DVO_OK};
-    HIP_TRY(st.put(dE, E, 9 * sizeof(double)));
-    HIP_TRY(st.put(dinfo, info, sizeof(info)));
+    CallMem mem(ctx->call, ctx->stream);
     GeomArgs g{};
-    g.pts_d = (const double*)dpts;
     g.m_const = m;
     g.pts_stride = mm;
-    g.fx = K[0];
-    g.fy = K[4];
-    g.cx = K[2];
-    g.cy = K[5];
+    set_camera(g, K);
     g.dist_thresh = dist_thresh;
-    g.npts = (double*)dn;
-    g.E = (double*)dE;
-    g.info = (int32_t*)dinfo;
-    g.mask_in = (const uint8_t*)dmin;
-    g.Rt = (double*)dRt;
-    g.good = (int32_t*)dgood;
-    g.pick = (int32_t*)dpick;
-    g.pose_mask = (uint8_t*)dpm;
-    g.pose_P = (double*)dpP;
-    g.pose_cnt = (int32_t*)dpc;
+    g.npts = mem.dev<double>((size_t)mm * 4);
+    g.E = mem.dev<double>(90);
+    g.info = mem.dev<int32_t>(4);
+    g.Rt = mem.dev<double>(12);
+    g.good = mem.dev<int32_t>(2);
+    g.pick = mem.dev<int32_t>(2);
+    g.pose_mask = mem.dev<uint8_t>((size_t)mm * 4);
+    g.pose_P = mem.dev<double>(72);
+    g.pose_cnt = mem.dev<int32_t>(5);
+    uint8_t* dmin = mask_in ? mem.dev<uint8_t>(mm) : nullptr;
+    g.mask_in = dmin;
+    int rc = upload_points(ctx, mem, p1, p2, m, &g.pts_d);
+    if (rc) return rc;
+    if (mask_in) HIP_TRY(mem.put(dmin, mask_in, (size_t)m));
+    const int info[4] = {3, 0, 0, DVO_OK};
+    HIP_TRY(mem.put(g.E, E, 9 * sizeof(double)));
+    HIP_TRY(mem.put(g.info, info, sizeof(info)));
     HIP_TRY(launch_geometry_args(g, 1, kStageNormalize | kStagePose, ctx->stream));
     uint8_t *hRt, *hgood, *hpick, *hpm = nullptr;
-    HIP_TRY(st.get(dRt, 12 * sizeof(double), &hRt));
-    HIP_TRY(st.get(dgood, sizeof(int), &hgood));
-    HIP_TRY(st.get(dpick, sizeof(int), &hpick));
-    if (mask_out && m > 0) HIP_TRY(st.get(dpm, (size_t)m * 4, &hpm));
+    HIP_TRY(mem.get(g.Rt, 12 * sizeof(double), &hRt));
+    HIP_TRY(mem.get(g.good, sizeof(int), &hgood));
+    HIP_TRY(mem.get(g.pick, sizeof(int), &hpick));
+    if (mask_out && m > 0) HIP_TRY(mem.get(g.pose_mask, (size_t)m * 4, &hpm));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     std::memcpy(R, hRt, 9 * sizeof(double));
     std::memcpy(t, hRt + 9 * sizeof(double), 3 * sizeof(double));
@@ -1911,24 +1694,22 @@ int dvo_triangulate_points(dvo_ctx* ctx, const double* P1, const double* P2, con
     if (!ctx || !P1 || !P2 || !X || k < 0 || (k > 0 && (!x1 || !x2))) return DVO_EINVAL;
     if (k == 0) return DVO_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    void *dP, *dx, *dX;
-    int rc;
-    if ((rc = scratch(ctx, 16, 24 * 8, &dP)) || (rc = scratch(ctx, 17, (size_t)k * 32, &dx)) ||
-        (rc = scratch(ctx, 18, (size_t)k * 32, &dX)))
-        return rc;
-    Staging st;
-    if ((rc = staging(ctx, Staging::round(24 * 8) + Staging::round((size_t)k * 32) * 2, ctx->stream, &st))) return rc;
-    uint8_t* hP = st.take(24 * 8);
+    CallMem mem(ctx->call, ctx->stream);
+    double* dP = mem.dev<double>(24);
+    double* dx = mem.dev<double>((size_t)k * 4);
+    double* dX = mem.dev<double>((size_t)k * 4);
+    uint8_t* hP = mem.host(24 * 8);
+    uint8_t* hx = mem.host((size_t)k * 32);
+    HIP_TRY(mem.error());
     std::memcpy(hP, P1, 12 * sizeof(double));
     std::memcpy(hP + 12 * sizeof(double), P2, 12 * sizeof(double));
-    HIP_TRY(st.send(dP, hP, 24 * 8));
-    uint8_t* hx = st.take((size_t)k * 32);
+    HIP_TRY(mem.send(dP, hP, 24 * 8));
     std::memcpy(hx, x1, (size_t)k * 16);
     std::memcpy(hx + (size_t)k * 16, x2, (size_t)k * 16);
-    HIP_TRY(st.send(dx, hx, (size_t)k * 32));
-    HIP_TRY(launch_triangulate((const double*)dP, (const double*)dx, k, (double*)dX, ctx->stream));
+    HIP_TRY(mem.send(dx, hx, (size_t)k * 32));
+    HIP_TRY(launch_triangulate(dP, dx, k, dX, ctx->stream));
     uint8_t* hX;
-    HIP_TRY(st.get(dX, (size_t)k * 32, &hX));
+    HIP_TRY(mem.get(dX, (size_t)k * 32, &hX));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     std::memcpy(X, hX, (size_t)k * 32);
     return DVO_OK;
@@ -1940,19 +1721,19 @@ int dvo_test_retain_best(dvo_ctx* ctx, const float* resp, int n, int n_points, i
     if (!ctx || !resp || !perm || !k_out || n < 0) return DVO_EINVAL;
     if (semantics != DVO_OPENCV_4X && semantics != DVO_OPENCV_32) return fail(ctx, DVO_EINVAL, "bad semantics");
     HIP_TRY(hipSetDevice(ctx->device));
-    void *dv, *dk, *dt, *dkk;
-    int rc;
-    if ((rc = scratch(ctx, 20, (size_t)(n + 1) * 4, &dv)) || (rc = scratch(ctx, 21, (size_t)(n + 1) * 4, &dk)) ||
-        (rc = scratch(ctx, 22, (size_t)(2 * n + 2) * 4, &dt)) || (rc = scratch(ctx, 23, 8, &dkk)))
-        return rc;
+    CallMem mem(ctx->call, ctx->stream);
+    float* dv = mem.dev<float>((size_t)n + 1);
+    uint32_t* dk = mem.dev<uint32_t>((size_t)n + 1);
+    int32_t* dt = mem.dev<int32_t>((size_t)2 * n + 2);
+    int* dkk = mem.dev<int>(2);
+    HIP_TRY(mem.error());
     std::vector<uint32_t> ids(n);
     for (int i = 0; i < n; ++i) ids[i] = (uint32_t)i;
     if (n) {
         HIP_TRY(hipMemcpy(dv, resp, (size_t)n * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(dk, ids.data(), (size_t)n * 4, hipMemcpyHostToDevice));
     }
-    HIP_TRY(launch_test_retain_best((float*)dv, (uint32_t*)dk, (int32_t*)dt, n, n_points, depth, semantics, (int*)dkk,
-                                    ctx->stream));
+    HIP_TRY(launch_test_retain_best(dv, dk, dt, n, n_points, depth, semantics, dkk, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     int k = 0;
     HIP_TRY(hipMemcpy(&k, dkk, sizeof(int), hipMemcpyDeviceToHost));
@@ -1966,11 +1747,12 @@ int dvo_test_update_num_iters(dvo_ctx* ctx, double p, const double* ep, int n, i
     if (!ctx || !ep || !out || n < 0) return DVO_EINVAL;
     if (n == 0) return DVO_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    void *de, *dout;
-    int rc;
-    if ((rc = scratch(ctx, 24, (size_t)n * 8, &de)) || (rc = scratch(ctx, 25, (size_t)n * 4, &dout))) return rc;
+    CallMem mem(ctx->call, ctx->stream);
+    double* de = mem.dev<double>(n);
+    int32_t* dout = mem.dev<int32_t>(n);
+    HIP_TRY(mem.error());
     HIP_TRY(hipMemcpy(de, ep, (size_t)n * 8, hipMemcpyHostToDevice));
-    HIP_TRY(launch_test_update_num_iters(p, (const double*)de, n, model_points, max_iters, (int32_t*)dout, ctx->stream));
+    HIP_TRY(launch_test_update_num_iters(p, de, n, model_points, max_iters, dout, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     HIP_TRY(hipMemcpy(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost));
     return DVO_OK;
@@ -1979,17 +1761,18 @@ int dvo_test_update_num_iters(dvo_ctx* ctx, double p, const double* ep, int n, i
 int dvo_test_ransac_subsets(dvo_ctx* ctx, int m, int n, int32_t* idx) {
     if (!ctx || !idx || m < 6 || n < 1) return DVO_EINVAL;
     HIP_TRY(hipSetDevice(ctx->device));
-    void *drs, *dsub;
-    int rc;
-    if ((rc = scratch(ctx, 19, sizeof(RansacState), &drs)) || (rc = scratch(ctx, 18, (size_t)n * 20, &dsub))) return rc;
+    CallMem mem(ctx->call, ctx->stream);
+    RansacState* drs = mem.dev<RansacState>(1);
+    int32_t* dsub = mem.dev<int32_t>((size_t)n * 5);
+    HIP_TRY(mem.error());
     RansacState S{};
     S.rng = ~0ull;
     S.m = m;
     S.niters = n;  // round 2 of the sampler covers [h1, niters) = [0, n)
     HIP_TRY(hipMemcpyAsync(drs, &S, sizeof(S), hipMemcpyHostToDevice, ctx->stream));
     GeomArgs g{};
-    g.rs = (RansacState*)drs;
-    g.subsets = (int32_t*)dsub;
+    g.rs = drs;
+    g.subsets = dsub;
     g.hyp_cap = n;
     g.m_const = m;
     HIP_TRY(launch_test_ransac_sample(g, ctx->stream));
@@ -2002,11 +1785,11 @@ int dvo_test_ransac_replay(dvo_ctx* ctx, const int32_t* nmod, const int32_t* cnt
                            int max_iters, int32_t* out) {
     if (!ctx || !nmod || !cnt || !out || n < 1 || m < 6) return DVO_EINVAL;
     HIP_TRY(hipSetDevice(ctx->device));
-    void *drs, *dn, *dc;
-    int rc;
-    if ((rc = scratch(ctx, 19, sizeof(RansacState), &drs)) || (rc = scratch(ctx, 16, (size_t)n * 4, &dn)) ||
-        (rc = scratch(ctx, 17, (size_t)n * 40, &dc)))
-        return rc;
+    CallMem mem(ctx->call, ctx->stream);
+    RansacState* drs = mem.dev<RansacState>(1);
+    int32_t* dn = mem.dev<int32_t>(n);
+    int32_t* dc = mem.dev<int32_t>((size_t)n * 10);
+    HIP_TRY(mem.error());
     RansacState S{};
     S.m = m;
     S.niters = max_iters > 1 ? max_iters : 1;
@@ -2017,9 +1800,9 @@ int dvo_test_ransac_replay(dvo_ctx* ctx, const int32_t* nmod, const int32_t* cnt
     HIP_TRY(hipMemcpyAsync(dn, nmod, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(dc, cnt, (size_t)n * 40, hipMemcpyHostToDevice, ctx->stream));
     GeomArgs g{};
-    g.rs = (RansacState*)drs;
-    g.nmod = (int32_t*)dn;
-    g.cnt = (int32_t*)dc;
+    g.rs = drs;
+    g.nmod = dn;
+    g.cnt = dc;
     g.hyp_cap = n;
     g.prob = prob;
     HIP_TRY(launch_test_ransac_replay(g, ctx->stream));
@@ -2036,10 +1819,11 @@ int dvo_test_ransac_replay(dvo_ctx* ctx, const int32_t* nmod, const int32_t* cnt
 int dvo_test_five_point(dvo_ctx* ctx, const double* q1, const double* q2, double* models, int* n) {
     if (!ctx || !q1 || !q2 || !models || !n) return DVO_EINVAL;
     HIP_TRY(hipSetDevice(ctx->device));
-    void *dq, *dm, *dn;
-    int rc;
-    if ((rc = scratch(ctx, 26, 20 * 8, &dq)) || (rc = scratch(ctx, 27, 90 * 8, &dm)) || (rc = scratch(ctx, 28, 8, &dn)))
-        return rc;
+    CallMem mem(ctx->call, ctx->stream);
+    double* dq = mem.dev<double>(20);
+    double* dm = mem.dev<double>(90);
+    int* dn = mem.dev<int>(2);
+    HIP_TRY(mem.error());
     double q[20];
     for (int i = 0; i < 5; ++i) {
         q[4 * i] = q1[2 * i];
@@ -2048,7 +1832,7 @@ int dvo_test_five_point(dvo_ctx* ctx, const double* q1, const double* q2, double
         q[4 * i + 3] = q2[2 * i + 1];
     }
     HIP_TRY(hipMemcpy(dq, q, sizeof(q), hipMemcpyHostToDevice));
-    HIP_TRY(launch_test_five_point((const double*)dq, (double*)dm, (int*)dn, ctx->stream));
+    HIP_TRY(launch_test_five_point(dq, dm, dn, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     HIP_TRY(hipMemcpy(n, dn, sizeof(int), hipMemcpyDeviceToHost));
     if (*n > 0) HIP_TRY(hipMemcpy(models, dm, (size_t)*n * 72, hipMemcpyDeviceToHost));
@@ -2060,14 +1844,15 @@ int dvo_test_sampson(dvo_ctx* ctx, const double* E, const double* pts, int n, fl
     if (!ctx || !E || n < 0 || (n > 0 && (!pts || !dec || !exact))) return DVO_EINVAL;
     if (n == 0) return DVO_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    void *dE, *dp, *dd, *dx;
-    int rc;
-    if ((rc = scratch(ctx, 26, 9 * 8, &dE)) || (rc = scratch(ctx, 27, (size_t)n * 32, &dp)) ||
-        (rc = scratch(ctx, 28, (size_t)n, &dd)) || (rc = scratch(ctx, 29, (size_t)n, &dx)))
-        return rc;
+    CallMem mem(ctx->call, ctx->stream);
+    double* dE = mem.dev<double>(9);
+    double* dp = mem.dev<double>((size_t)n * 4);
+    int8_t* dd = mem.dev<int8_t>(n);
+    uint8_t* dx = mem.dev<uint8_t>(n);
+    HIP_TRY(mem.error());
     HIP_TRY(hipMemcpy(dE, E, 9 * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dp, pts, (size_t)n * 32, hipMemcpyHostToDevice));
-    HIP_TRY(launch_test_sampson((const double*)dE, (const double*)dp, n, t, (int8_t*)dd, (uint8_t*)dx, ctx->stream));
+    HIP_TRY(launch_test_sampson(dE, dp, n, t, dd, dx, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     HIP_TRY(hipMemcpy(dec, dd, (size_t)n, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(exact, dx, (size_t)n, hipMemcpyDeviceToHost));
@@ -2155,6 +1940,7 @@ bool inv3(const double* M, double* out) {
 struct dvo_undistort {
     dvo_ctx* ctx = nullptr;
     UndistortGeom U{};
+    DeviceAllocs mem;
     double* d_ir = nullptr;
     int16_t* d_xy = nullptr;
     uint16_t* d_frac = nullptr;
@@ -2229,18 +2015,13 @@ int dvo_undistort_create(dvo_ctx* ctx, const double* K, const double* dist, int 
         if (!inv3(Ar, &ir[(size_t)s * 9])) return fail(ctx, DVO_EINVAL, "new camera matrix is singular");
     }
     HIP_TRY(hipSetDevice(ctx->device));
-    bool ok = hipMalloc(&u->d_ir, ir.size() * sizeof(double)) == hipSuccess &&
-              hipMalloc(&u->d_xy, (size_t)w * h * 2 * sizeof(int16_t)) == hipSuccess &&
-              hipMalloc(&u->d_frac, (size_t)w * h * sizeof(uint16_t)) == hipSuccess;
+    bool ok = u->mem.alloc(&u->d_ir, ir.size() * sizeof(double)) == hipSuccess &&
+              u->mem.alloc(&u->d_xy, (size_t)w * h * 2 * sizeof(int16_t)) == hipSuccess &&
+              u->mem.alloc(&u->d_frac, (size_t)w * h * sizeof(uint16_t)) == hipSuccess;
     if (ok) ok = hipMemcpy(u->d_ir, ir.data(), ir.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
     if (ok) ok = launch_undistort_map(U, u->d_ir, u->d_xy, u->d_frac, ctx->stream) == hipSuccess;
     if (ok) ok = hipStreamSynchronize(ctx->stream) == hipSuccess;
-    if (!ok) {
-        hipFree(u->d_ir);
-        hipFree(u->d_xy);
-        hipFree(u->d_frac);
-        return fail(ctx, DVO_EHIP, "undistort map construction failed");
-    }
+    if (!ok) return fail(ctx, DVO_EHIP, "undistort map construction failed");
     *out = u.release();
     return DVO_OK;
 }
@@ -2248,9 +2029,6 @@ int dvo_undistort_create(dvo_ctx* ctx, const double* K, const double* dist, int 
 void dvo_undistort_destroy(dvo_undistort* u) {
     if (!u) return;
     hipSetDevice(u->ctx->device);
-    hipFree(u->d_ir);
-    hipFree(u->d_xy);
-    hipFree(u->d_frac);
     delete u;
 }
 
@@ -2282,13 +2060,13 @@ int dvo_undistort_image(dvo_undistort* u, const uint8_t* img, int stride, uint8_
     const int w = u->U.w, h = u->U.h;
     if (stride < w || out_stride < w) return fail(ctx, DVO_EINVAL, "bad strides");
     HIP_TRY(hipSetDevice(ctx->device));
-    void *dsrc, *ddst;
-    int rc;
     const int pw = (w + 15) & ~15;
-    if ((rc = scratch(ctx, 24, (size_t)pw * h, &dsrc)) || (rc = scratch(ctx, 25, (size_t)pw * h, &ddst))) return rc;
+    CallMem mem(ctx->call, ctx->stream);
+    uint8_t* dsrc = mem.dev<uint8_t>((size_t)pw * h);
+    uint8_t* ddst = mem.dev<uint8_t>((size_t)pw * h);
+    HIP_TRY(mem.error());
     HIP_TRY(hipMemcpy2DAsync(dsrc, pw, img, stride, w, h, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(launch_undistort_remap(u->U, u->d_xy, u->d_frac, (const uint8_t*)dsrc, 1, 0, pw, (uint8_t*)ddst, 0, pw,
-                                   ctx->stream));
+    HIP_TRY(launch_undistort_remap(u->U, u->d_xy, u->d_frac, dsrc, 1, 0, pw, ddst, 0, pw, ctx->stream));
     HIP_TRY(hipMemcpy2DAsync(out, out_stride, ddst, pw, w, h, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return DVO_OK;

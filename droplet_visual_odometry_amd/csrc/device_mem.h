@@ -1,0 +1,233 @@
+// Host-side ownership of the library's device memory (api.cpp): DeviceAllocs frees what it
+// allocated, PairSets owns a stream's per-pair arrays and describes them once.  Host code only.
+#pragma once
+
+#include <cstring>
+#include <utility>
+#include <vector>
+
+#include "dvo_internal.h"
+
+namespace dvo {
+
+// Device allocations that are freed together.  alloc() asks hipMalloc for exactly the bytes it
+// is given: padding is the caller's decision.
+class DeviceAllocs {
+  public:
+    DeviceAllocs() = default;
+    DeviceAllocs(DeviceAllocs&& o) noexcept : ptrs_(std::move(o.ptrs_)) { o.ptrs_.clear(); }  // so: no copies
+    DeviceAllocs& operator=(DeviceAllocs&& o) noexcept {
+        if (this != &o) {
+            release();
+            ptrs_ = std::move(o.ptrs_);
+            o.ptrs_.clear();
+        }
+        return *this;
+    }
+    ~DeviceAllocs() { release(); }
+
+    template <class T>
+    hipError_t alloc(T** p, size_t bytes) {
+        ptrs_.reserve(ptrs_.size() + 1);  // so that nothing can throw between hipMalloc and the record
+        void* q = nullptr;
+        const hipError_t e = hipMalloc(&q, bytes);
+        if (e != hipSuccess) return e;
+        ptrs_.push_back(q);
+        *p = static_cast<T*>(q);
+        return hipSuccess;
+    }
+    void release() {
+        for (void* q : ptrs_) (void)hipFree(q);
+        ptrs_.clear();
+    }
+    bool empty() const { return ptrs_.empty(); }
+
+  private:
+    std::vector<void*> ptrs_;
+};
+
+// The per-pair arrays of a stream's pair sets: of all sets (pairs [0, nsets F)), or one set's view.
+// g's configuration scalars and its round-local fprec / dk_ctl / dk_list belong to the stream and
+// are the same in every view; g.pts_f and g.m_arr alias pts and nmatch.
+struct PairArrays {
+    GeomArgs g{};
+    float* pts = nullptr;       // [pairs][kp_cap][4] (x1, y1, x2, y2) KeyPoint_convert pixel coords
+    int32_t* nmatch = nullptr;  // [pairs]
+    PairHeader* hdr = nullptr;  // [pairs]
+};
+
+// The per-pair geometry, one copy per pair set.  A stream starts with one set: the drained calls
+// (dvo_stream_process, _process_pairs, _pair) run a batch's rounds back to back in it.  The first
+// dvo_stream_submit / _submit_pairs grows it to kRansacRounds sets (the pipeline depth); no set is
+// occupied then, since every drained call retires what it started.
+// At 1280x720, N 2000, maxIters 1000 a set costs about 0.9 MB per pair (models 720 KB of it).
+struct PairSets {
+    PairArrays all;  // null pointers while nsets == 0
+    int nsets = 0;   // sets allocated (0: none)
+    int F = 0, cap = 0;
+    size_t hc = 0;
+    hipStream_t stream = nullptr;  // the stream whose kernels use the arrays (ensure waits for it)
+    DeviceAllocs mem;
+
+    // The one description of the arrays: f(pointer, elements per pair, whole-launch) per array, in
+    // allocation order.  A whole-launch array has sets F + 1 elements and is not offset in a view.
+    template <class Fn>
+    static void rows(PairArrays& a, size_t cap, size_t hc, Fn&& f) {
+        GeomArgs& g = a.g;
+        f(a.nmatch, 1, false);
+        f(a.pts, cap * 4, false);
+        f(g.npts, cap * 4, false);
+        f(g.models, hc * 90, false);
+        f(g.nmod, hc, false);
+        f(g.cnt, hc * 10, false);
+        f(g.subsets, hc * 5, false);
+        f(g.rs, 1, false);
+        f(a.hdr, 1, false);
+        f(g.dk_off, 1, true);
+        f(g.a_off, 1, true);
+        f(g.s_off, 1, true);
+        f(g.E, 90, false);
+        f(g.info, 4, false);
+        f(g.Rt, 12, false);
+        f(g.good, 1, false);
+        f(g.pose_P, 72, false);
+        f(g.pose_cnt, 5, false);
+    }
+
+    void release() {
+        mem.release();
+        rows(all, 0, 0, [](auto*& p, size_t, bool) { p = nullptr; });
+        all.g.pts_f = nullptr;
+        all.g.m_arr = nullptr;
+        nsets = 0;
+    }
+
+    // At least `want` sets of F pairs (kp_cap cap, hc hypotheses per pair).  Growing waits for the
+    // stream, frees the old sets, then allocates the new ones (never both at once: batches are
+    // sized to fill the card), each array n * sizeof(T) + 256 bytes.  On failure no set is left:
+    // nsets == 0 and every pointer is null, and a later ensure() starts afresh.
+    hipError_t ensure(int want, int F_, int cap_, size_t hc_) {
+        if (nsets >= want) return hipSuccess;
+        hipError_t e = hipSuccess;
+        if (!mem.empty() && (e = hipStreamSynchronize(stream)) != hipSuccess) return e;
+        release();
+        F = F_;
+        cap = cap_;
+        hc = hc_;
+        const size_t SF = (size_t)want * F;
+        rows(all, cap, hc, [&](auto*& p, size_t per_pair, bool whole) {
+            if (e == hipSuccess) e = mem.alloc(&p, (whole ? SF + 1 : SF * per_pair) * sizeof(*p) + 256);
+        });
+        if (e != hipSuccess) {
+            release();
+            return e;
+        }
+        all.g.pts_f = all.pts;
+        all.g.m_arr = all.nmatch;
+        nsets = want;
+        return hipSuccess;
+    }
+
+    // Set k's view: pairs [k F, (k + 1) F) of every per-set array.
+    PairArrays view(int k) const {
+        PairArrays v = all;
+        if (k > 0)
+            rows(v, cap, hc, [&](auto*& p, size_t per_pair, bool whole) {
+                if (!whole) p += (size_t)k * F * per_pair;
+            });
+        v.g.pts_f = v.pts;
+        v.g.m_arr = v.nmatch;
+        return v;
+    }
+};
+
+// Grow-only buffers of a context, device (hipMalloc) or pinned host (hipHostMalloc) memory: slot k
+// holds at least what the largest k-th request so far asked for (4096 bytes at least, 25 % spare
+// when it grows).
+class Slots {
+  public:
+    explicit Slots(bool pinned) : pinned_(pinned) {}
+    Slots(const Slots&) = delete;
+    Slots& operator=(const Slots&) = delete;
+    ~Slots() { release(); }
+
+    hipError_t get(size_t k, size_t bytes, void** out) {
+        if (slots_.size() <= k) slots_.resize(k + 1);
+        Slot& e = slots_[k];
+        if (!e.p || e.cap < bytes) {  // an empty request still gets a buffer: null means failure
+            hipError_t err = e.p ? free_(e.p) : hipSuccess;
+            e = Slot{};
+            if (err != hipSuccess) return err;
+            const size_t nb = bytes < 4096 ? 4096 : bytes + bytes / 4;
+            err = pinned_ ? hipHostMalloc(&e.p, nb, hipHostMallocDefault) : hipMalloc(&e.p, nb);
+            if (err != hipSuccess) return err;
+            e.cap = nb;
+        }
+        *out = e.p;
+        return hipSuccess;
+    }
+    void release() {
+        for (Slot& e : slots_)
+            if (e.p) (void)free_(e.p);
+        slots_.clear();
+    }
+
+  private:
+    struct Slot {
+        void* p = nullptr;
+        size_t cap = 0;
+    };
+    hipError_t free_(void* p) const { return pinned_ ? hipHostFree(p) : hipFree(p); }
+    const bool pinned_;
+    std::vector<Slot> slots_;
+};
+
+struct CallSlots {
+    Slots dev{false}, pin{true};
+};
+
+// The memory of one synchronous per-call entry point: its k-th device request is the context's
+// k-th device slot, its k-th pinned request the k-th pinned slot.  Entry points share the slots
+// because each synchronises before it returns, so a call must not keep these pointers across a
+// call into another entry point that makes its own CallMem.  A request that fails returns null and
+// error() keeps the first failure: take every buffer, then check once.
+// Host traffic goes through the pinned buffers: inputs are packed there and sent with asynchronous
+// copies on the call's stream, outputs come back the same way, and the caller synchronises once
+// (a pageable hipMemcpy is a blocking staged copy each: ~10-20 us apiece).
+class CallMem {
+  public:
+    CallMem(CallSlots& slots, hipStream_t s) : slots_(slots), s_(s) {}
+
+    template <class T>
+    T* dev(size_t n) { return static_cast<T*>(take(slots_.dev, ndev_, n * sizeof(T))); }
+    uint8_t* host(size_t bytes) { return static_cast<uint8_t*>(take(slots_.pin, npin_, bytes)); }
+    hipError_t error() const { return err_; }
+
+    hipError_t send(void* dev, const uint8_t* h, size_t n) {  // host -> device of pinned bytes
+        return n ? hipMemcpyAsync(dev, h, n, hipMemcpyHostToDevice, s_) : hipSuccess;
+    }
+    hipError_t put(void* dev, const void* src, size_t n) {
+        uint8_t* h = host(n);
+        if (!h) return err_;
+        if (n) std::memcpy(h, src, n);
+        return send(dev, h, n);
+    }
+    hipError_t get(const void* dev, size_t n, uint8_t** h) {  // device -> host, valid after synchronising
+        if (!(*h = host(n))) return err_;
+        return n ? hipMemcpyAsync(*h, dev, n, hipMemcpyDeviceToHost, s_) : hipSuccess;
+    }
+
+  private:
+    void* take(Slots& sl, size_t& k, size_t bytes) {
+        void* p = nullptr;
+        const hipError_t e = sl.get(k++, bytes, &p);
+        if (err_ == hipSuccess) err_ = e;
+        return p;
+    }
+    CallSlots& slots_;
+    hipStream_t s_;
+    size_t ndev_ = 0, npin_ = 0;
+    hipError_t err_ = hipSuccess;
+};
+
+}  // namespace dvo

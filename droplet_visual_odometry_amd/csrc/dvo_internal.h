@@ -143,29 +143,11 @@ struct Buffers {
     int32_t* mq;          // [F][kp_cap] match queryIdx (sorted by (dist, q))
     int32_t* mt;          // [F][kp_cap] match trainIdx
     float* md;            // [F][kp_cap] match distance
-    int32_t* nmatch;      // [sets F]
-    // per pair, one copy per pair set ([sets][F] pairs: a set holds one batch until it retires)
-    float* pts;           // [sets F][kp_cap][4] (x1, y1, x2, y2) KeyPoint_convert pixel coords
-    double* npts;         // [sets F][kp_cap][4] normalised coords for RANSAC / recoverPose
-    double* models;       // [sets F][hyp_cap][10][9]
-    int32_t* nmod;        // [sets F][hyp_cap]
-    int32_t* rcnt;        // [sets F][hyp_cap][10]
-    int32_t* subsets;     // [sets F][hyp_cap][5]
-    RansacState* rs;      // [sets F]
-    double* fprec;        // [round blocks][128][64] five-point records of one round (a_off)
-    int32_t* dk_off;      // [sets F + 1] round work list: hypotheses before each pair
-    int32_t* a_off;       // [sets F + 1] 64-hypothesis blocks before each pair (stage A / C, records)
-    int32_t* s_off;       // [sets F + 1] score blocks before each pair
-    PairHeader* hdr;      // [sets][F]
-    int32_t* dk_ctl;      // [2 + kDkMaxPasses]
-    int32_t* dk_list;     // [kDkMaxPasses - 1][F * hyp_cap] parked Durand-Kerner polynomials
     int32_t* status;      // [F] per-frame error flags
-    double* E;            // [sets F][90]
-    int32_t* info;        // [sets F][4] rows, inliers, iters, status
-    double* Rt;           // [sets F][12]
-    int32_t* good;        // [sets F]
-    double* pose_P;       // [sets F][72] recoverPose decompositions (4 P, R1, R2, t)
-    int32_t* pose_cnt;    // [sets F][5] decomposition valid flag, cheirality counts
+    // the match stage's outputs, in the pair set the batch fills (PairSets::view, device_mem.h)
+    int32_t* nmatch;      // [F]
+    float* pts;           // [F][kp_cap][4] (x1, y1, x2, y2) KeyPoint_convert pixel coords
+    PairHeader* hdr;      // [F]
 };
 
 
@@ -336,12 +318,12 @@ hipError_t launch_geometry(const StreamParams& P, const GeomArgs& g, dvo_pair_re
                            hipEvent_t* ev = nullptr, bool one_round = false);
 hipError_t launch_geometry_args(const GeomArgs& g, int pairs, int stages, hipStream_t s);
 // Stream batches (api.cpp dvo_stream_submit): the per-set pieces.  g_all spans every set (pairs
-// [0, nsets F)); g_set is one set's view (geom_set).
+// [0, nsets F)); g_set is one set's view (PairSets::view).
 hipError_t launch_pair_header(const StreamParams& P, PairHeader* hdr, hipStream_t s);
 hipError_t launch_ransac_round(const GeomArgs& g_all, const RoundSpec& spec, hipStream_t s);
 hipError_t launch_retire(const GeomArgs& g_set, int pairs, const PairHeader* hdr, dvo_pair_record* records,
                          hipStream_t s);
-// five-point record blocks a merged round can need (sizes Buffers::fprec, dk_list)
+// five-point record blocks a merged round can need (sizes the stream's GeomArgs::fprec, dk_list)
 int64_t round_blocks_bound(int F, int hyp_cap);
 int64_t round_items_bound(int F, int hyp_cap);
 // Undistortion (undistort.hip): camera K, distortion k1 k2 p1 p2 k3 k4 k5 k6 s1..s4.

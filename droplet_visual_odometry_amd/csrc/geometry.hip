@@ -1969,7 +1969,7 @@ static RoundWork round_work(const RoundSpec& spec, int cap, int sh) {
     return w;
 }
 
-// A stream's round of the largest total work: one set at each round (Buffers::fprec, dk_list).
+// A stream's round of the largest total work: one set at each round (the stream's GeomArgs::fprec, dk_list).
 static RoundSpec full_spec(int F) {
     RoundSpec sp{};
     sp.nsets = kRansacRounds;

@@ -253,7 +253,10 @@ int dvo_stream_process_pairs(dvo_stream* s, const uint8_t* d_frames, int n_pairs
  * held once per pair set, about 0.9 MB per pair at 1280x720, N 2000, maxIters 1000
  * (the models, max_iters x 720 B, dominate).  A stream is created with one set; its
  * first submit grows it to dvo_pipeline_depth() sets (synchronising the stream once),
- * so streams that only process / pair never pay for the pipeline. */
+ * so streams that only process / pair never pay for the pipeline.  If that grow runs out
+ * of device memory the submit returns DVO_EHIP and the stream holds no pair set; it stays
+ * usable: the next process / pair call allocates one set again, the next submit retries
+ * the grow. */
 int dvo_pipeline_depth(void);
 int dvo_stream_submit(dvo_stream* s, const uint8_t* d_frames, int n_frames, int64_t frame_stride, int stride,
                       dvo_pair_record* d_records);

@@ -130,6 +130,57 @@ def test_process_drains_pending_submits(gpu_ctx):
     fs.close()
 
 
+def test_submit_after_process_grows_the_sets(gpu_ctx):
+    """A stream that has already run a drained batch in its one pair set, then pipelines: the first
+    submit frees that set and allocates pipeline_depth() of them.  Records, poses and the last
+    batch's matches must equal a stream that only ever processed."""
+    import torch
+    from droplet_visual_odometry_amd.stream import FrameStream
+    from droplet_visual_odometry_amd.synth import MARKER_LEN
+    W, H, m = 640, 480, 5
+    starts = (0, 4, 8, 12)
+    frames, corners, K = _stream(W, H, 17)
+    dev = torch.from_numpy(frames).cuda()
+    dc = torch.from_numpy(corners).cuda()
+    a = FrameStream(W, H, K, nfeatures=500, max_frames=m, ctx=gpu_ctx)
+    b = FrameStream(W, H, K, nfeatures=500, max_frames=m, ctx=gpu_ctx)
+    a.reset_pose()
+    b.reset_pose()
+
+    def processed(fs, s0):
+        r = fs.process(dev[s0:s0 + m])
+        Tr, Ta = fs.pose_tail(dc[s0:s0 + m - 1], dc[s0 + 1:s0 + m], MARKER_LEN)
+        fs.sync()
+        return FrameStream.records_numpy(r, m - 1), Tr.cpu().numpy(), Ta.cpu().numpy()
+
+    want = [processed(a, s0) for s0 in starts]
+    want_matches = a.matches(0)
+    got = [processed(b, starts[0])]
+    recs = [b.new_records(m - 1) for _ in starts[1:]]
+    torch.cuda.synchronize()
+    retired = []
+    for s0, r in zip(starts[1:], recs):
+        retired += b.submit(dev[s0:s0 + m], r, wait_torch=False)
+    got_matches = b.matches(0)
+    retired += b.drain()
+    assert [(r.data_ptr(), p) for r, p in retired] == [(r.data_ptr(), m - 1) for r in recs]
+    tails = []
+    for s0, (rec, pairs) in zip(starts[1:], retired):
+        Tr = torch.empty((pairs, 4, 4), dtype=torch.float64, device=dev.device)
+        Ta = torch.empty_like(Tr)
+        b.pose_tail_batch(rec, pairs, dc[s0:s0 + pairs], dc[s0 + 1:s0 + pairs + 1], MARKER_LEN, Tr, Ta)
+        tails.append((Tr, Ta))
+    b.sync()
+    got += [(FrameStream.records_numpy(r, m - 1), Tr.cpu().numpy(), Ta.cpu().numpy()) for r, (Tr, Ta) in zip(recs, tails)]
+    for i, ((gr, gTr, gTa), (wr, wTr, wTa)) in enumerate(zip(got, want)):
+        assert [k for k in gr.dtype.names if not np.array_equal(gr[k], wr[k])] == [], f"batch {i}"
+        assert gTr.tobytes() == wTr.tobytes() and gTa.tobytes() == wTa.tobytes(), f"batch {i} poses"
+    assert len(want_matches) > 0
+    assert got_matches.tobytes() == want_matches.tobytes()
+    a.close()
+    b.close()
+
+
 def test_submit_pairs_equals_process_pairs(gpu_ctx):
     import torch
     from droplet_visual_odometry_amd.stream import FrameStream
