@@ -129,6 +129,12 @@ _SIGNATURES = {
     "dvo_undistort_image": ([_vp, _vp, _c, _vp, _c], _c),
     "dvo_undistort_get_map": ([_vp, _vp, _vp], _c),
     "dvo_stream_process_undistorted": ([_vp, _vp, _vp, _c, _i64, _c, _vp], _c),
+    "dvo_bgr2gray": ([_vp, _vp, _c, _i64, _c, _c, _c, _c, _vp, _i64, _c, _vp], _c),
+    "dvo_bgr2gray_image": ([_vp, _vp, _c, _c, _c, _c, _vp, _c], _c),
+    "dvo_undistort_apply_bgr": ([_vp, _vp, _c, _i64, _c, _c, _vp, _i64, _c, _vp], _c),
+    "dvo_undistort_image_bgr": ([_vp, _vp, _c, _c, _vp, _c], _c),
+    "dvo_stream_process_bgr": ([_vp, _vp, _vp, _c, _i64, _c, _c, _vp], _c),
+    "dvo_stream_submit_bgr": ([_vp, _vp, _vp, _c, _i64, _c, _c, _vp], _c),
     "dvo_stream_share_pose": ([_vp, _vp], _c),
     "dvo_stream_pose_tail": ([_vp, _vp, _vp, _c, _d, _vp, _vp], _c),
     "dvo_pose_tail_records": ([_vp, _vp, _c, _vp, _vp, _vp, _c, _d, _vp, _vp, _vp, _vp], _c),

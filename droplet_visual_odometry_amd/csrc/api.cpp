@@ -2087,3 +2087,130 @@ int dvo_stream_process_undistorted(dvo_stream* s, dvo_undistort* u, const uint8_
                                    pw, s->hs));
     return run_stream(s, s->d_frames, n_frames, fs, pw, d_records, false);
 }
+
+// ---------------------------------------------------------------------------
+// Colour frames: cv.cvtColor(image_np, COLOR_BGR2GRAY) (v3:132), alone and fused
+// into the undistortion that follows it (v3:133).  Kernels in color.hip.
+// ---------------------------------------------------------------------------
+namespace {
+
+bool channels_ok(int channels) { return channels == 3 || channels == 4; }
+
+// the colour batch of a stream call, then the stream's size against the undistorter's
+int check_stream_bgr(dvo_stream* s, const dvo_undistort* u, const uint8_t* d_frames, int n_frames, int n_min,
+                     int stride, int channels, const dvo_pair_record* d_records) {
+    dvo_ctx* ctx = s->ctx;
+    if (!channels_ok(channels)) return fail(ctx, DVO_EINVAL, "channels must be 3 or 4");
+    if (u && (u->U.w != s->cfg.width || u->U.h != s->cfg.height))
+        return fail(ctx, DVO_EINVAL, "undistort size != stream size");
+    if (n_frames < n_min || n_frames > s->cfg.max_frames) return fail(ctx, DVO_EINVAL, "n_frames out of range");
+    if (!d_frames || (int64_t)stride < (int64_t)s->cfg.width * channels)
+        return fail(ctx, DVO_EINVAL, "bad frame buffer (null, or rows shorter than width * channels)");
+    if (n_frames > 1 && !d_records) return fail(ctx, DVO_EINVAL, "null records");
+    return DVO_OK;
+}
+
+// colour frames -> (undistorted) gray in the stream's slab on its HIP stream, then the batch
+int run_stream_bgr(dvo_stream* s, dvo_undistort* u, const uint8_t* d_frames, int n_frames, int64_t frame_stride,
+                   int stride, int channels, dvo_pair_record* d_records, bool drain) {
+    dvo_ctx* ctx = s->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int pw = frame_pitch(s);
+    const int64_t fs = (int64_t)pw * s->cfg.height;
+    if (u)
+        HIP_TRY(launch_undistort_remap_bgr(u->U, u->d_xy, u->d_frac, kGray14, d_frames, n_frames, frame_stride, stride,
+                                           channels, s->d_frames, fs, pw, s->hs));
+    else
+        HIP_TRY(launch_bgr2gray(kGray14, d_frames, n_frames, frame_stride, stride, channels, s->cfg.width,
+                                s->cfg.height, s->d_frames, fs, pw, s->hs));
+    return run_stream(s, s->d_frames, n_frames, fs, pw, d_records, false, 1, drain);
+}
+
+}  // namespace
+
+int dvo_bgr2gray(dvo_ctx* ctx, const uint8_t* d_src, int n, int64_t src_frame_stride, int src_pitch, int channels,
+                 int w, int h, uint8_t* d_dst, int64_t dst_frame_stride, int dst_pitch, void* hip_stream) {
+    if (!ctx) return DVO_EINVAL;
+    if (!channels_ok(channels)) return fail(ctx, DVO_EINVAL, "channels must be 3 or 4");
+    if (w < 1 || h < 1 || w >= 32768 || h >= 32768) return fail(ctx, DVO_EINVAL, "image size out of range");
+    if (n < 0 || (n > 0 && (!d_src || !d_dst))) return fail(ctx, DVO_EINVAL, "bad frame buffers");
+    if (src_pitch < w * channels || dst_pitch < w)
+        return fail(ctx, DVO_EINVAL, "bad pitches (source rows hold width * channels bytes, destination rows width)");
+    if (n == 0) return DVO_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(launch_bgr2gray(kGray14, d_src, n, src_frame_stride, src_pitch, channels, w, h, d_dst, dst_frame_stride,
+                            dst_pitch, hip_stream ? (hipStream_t)hip_stream : ctx->stream));
+    return DVO_OK;
+}
+
+int dvo_bgr2gray_image(dvo_ctx* ctx, const uint8_t* img, int w, int h, int stride, int channels, uint8_t* out,
+                       int out_stride) {
+    if (!ctx || !img || !out) return DVO_EINVAL;
+    if (!channels_ok(channels)) return fail(ctx, DVO_EINVAL, "channels must be 3 or 4");
+    if (w < 1 || h < 1 || w >= 32768 || h >= 32768) return fail(ctx, DVO_EINVAL, "image size out of range");
+    if (stride < w * channels || out_stride < w) return fail(ctx, DVO_EINVAL, "bad strides");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int pw = (w + 15) & ~15, ps = (w * channels + 15) & ~15;
+    CallMem mem(ctx->call, ctx->stream);
+    uint8_t* dsrc = mem.dev<uint8_t>((size_t)ps * h);
+    uint8_t* ddst = mem.dev<uint8_t>((size_t)pw * h);
+    HIP_TRY(mem.error());
+    HIP_TRY(hipMemcpy2DAsync(dsrc, ps, img, stride, (size_t)w * channels, h, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(launch_bgr2gray(kGray14, dsrc, 1, 0, ps, channels, w, h, ddst, 0, pw, ctx->stream));
+    HIP_TRY(hipMemcpy2DAsync(out, out_stride, ddst, pw, w, h, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return DVO_OK;
+}
+
+int dvo_undistort_apply_bgr(dvo_undistort* u, const uint8_t* d_src, int n, int64_t src_frame_stride, int src_pitch,
+                            int channels, uint8_t* d_dst, int64_t dst_frame_stride, int dst_pitch, void* hip_stream) {
+    if (!u) return DVO_EINVAL;
+    dvo_ctx* ctx = u->ctx;
+    if (!channels_ok(channels)) return fail(ctx, DVO_EINVAL, "channels must be 3 or 4");
+    if (n < 0 || (n > 0 && (!d_src || !d_dst))) return fail(ctx, DVO_EINVAL, "bad frame buffers");
+    if (src_pitch < u->U.w * channels || dst_pitch < u->U.w)
+        return fail(ctx, DVO_EINVAL, "bad pitches (source rows hold width * channels bytes, destination rows width)");
+    if (n == 0) return DVO_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(launch_undistort_remap_bgr(u->U, u->d_xy, u->d_frac, kGray14, d_src, n, src_frame_stride, src_pitch,
+                                       channels, d_dst, dst_frame_stride, dst_pitch,
+                                       hip_stream ? (hipStream_t)hip_stream : ctx->stream));
+    return DVO_OK;
+}
+
+int dvo_undistort_image_bgr(dvo_undistort* u, const uint8_t* img, int stride, int channels, uint8_t* out,
+                            int out_stride) {
+    if (!u || !img || !out) return DVO_EINVAL;
+    dvo_ctx* ctx = u->ctx;
+    const int w = u->U.w, h = u->U.h;
+    if (!channels_ok(channels)) return fail(ctx, DVO_EINVAL, "channels must be 3 or 4");
+    if (stride < w * channels || out_stride < w) return fail(ctx, DVO_EINVAL, "bad strides");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int pw = (w + 15) & ~15, ps = (w * channels + 15) & ~15;
+    CallMem mem(ctx->call, ctx->stream);
+    uint8_t* dsrc = mem.dev<uint8_t>((size_t)ps * h);
+    uint8_t* ddst = mem.dev<uint8_t>((size_t)pw * h);
+    HIP_TRY(mem.error());
+    HIP_TRY(hipMemcpy2DAsync(dsrc, ps, img, stride, (size_t)w * channels, h, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(launch_undistort_remap_bgr(u->U, u->d_xy, u->d_frac, kGray14, dsrc, 1, 0, ps, channels, ddst, 0, pw,
+                                       ctx->stream));
+    HIP_TRY(hipMemcpy2DAsync(out, out_stride, ddst, pw, w, h, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return DVO_OK;
+}
+
+int dvo_stream_process_bgr(dvo_stream* s, dvo_undistort* u, const uint8_t* d_frames, int n_frames,
+                           int64_t frame_stride, int stride, int channels, dvo_pair_record* d_records) {
+    if (!s) return DVO_EINVAL;
+    int rc = check_stream_bgr(s, u, d_frames, n_frames, 1, stride, channels, d_records);
+    if (rc) return rc;
+    return run_stream_bgr(s, u, d_frames, n_frames, frame_stride, stride, channels, d_records, true);
+}
+
+int dvo_stream_submit_bgr(dvo_stream* s, dvo_undistort* u, const uint8_t* d_frames, int n_frames,
+                          int64_t frame_stride, int stride, int channels, dvo_pair_record* d_records) {
+    if (!s) return DVO_EINVAL;
+    int rc = check_stream_bgr(s, u, d_frames, n_frames, 2, stride, channels, d_records);
+    if (rc) return rc;
+    return run_stream_bgr(s, u, d_frames, n_frames, frame_stride, stride, channels, d_records, false);
+}

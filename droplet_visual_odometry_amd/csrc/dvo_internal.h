@@ -337,6 +337,22 @@ hipError_t launch_undistort_map(const UndistortGeom& U, const double* d_ir, int1
 hipError_t launch_undistort_remap(const UndistortGeom& U, const int16_t* d_xy, const uint16_t* d_frac,
                                   const uint8_t* d_src, int n, int64_t src_fstride, int src_pitch, uint8_t* d_dst,
                                   int64_t dst_fstride, int dst_pitch, hipStream_t s);
+// Colour input (color.hip): gray = (B cb + G cg + R cr + (1 << (shift - 1))) >> shift, the pixel's
+// bytes in B, G, R order (a fourth byte is ignored).  The kernels take the set as an argument;
+// kGray14 is cv.cvtColor(COLOR_BGR2GRAY)'s, the only one the ABI exposes.
+struct GrayCoef {
+    int cb, cg, cr, shift;
+};
+constexpr GrayCoef kGray14{1868, 9617, 4899, 14};
+// n frames of w x h pixels of `channels` (3 or 4) bytes -> n mono8 frames; src and dst must not overlap
+hipError_t launch_bgr2gray(const GrayCoef& c, const uint8_t* d_src, int n, int64_t src_fstride, int src_pitch,
+                           int channels, int w, int h, uint8_t* d_dst, int64_t dst_fstride, int dst_pitch,
+                           hipStream_t s);
+// launch_undistort_remap of the gray image of colour frames, without storing that image
+hipError_t launch_undistort_remap_bgr(const UndistortGeom& U, const int16_t* d_xy, const uint16_t* d_frac,
+                                      const GrayCoef& c, const uint8_t* d_src, int n, int64_t src_fstride,
+                                      int src_pitch, int channels, uint8_t* d_dst, int64_t dst_fstride,
+                                      int dst_pitch, hipStream_t s);
 
 // carry: device [12 P_prev | 16 T_abs_prev]; updated in place.
 // rec: the pairs' records (R, t, status, n_models are read).

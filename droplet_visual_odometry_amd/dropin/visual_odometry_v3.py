@@ -188,6 +188,10 @@ class VisualOdometry:
             image_np = raw.reshape((image_message.height, image_message.width, -1))
         if image_np is None:
             raise cv.error("(-215:Assertion failed) !_src.empty() in function 'cvtColor'")
+        if image_np.ndim == 3 and image_np.shape[2] in (3, 4) and image_np.dtype == np.uint8:
+            # cvtColor + undistort (v3:132-133) in one GPU call: the colour image goes up, gray comes back
+            return cv._undistort_bgr2gray(image_np, self.intrinsic_coefficient_matrix,
+                                          self.distortion_coefficient_matrix, new_camera_matrix)
         grey_image = cv.cvtColor(src=image_np, code=cv.COLOR_BGR2GRAY)
         return self.undistort_image(grey_image, new_camera_matrix)
 

@@ -13,6 +13,8 @@ mirrors its argument meaning, output layout and failure points:
   triangulate_points   cv::triangulatePoints              visual_odometry_v3.py:265
   get_optimal_new_camera_matrix, Undistorter
                        cv::getOptimalNewCameraMatrix, cv::undistort  v3:117, v3:120
+  bgr2gray, bgr2gray_device
+                       cv::cvtColor(COLOR_BGR2GRAY)       visual_odometry_v3.py:132
 """
 from __future__ import annotations
 
@@ -284,9 +286,86 @@ def get_optimal_new_camera_matrix(K, dist, size, alpha=1.0, new_size=None) -> np
     return out.reshape(3, 3)
 
 
+def _colour_image(img) -> np.ndarray:
+    """A host H x W x C colour image (uint8, C = 3 or 4: B, G, R first), rows contiguous."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] not in (3, 4) or img.shape[0] < 1 or img.shape[1] < 1:
+        raise ValueError(f"expected a uint8 [H, W, 3 or 4] colour image, got {img.dtype} {img.shape}")
+    return np.ascontiguousarray(img)
+
+
+def check_colour_frames(src, what="frames", size=None, owner=""):
+    """(n, H, W, C) of a colour batch: a uint8 [n, H, W, C] torch device tensor, C = 3 or 4,
+    with the channels of a pixel and the pixels of a row adjacent (stride(3) == 1,
+    stride(2) == C, stride(1) >= W * C), of `owner`'s size = (W, H) if given.
+    ValueError otherwise, before any library call."""
+    import torch
+    if not isinstance(src, torch.Tensor) or src.dtype != torch.uint8 or src.dim() != 4:
+        raise ValueError(f"{what} must be a uint8 [n, H, W, C] device tensor")
+    n, h, w, c = src.shape
+    if c not in (3, 4):
+        raise ValueError(f"{what} must have 3 or 4 channels (B, G, R first), got {c}")
+    if src.stride(3) != 1 or src.stride(2) != c or src.stride(1) < w * c:
+        raise ValueError(f"{what} must keep a pixel's channels and a row's pixels adjacent "
+                         "(stride(3) == 1, stride(2) == C, stride(1) >= W * C)")
+    if size is not None and (w, h) != tuple(size):
+        raise ValueError(f"frame size {w}x{h} != {owner} size {size[0]}x{size[1]}")
+    if not src.is_cuda:
+        raise ValueError(f"{what} must be a device tensor")
+    return n, h, w, c
+
+
+def _check_gray_frames(dst, n, h, w, device):
+    import torch
+    if not isinstance(dst, torch.Tensor) or dst.dtype != torch.uint8 or dst.dim() != 3 \
+            or tuple(dst.shape) != (n, h, w):
+        raise ValueError(f"dst must be a uint8 [{n}, {h}, {w}] device tensor")
+    if dst.stride(2) != 1 or dst.stride(1) < w:
+        raise ValueError("dst rows must be contiguous")
+    if dst.device != device:
+        raise ValueError("dst must be on the frames' device")
+
+
+def _on_stream(device, hip_stream, call):
+    if hip_stream:
+        call(hip_stream)
+    else:
+        from .stream import ordered_side_stream
+        with ordered_side_stream(device) as st:
+            call(st)
+
+
+def bgr2gray(img: np.ndarray, ctx=None) -> np.ndarray:
+    """cv.cvtColor(img, COLOR_BGR2GRAY) (v3:132) of a host H x W x C image (C = 3 or 4,
+    B, G, R first; a fourth channel is ignored) on the GPU: H x W mono8."""
+    img = _colour_image(img)
+    h, w, ch = img.shape
+    c = _ctx(ctx)
+    out = np.empty((h, w), np.uint8)
+    c.check(c.lib.dvo_bgr2gray_image(c.h, ptr(img), w, h, img.strides[0], ch, ptr(out), out.strides[0]))
+    return out
+
+
+def bgr2gray_device(src, dst, stream=None, ctx=None):
+    """cv.cvtColor(COLOR_BGR2GRAY) (v3:132) of n device frames: uint8 torch tensors
+    [n, H, W, C] -> [n, H, W] (which must not overlap), on `stream` (a non-NULL
+    hipStream_t handle), by default ordered with torch's current stream."""
+    n, h, w, ch = check_colour_frames(src, "src")
+    _check_gray_frames(dst, n, h, w, src.device)
+    c = ctx if ctx is not None else Context.default(src.device.index or 0)
+
+    def call(st):
+        c.check(c.lib.dvo_bgr2gray(c.h, src.data_ptr(), n, src.stride(0), src.stride(1), ch, w, h, dst.data_ptr(),
+                                   dst.stride(0), dst.stride(1), ctypes.c_void_p(st)))
+    _on_stream(src.device, stream, call)
+    return dst
+
+
 class Undistorter:
     """cv.undistort(img, K, dist, None, newK) (v3:120) with the remap table built
-    once on the device.  image(): host in/out; apply(): device frames."""
+    once on the device.  image(): host in/out; apply(): device frames.  Both take
+    colour input too (a trailing channel axis of 3 or 4: B, G, R first) and then
+    return the undistorted GRAY image, cvtColor + undistort (v3:132-133) in one kernel."""
 
     def __init__(self, K, dist, newK, width: int, height: int, ctx=None):
         self.ctx = _ctx(ctx)
@@ -298,7 +377,28 @@ class Undistorter:
                                                          ptr(d), len(d), ptr(nk), self.w, self.h, ctypes.byref(h)))
         self.h_ = h
 
+    def _image_bgr(self, img) -> np.ndarray:
+        img = _colour_image(img)
+        if img.shape[:2] != (self.h, self.w):
+            raise ValueError(f"image {img.shape[:2]} != undistorter size {(self.h, self.w)}")
+        out = np.empty((self.h, self.w), np.uint8)
+        self.ctx.check(self.ctx.lib.dvo_undistort_image_bgr(self.h_, ptr(img), img.strides[0], img.shape[2], ptr(out),
+                                                            out.strides[0]))
+        return out
+
+    def _apply_bgr(self, src, dst, hip_stream):
+        n, h, w, ch = check_colour_frames(src, "src", (self.w, self.h), "undistorter")
+        _check_gray_frames(dst, n, h, w, src.device)
+
+        def call(st):
+            self.ctx.check(self.ctx.lib.dvo_undistort_apply_bgr(self.h_, src.data_ptr(), n, src.stride(0), src.stride(1),
+                                                                ch, dst.data_ptr(), dst.stride(0), dst.stride(1),
+                                                                ctypes.c_void_p(st)))
+        _on_stream(src.device, hip_stream, call)
+
     def image(self, img: np.ndarray) -> np.ndarray:
+        if np.ndim(img) == 3:  # H x W x C colour: the undistorted gray image
+            return self._image_bgr(img)
         img = np.ascontiguousarray(img, np.uint8)
         if img.shape != (self.h, self.w):
             raise DVOError(-1, f"image {img.shape} != undistorter size {(self.h, self.w)}")
@@ -309,7 +409,10 @@ class Undistorter:
     def apply(self, src, dst, hip_stream=None):
         """Remap n device frames (uint8 torch tensors [n, H, W], rows contiguous)
         on `hip_stream` (a non-NULL hipStream_t handle), by default ordered
-        with torch's current stream."""
+        with torch's current stream.  Colour frames [n, H, W, C] (C = 3 or 4) are
+        converted and remapped in one kernel into the same [n, H, W] dst."""
+        if src.dim() == 4:
+            return self._apply_bgr(src, dst, hip_stream)
         n = src.shape[0]
 
         def call(st):

@@ -67,7 +67,11 @@ class FrameStream:
                 undistort=None) -> torch.Tensor:
         """Enqueue the batch on the stream's HIP stream (asynchronous).  With
         wait_torch the batch is ordered after work queued on torch's current
-        stream (the frames' producer); pass False for frames already resident."""
+        stream (the frames' producer); pass False for frames already resident.
+        Colour frames (uint8 [n, H, W, C], C = 3 or 4: B, G, R first) are converted
+        to gray, and undistorted if asked, on the way into the stream's slab."""
+        if frames.dim() == 4:
+            return self._process_bgr(frames, records, wait_torch, undistort)
         if frames.dtype != torch.uint8 or frames.dim() != 3 or not frames.is_cuda:
             raise ValueError("frames must be a uint8 [n, H, W] device tensor")
         n, h, w = frames.shape
@@ -140,12 +144,61 @@ class FrameStream:
             raise ValueError("frames must hold an even, non-zero number of frames (pairs 2p, 2p+1)")
         return n
 
-    def submit(self, frames: torch.Tensor, records: torch.Tensor, wait_torch: bool = True) -> list:
+    def _check_frames_bgr(self, frames, undistort):
+        from .ops import check_colour_frames
+        n, h, w, c = check_colour_frames(frames, "frames", (self.width, self.height), "stream")
+        if undistort is not None and (undistort.w, undistort.h) != (self.width, self.height):
+            raise ValueError(f"undistorter size {undistort.w}x{undistort.h} != stream {self.width}x{self.height}")
+        return n, c
+
+    def _process_bgr(self, frames, records, wait_torch, undistort):
+        """process() of colour frames (dvo_stream_process_bgr)."""
+        n, c = self._check_frames_bgr(frames, undistort)
+        if records is None:
+            records = self.new_records(n - 1)
+            wait_torch = True  # the zero-fill runs on torch's stream: order the library's writes after it
+        if wait_torch:
+            self._after_torch()
+        if n > 1:
+            self._pending[records.data_ptr()] = records
+        self.ctx.check(self.ctx.lib.dvo_stream_process_bgr(
+            self.h, undistort.h_ if undistort is not None else None, frames.data_ptr(), n, frames.stride(0),
+            frames.stride(1), c, records.data_ptr() if n > 1 else None))
+        self._take_retired()
+        self._last = (frames, records)
+        self._hold(frames, records)
+        return records
+
+    def _submit_bgr(self, frames, records, wait_torch, undistort):
+        """submit() of colour frames (dvo_stream_submit_bgr)."""
+        n, c = self._check_frames_bgr(frames, undistort)
+        if n < 2:
+            raise ValueError("a submitted batch needs >= 2 frames")
+        if records.numel() < (n - 1) * PAIR_RECORD_DTYPE.itemsize:
+            raise ValueError("records too small")
+        if wait_torch:
+            self._after_torch()
+        self.ctx.check(self.ctx.lib.dvo_stream_submit_bgr(
+            self.h, undistort.h_ if undistort is not None else None, frames.data_ptr(), n, frames.stride(0),
+            frames.stride(1), c, records.data_ptr()))
+        self._pending[records.data_ptr()] = records
+        self._hold(frames, records)
+        return self._take_retired()
+
+    def submit(self, frames: torch.Tensor, records: torch.Tensor, wait_torch: bool = True, undistort=None) -> list:
         """Pipelined batch (dvo_stream_submit): detection and matching of these
         frames, then one merged RANSAC round of the pending batches.  `records`
         (n - 1 records) is complete once the batch retires, pipeline_depth() - 1
         submits later or at drain(); it is kept referenced until then.  Returns
-        the batches this call retired, oldest first, as (records, pairs)."""
+        the batches this call retired, oldest first, as (records, pairs).
+        Colour frames (uint8 [n, H, W, C], C = 3 or 4) are converted to gray, and
+        remapped by `undistort` (ops.Undistorter) if given, into the stream's slab
+        first.  The library has no undistorting submit for mono8 frames: remap them
+        with Undistorter.apply and submit the result."""
+        if frames.dim() == 4:
+            return self._submit_bgr(frames, records, wait_torch, undistort)
+        if undistort is not None:
+            raise ValueError("submit(undistort=) takes colour frames; remap mono8 frames with Undistorter.apply first")
         n = self._check_frames(frames)
         if n < 2:
             raise ValueError("a submitted batch needs >= 2 frames")

@@ -186,6 +186,33 @@ int dvo_undistort_image(dvo_undistort* u, const uint8_t* img, int stride, uint8_
 /* Test hook: the device remap table (w*h*2 int16, w*h uint16). */
 int dvo_undistort_get_map(dvo_undistort* u, int16_t* xy, uint16_t* frac);
 
+/* Colour frames.  A colour image has `channels` = 3 or 4 bytes per pixel in B, G, R
+ * order (a fourth byte is ignored); its rows hold w * channels bytes, `src_pitch`
+ * (`stride`) bytes apart.  Gray is cv::cvtColor(COLOR_BGR2GRAY)'s 8-bit fixed point,
+ *   Y = (B 1868 + G 9617 + R 4899 + 8192) >> 14.
+ * Source and destination must not overlap.  Pitches need no alignment (4-byte
+ * aligned rows take the wide loads).  DVO_EINVAL: channels not 3 or 4, src_pitch <
+ * w * channels, dst_pitch < w, a null pointer with n > 0; n == 0 launches nothing. */
+/* Replaces cv::cvtColor(image_np, COLOR_BGR2GRAY) — visual_odometry_v3.py:132 — for n
+ * device frames (frame i at d_src + i * src_frame_stride -> d_dst + i * dst_frame_stride).
+ * Asynchronous on hip_stream; NULL = the context's stream. */
+int dvo_bgr2gray(dvo_ctx* ctx, const uint8_t* d_src, int n, int64_t src_frame_stride, int src_pitch, int channels,
+                 int w, int h, uint8_t* d_dst, int64_t dst_frame_stride, int dst_pitch, void* hip_stream);
+/* Replaces cv::cvtColor(image_np, COLOR_BGR2GRAY) — visual_odometry_v3.py:132.  Host
+ * image in, host image out (synchronous; the counterpart of dvo_undistort_image). */
+int dvo_bgr2gray_image(dvo_ctx* ctx, const uint8_t* img, int w, int h, int stride, int channels, uint8_t* out,
+                       int out_stride);
+/* Replaces cv::cvtColor followed by cv::undistort — visual_odometry_v3.py:132-133 — in
+ * one kernel: dvo_undistort_apply of the gray image of n colour device frames, byte for
+ * byte, without storing that image (each bilinear tap is converted on its own; a tap
+ * outside the source is gray 0 and is not read).  Frames are u's w x h. */
+int dvo_undistort_apply_bgr(dvo_undistort* u, const uint8_t* d_src, int n, int64_t src_frame_stride, int src_pitch,
+                            int channels, uint8_t* d_dst, int64_t dst_frame_stride, int dst_pitch, void* hip_stream);
+/* Replaces cv::cvtColor followed by cv::undistort — visual_odometry_v3.py:132-133.
+ * Host colour image in, host mono8 image out (synchronous; ros_img_msg_to_opencv_image). */
+int dvo_undistort_image_bgr(dvo_undistort* u, const uint8_t* img, int stride, int channels, uint8_t* out,
+                            int out_stride);
+
 /* ---------------------------------------------------------------------------
  * Batched frame stream: the whole per-pair path of visual_odometry_calculations
  * (v3:384-408: detect both frames, match, E/RANSAC, recoverPose) for n_frames
@@ -287,6 +314,28 @@ int dvo_stream_pair(dvo_stream* s, const uint8_t* prev_img, const uint8_t* cur_i
  * undistorts every frame before detection (v3:120, v3:135). */
 int dvo_stream_process_undistorted(dvo_stream* s, dvo_undistort* u, const uint8_t* d_frames, int n_frames,
                                    int64_t frame_stride, int stride, dvo_pair_record* d_records);
+/* dvo_stream_process / dvo_stream_submit on colour frames (channels = 3 or 4 bytes per
+ * pixel, B G R first; rows `stride` >= width * channels bytes apart), as the reference
+ * converts and undistorts every frame before detection — visual_odometry_v3.py:132-133
+ * (u given), v3:132 alone (u NULL: no undistortion).  The frames are converted
+ * (dvo_bgr2gray), or converted and remapped (dvo_undistort_apply_bgr), into the
+ * stream's own frame slab on the stream's HIP stream, outside the stage timers; the
+ * batch then runs on the slab exactly as after dvo_stream_process_undistorted, so
+ * records and features are those of dvo_stream_process / _submit on the gray frames.
+ * The caller's frames may be released once the conversion has run.
+ * dvo_stream_submit_bgr reuses the slab at every submit.  That is safe: a submit
+ * queues its batch's whole detection (pyramid to descriptors, the only readers of the
+ * frames) on the same HIP stream before it returns, so the next submit's conversion is
+ * ordered after it, and what a pair's record needs from its frames is kept with the
+ * pair set, not read from the frames when the batch retires.  dvo_stream_get_pyramid
+ * (blurred) after a submit reads the slab, i.e. the last submitted batch's frames.
+ * DVO_EINVAL: channels not 3 or 4, u's size != the stream's, n_frames outside
+ * 1..max_frames (submit: 2..max_frames), null frames, stride < width * channels,
+ * null records with n_frames > 1. */
+int dvo_stream_process_bgr(dvo_stream* s, dvo_undistort* u /* NULL: no undistortion */, const uint8_t* d_frames,
+                           int n_frames, int64_t frame_stride, int stride, int channels, dvo_pair_record* d_records);
+int dvo_stream_submit_bgr(dvo_stream* s, dvo_undistort* u /* NULL: no undistortion */, const uint8_t* d_frames,
+                          int n_frames, int64_t frame_stride, int stride, int channels, dvo_pair_record* d_records);
 /* HIP stream the batch runs on (hipStream_t as void*; each dvo_stream owns
  * one, so batches on different dvo_streams may overlap on the device). */
 void* dvo_stream_hip_stream(dvo_stream* s);
