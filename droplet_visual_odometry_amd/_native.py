@@ -30,6 +30,8 @@ DVO_EFEWPTS = -3
 DVO_EHIP = -4
 DVO_ECAP = -5
 DVO_ENOMODEL = -6
+DVO_EUNSUPPORTED = -7
+DVO_ECORRUPT = -8
 DVO_NSTAGES = 9
 STAGE_NAMES = ["pyramid", "blur", "fast", "select_harris", "describe", "match", "ransac", "recover_pose",
                "pose_tail"]
@@ -63,6 +65,15 @@ class StreamConfig(ctypes.Structure):
                 ("orb", OrbParams), ("K", ctypes.c_double * 9), ("prob", ctypes.c_double),
                 ("threshold", ctypes.c_double), ("max_iters", ctypes.c_int32), ("cross_check", ctypes.c_int32),
                 ("dist_thresh", ctypes.c_double)]
+
+
+class JpegLayout(ctypes.Structure):
+    """dvo_jpeg_layout: what dvo_jpeg_entropy_host produces for one image."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("components", ctypes.c_int32),
+                ("sampling", ctypes.c_int32), ("restart_interval", ctypes.c_int32), ("segments", ctypes.c_int32),
+                ("blocks_w", ctypes.c_int32 * 3), ("blocks_h", ctypes.c_int32 * 3),
+                ("coef_offset", ctypes.c_int64 * 3), ("coef_count", ctypes.c_int64),
+                ("quant", (ctypes.c_uint16 * 64) * 3)]
 
 
 # OpenCV semantics of the ORB path (include/dvo.h DVO_OPENCV_*): "4.x" (default) or "3.2"
@@ -135,6 +146,17 @@ _SIGNATURES = {
     "dvo_undistort_image_bgr": ([_vp, _vp, _c, _c, _vp, _c], _c),
     "dvo_stream_process_bgr": ([_vp, _vp, _vp, _c, _i64, _c, _c, _vp], _c),
     "dvo_stream_submit_bgr": ([_vp, _vp, _vp, _c, _i64, _c, _c, _vp], _c),
+    "dvo_jpeg_probe": ([_vp, _i64, _ip, _ip, _ip, _ip], _c),
+    "dvo_jpeg_entropy_host": ([_vp, _i64, _vp, _vp, _i64, _ip], _c),
+    "dvo_jpeg_create": ([_vp, _c, _c, _c, ctypes.POINTER(_vp)], _c),
+    "dvo_jpeg_destroy": ([_vp], None),
+    "dvo_jpeg_decode": ([_vp, _vp, _vp, _c, _c, _vp, _i64, _c, _c, _vp], _c),
+    "dvo_jpeg_status": ([_vp, _vp, _c], _c),
+    "dvo_jpeg_decode_image": ([_vp, _vp, _i64, _c, _vp, _c], _c),
+    "dvo_undistort_image_jpeg": ([_vp, _vp, _vp, _i64, _vp, _c], _c),
+    "dvo_stream_process_jpeg": ([_vp, _vp, _vp, _vp, _vp, _c, _vp], _c),
+    "dvo_stream_submit_jpeg": ([_vp, _vp, _vp, _vp, _vp, _c, _vp], _c),
+    "dvo_jpeg_get_coefficients": ([_vp, _c, _vp, _i64, ctypes.POINTER(_i64)], _c),
     "dvo_stream_share_pose": ([_vp, _vp], _c),
     "dvo_stream_pose_tail": ([_vp, _vp, _vp, _c, _d, _vp, _vp], _c),
     "dvo_pose_tail_records": ([_vp, _vp, _c, _vp, _vp, _vp, _c, _d, _vp, _vp, _vp, _vp], _c),

@@ -14,6 +14,7 @@
 
 #include "device_mem.h"
 #include "dvo_internal.h"
+#include "jpeg_entropy.h"
 
 using namespace dvo;
 
@@ -2213,4 +2214,389 @@ int dvo_stream_submit_bgr(dvo_stream* s, dvo_undistort* u, const uint8_t* d_fram
     int rc = check_stream_bgr(s, u, d_frames, n_frames, 2, stride, channels, d_records);
     if (rc) return rc;
     return run_stream_bgr(s, u, d_frames, n_frames, frame_stride, stride, channels, d_records, false);
+}
+
+// ---------------------------------------------------------------------------
+// JPEG frames: cv.imdecode (v3:127) of baseline JPEGs.  Parser in jpeg_parse.cpp, the entropy
+// decoder (host and device) in jpeg_entropy.h, kernels in jpeg.hip.
+// ---------------------------------------------------------------------------
+struct dvo_jpeg {
+    dvo_ctx* ctx = nullptr;
+    int max_w = 0, max_h = 0, group = 0;
+    size_t frame_elems = 0;  // coefficients (and plane bytes) of the largest frame: 3 components at 16-pixel MCUs
+    size_t coef_cap = 0;     // coefficients (and plane bytes) of a group
+    size_t stage_cap = 0;    // scan bytes of a group
+    size_t seg_cap = 0;      // segments of a group
+    int gray_pitch = 0;
+    DeviceAllocs mem;
+    PinnedAllocs pin;
+    // Pinned staging in two halves: the host fills one while the copies out of the other run.
+    // ev[k] follows the last copy out of half k.
+    uint8_t* h_bytes[2] = {nullptr, nullptr};
+    jpeg::FramePlan* h_plans[2] = {nullptr, nullptr};
+    jpeg::Segment* h_segs[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool ev_used[2] = {false, false};
+    int half = 0;
+    int16_t* h_coef = nullptr;  // host entropy: a group's coefficients 
+    hipEvent_t ev_coef = nullptr;
+    bool ev_coef_used = false;
+    int32_t* h_status = nullptr;  // [kMaxCall] the device statuses of the last call, after its copies ran
+    uint8_t* d_bytes = nullptr;
+    jpeg::FramePlan* d_plans = nullptr;
+    jpeg::Segment* d_segs = nullptr;
+    int16_t* d_coef = nullptr;
+    uint8_t* d_planes = nullptr;
+    uint8_t* d_gray = nullptr;  // a group of gray frames (decode -> undistort)
+    int32_t* d_status = nullptr;
+    std::vector<int> host_status;  // per frame of the last call: what the host found
+    std::vector<jpeg::Parsed> parsed;
+    std::vector<int64_t> last_base, last_count;  // the last group's frames in d_coef
+    hipStream_t last_stream = nullptr;
+    static constexpr int kMaxCall = 65536;
+
+    ~dvo_jpeg() {
+        for (hipEvent_t e : {ev[0], ev[1], ev_coef})
+            if (e) hipEventDestroy(e);
+    }
+};
+
+namespace {
+
+void fill_layout(const jpeg::Parsed& P, dvo_jpeg_layout* L) {
+    const jpeg::FramePlan& p = P.plan;
+    std::memset(L, 0, sizeof(*L));
+    L->width = p.w, L->height = p.h, L->components = p.ncomp, L->sampling = p.hs << 4 | p.vs;
+    L->restart_interval = p.restart, L->segments = (int)P.segs.size();
+    for (int c = 0; c < p.ncomp; ++c) {
+        L->blocks_w[c] = p.bw[c], L->blocks_h[c] = p.bh[c], L->coef_offset[c] = (int64_t)p.blk0[c] * 64;
+        std::memcpy(L->quant[c], p.qt[c], sizeof(L->quant[c]));
+    }
+    L->coef_count = (int64_t)p.nblk * 64;
+}
+
+// every segment of a parsed file into zeroed coefficients; kOk or kCorrupt
+int entropy_host(const jpeg::Parsed& P, const uint8_t* buf, int16_t* coef) {
+    int st = P.scan_status;
+    for (const jpeg::Segment& sg : P.segs)
+        if (jpeg::decode_segment(P.plan, buf + sg.offset, sg.length, sg.mcu0, sg.nmcu, coef)) st = jpeg::kCorrupt;
+    return st;
+}
+
+size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// n JPEGs -> n frames of out_channels bytes per pixel at d_dst, group after group on st; with u
+// (out_channels 1) each group is decoded into j->d_gray and remapped into d_dst.  need_w/need_h:
+// the size every frame must have (0: that of the first frame).
+int jpeg_decode_impl(dvo_jpeg* j, const uint8_t* const* bufs, const int64_t* lens, int n, int out_channels,
+                     uint8_t* d_dst, int64_t dst_fstride, int dst_pitch, int entropy, hipStream_t st, dvo_undistort* u,
+                     int need_w, int need_h) {
+    dvo_ctx* ctx = j->ctx;
+    if (n < 0 || n > dvo_jpeg::kMaxCall) return fail(ctx, DVO_EINVAL, "frame count out of range (0..65536)");
+    if (out_channels != 1 && out_channels != 3 && out_channels != 4)
+        return fail(ctx, DVO_EINVAL, "out_channels must be 1, 3 or 4");
+    if (entropy != DVO_JPEG_ENTROPY_HOST && entropy != DVO_JPEG_ENTROPY_DEVICE)
+        return fail(ctx, DVO_EINVAL, "entropy must be DVO_JPEG_ENTROPY_HOST or DVO_JPEG_ENTROPY_DEVICE");
+    if (n > 0 && (!bufs || !lens || !d_dst)) return fail(ctx, DVO_EINVAL, "null buffer");
+    j->host_status.assign((size_t)n, DVO_OK);
+    j->last_base.clear();
+    j->last_count.clear();
+    if (n == 0) return DVO_OK;
+    // every header first: nothing is launched for a batch with a frame that cannot be decoded
+    if ((int)j->parsed.size() < n) j->parsed.resize((size_t)n);
+    for (int f = 0; f < n; ++f) {
+        if (!bufs[f] || lens[f] < 0) return fail(ctx, DVO_EINVAL, "frame " + std::to_string(f) + ": null buffer");
+        jpeg::Parsed& P = j->parsed[(size_t)f];
+        const int rc = jpeg::parse(bufs[f], (size_t)lens[f], &P);
+        if (rc) return fail(ctx, rc, "frame " + std::to_string(f) + ": " + P.why);
+        if (f == 0 && !need_w) need_w = P.plan.w, need_h = P.plan.h;
+        if (P.plan.w != need_w || P.plan.h != need_h)
+            return fail(ctx, DVO_EINVAL, "frame " + std::to_string(f) + ": size " + std::to_string(P.plan.w) + "x" +
+                                             std::to_string(P.plan.h) + ", expected " + std::to_string(need_w) + "x" +
+                                             std::to_string(need_h));
+        if (P.plan.w > j->max_w || P.plan.h > j->max_h)
+            return fail(ctx, DVO_EINVAL, "frame " + std::to_string(f) + ": larger than the decoder's maximum");
+        if (align_up(P.scan_end - P.scan_begin, 16) > j->stage_cap)
+            return fail(ctx, DVO_ECAP, "frame " + std::to_string(f) + ": scan larger than the decoder's staging buffer");
+        j->host_status[(size_t)f] = P.scan_status;
+    }
+    if ((int64_t)dst_pitch < (int64_t)need_w * out_channels) return fail(ctx, DVO_EINVAL, "destination pitch too small");
+    if (u && (out_channels != 1 || u->U.w != need_w || u->U.h != need_h))
+        return fail(ctx, DVO_EINVAL, "undistort size != frame size");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const bool on_host = entropy == DVO_JPEG_ENTROPY_HOST;
+    j->last_stream = st;
+    HIP_TRY(hipMemsetAsync(j->d_status, 0, (size_t)n * sizeof(int32_t), st));
+    for (int f0 = 0; f0 < n;) {
+        const int k = j->half;
+        j->half ^= 1;
+        if (j->ev_used[k]) HIP_TRY(hipEventSynchronize(j->ev[k]));
+        // the group: up to `group` frames whose scans fit the staging half
+        int nf = 0, nseg = 0, max_nblk = 0;
+        size_t bytes = 0;
+        int64_t elems = 0;
+        j->last_base.clear();
+        j->last_count.clear();
+        while (f0 + nf < n && nf < j->group) {
+            jpeg::Parsed& P = j->parsed[(size_t)(f0 + nf)];
+            const size_t sb = P.scan_end - P.scan_begin;
+            if (bytes + align_up(sb, 16) > j->stage_cap || (size_t)elems + (size_t)P.plan.nblk * 64 > j->coef_cap ||
+                (size_t)nseg + P.segs.size() > (size_t)0x7FFFFFFF)
+                break;
+            P.plan.base = elems;
+            j->h_plans[k][nf] = P.plan;
+            if (!on_host) {
+                std::memcpy(j->h_bytes[k] + bytes, bufs[f0 + nf] + P.scan_begin, sb);
+                for (const jpeg::Segment& sg : P.segs)
+                    j->h_segs[k][nseg++] =
+                        jpeg::Segment{nf, (uint32_t)(bytes + (sg.offset - P.scan_begin)), sg.length, sg.mcu0, sg.nmcu};
+            }
+            j->last_base.push_back(elems);
+            j->last_count.push_back((int64_t)P.plan.nblk * 64);
+            bytes += align_up(sb, 16);
+            elems += (int64_t)P.plan.nblk * 64;
+            max_nblk = std::max(max_nblk, P.plan.nblk);
+            ++nf;
+        }
+        HIP_TRY(hipMemcpyAsync(j->d_plans, j->h_plans[k], (size_t)nf * sizeof(jpeg::FramePlan), hipMemcpyHostToDevice, st));
+        if (on_host) {
+            if (j->ev_coef_used) HIP_TRY(hipEventSynchronize(j->ev_coef));
+            std::memset(j->h_coef, 0, (size_t)elems * sizeof(int16_t));
+            for (int i = 0; i < nf; ++i) {
+                const jpeg::Parsed& P = j->parsed[(size_t)(f0 + i)];
+                if (entropy_host(P, bufs[f0 + i], j->h_coef + P.plan.base)) j->host_status[(size_t)(f0 + i)] = DVO_ECORRUPT;
+            }
+            HIP_TRY(hipMemcpyAsync(j->d_coef, j->h_coef, (size_t)elems * sizeof(int16_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipEventRecord(j->ev_coef, st));
+            j->ev_coef_used = true;
+        } else {
+            HIP_TRY(hipMemsetAsync(j->d_coef, 0, (size_t)elems * sizeof(int16_t), st));
+            if (bytes) HIP_TRY(hipMemcpyAsync(j->d_bytes, j->h_bytes[k], bytes, hipMemcpyHostToDevice, st));
+            if (nseg)
+                HIP_TRY(hipMemcpyAsync(j->d_segs, j->h_segs[k], (size_t)nseg * sizeof(jpeg::Segment), hipMemcpyHostToDevice,
+                                       st));
+        }
+        HIP_TRY(hipEventRecord(j->ev[k], st));
+        j->ev_used[k] = true;
+        if (!on_host)
+            HIP_TRY(launch_jpeg_entropy(j->d_plans, j->d_segs, nseg, j->d_bytes, j->d_coef, j->d_status + f0, st));
+        HIP_TRY(launch_jpeg_idct(j->d_plans, nf, max_nblk, j->d_coef, j->d_planes, st));
+        uint8_t* dst = d_dst + (int64_t)f0 * dst_fstride;
+        if (u) {
+            const int64_t gfs = (int64_t)j->gray_pitch * j->max_h;
+            HIP_TRY(launch_jpeg_color(kGray14, j->d_plans, nf, need_w, need_h, j->d_planes, 1, j->d_gray, gfs,
+                                      j->gray_pitch, st));
+            HIP_TRY(launch_undistort_remap(u->U, u->d_xy, u->d_frac, j->d_gray, nf, gfs, j->gray_pitch, dst, dst_fstride,
+                                           dst_pitch, st));
+        } else {
+            HIP_TRY(launch_jpeg_color(kGray14, j->d_plans, nf, need_w, need_h, j->d_planes, out_channels, dst,
+                                      dst_fstride, dst_pitch, st));
+        }
+        f0 += nf;
+    }
+    HIP_TRY(hipMemcpyAsync(j->h_status, j->d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    return DVO_OK;
+}
+
+int check_stream_jpeg(dvo_stream* s, dvo_jpeg* j, const dvo_undistort* u, const uint8_t* const* bufs,
+                      const int64_t* lens, int n, int n_min, const dvo_pair_record* d_records) {
+    dvo_ctx* ctx = s->ctx;
+    if (!j) return fail(ctx, DVO_EINVAL, "null decoder");
+    if (j->ctx->device != ctx->device) return fail(ctx, DVO_EINVAL, "decoder and stream are on different devices");
+    if (u && (u->U.w != s->cfg.width || u->U.h != s->cfg.height))
+        return fail(ctx, DVO_EINVAL, "undistort size != stream size");
+    if (n < n_min || n > s->cfg.max_frames) return fail(ctx, DVO_EINVAL, "n_frames out of range");
+    if (!bufs || !lens) return fail(ctx, DVO_EINVAL, "null buffer");
+    if (n > 1 && !d_records) return fail(ctx, DVO_EINVAL, "null records");
+    return DVO_OK;
+}
+
+int run_stream_jpeg(dvo_stream* s, dvo_jpeg* j, dvo_undistort* u, const uint8_t* const* bufs, const int64_t* lens, int n,
+                    dvo_pair_record* d_records, bool drain) {
+    dvo_ctx* ctx = s->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int pw = frame_pitch(s);
+    const int64_t fs = (int64_t)pw * s->cfg.height;
+    const int rc = jpeg_decode_impl(j, bufs, lens, n, 1, s->d_frames, fs, pw, DVO_JPEG_ENTROPY_DEVICE, s->hs, u,
+                                    s->cfg.width, s->cfg.height);
+    if (rc) return fail(ctx, rc, j->ctx->err);
+    return run_stream(s, s->d_frames, n, fs, pw, d_records, false, 1, drain);
+}
+
+}  // namespace
+
+int dvo_jpeg_probe(const uint8_t* buf, int64_t len, int* w, int* h, int* components, int* sampling) {
+    if (!buf || len < 0) return DVO_EINVAL;
+    jpeg::Parsed P;
+    const int rc = jpeg::parse(buf, (size_t)len, &P);
+    if (rc) return rc;
+    if (w) *w = P.plan.w;
+    if (h) *h = P.plan.h;
+    if (components) *components = P.plan.ncomp;
+    if (sampling) *sampling = P.plan.hs << 4 | P.plan.vs;
+    return DVO_OK;
+}
+
+int dvo_jpeg_entropy_host(const uint8_t* buf, int64_t len, dvo_jpeg_layout* layout, int16_t* coef, int64_t cap,
+                          int* status) {
+    if (!buf || len < 0 || !layout) return DVO_EINVAL;
+    jpeg::Parsed P;
+    const int rc = jpeg::parse(buf, (size_t)len, &P);
+    if (rc) return rc;
+    fill_layout(P, layout);
+    if (!coef) return DVO_OK;
+    if (cap < layout->coef_count) return DVO_ECAP;
+    std::memset(coef, 0, (size_t)layout->coef_count * sizeof(int16_t));
+    const int st = entropy_host(P, buf, coef);
+    if (status) *status = st;
+    return DVO_OK;
+}
+
+int dvo_jpeg_create(dvo_ctx* ctx, int max_w, int max_h, int group_frames, dvo_jpeg** out) {
+    if (!ctx || !out) return DVO_EINVAL;
+    *out = nullptr;
+    if (max_w < 1 || max_h < 1 || max_w > 65535 || max_h > 65535) return fail(ctx, DVO_EINVAL, "maximum size out of range");
+    if (group_frames < 1 || group_frames > 65535) return fail(ctx, DVO_EINVAL, "group_frames out of range (1..65535)");
+    auto j = std::make_unique<dvo_jpeg>();
+    j->ctx = ctx;
+    j->max_w = max_w, j->max_h = max_h, j->group = group_frames;
+    const size_t pw = align_up((size_t)max_w, 16), ph = align_up((size_t)max_h, 16);
+    j->frame_elems = 3 * pw * ph;
+    // A group is sized for 4:2:2 frames (two thirds of 4:4:4's coefficients) of half a byte per pixel
+    // of scan; frames that need more close their group early, and one frame of any kind fits.
+    const size_t G = (size_t)group_frames;
+    j->coef_cap = std::max(G * (j->frame_elems / 3 * 2), j->frame_elems);
+    // (segment offsets into a group's bytes are 32-bit: a larger scan is refused with DVO_ECAP)
+    j->stage_cap = align_up(std::max(G * ((size_t)max_w * max_h / 2 + 4096), 4 * (size_t)max_w * max_h + 65536), 256);
+    j->stage_cap = std::min(j->stage_cap, (size_t)0xFFFFFF00u);
+    j->seg_cap = (size_t)group_frames * (pw / 8) * (ph / 8);  // at most one segment per MCU
+    j->gray_pitch = (int)pw;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipError_t e = hipSuccess;
+    auto dev = [&](auto** p, size_t bytes) {
+        if (e == hipSuccess) e = j->mem.alloc(p, bytes + 256);
+    };
+    auto pinned = [&](auto** p, size_t bytes) {
+        if (e == hipSuccess) e = j->pin.alloc(p, bytes + 256);
+    };
+    dev(&j->d_bytes, j->stage_cap);
+    dev(&j->d_plans, G * sizeof(jpeg::FramePlan));
+    dev(&j->d_segs, j->seg_cap * sizeof(jpeg::Segment));
+    dev(&j->d_coef, j->coef_cap * sizeof(int16_t));
+    dev(&j->d_planes, j->coef_cap);
+    dev(&j->d_gray, G * pw * (size_t)max_h);
+    dev(&j->d_status, (size_t)dvo_jpeg::kMaxCall * sizeof(int32_t));
+    for (int k = 0; k < 2; ++k) {
+        pinned(&j->h_bytes[k], j->stage_cap);
+        pinned(&j->h_plans[k], G * sizeof(jpeg::FramePlan));
+        pinned(&j->h_segs[k], j->seg_cap * sizeof(jpeg::Segment));
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&j->ev[k], hipEventDisableTiming);
+    }
+    pinned(&j->h_status, (size_t)dvo_jpeg::kMaxCall * sizeof(int32_t));
+    pinned(&j->h_coef, j->coef_cap * sizeof(int16_t));
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&j->ev_coef, hipEventDisableTiming);
+    if (e != hipSuccess) return fail(ctx, DVO_EHIP, std::string("JPEG decoder buffers: ") + hipGetErrorString(e));
+    std::memset(j->h_status, 0, (size_t)dvo_jpeg::kMaxCall * sizeof(int32_t));
+    *out = j.release();
+    return DVO_OK;
+}
+
+void dvo_jpeg_destroy(dvo_jpeg* j) {
+    if (!j) return;
+    hipSetDevice(j->ctx->device);
+    delete j;
+}
+
+int dvo_jpeg_decode(dvo_jpeg* j, const uint8_t* const* bufs, const int64_t* lens, int n, int out_channels,
+                    uint8_t* d_dst, int64_t dst_frame_stride, int dst_pitch, int entropy, void* hip_stream) {
+    if (!j) return DVO_EINVAL;
+    return jpeg_decode_impl(j, bufs, lens, n, out_channels, d_dst, dst_frame_stride, dst_pitch, entropy,
+                            hip_stream ? (hipStream_t)hip_stream : j->ctx->stream, nullptr, 0, 0);
+}
+
+int dvo_jpeg_status(dvo_jpeg* j, int* st, int n) {
+    if (!j || n < 0 || (n > 0 && !st)) return DVO_EINVAL;
+    if (n > (int)j->host_status.size()) return fail(j->ctx, DVO_EINVAL, "more frames than the last call decoded");
+    for (int i = 0; i < n; ++i) st[i] = j->host_status[(size_t)i] || j->h_status[i] ? DVO_ECORRUPT : DVO_OK;
+    return DVO_OK;
+}
+
+int dvo_jpeg_decode_image(dvo_jpeg* j, const uint8_t* buf, int64_t len, int out_channels, uint8_t* out,
+                          int out_stride) {
+    if (!j || !buf || !out) return DVO_EINVAL;
+    dvo_ctx* ctx = j->ctx;
+    int w = 0, h = 0;
+    const int prc = dvo_jpeg_probe(buf, len, &w, &h, nullptr, nullptr);
+    if (prc) return fail(ctx, prc, "not a decodable JPEG");
+    if (out_channels != 1 && out_channels != 3 && out_channels != 4)
+        return fail(ctx, DVO_EINVAL, "out_channels must be 1, 3 or 4");
+    if ((int64_t)out_stride < (int64_t)w * out_channels) return fail(ctx, DVO_EINVAL, "bad stride");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int pitch = (w * out_channels + 15) & ~15;
+    CallMem mem(ctx->call, ctx->stream);
+    uint8_t* ddst = mem.dev<uint8_t>((size_t)pitch * h);
+    HIP_TRY(mem.error());
+    const int64_t len64 = len;
+    int rc = jpeg_decode_impl(j, &buf, &len64, 1, out_channels, ddst, 0, pitch, DVO_JPEG_ENTROPY_HOST, ctx->stream,
+                              nullptr, 0, 0);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy2DAsync(out, out_stride, ddst, pitch, (size_t)w * out_channels, h, hipMemcpyDeviceToHost,
+                             ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    int st = 0;
+    rc = dvo_jpeg_status(j, &st, 1);
+    if (rc) return rc;
+    return st ? fail(ctx, DVO_ECORRUPT, "frame 0: corrupt entropy-coded data") : DVO_OK;
+}
+
+int dvo_undistort_image_jpeg(dvo_undistort* u, dvo_jpeg* j, const uint8_t* buf, int64_t len, uint8_t* out,
+                             int out_stride) {
+    if (!u || !j || !buf || !out) return DVO_EINVAL;
+    dvo_ctx* ctx = j->ctx;
+    if (u->ctx->device != ctx->device) return fail(ctx, DVO_EINVAL, "decoder and undistorter are on different devices");
+    const int w = u->U.w, h = u->U.h;
+    if (out_stride < w) return fail(ctx, DVO_EINVAL, "bad stride");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int pw = (w + 15) & ~15;
+    CallMem mem(ctx->call, ctx->stream);
+    uint8_t* ddst = mem.dev<uint8_t>((size_t)pw * h);
+    HIP_TRY(mem.error());
+    const int64_t len64 = len;
+    int rc = jpeg_decode_impl(j, &buf, &len64, 1, 1, ddst, 0, pw, DVO_JPEG_ENTROPY_HOST, ctx->stream, u, w, h);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy2DAsync(out, out_stride, ddst, pw, w, h, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    int st = 0;
+    rc = dvo_jpeg_status(j, &st, 1);
+    if (rc) return rc;
+    return st ? fail(ctx, DVO_ECORRUPT, "frame 0: corrupt entropy-coded data") : DVO_OK;
+}
+
+int dvo_stream_process_jpeg(dvo_stream* s, dvo_jpeg* j, dvo_undistort* u, const uint8_t* const* bufs,
+                            const int64_t* lens, int n, dvo_pair_record* d_records) {
+    if (!s) return DVO_EINVAL;
+    const int rc = check_stream_jpeg(s, j, u, bufs, lens, n, 1, d_records);
+    if (rc) return rc;
+    return run_stream_jpeg(s, j, u, bufs, lens, n, d_records, true);
+}
+
+int dvo_stream_submit_jpeg(dvo_stream* s, dvo_jpeg* j, dvo_undistort* u, const uint8_t* const* bufs,
+                           const int64_t* lens, int n, dvo_pair_record* d_records) {
+    if (!s) return DVO_EINVAL;
+    const int rc = check_stream_jpeg(s, j, u, bufs, lens, n, 2, d_records);
+    if (rc) return rc;
+    return run_stream_jpeg(s, j, u, bufs, lens, n, d_records, false);
+}
+
+int dvo_jpeg_get_coefficients(dvo_jpeg* j, int frame, int16_t* out, int64_t cap, int64_t* n_out) {
+    if (!j || !out || !n_out) return DVO_EINVAL;
+    dvo_ctx* ctx = j->ctx;
+    if (frame < 0 || frame >= (int)j->last_base.size()) return fail(ctx, DVO_EINVAL, "frame not in the last group");
+    *n_out = j->last_count[(size_t)frame];
+    if (cap < *n_out) return fail(ctx, DVO_ECAP, "caller capacity too small");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(j->last_stream));
+    HIP_TRY(hipMemcpy(out, j->d_coef + j->last_base[(size_t)frame], (size_t)*n_out * sizeof(int16_t),
+                      hipMemcpyDeviceToHost));
+    return DVO_OK;
 }

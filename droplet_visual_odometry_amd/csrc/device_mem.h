@@ -46,6 +46,33 @@ class DeviceAllocs {
     std::vector<void*> ptrs_;
 };
 
+// Pinned host allocations (hipHostMalloc) that are freed together.
+class PinnedAllocs {
+  public:
+    PinnedAllocs() = default;
+    PinnedAllocs(const PinnedAllocs&) = delete;
+    PinnedAllocs& operator=(const PinnedAllocs&) = delete;
+    ~PinnedAllocs() { release(); }
+
+    template <class T>
+    hipError_t alloc(T** p, size_t bytes) {
+        ptrs_.reserve(ptrs_.size() + 1);
+        void* q = nullptr;
+        const hipError_t e = hipHostMalloc(&q, bytes, hipHostMallocDefault);
+        if (e != hipSuccess) return e;
+        ptrs_.push_back(q);
+        *p = static_cast<T*>(q);
+        return hipSuccess;
+    }
+    void release() {
+        for (void* q : ptrs_) (void)hipHostFree(q);
+        ptrs_.clear();
+    }
+
+  private:
+    std::vector<void*> ptrs_;
+};
+
 // The per-pair arrays of a stream's pair sets: of all sets (pairs [0, nsets F)), or one set's view.
 // g's configuration scalars and its round-local fprec / dk_ctl / dk_list belong to the stream and
 // are the same in every view; g.pts_f and g.m_arr alias pts and nmatch.

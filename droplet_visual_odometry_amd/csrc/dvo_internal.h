@@ -354,6 +354,21 @@ hipError_t launch_undistort_remap_bgr(const UndistortGeom& U, const int16_t* d_x
                                       int src_pitch, int channels, uint8_t* d_dst, int64_t dst_fstride,
                                       int dst_pitch, hipStream_t s);
 
+// Baseline JPEG frames (jpeg.hip; plans and segments: jpeg.h).  Entropy: every segment of a frame
+// group into the frames' zeroed coefficients, status[frame] = DVO_ECORRUPT where one is corrupt.
+// IDCT: coefficients -> u8 component planes.  Colour: planes -> gray (1), BGR (3) or BGRA (4) frames.
+namespace jpeg {
+struct FramePlan;
+struct Segment;
+}  // namespace jpeg
+hipError_t launch_jpeg_entropy(const jpeg::FramePlan* d_plans, const jpeg::Segment* d_segs, int nseg,
+                               const uint8_t* d_bytes, int16_t* d_coef, int32_t* d_status, hipStream_t s);
+hipError_t launch_jpeg_idct(const jpeg::FramePlan* d_plans, int nframes, int max_nblk, const int16_t* d_coef,
+                            uint8_t* d_planes, hipStream_t s);
+hipError_t launch_jpeg_color(const GrayCoef& c, const jpeg::FramePlan* d_plans, int nframes, int w, int h,
+                             const uint8_t* d_planes, int out_channels, uint8_t* d_dst, int64_t dst_fstride,
+                             int dst_pitch, hipStream_t s);
+
 // carry: device [12 P_prev | 16 T_abs_prev]; updated in place.
 // rec: the pairs' records (R, t, status, n_models are read).
 hipError_t launch_pose_tail(const dvo_pair_record* rec, int pairs, const double* K, const double* cprev, const double* ccur, int k, double marker_length,

@@ -27,7 +27,7 @@ from collections.abc import Sequence
 import numpy as np
 
 from . import ops
-from ._native import DVOError, opencv_semantics
+from ._native import DVO_ECORRUPT, DVO_EUNSUPPORTED, DVOError, opencv_semantics
 
 # Which OpenCV release's semantics the cv2 stand-ins reproduce (include/dvo.h
 # DVO_OPENCV_*): "4.x" by default, or "3.2" -- the version the reference most
@@ -527,6 +527,35 @@ def _undistort_bgr2gray(src, cameraMatrix, distCoeffs, newCameraMatrix=None):
     try:
         return _undistort_cache.get(cameraMatrix, d, newCameraMatrix, w, h).image(img)
     except (DVOError, ValueError) as e:
+        raise error(str(e)) from e
+
+
+_jpeg_decoders = {}  # (w, h) -> ops.JpegDecoder of one frame
+
+
+def _undistort_jpeg2gray(buf, cameraMatrix, distCoeffs, newCameraMatrix=None):
+    """undistort(cvtColor(imdecode(buf, IMREAD_COLOR), COLOR_BGR2GRAY), ...) of a JPEG file in
+    one GPU call (v3:127-133; the drop-in's "compressed" messages), byte for byte.  None when
+    the file is outside the device decoder's set (ops.JpegDecoder) or corrupt: the caller then
+    takes imdecode and _undistort_bgr2gray."""
+    data = np.frombuffer(buf, np.uint8) if isinstance(buf, (bytes, bytearray, memoryview)) \
+        else np.ascontiguousarray(buf, np.uint8).ravel()
+    try:
+        w, h, _, _ = ops.jpeg_probe(data)
+    except DVOError:
+        return None
+    d = np.asarray(distCoeffs if distCoeffs is not None else np.zeros(5), np.float64).ravel()
+    try:
+        u = _undistort_cache.get(cameraMatrix, d, newCameraMatrix, w, h)
+        if (w, h) not in _jpeg_decoders:
+            for old in _jpeg_decoders.values():  # its calls were synchronous: nothing of it is in flight
+                old.close()
+            _jpeg_decoders.clear()
+            _jpeg_decoders[(w, h)] = ops.JpegDecoder(w, h, group_frames=1)
+        return _jpeg_decoders[(w, h)].undistort_image(u, data)
+    except DVOError as e:
+        if e.code in (DVO_EUNSUPPORTED, DVO_ECORRUPT):
+            return None
         raise error(str(e)) from e
 
 

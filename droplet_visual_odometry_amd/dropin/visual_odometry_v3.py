@@ -182,6 +182,12 @@ class VisualOdometry:
                                                             self.distortion_coefficient_matrix, size, 1, size)
         image_np = None
         if msg_type == "compressed":
+            # imdecode + cvtColor + undistort (v3:127-133) in one GPU call for a baseline JPEG: the
+            # file goes up, gray comes back; None for any other file, which takes the host decode
+            fused = cv._undistort_jpeg2gray(image_message.data, self.intrinsic_coefficient_matrix,
+                                            self.distortion_coefficient_matrix, new_camera_matrix)
+            if fused is not None:
+                return fused
             image_np = cv.imdecode(np.frombuffer(image_message.data, np.uint8), cv.IMREAD_COLOR)
         elif msg_type == "usb_raw":
             raw = np.frombuffer(image_message.data, dtype=np.uint8)

@@ -15,6 +15,8 @@ mirrors its argument meaning, output layout and failure points:
                        cv::getOptimalNewCameraMatrix, cv::undistort  v3:117, v3:120
   bgr2gray, bgr2gray_device
                        cv::cvtColor(COLOR_BGR2GRAY)       visual_odometry_v3.py:132
+  JpegDecoder, jpeg_probe, jpeg_entropy_host
+                       cv::imdecode(IMREAD_COLOR) of baseline JPEGs  visual_odometry_v3.py:127
 """
 from __future__ import annotations
 
@@ -22,7 +24,7 @@ import ctypes
 
 import numpy as np
 
-from ._native import (DMATCH_DTYPE, DVO_ECAP, DVO_OK, KEYPOINT_DTYPE, PAIR_RECORD_DTYPE, Context, DVOError, StreamConfig,
+from ._native import (DMATCH_DTYPE, DVO_ECAP, DVO_ECORRUPT, DVO_EUNSUPPORTED, DVO_OK, KEYPOINT_DTYPE, PAIR_RECORD_DTYPE, Context, DVOError, StreamConfig,
                       load_library, orb_params, ptr)
 
 
@@ -435,6 +437,194 @@ class Undistorter:
     def close(self):
         if getattr(self, "h_", None):
             self.ctx.lib.dvo_undistort_destroy(self.h_)
+            self.h_ = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- JPEG frames: cv.imdecode(np_arr, IMREAD_COLOR) (v3:127) of baseline JPEGs ----
+JPEG_COLORS = {"gray": 1, "bgr": 3, "bgra": 4}
+JPEG_ENTROPY = {"host": 0, "device": 1}
+# the faster of the two at 256 frames of 1280x720 4:2:0 without restart markers (tools/time_jpeg.py)
+JPEG_DEFAULT_ENTROPY = "device"
+
+
+def jpeg_blobs(blobs, max_frames=None):
+    """A batch of JPEG files as (uint8 arrays, pointer array, length array): a non-empty
+    list of bytes-like objects (bytes, bytearray, memoryview, uint8 numpy arrays).
+    ValueError otherwise, before any library call."""
+    if isinstance(blobs, (bytes, bytearray, memoryview, np.ndarray, str)) or not hasattr(blobs, "__len__"):
+        raise ValueError("blobs must be a list of bytes-like JPEG files")
+    if len(blobs) == 0:
+        raise ValueError("blobs is empty")
+    if max_frames is not None and len(blobs) > max_frames:
+        raise ValueError(f"{len(blobs)} frames > the maximum of {max_frames}")
+    arrs = []
+    for i, b in enumerate(blobs):
+        if isinstance(b, np.ndarray):
+            if b.dtype != np.uint8 or b.ndim != 1:
+                raise ValueError(f"blob {i}: expected a 1-D uint8 array")
+            a = np.ascontiguousarray(b)
+        elif isinstance(b, (bytes, bytearray, memoryview)):
+            try:
+                a = np.frombuffer(b, np.uint8)
+            except (ValueError, TypeError) as e:
+                raise ValueError(f"blob {i}: {e}") from e
+        else:
+            raise ValueError(f"blob {i}: not bytes-like ({type(b).__name__})")
+        if a.size == 0:
+            raise ValueError(f"blob {i} is empty")
+        arrs.append(a)
+    ptrs = (ctypes.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+    lens = (ctypes.c_int64 * len(arrs))(*[a.size for a in arrs])
+    return arrs, ptrs, lens
+
+
+def _jpeg_bytes(blob) -> np.ndarray:
+    """One JPEG file as a uint8 array, without a copy where the object allows it."""
+    if isinstance(blob, np.ndarray):
+        return np.ascontiguousarray(blob, np.uint8).ravel()
+    return np.frombuffer(blob, np.uint8)
+
+
+def _jpeg_error(rc):
+    return DVOError(rc, "unsupported JPEG" if rc == DVO_EUNSUPPORTED else "corrupt JPEG")
+
+
+def jpeg_probe(blob):
+    """(width, height, components, sampling) of a JPEG header, on the host; sampling is the
+    luma factors h << 4 | v.  DVOError with code DVO_EUNSUPPORTED or DVO_ECORRUPT otherwise."""
+    lib = load_library()
+    a = _jpeg_bytes(blob)
+    w, h, nc, sm = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    rc = lib.dvo_jpeg_probe(ptr(a), a.size, ctypes.byref(w), ctypes.byref(h), ctypes.byref(nc), ctypes.byref(sm))
+    if rc != DVO_OK:
+        raise _jpeg_error(rc)
+    return w.value, h.value, nc.value, sm.value
+
+
+def jpeg_entropy_host(blob):
+    """Parser + Huffman decoder of one JPEG on the host (dvo_jpeg_entropy_host): the
+    layout (_native.JpegLayout), the int16 coefficients and the entropy status."""
+    from ._native import JpegLayout
+    lib = load_library()
+    a = _jpeg_bytes(blob)
+    lay = JpegLayout()
+    rc = lib.dvo_jpeg_entropy_host(ptr(a), a.size, ctypes.byref(lay), None, 0, None)
+    if rc != DVO_OK:
+        raise _jpeg_error(rc)
+    coef = np.zeros(lay.coef_count, np.int16)
+    st = ctypes.c_int()
+    rc = lib.dvo_jpeg_entropy_host(ptr(a), a.size, ctypes.byref(lay), ptr(coef), coef.size, ctypes.byref(st))
+    if rc != DVO_OK:
+        raise DVOError(rc, "dvo_jpeg_entropy_host failed")
+    return lay, coef, st.value
+
+
+class JpegDecoder:
+    """cv.imdecode(buf, IMREAD_COLOR) (v3:127) of baseline JPEGs on the GPU, byte for
+    byte libjpeg-turbo's default decode, for batches of frames of one size up to
+    max_w x max_h.  Scratch (about 7 device and 5 pinned host bytes per pixel of a frame) is sized here for one
+    group of `group_frames` frames; a batch runs group after group.  The device entropy
+    decoder takes a group's restart segments one lane each: files without restart
+    markers decode `group_frames` at a time, which is what the default is for."""
+
+    @staticmethod
+    def default_group_frames(max_w: int, max_h: int) -> int:
+        """256 frames, fewer where that would take more than 2 GiB of device memory."""
+        return max(1, min(256, (2 << 30) // (7 * int(max_w) * int(max_h))))
+
+    def __init__(self, max_w: int, max_h: int, group_frames: int | None = None, ctx=None):
+        self.ctx = _ctx(ctx)
+        if group_frames is None:
+            group_frames = self.default_group_frames(max_w, max_h)
+        self.max_w, self.max_h, self.group_frames = int(max_w), int(max_h), int(group_frames)
+        h = ctypes.c_void_p()
+        self.ctx.check(self.ctx.lib.dvo_jpeg_create(self.ctx.h, self.max_w, self.max_h, self.group_frames,
+                                                    ctypes.byref(h)))
+        self.h_ = h
+        self._n = 0
+
+    probe = staticmethod(jpeg_probe)
+
+    def decode(self, blobs, color="gray", entropy=None, out=None, stream=None):
+        """n JPEG files of one size -> a uint8 device tensor [n, H, W] (gray:
+        cvtColor(BGR2GRAY) of the decoded bytes) or [n, H, W, 3 | 4] (bgr, bgra),
+        asynchronously on `stream` (a hipStream_t handle; default: ordered with torch's
+        current stream).  entropy: "device" or "host" Huffman decoding (default
+        JPEG_DEFAULT_ENTROPY).  status() tells which frames were corrupt."""
+        import torch
+        if color not in JPEG_COLORS:
+            raise ValueError(f"color must be one of {sorted(JPEG_COLORS)}")
+        entropy = JPEG_DEFAULT_ENTROPY if entropy is None else entropy
+        if entropy not in JPEG_ENTROPY:
+            raise ValueError(f"entropy must be one of {sorted(JPEG_ENTROPY)}")
+        arrs, ptrs, lens = jpeg_blobs(blobs, 65536)
+        ch = JPEG_COLORS[color]
+        w, h, _, _ = jpeg_probe(arrs[0])
+        n = len(arrs)
+        shape = (n, h, w) if ch == 1 else (n, h, w, ch)
+        dev = torch.device("cuda", self.ctx.device)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != shape \
+                or not out.is_cuda or out.stride(-1) != 1 or (ch > 1 and out.stride(2) != ch) \
+                or out.stride(1) < w * ch:
+            raise ValueError(f"out must be a uint8 {list(shape)} device tensor with adjacent pixels")
+
+        def call(st):
+            self.ctx.check(self.ctx.lib.dvo_jpeg_decode(self.h_, ptrs, lens, n, ch, out.data_ptr(), out.stride(0),
+                                                        out.stride(1), JPEG_ENTROPY[entropy], ctypes.c_void_p(st)))
+        _on_stream(out.device, stream, call)
+        self._n = n
+        return out
+
+    def decode_image(self, blob, color="bgr") -> np.ndarray:
+        """One host JPEG -> a host image (H x W, or H x W x 3 | 4), synchronously."""
+        if color not in JPEG_COLORS:
+            raise ValueError(f"color must be one of {sorted(JPEG_COLORS)}")
+        a = _jpeg_bytes(blob)
+        w, h, _, _ = jpeg_probe(a)
+        ch = JPEG_COLORS[color]
+        out = np.empty((h, w) if ch == 1 else (h, w, ch), np.uint8)
+        self.ctx.check(self.ctx.lib.dvo_jpeg_decode_image(self.h_, ptr(a), a.size, ch, ptr(out), out.strides[0]))
+        self._n = 1
+        return out
+
+    def undistort_image(self, undistorter, blob) -> np.ndarray:
+        """undistort(cvtColor(imdecode(blob))) (v3:127-133) of one host JPEG: mono8."""
+        a = _jpeg_bytes(blob)
+        out = np.empty((undistorter.h, undistorter.w), np.uint8)
+        self.ctx.check(self.ctx.lib.dvo_undistort_image_jpeg(undistorter.h_, self.h_, ptr(a), a.size, ptr(out),
+                                                             out.strides[0]))
+        self._n = 1
+        return out
+
+    def status(self, n=None) -> np.ndarray:
+        """Per frame of the last call, after synchronising: 0 or DVO_ECORRUPT."""
+        n = self._n if n is None else int(n)
+        st = np.zeros(n, np.int32)
+        self.ctx.check(self.ctx.lib.dvo_jpeg_status(self.h_, ptr(st), n))
+        return st
+
+    def coefficients(self, frame: int) -> np.ndarray:
+        """Test hook: the coefficients of a frame of the last group decoded."""
+        n = ctypes.c_int64()
+        out = np.zeros(1, np.int16)
+        rc = self.ctx.lib.dvo_jpeg_get_coefficients(self.h_, int(frame), ptr(out), 0, ctypes.byref(n))  # the count
+        if rc != DVO_ECAP:
+            self.ctx.check(rc)
+        out = np.zeros(n.value, np.int16)
+        self.ctx.check(self.ctx.lib.dvo_jpeg_get_coefficients(self.h_, int(frame), ptr(out), out.size, ctypes.byref(n)))
+        return out
+
+    def close(self):
+        if getattr(self, "h_", None):
+            self.ctx.lib.dvo_jpeg_destroy(self.h_)
             self.h_ = None
 
     def __del__(self):

@@ -185,6 +185,62 @@ class FrameStream:
         self._hold(frames, records)
         return self._take_retired()
 
+    # ---- JPEG frames (dvo_stream_process_jpeg / _submit_jpeg): see include/dvo.h ---------------
+    def _check_jpeg(self, blobs, undistort, n_min):
+        from .ops import jpeg_blobs
+        arrs, ptrs, lens = jpeg_blobs(blobs, self.max_frames)
+        if len(arrs) < n_min:
+            raise ValueError(f"a submitted batch needs >= {n_min} frames")
+        if undistort is not None and (undistort.w, undistort.h) != (self.width, self.height):
+            raise ValueError(f"undistorter size {undistort.w}x{undistort.h} != stream {self.width}x{self.height}")
+        return arrs, ptrs, lens
+
+    @property
+    def jpeg_decoder(self):
+        """The stream's ops.JpegDecoder (made at the first JPEG batch); its status() tells
+        which frames of the last JPEG batch were corrupt, after a sync()."""
+        if getattr(self, "_jpeg", None) is None:
+            from .ops import JpegDecoder
+            group = min(int(self.max_frames), JpegDecoder.default_group_frames(self.width, self.height))
+            self._jpeg = JpegDecoder(self.width, self.height, group_frames=group, ctx=self.ctx)
+        return self._jpeg
+
+    def process_jpeg(self, blobs, records: torch.Tensor | None = None, undistort=None) -> torch.Tensor:
+        """process() of a list of JPEG files (bytes-like) of the stream's size: decoded to
+        gray on the device, and remapped by `undistort` (ops.Undistorter) if given, into
+        the stream's slab; from there exactly process() of colour frames."""
+        arrs, ptrs, lens = self._check_jpeg(blobs, undistort, 1)
+        n = len(arrs)
+        dec = self.jpeg_decoder
+        if records is None:
+            records = self.new_records(n - 1)
+        self._after_torch()
+        if n > 1:
+            self._pending[records.data_ptr()] = records
+        self.ctx.check(self.ctx.lib.dvo_stream_process_jpeg(
+            self.h, dec.h_, undistort.h_ if undistort is not None else None, ptrs, lens, n,
+            records.data_ptr() if n > 1 else None))
+        dec._n = n
+        self._take_retired()
+        self._last = (records,)
+        self._hold(records)
+        return records
+
+    def submit_jpeg(self, blobs, records: torch.Tensor, undistort=None) -> list:
+        """submit() of a list of JPEG files (see process_jpeg)."""
+        arrs, ptrs, lens = self._check_jpeg(blobs, undistort, 2)
+        n = len(arrs)
+        if not isinstance(records, torch.Tensor) or records.numel() < (n - 1) * PAIR_RECORD_DTYPE.itemsize:
+            raise ValueError("records too small")
+        dec = self.jpeg_decoder
+        self._after_torch()
+        self.ctx.check(self.ctx.lib.dvo_stream_submit_jpeg(
+            self.h, dec.h_, undistort.h_ if undistort is not None else None, ptrs, lens, n, records.data_ptr()))
+        dec._n = n
+        self._pending[records.data_ptr()] = records
+        self._hold(records)
+        return self._take_retired()
+
     def submit(self, frames: torch.Tensor, records: torch.Tensor, wait_torch: bool = True, undistort=None) -> list:
         """Pipelined batch (dvo_stream_submit): detection and matching of these
         frames, then one merged RANSAC round of the pending batches.  `records`
@@ -374,6 +430,9 @@ class FrameStream:
         if getattr(self, "h", None):
             self.ctx.lib.dvo_stream_destroy(self.h)  # synchronises the stream first
             self.h = None
+            if getattr(self, "_jpeg", None) is not None:  # its work ran on the stream just synchronised
+                self._jpeg.close()
+                self._jpeg = None
             if getattr(self, "_held", None):
                 self._held.clear()
             self._last = ()

@@ -27,10 +27,13 @@ extern "C" {
 #define DVO_EHIP (-4)     /* HIP runtime failure                                   */
 #define DVO_ECAP (-5)     /* caller buffer too small; *_out holds the needed size  */
 #define DVO_ENOMODEL (-6) /* RANSAC found no model (E empty)                       */
+#define DVO_EUNSUPPORTED (-7) /* a legal JPEG outside the supported set            */
+#define DVO_ECORRUPT (-8) /* malformed JPEG header or entropy-coded data           */
 
 typedef struct dvo_ctx dvo_ctx;
 typedef struct dvo_stream dvo_stream;
 typedef struct dvo_undistort dvo_undistort;
+typedef struct dvo_jpeg dvo_jpeg;
 
 /* cv::KeyPoint as the reference's Python sees it (28 bytes). */
 typedef struct {
@@ -406,6 +409,89 @@ int dvo_pose_chain_host(const double* T_rel, int n, double* T_carry, double* T_a
  * before the first pair on entry and after the last on return; d_T_abs: device
  * [n][16].  Asynchronous on hip_stream (NULL = the context's stream). */
 int dvo_pose_chain(dvo_ctx* ctx, const double* d_T_rel, int n, double* d_T_carry, double* d_T_abs, void* hip_stream);
+
+/* ---------------------------------------------------------------------------
+ * JPEG frames: cv.imdecode(np_arr, IMREAD_COLOR) (v3:127) of baseline JPEGs on the
+ * device, byte for byte what libjpeg-turbo's default decode (JDCT_ISLOW, fancy
+ * upsampling: cv.imdecode's and Pillow's) gives, and the cvtColor that follows.
+ *
+ * Supported: SOF0, 8-bit, Huffman, one interleaved scan; 1 component, or 3 (YCbCr)
+ * with Cb = Cr = 1x1 and Y 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0); any 8-bit DQT,
+ * any DHT, any restart interval, any size >= 1.  DVO_EUNSUPPORTED, found in the
+ * header before anything is launched: progressive, arithmetic, 12-bit, 16-bit
+ * quantisation tables, 4 components, Adobe transform 0, component ids R G B, other
+ * sampling factors, more than one scan.  A malformed header is DVO_ECORRUPT in the
+ * same way; malformed entropy-coded data is found while decoding and gives the
+ * frame the status DVO_ECORRUPT (dvo_jpeg_status): its blocks from the first bad
+ * one of a segment on stay zero, and the call itself succeeds.
+ * --------------------------------------------------------------------------- */
+
+/* Header of one JPEG, on the host (ctx-free).  sampling: luma factors h << 4 | v
+ * (0x11, 0x21, 0x22; 0x11 for one component).  DVO_OK, DVO_EUNSUPPORTED, DVO_ECORRUPT. */
+int dvo_jpeg_probe(const uint8_t* buf, int64_t len, int* w, int* h, int* components, int* sampling);
+
+/* What the entropy decoder produces for one image: int16 coefficients in natural
+ * order, per component [block row][block column][64] padded to whole MCUs
+ * (blocks_w x blocks_h blocks from element coef_offset), coef_count in all. */
+typedef struct {
+    int32_t width, height, components, sampling;
+    int32_t restart_interval, segments;
+    int32_t blocks_w[3], blocks_h[3];
+    int64_t coef_offset[3];
+    int64_t coef_count;
+    uint16_t quant[3][64]; /* per component, natural order */
+} dvo_jpeg_layout;
+
+/* Parser + entropy decoder of one image on the host (ctx-free): the layout, and,
+ * when coef is not NULL, coef_count coefficients (DVO_ECAP if cap is smaller) with
+ * *status = DVO_OK or DVO_ECORRUPT for the entropy-coded data. */
+int dvo_jpeg_entropy_host(const uint8_t* buf, int64_t len, dvo_jpeg_layout* layout, int16_t* coef, int64_t cap,
+                          int* status);
+
+/* A decoder for frames up to max_w x max_h.  All its scratch (pinned staging, plans,
+ * coefficients, component planes, a gray frame group) is sized here for one group of
+ * group_frames frames (of 4:2:2 at half a byte of scan per pixel: about 7 bytes of
+ * device and 5 of pinned host memory per pixel of the maximum size and frame; frames that need more close their group
+ * early); a batch runs group after group and nothing is allocated per call.  The device
+ * entropy decoder works on one group's segments at a time, one lane each, so frames
+ * without restart markers decode as many at a time as the group holds.  A decoder
+ * serves one HIP stream at a time. */
+int dvo_jpeg_create(dvo_ctx* ctx, int max_w, int max_h, int group_frames, dvo_jpeg** out);
+void dvo_jpeg_destroy(dvo_jpeg* j);
+
+#define DVO_JPEG_ENTROPY_HOST 0   /* Huffman decoding on the calling thread     */
+#define DVO_JPEG_ENTROPY_DEVICE 1 /* one GPU lane per restart segment (default) */
+
+/* n JPEGs of one size w x h <= max (sampling, tables and restart interval may differ
+ * per frame) -> n device frames of out_channels bytes per pixel: 1 gray
+ * (cvtColor(BGR2GRAY) of the decoded bytes, not the Y plane), 3 BGR, 4 BGRA (A 255).
+ * Asynchronous on hip_stream (NULL = the context's); the byte buffers are free at
+ * return.  An unsupported or header-corrupt frame fails the call before anything is
+ * launched, and dvo_last_error names its index.  n == 0 launches nothing.  At most
+ * 65536 frames per call. */
+int dvo_jpeg_decode(dvo_jpeg* j, const uint8_t* const* bufs, const int64_t* lens, int n, int out_channels,
+                    uint8_t* d_dst, int64_t dst_frame_stride, int dst_pitch, int entropy, void* hip_stream);
+/* After synchronising: DVO_OK or DVO_ECORRUPT per frame of the last decode (or stream) call. */
+int dvo_jpeg_status(dvo_jpeg* j, int* st, int n);
+/* Host in, host out, synchronous, host entropy; size the output with dvo_jpeg_probe.
+ * DVO_ECORRUPT (with the decodable part written) if the entropy-coded data is corrupt. */
+int dvo_jpeg_decode_image(dvo_jpeg* j, const uint8_t* buf, int64_t len, int out_channels, uint8_t* out,
+                          int out_stride);
+/* imdecode + cvtColor + undistort (v3:127-133) of one host JPEG of u's size: mono8 out. */
+int dvo_undistort_image_jpeg(dvo_undistort* u, dvo_jpeg* j, const uint8_t* buf, int64_t len, uint8_t* out,
+                             int out_stride);
+/* dvo_stream_process / dvo_stream_submit of n JPEG frames of the stream's size: decoded to
+ * gray into the stream's frame slab on its HIP stream (with u: into j's gray frame group,
+ * then dvo_undistort_apply into the slab), outside the stage timers; from there exactly
+ * dvo_stream_process_bgr / dvo_stream_submit_bgr. */
+int dvo_stream_process_jpeg(dvo_stream* s, dvo_jpeg* j, dvo_undistort* u, const uint8_t* const* bufs,
+                            const int64_t* lens, int n, dvo_pair_record* d_records);
+int dvo_stream_submit_jpeg(dvo_stream* s, dvo_jpeg* j, dvo_undistort* u, const uint8_t* const* bufs,
+                           const int64_t* lens, int n, dvo_pair_record* d_records);
+/* Test hook: the coefficients of frame `frame` of the last frame group decoded
+ * (dvo_jpeg_entropy_host's layout); *n_out is their count, DVO_ECAP if cap is
+ * smaller; synchronises. */
+int dvo_jpeg_get_coefficients(dvo_jpeg* j, int frame, int16_t* out, int64_t cap, int64_t* n_out);
 
 /* Per-stage device time via HIP events recorded on the stream's HIP stream
  * around each kernel group (0 pyramid, 1 blur, 2 fast, 3 select+harris,
