@@ -67,6 +67,15 @@ class StreamConfig(ctypes.Structure):
                 ("dist_thresh", ctypes.c_double)]
 
 
+class KnnPairConfig(ctypes.Structure):
+    """dvo_knn_pair_config: the k-NN modes' one-call pair path (dvo_knn_pair_run)."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("detector", ctypes.c_int32),
+                ("matcher", ctypes.c_int32), ("hessian_threshold", ctypes.c_double), ("trees", ctypes.c_int32),
+                ("checks", ctypes.c_int32), ("ratio", ctypes.c_double), ("K", ctypes.c_double * 9),
+                ("prob", ctypes.c_double), ("threshold", ctypes.c_double), ("max_iters", ctypes.c_int32),
+                ("dist_thresh", ctypes.c_double)]
+
+
 class JpegLayout(ctypes.Structure):
     """dvo_jpeg_layout: what dvo_jpeg_entropy_host produces for one image."""
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("components", ctypes.c_int32),
@@ -130,6 +139,11 @@ _SIGNATURES = {
     "dvo_stream_pose_tail_batch": ([_vp, _vp, _c, _vp, _vp, _c, _d, _vp, _vp], _c),
     "dvo_stream_pair": ([_vp, _vp, _vp, _c, _c, _vp], _c),
     "dvo_stream_sync": ([_vp], _c),
+    "dvo_knn_pair_create": ([_vp, ctypes.POINTER(KnnPairConfig), ctypes.POINTER(_vp)], _c),
+    "dvo_knn_pair_destroy": ([_vp], None),
+    "dvo_knn_pair_run": ([_vp, _vp, _vp, _c, _c, ctypes.POINTER(ctypes.c_uint64), _vp], _c),
+    "dvo_knn_pair_get_matches": ([_vp, _vp, _c, _ip], _c),
+    "dvo_knn_pair_get_features": ([_vp, _c, _vp, _vp, _c, _ip], _c),
     "dvo_stream_hip_stream": ([_vp], _vp),
     "dvo_stream_set_profiling": ([_vp, _c], _c),
     "dvo_stream_reset_pose": ([_vp, _vp, _vp], _c),
@@ -171,6 +185,7 @@ _SIGNATURES = {
     "dvo_test_update_num_iters": ([_vp, _d, _vp, _c, _c, _c, _vp], _c),
     "dvo_test_five_point": ([_vp, _vp, _vp, _vp, _ip], _c),
     "dvo_test_sampson": ([_vp, _vp, _vp, _c, ctypes.c_float, _vp, _vp], _c),
+    "dvo_test_ratio_gather": ([_vp, _vp, _vp, _c, _vp, _c, _vp, _c, _d, _c, _vp, _vp, _ip, _ip], _c),
     "dvo_test_ransac_subsets": ([_vp, _c, _c, _vp], _c),
     "dvo_test_ransac_replay": ([_vp, _vp, _vp, _c, _c, _d, _c, _vp], _c),
 }

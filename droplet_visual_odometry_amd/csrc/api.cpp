@@ -1220,28 +1220,15 @@ uint64_t therng_jump(uint64_t s, uint64_t k) {
 }
 }  // namespace
 
-// Replaces cv::FlannBasedMatcher(KDTREE, trees).knnMatch(query, train, k) with
-// search checks (the 'flann' mode, visual_odometry_v3.py:206-212); flann.hip.
-int dvo_flann_knn(dvo_ctx* ctx, const float* dq, int nq, const float* dt, int nt, int dim, int k, int trees,
-                  int checks, uint64_t* rng_state, int32_t* train_idx, float* dist) {
-    if (!ctx) return DVO_EINVAL;
-    if (!rng_state) return fail(ctx, DVO_EINVAL, "null theRNG state");
-    if (dim < 4 || dim > 256 || dim % 4) return fail(ctx, DVO_EINVAL, "dim must be a multiple of 4 in 4..256");
-    if (k < 1 || k > 4) return fail(ctx, DVO_EINVAL, "k must be 1..4");
-    if (trees < 1 || trees > 64 || checks < 1) return fail(ctx, DVO_EINVAL, "trees 1..64 and checks >= 1");
-    if (nq < 0 || nt < 0 || nq > (1 << 20) || nt > (1 << 16))
-        return fail(ctx, DVO_EINVAL, "descriptor counts out of range (queries 0..2^20, train 0..2^16)");
-    // DescriptorMatcher::knnMatch returns before training on an empty query or train set
-    if (nq == 0 || nt == 0) return DVO_OK;
-    if (!dq || !dt || !train_idx || !dist) return fail(ctx, DVO_EINVAL, "null buffer");
-    if (k > nt) return fail(ctx, DVO_EINVAL, "k exceeds the train set (FLANN asserts knn <= index size)");
-    HIP_TRY(hipSetDevice(ctx->device));
+// The kd-forest build and search of dvo_flann_knn on device descriptors (bq: nq x dim, bt: nt x dim,
+// already validated: nq, nt >= 1, k <= nt): scratch and the results (*d_idx, *d_dist: nq x k, valid
+// once the stream has run) come from the call's CallMem.  rng_state is the theRNG state before
+// the call; the caller advances it (flann_rng_after) when its call succeeds.
+static int flann_knn_device(dvo_ctx* ctx, CallMem& mem, const float* bq, int nq, const float* bt, int nt, int dim,
+                            int k, int trees, int checks, uint64_t rng_state, int32_t** d_idx, float** d_dist) {
     const int n = nt, draws = 2 * n - 1, nodes_per_tree = 2 * n - 1;
     constexpr int kChunks = 64;
     hipStream_t s = ctx->stream;
-    CallMem mem(ctx->call, s);
-    float* bq = mem.dev<float>((size_t)nq * dim);
-    float* bt = mem.dev<float>((size_t)nt * dim);
     uint32_t* bR = mem.dev<uint32_t>(draws);
     uint64_t* bcs = mem.dev<uint64_t>((size_t)trees * kChunks);
     int* bcnt = mem.dev<int>(n);
@@ -1267,9 +1254,7 @@ int dvo_flann_knn(dvo_ctx* ctx, const float* dq, int nq, const float* dt, int nt
     for (int t = 0; t < trees; ++t)
         for (int c = 0; c < kChunks; ++c)
             cs[(size_t)t * kChunks + c] =
-                therng_jump(*rng_state, (uint64_t)t * draws + (uint64_t)((int64_t)draws * c / kChunks));
-    HIP_TRY(mem.put(bq, dq, (size_t)nq * dim * 4));
-    HIP_TRY(mem.put(bt, dt, (size_t)nt * dim * 4));
+                therng_jump(rng_state, (uint64_t)t * draws + (uint64_t)((int64_t)draws * c / kChunks));
     HIP_TRY(mem.put(bcs, cs.data(), cs.size() * 8));
     // ind = 0..n-1 once; every tree shuffles the previous tree's final order (KDTreeIndex::buildIndex)
     {
@@ -1313,13 +1298,49 @@ int dvo_flann_knn(dvo_ctx* ctx, const float* dq, int nq, const float* dt, int nt
         HIP_TRY(launch_flann_search_global(sa, bredo + 1 + done, batch, bhd, bhn, s));
         done += batch;
     }
+    *d_idx = bidx;
+    *d_dist = bdist;
+    return DVO_OK;
+}
+// the theRNG state after a forest of `trees` trees over nt points: trees (2 nt - 1) draws on
+static uint64_t flann_rng_after(uint64_t state, int trees, int nt) {
+    return therng_jump(state, (uint64_t)trees * (uint64_t)(2 * nt - 1));
+}
+
+// Replaces cv::FlannBasedMatcher(KDTREE, trees).knnMatch(query, train, k) with
+// search checks (the 'flann' mode, visual_odometry_v3.py:206-212); flann.hip.
+int dvo_flann_knn(dvo_ctx* ctx, const float* dq, int nq, const float* dt, int nt, int dim, int k, int trees,
+                  int checks, uint64_t* rng_state, int32_t* train_idx, float* dist) {
+    if (!ctx) return DVO_EINVAL;
+    if (!rng_state) return fail(ctx, DVO_EINVAL, "null theRNG state");
+    if (dim < 4 || dim > 256 || dim % 4) return fail(ctx, DVO_EINVAL, "dim must be a multiple of 4 in 4..256");
+    if (k < 1 || k > 4) return fail(ctx, DVO_EINVAL, "k must be 1..4");
+    if (trees < 1 || trees > 64 || checks < 1) return fail(ctx, DVO_EINVAL, "trees 1..64 and checks >= 1");
+    if (nq < 0 || nt < 0 || nq > (1 << 20) || nt > (1 << 16))
+        return fail(ctx, DVO_EINVAL, "descriptor counts out of range (queries 0..2^20, train 0..2^16)");
+    // DescriptorMatcher::knnMatch returns before training on an empty query or train set
+    if (nq == 0 || nt == 0) return DVO_OK;
+    if (!dq || !dt || !train_idx || !dist) return fail(ctx, DVO_EINVAL, "null buffer");
+    if (k > nt) return fail(ctx, DVO_EINVAL, "k exceeds the train set (FLANN asserts knn <= index size)");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    CallMem mem(ctx->call, s);
+    float* bq = mem.dev<float>((size_t)nq * dim);
+    float* bt = mem.dev<float>((size_t)nt * dim);
+    HIP_TRY(mem.error());
+    HIP_TRY(mem.put(bq, dq, (size_t)nq * dim * 4));
+    HIP_TRY(mem.put(bt, dt, (size_t)nt * dim * 4));
+    int32_t* bidx = nullptr;
+    float* bdist = nullptr;
+    int rc = flann_knn_device(ctx, mem, bq, nq, bt, nt, dim, k, trees, checks, *rng_state, &bidx, &bdist);
+    if (rc) return rc;
     uint8_t *hi, *hd;
     HIP_TRY(mem.get(bidx, (size_t)nq * k * 4, &hi));
     HIP_TRY(mem.get(bdist, (size_t)nq * k * 4, &hd));
     HIP_TRY(hipStreamSynchronize(s));
     std::memcpy(train_idx, hi, (size_t)nq * k * 4);
     std::memcpy(dist, hd, (size_t)nq * k * 4);
-    *rng_state = therng_jump(*rng_state, (uint64_t)trees * draws);
+    *rng_state = flann_rng_after(*rng_state, trees, nt);
     return DVO_OK;
 }
 
@@ -1713,6 +1734,327 @@ int dvo_triangulate_points(dvo_ctx* ctx, const double* P1, const double* P2, con
     HIP_TRY(mem.get(dX, (size_t)k * 32, &hX));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     std::memcpy(X, hX, (size_t)k * 32);
+    return DVO_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The k-NN modes' pair path (knn_sift, surf, flann): detectAndCompute (v3:373), knnMatch(k = 2)
+// (v3:204, :212, :215), the ratio test and keypoint gather (v3:223-238, :355, :358),
+// findEssentialMat (v3:297) and recoverPose (v3:303) of one pair of host frames in one call.
+struct dvo_knn_pair {
+    dvo_ctx* ctx = nullptr;
+    dvo_knn_pair_config cfg{};
+    int dim = 0, kp_cap = 0, cus = 0;
+    struct Slot {  // one frame's features on the device
+        dvo_keypoint* kps = nullptr;
+        float* desc = nullptr;
+        int32_t* n = nullptr;  // device: count, detector overflow flags
+        int count = 0;         // the count, once read
+    };
+    Slot slot[2];
+    int prev = 0, cur = 1;      // the slots of the last pair's previous and current frame
+    bool cache_valid = false;   // slot[cur] may serve as the next pair's previous frame
+    bool have_pair = false;     // the slots and the match list describe the last call's pair
+    int last_m = 0;
+    float* pts = nullptr;            // [kp_cap][4]
+    dvo_dmatch* matches = nullptr;   // [kp_cap]
+    int32_t* words = nullptr;        // nmatch, missing-second-neighbour flag
+    PairHeader* hdr = nullptr;
+    dvo_pair_record* rec = nullptr;
+    DeviceAllocs mem;
+};
+
+namespace {
+int check_knn_pair_config(dvo_ctx* ctx, const dvo_knn_pair_config* c) {
+    if (c->width < 1 || c->height < 1 || c->width >= kMaxW || c->height >= kMaxW)
+        return fail(ctx, DVO_EINVAL, "image size out of range (1..4095)");
+    if (c->detector != DVO_DETECT_SIFT && c->detector != DVO_DETECT_SURF)
+        return fail(ctx, DVO_EINVAL, "detector must be DVO_DETECT_SIFT or DVO_DETECT_SURF");
+    if (c->matcher != DVO_MATCH_BF_L1 && c->matcher != DVO_MATCH_FLANN)
+        return fail(ctx, DVO_EINVAL, "matcher must be DVO_MATCH_BF_L1 or DVO_MATCH_FLANN");
+    if (c->detector == DVO_DETECT_SURF && !(c->hessian_threshold >= 0))
+        return fail(ctx, DVO_EINVAL, "hessianThreshold must be >= 0");
+    if (c->matcher == DVO_MATCH_FLANN && (c->trees < 1 || c->trees > 64 || c->checks < 1))
+        return fail(ctx, DVO_EINVAL, "trees 1..64 and checks >= 1");
+    if (!std::isfinite(c->ratio) || !(c->ratio > 0)) return fail(ctx, DVO_EINVAL, "ratio must be finite and > 0");
+    if (!(c->prob > 0 && c->prob < 1)) return fail(ctx, DVO_EINVAL, "prob must be in (0, 1)");
+    if (!(c->threshold > 0) || !std::isfinite(c->threshold))
+        return fail(ctx, DVO_EINVAL, "threshold must be finite and > 0");
+    if (c->max_iters < 1) return fail(ctx, DVO_EINVAL, "max_iters must be >= 1");
+    if (!std::isfinite(c->dist_thresh)) return fail(ctx, DVO_EINVAL, "distanceThresh must be finite");
+    return DVO_OK;
+}
+
+int knn_pair_plan(dvo_knn_pair* p) {
+    return p->cfg.detector == DVO_DETECT_SIFT ? sift_plan(p->ctx, p->cfg.width, p->cfg.height)
+                                              : surf_plan(p->ctx, p->cfg.width, p->cfg.height);
+}
+}  // namespace
+
+int dvo_knn_pair_create(dvo_ctx* ctx, const dvo_knn_pair_config* cfg, dvo_knn_pair** out) {
+    if (!ctx || !cfg || !out) return DVO_EINVAL;
+    *out = nullptr;
+    int rc = check_knn_pair_config(ctx, cfg);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::unique_ptr<dvo_knn_pair> p(new dvo_knn_pair);
+    p->ctx = ctx;
+    p->cfg = *cfg;
+    HIP_TRY(hipDeviceGetAttribute(&p->cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    if ((rc = knn_pair_plan(p.get()))) return rc;  // the context's detector plan sets the list capacity
+    const bool sift = cfg->detector == DVO_DETECT_SIFT;
+    p->dim = sift ? 128 : 64;
+    p->kp_cap = sift ? ctx->sift.a.kp_cap : ctx->surf.a.kp_cap;
+    const size_t kc = (size_t)p->kp_cap;
+    for (auto& sl : p->slot) {
+        HIP_TRY(p->mem.alloc(&sl.kps, kc * sizeof(dvo_keypoint)));
+        HIP_TRY(p->mem.alloc(&sl.desc, kc * p->dim * sizeof(float)));
+        HIP_TRY(p->mem.alloc(&sl.n, 2 * sizeof(int32_t)));
+    }
+    HIP_TRY(p->mem.alloc(&p->pts, kc * 4 * sizeof(float)));
+    HIP_TRY(p->mem.alloc(&p->matches, kc * sizeof(dvo_dmatch)));
+    HIP_TRY(p->mem.alloc(&p->words, 2 * sizeof(int32_t)));
+    HIP_TRY(p->mem.alloc(&p->hdr, sizeof(PairHeader)));
+    HIP_TRY(p->mem.alloc(&p->rec, sizeof(dvo_pair_record)));
+    *out = p.release();
+    return DVO_OK;
+}
+
+void dvo_knn_pair_destroy(dvo_knn_pair* p) {
+    if (!p) return;
+    hipSetDevice(p->ctx->device);
+    hipStreamSynchronize(p->ctx->stream);
+    delete p;
+}
+
+int dvo_knn_pair_run(dvo_knn_pair* p, const uint8_t* prev_img, const uint8_t* cur_img, int stride, int reuse_prev,
+                     uint64_t* rng_state, dvo_pair_record* rec_out) {
+    if (!p) return DVO_EINVAL;
+    dvo_ctx* ctx = p->ctx;
+    const dvo_knn_pair_config& c = p->cfg;
+    const int w = c.width, h = c.height;
+    const bool sift = c.detector == DVO_DETECT_SIFT, flann = c.matcher == DVO_MATCH_FLANN;
+    if (!cur_img || !rec_out || stride < w || (!reuse_prev && !prev_img)) return fail(ctx, DVO_EINVAL, "bad image buffer");
+    if (flann && !rng_state) return fail(ctx, DVO_EINVAL, "null theRNG state");
+    if (reuse_prev && !p->cache_valid)
+        return fail(ctx, DVO_EINVAL, "reuse_prev needs a preceding dvo_knn_pair_run that succeeded");
+    // the slots swap roles: the last pair's current frame is this pair's previous one
+    const int sp = reuse_prev ? p->cur : 0, sc = 1 - sp;
+    p->cache_valid = false;
+    p->have_pair = false;
+    HIP_TRY(hipSetDevice(ctx->device));
+    int rc = knn_pair_plan(p);  // another size may have taken the context's plan since
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    CallMem mem(ctx->call, s);
+    dvo_knn_pair::Slot &P = p->slot[sp], &C = p->slot[sc];
+    // host frames go up through pinned staging; the detection's n features go device to device into the slot
+    auto detect = [&](const uint8_t* img, dvo_knn_pair::Slot& sl) -> int {
+        uint8_t* hp = mem.host((size_t)w * h);
+        HIP_TRY(mem.error());
+        for (int y = 0; y < h; ++y) std::memcpy(hp + (size_t)y * w, img + (size_t)y * stride, w);
+        if (sift) {
+            SiftPlanDev& D = ctx->sift;
+            HIP_TRY(hipMemsetAsync(D.a.ncand, 0, 16, s));
+            HIP_TRY(hipMemcpy2DAsync(D.img, D.pitch, hp, w, w, h, hipMemcpyHostToDevice, s));
+            HIP_TRY(launch_sift(D.a, D.img, w, h, D.pitch, D.taps, D.tap_off, D.tap_n, s));
+            HIP_TRY(launch_feature_copy(D.a.kps, D.a.desc, D.a.nkp, D.a.flags, p->kp_cap, 128, sl.kps, sl.desc, sl.n, s));
+        } else {
+            SurfPlanDev& D = ctx->surf;
+            D.a.thr = (float)c.hessian_threshold;
+            HIP_TRY(hipMemsetAsync(D.a.nraw, 0, 16, s));
+            const int64_t cells = D.a.off[kSurfTot - 1] + (int64_t)D.a.rows[kSurfOct - 1] * D.a.cols[kSurfOct - 1];
+            HIP_TRY(hipMemsetAsync(D.a.det, 0, (size_t)cells * 4, s));
+            HIP_TRY(hipMemsetAsync(D.a.trace, 0, (size_t)cells * 4, s));
+            HIP_TRY(hipMemcpy2DAsync(D.img, D.a.pitch, hp, w, w, h, hipMemcpyHostToDevice, s));
+            HIP_TRY(launch_surf(D.a, s));
+            HIP_TRY(launch_feature_copy(D.a.out, D.a.desc, D.a.nout, D.a.flags, p->kp_cap, 64, sl.kps, sl.desc, sl.n, s));
+        }
+        return DVO_OK;
+    };
+    int m_kept = 0;
+    // after the first upload an error drains the stream before returning: its DMAs read the context's
+    // pinned buffers, which the next per-call entry point rewrites
+    auto body = [&]() -> int {
+        if (!reuse_prev && (rc = detect(prev_img, P))) return rc;
+        if ((rc = detect(cur_img, C))) return rc;
+        uint8_t *hnp = nullptr, *hnc = nullptr;
+        if (!reuse_prev) HIP_TRY(mem.get(P.n, 8, &hnp));
+        HIP_TRY(mem.get(C.n, 8, &hnc));
+        HIP_TRY(hipStreamSynchronize(s));
+        int32_t np2[2] = {P.count, 0}, nc2[2];
+        if (hnp) std::memcpy(np2, hnp, 8);
+        std::memcpy(nc2, hnc, 8);
+        if (np2[1] || nc2[1] || np2[0] > p->kp_cap || nc2[0] > p->kp_cap)
+            return fail(ctx, DVO_ECAP, sift ? "SIFT: more extrema / keypoints than the device lists hold"
+                                            : "SURF: more keypoints than the device lists hold");
+        const int nq = P.count = np2[0], nt = C.count = nc2[0];
+        dvo_pair_record r{};
+        r.n_kp_prev = nq;
+        r.n_kp_cur = nt;
+        // no descriptors (knnMatch on None raises, v3:204-215), or one train: `for m, n in matches`
+        // cannot unpack (v3:223) / FLANN asserts knn <= index size
+        if (nq == 0 || nt < 2) {
+            r.status = DVO_ENOFEAT;
+            *rec_out = r;
+            return DVO_OK;
+        }
+        int32_t* d_idx = nullptr;
+        float* d_dist = nullptr;
+        if (flann) {
+            if ((rc = flann_knn_device(ctx, mem, P.desc, nq, C.desc, nt, p->dim, 2, c.trees, c.checks, *rng_state, &d_idx,
+                                       &d_dist)))
+                return rc;
+        } else {
+            const int ranges = knn_ranges(nq, nt, p->cus);
+            const size_t out_n = (size_t)nq * 2, part_n = ranges > 1 ? (size_t)ranges * nq * 2 : 1;
+            d_dist = mem.dev<float>(out_n);
+            d_idx = mem.dev<int32_t>(out_n);
+            float* bpd = mem.dev<float>(part_n);
+            int32_t* bpi = mem.dev<int32_t>(part_n);
+            uint8_t* bb = mem.dev<uint8_t>(knn_bytes_size(nq, nt, p->dim));
+            HIP_TRY(mem.error());
+            HIP_TRY(launch_knn_float(P.desc, nq, C.desc, nt, p->dim, 2, DVO_NORM_L1, ranges, bb, bpd, bpi, d_dist, d_idx, s));
+        }
+        RatioArgs ra{d_idx, d_dist, P.kps, C.kps, nq, nq, nt, c.ratio, flann ? 1 : 0, p->pts, p->matches, p->words,
+                     p->hdr, p->words + 1};
+        HIP_TRY(launch_ratio_gather(ra, s));
+        // findEssentialMat and recoverPose as the per-call operators run them, on the kernel's count
+        const size_t hc = (size_t)c.max_iters;
+        GeomArgs g{};
+        g.pts_f = p->pts;
+        g.m_arr = p->words;
+        g.pts_stride = nq;
+        set_camera(g, c.K);
+        g.prob = c.prob;
+        g.threshold = c.threshold;
+        g.max_iters = c.max_iters;
+        g.dist_thresh = c.dist_thresh;
+        g.npts = mem.dev<double>((size_t)nq * 4);
+        g.models = mem.dev<double>(hc * 90);
+        g.E = mem.dev<double>(90);
+        g.info = mem.dev<int32_t>(4);
+        g.nmod = mem.dev<int32_t>(hc);
+        g.cnt = mem.dev<int32_t>(hc * 10);
+        g.subsets = mem.dev<int32_t>(hc * 5);
+        g.rs = mem.dev<RansacState>(1);
+        g.fprec = mem.dev<double>(((hc + 63) / 64) * 128 * 64);
+        g.dk_off = mem.dev<int32_t>(2);
+        g.a_off = mem.dev<int32_t>(2);
+        g.s_off = mem.dev<int32_t>(2);
+        g.dk_ctl = mem.dev<int32_t>(2 + kDkMaxPasses);
+        g.dk_list = mem.dev<int32_t>(hc * 2);
+        g.dk_list_cap = (int64_t)hc;
+        g.hyp_cap = (int)hc;
+        g.Rt = mem.dev<double>(12);
+        g.good = mem.dev<int32_t>(2);
+        g.pose_P = mem.dev<double>(72);
+        g.pose_cnt = mem.dev<int32_t>(5);
+        HIP_TRY(mem.error());
+        HIP_TRY(launch_geometry_args(g, 1, kStageNormalize | kStageRansac | kStageOneRound, s));
+        HIP_TRY(launch_retire(g, 1, p->hdr, p->rec, s));  // kStagePose and the record
+        uint8_t *hr = nullptr, *hw = nullptr;
+        HIP_TRY(mem.get(p->rec, sizeof(dvo_pair_record), &hr));
+        HIP_TRY(mem.get(p->words, 8, &hw));
+        HIP_TRY(hipStreamSynchronize(s));
+        int32_t words[2];
+        std::memcpy(&r, hr, sizeof(r));
+        std::memcpy(words, hw, 8);
+        // a query without a second neighbour (FLANN's approximate search only): `for m, n in matches` raises
+        if (words[1]) r.status = DVO_ENOFEAT;
+        m_kept = words[0];
+        *rec_out = r;
+        if (flann) *rng_state = flann_rng_after(*rng_state, c.trees, nt);
+        return DVO_OK;
+    };
+    if ((rc = body())) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    p->prev = sp;
+    p->cur = sc;
+    p->last_m = m_kept;
+    p->have_pair = true;
+    // the current frame's features serve the next pair only after a pair that got through: a failing
+    // pair (a status in the record, or an error) is redone from both frames
+    p->cache_valid = rec_out->status == DVO_OK;
+    return DVO_OK;
+}
+
+int dvo_knn_pair_get_matches(dvo_knn_pair* p, dvo_dmatch* out, int cap, int* m) {
+    if (!p || !m) return DVO_EINVAL;
+    dvo_ctx* ctx = p->ctx;
+    *m = 0;
+    if (!p->have_pair) return fail(ctx, DVO_EINVAL, "no pair has run");
+    *m = p->last_m;
+    if (p->last_m > cap) return fail(ctx, DVO_ECAP, "caller capacity too small");
+    if (p->last_m == 0) return DVO_OK;
+    if (!out) return fail(ctx, DVO_EINVAL, "null buffer");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(out, p->matches, (size_t)p->last_m * sizeof(dvo_dmatch), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return DVO_OK;
+}
+
+int dvo_knn_pair_get_features(dvo_knn_pair* p, int which, dvo_keypoint* kps, float* desc, int cap, int* n) {
+    if (!p || !n) return DVO_EINVAL;
+    dvo_ctx* ctx = p->ctx;
+    *n = 0;
+    if (which != 0 && which != 1) return fail(ctx, DVO_EINVAL, "which must be 0 (previous) or 1 (current)");
+    if (!p->have_pair) return fail(ctx, DVO_EINVAL, "no pair has run");
+    const dvo_knn_pair::Slot& sl = p->slot[which ? p->cur : p->prev];
+    *n = sl.count;
+    if (sl.count > cap) return fail(ctx, DVO_ECAP, "caller capacity too small");
+    if (sl.count == 0) return DVO_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (kps) HIP_TRY(hipMemcpyAsync(kps, sl.kps, (size_t)sl.count * sizeof(dvo_keypoint), hipMemcpyDeviceToHost, ctx->stream));
+    if (desc) HIP_TRY(hipMemcpyAsync(desc, sl.desc, (size_t)sl.count * p->dim * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return DVO_OK;
+}
+
+// Test hook: ratio_gather_kernel on host arrays.
+int dvo_test_ratio_gather(dvo_ctx* ctx, const int32_t* idx, const float* dist, int nq, const dvo_keypoint* kq, int nkq,
+                          const dvo_keypoint* kt, int nkt, double ratio, int squared, float* pts, dvo_dmatch* matches,
+                          int* m, int* missing_second) {
+    if (!ctx || !m || !missing_second) return DVO_EINVAL;
+    *m = 0;
+    *missing_second = 0;
+    if (nq < 0 || nq > (1 << 20) || nkq < nq || nkt < 0 || nkq > (1 << 20) || nkt > (1 << 20))
+        return fail(ctx, DVO_EINVAL, "counts out of range (0 <= nq <= nkq <= 2^20, 0 <= nkt <= 2^20)");
+    if (!std::isfinite(ratio) || !(ratio > 0)) return fail(ctx, DVO_EINVAL, "ratio must be finite and > 0");
+    if (nq > 0 && (!idx || !dist || !kq || !pts || !matches || (nkt > 0 && !kt))) return fail(ctx, DVO_EINVAL, "null buffer");
+    HIP_TRY(hipSetDevice(ctx->device));
+    CallMem mem(ctx->call, ctx->stream);
+    const size_t n1 = (size_t)std::max(nq, 1);
+    int32_t* d_idx = mem.dev<int32_t>(n1 * 2);
+    float* d_dist = mem.dev<float>(n1 * 2);
+    dvo_keypoint* d_kq = mem.dev<dvo_keypoint>((size_t)std::max(nkq, 1));
+    dvo_keypoint* d_kt = mem.dev<dvo_keypoint>((size_t)std::max(nkt, 1));
+    float* d_pts = mem.dev<float>(n1 * 4);
+    dvo_dmatch* d_m = mem.dev<dvo_dmatch>(n1);
+    int32_t* d_words = mem.dev<int32_t>(2);
+    PairHeader* d_hdr = mem.dev<PairHeader>(1);
+    HIP_TRY(mem.error());
+    HIP_TRY(mem.put(d_idx, idx, (size_t)nq * 8));
+    HIP_TRY(mem.put(d_dist, dist, (size_t)nq * 8));
+    HIP_TRY(mem.put(d_kq, kq, (size_t)nkq * sizeof(dvo_keypoint)));
+    HIP_TRY(mem.put(d_kt, kt, (size_t)nkt * sizeof(dvo_keypoint)));
+    RatioArgs ra{d_idx, d_dist, d_kq, d_kt, nq, nkq, nkt, ratio, squared ? 1 : 0, d_pts, d_m, d_words, d_hdr, d_words + 1};
+    HIP_TRY(launch_ratio_gather(ra, ctx->stream));
+    uint8_t *hw, *hp, *hm;
+    HIP_TRY(mem.get(d_words, 8, &hw));
+    HIP_TRY(mem.get(d_pts, (size_t)nq * 16, &hp));
+    HIP_TRY(mem.get(d_m, (size_t)nq * sizeof(dvo_dmatch), &hm));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    int32_t words[2];
+    std::memcpy(words, hw, 8);
+    *m = words[0];
+    *missing_second = words[1];
+    if (words[0] > 0) {
+        std::memcpy(pts, hp, (size_t)words[0] * 16);
+        std::memcpy(matches, hm, (size_t)words[0] * sizeof(dvo_dmatch));
+    }
     return DVO_OK;
 }
 

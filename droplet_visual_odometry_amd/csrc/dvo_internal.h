@@ -434,6 +434,28 @@ hipError_t launch_flann_search(const FlannSearchArgs& a, hipStream_t s);
 hipError_t launch_flann_redo_list(const int32_t* d_flag, int nq, int32_t* d_list, int32_t* d_count, hipStream_t s);
 hipError_t launch_flann_search_global(const FlannSearchArgs& a, const int32_t* d_list, int count, float* d_heap_d,
                                       int32_t* d_heap_n, hipStream_t s);
+// The k-NN modes' ratio test, ordered compaction and keypoint gather (ratio.hip): query q of the
+// matcher's k = 2 output is kept when (double)d0 < ratio * (double)d1, d the float32 values
+// DMatch.distance holds (squared: sqrtf of FLANN's squared L2).  Kept matches in ascending q.
+struct RatioArgs {
+    const int32_t* idx;       // [nq][2] train indices (-1: no such neighbour)
+    const float* dist;        // [nq][2]
+    const dvo_keypoint* kq;   // [nkq] query (previous frame) keypoints, nkq >= nq
+    const dvo_keypoint* kt;   // [nkt] train (current frame) keypoints
+    int nq, nkq, nkt;
+    double ratio;
+    int squared;
+    float* pts;               // [nq][4] (x1, y1, x2, y2): GeomArgs::pts_f
+    dvo_dmatch* matches;      // [nq] (q, idx[q][0], 0, d0)
+    int32_t* nmatch;          // kept count: GeomArgs::m_arr
+    PairHeader* hdr;          // {nkq, nkt, 0, 0}
+    int32_t* missing;         // 1 when some query has idx[q][1] < 0
+};
+hipError_t launch_ratio_gather(const RatioArgs& a, hipStream_t s);
+// dvo_knn_pair_run: min(*cnt, kp_cap) keypoints and dim-float descriptors of a detection into a
+// feature slot, dn = {*cnt, *flags}
+hipError_t launch_feature_copy(const dvo_keypoint* skps, const float* sdesc, const int32_t* cnt, const int32_t* flags,
+                               int kp_cap, int dim, dvo_keypoint* dkps, float* ddesc, int32_t* dn, hipStream_t s);
 hipError_t launch_test_retain_best(float* d_resp, uint32_t* d_payload, int32_t* d_tmp, int n, int n_points, int depth,
                                    int semantics, int* d_k, hipStream_t s);
 hipError_t launch_test_update_num_iters(double p, const double* d_ep, int n, int model_points, int max_iters,

@@ -28,6 +28,15 @@ Behaviour notes versus the reference:
       operator-by-operator path, so the 4x4s are identical.  Any pair the
       library reports as failing (status, or not exactly one E) is redone
       operator by operator, which raises where the reference raises.
+  D8  the same for the k-NN modes "knn_sift", "surf" and "flann" with the stock
+      SIFT / SURF detector and BFMatcher(NORM_L1) (flann: OpenCV 4.x semantics):
+      detect -> knnMatch(k=2) -> ratio test and keypoint gather -> findEssentialMat
+      -> recoverPose in ONE library call (ops.KnnPairStream / dvo_knn_pair_run);
+      descriptors, neighbour lists and kept points stay on the device.  In flann
+      mode the call starts from cv's theRNG state and the state it leaves is
+      committed only when the fused result is used; a failing pair is redone
+      operator by operator from the uncommitted state.  Mode "sift" (bf.match,
+      no neighbour list) stays operator by operator.
 
 Matches and keypoints are array-backed sequences (cv.DMatches, cv.KeyPoints):
 the ORB branch sorts by distance with a stable argsort (Python's sorted() is
@@ -153,7 +162,7 @@ class VisualOdometry:
         self.projection_matrix_list = []
         self.plot_4D_counter = 1
         self._features = _FeatureCache()
-        self._pair_engine = None  # (config key, FrameStream) of the fused pair path (D7)
+        self._pair_engine = None  # (config key, PairStream / KnnPairStream) of the fused pair path (D7, D8)
         self._pair_last = None    # content key of the last fused pair's current frame
         self.robot_curr_position = self.make_transform_mat(translation=self.starting_translation,
                                                            euler=self.starting_euler)
@@ -334,50 +343,92 @@ class VisualOdometry:
             self._features.put(key, hit)
         return hit
 
+    _PAIR_METHODS = ("compute_current_image_elements", "get_matches_between_two_frames", "previous_current_matching",
+                     "get_transformation_between_two_frames")
+    # k-NN modes -> (detector, matcher) of ops.KnnPairStream (D8); "sift" (bf.match, v3:201) is not one
+    _KNN_MODES = {"knn_sift": ("sift", "bf"), "surf": ("surf", "bf"), "flann": ("sift", "flann")}
+    # the modes whose fused path beat the operator path by the A/B margin (tools/time_knn_pair.py,
+    # profiles/knn_pair_time.txt); a mode left out stays operator by operator
+    _KNN_FUSED_MODES = frozenset(("knn_sift", "surf", "flann"))
+
     def _fused_pair(self, previous_image, current_image):
-        """(E, R, t) of the pair from one library call (D7), or None when the
-        stock operators are not in use or the library reports a failing pair."""
+        """(E, R, t) of the pair from one library call (D7: orb, D8: the k-NN modes), or
+        None when the stock operators are not in use or the library reports a failing pair."""
         cls = type(self)
-        if (self.mode != "orb" or type(self.feature_detector) is not cv.ORB or type(self.bf) is not cv.BFMatcher
-                or self.bf.normType != cv.NORM_HAMMING or not self.bf.crossCheck
-                or any(getattr(cls, m) is not getattr(VisualOdometry, m) for m in (
-                    "compute_current_image_elements", "get_matches_between_two_frames", "previous_current_matching",
-                    "get_transformation_between_two_frames"))):
+        if any(getattr(cls, m) is not getattr(VisualOdometry, m) for m in self._PAIR_METHODS):
+            return None
+        if type(self.bf) is not cv.BFMatcher:
+            return None
+        if self.mode == "orb":
+            if (type(self.feature_detector) is not cv.ORB or self.bf.normType != cv.NORM_HAMMING
+                    or not self.bf.crossCheck):
+                return None
+            min_side = 8
+        elif self.mode in self._KNN_MODES and self.mode in self._KNN_FUSED_MODES:
+            want = cv.SURF if self.mode == "surf" else cv.SIFT
+            if type(self.feature_detector) is not want or self.bf.normType != cv.NORM_L1 or self.bf.crossCheck:
+                return None
+            if self.mode == "flann" and cv.opencv_semantics(cv.OPENCV_SEMANTICS) != 0:
+                return None  # FlannBasedMatcher raises for OpenCV 3.2: the operator path says so
+            min_side = 1
+        else:
             return None
         prev = np.asarray(previous_image)
         cur = np.asarray(current_image)
         if prev.dtype != np.uint8 or cur.dtype != np.uint8 or prev.ndim != 2 or prev.shape != cur.shape:
             return None
         h, w = cur.shape
-        if not (8 <= w < 4096 and 8 <= h < 4096):
+        if not (min_side <= w < 4096 and min_side <= h < 4096):
             return None
         K = np.ascontiguousarray(self.intrinsic_coefficient_matrix, np.float64)
         if K.shape != (3, 3):
             return None
+        from droplet_visual_odometry_amd import ops
         det = self.feature_detector
-        cc = 2 if self.bf.legacy_crosscheck else 1
-        cfg = (w, h, det.nfeatures, det.fastThreshold, det.opencv, K.tobytes(), cc)
+        if self.mode == "orb":
+            cc = 2 if self.bf.legacy_crosscheck else 1
+            cfg = (w, h, det.nfeatures, det.fastThreshold, det.opencv, K.tobytes(), cc)
+        else:
+            hessian = det.hessianThreshold if self.mode == "surf" else None
+            cfg = (w, h, self.mode, hessian, K.tobytes())
         if self._pair_engine is None or self._pair_engine[0] != cfg:
-            from droplet_visual_odometry_amd import ops
             self._pair_engine = None
             self._pair_last = None
-            self._pair_engine = (cfg, ops.PairStream(w, h, K, nfeatures=det.nfeatures, fast_threshold=det.fastThreshold,
-                                                     cross_check=cc, opencv=det.opencv))
+            if self.mode == "orb":
+                engine = ops.PairStream(w, h, K, nfeatures=det.nfeatures, fast_threshold=det.fastThreshold,
+                                        cross_check=cc, opencv=det.opencv)
+            else:
+                detector, matcher = self._KNN_MODES[self.mode]
+                engine = ops.KnnPairStream(w, h, K, detector=detector, matcher=matcher,
+                                           hessian_threshold=400.0 if hessian is None else hessian)
+            self._pair_engine = (cfg, engine)
         fs = self._pair_engine[1]
         kprev, kcur = _FeatureCache.key(prev), _FeatureCache.key(cur)
         reuse = self._pair_last is not None and self._pair_last == kprev
         self._pair_last = None
-        rec = fs.pair(None if reuse else prev, cur, reuse_prev=reuse)
-        self._pair_last = kcur
+        if self.mode == "orb":
+            rec = fs.pair(None if reuse else prev, cur, reuse_prev=reuse)
+            self._pair_last = kcur
+        else:
+            # D8.  flann: the forest is drawn from cv::theRNG(); the state it leaves is committed only
+            # when this result is used, so a pair redone operator by operator starts from the same state
+            try:
+                rec, rng_after = fs.pair(None if reuse else prev, cur, reuse_prev=reuse, rng_state=cv._the_rng())
+            except ops.DVOError:
+                return None
+            if rec["status"] == 0:  # the engine keeps the current frame's features only after such a pair
+                self._pair_last = kcur
         if rec["status"] != 0 or rec["n_models"] != 1:
             return None
+        if self.mode == "flann":
+            cv._rng_tls.state = rng_after
         return rec["E"].reshape(3, 3).copy(), rec["R"].reshape(3, 3).copy(), rec["t"].reshape(3, 1).copy()
 
     def visual_odometry_calculations(self, previous_image, current_image, robot_previous_position_transformation,
                                      previous_marker_corners, current_marker_corners):
         """(T_robot_current, T_previous_to_current) for one frame pair (v3:384-408)."""
         fused = self._fused_pair(previous_image, current_image)
-        if fused is not None:  # D7: detect -> match -> E -> R, t in one call, then the same host tail
+        if fused is not None:  # D7 / D8: detect -> match -> E -> R, t in one call, then the same host tail
             self.essential_matrix, relative_rotation, translation = fused
             rel = self._relative_transform(relative_rotation, translation, previous_marker_corners,
                                            current_marker_corners)

@@ -8,6 +8,9 @@ mirrors its argument meaning, output layout and failure points:
   bf_match             cv::BFMatcher(NORM_HAMMING).match  visual_odometry_v3.py:75, :219
   bf_knn_float         cv::BFMatcher(NORM_L1).knnMatch / .match, FLANN knnMatch
                                                           visual_odometry_v3.py:99-106, :200-215
+  flann_knn            cv::FlannBasedMatcher(KDTREE).knnMatch  visual_odometry_v3.py:206-212
+  KnnPairStream        detect + knnMatch + ratio test + E + recoverPose of one pair in the
+                       knn_sift / surf / flann modes      visual_odometry_v3.py:373, :204-238, :297, :303
   find_essential_mat   cv::findEssentialMat(RANSAC)       visual_odometry_v3.py:297-300
   recover_pose         cv::recoverPose                    visual_odometry_v3.py:303-306
   triangulate_points   cv::triangulatePoints              visual_odometry_v3.py:265
@@ -677,6 +680,112 @@ class PairStream:
     def close(self):
         if getattr(self, "h", None):
             self.ctx.lib.dvo_stream_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def test_ratio_gather(idx, dist, kq, kt, ratio=0.75, squared=False, ctx=None):
+    """Device ratio test + ordered keypoint gather (ratio_gather_kernel) on a matcher's
+    k = 2 output: (pts float32[M, 4], matches DMATCH_DTYPE[M], missing_second flag)."""
+    c = _ctx(ctx)
+    idx = np.ascontiguousarray(idx, np.int32).reshape(-1, 2)
+    dist = np.ascontiguousarray(dist, np.float32).reshape(-1, 2)
+    kq = np.ascontiguousarray(kq, KEYPOINT_DTYPE)
+    kt = np.ascontiguousarray(kt, KEYPOINT_DTYPE)
+    nq = len(idx)
+    pts = np.zeros((max(nq, 1), 4), np.float32)
+    matches = np.zeros(max(nq, 1), DMATCH_DTYPE)
+    m, miss = ctypes.c_int(), ctypes.c_int()
+    c.check(c.lib.dvo_test_ratio_gather(c.h, ptr(idx), ptr(dist), nq, ptr(kq), len(kq), ptr(kt), len(kt), float(ratio),
+                                        int(bool(squared)), ptr(pts), ptr(matches), ctypes.byref(m), ctypes.byref(miss)))
+    return pts[:m.value].copy(), matches[:m.value].copy(), bool(miss.value)
+
+
+KNN_DETECTORS = {"sift": 0, "surf": 1}
+KNN_MATCHERS = {"bf": 0, "flann": 1}
+
+
+class KnnPairStream:
+    """One pair of host frames per call through the whole per-pair path of the
+    k-NN modes (dvo_knn_pair_run): SIFT / SURF detectAndCompute of both frames,
+    knnMatch(k=2) with BFMatcher(NORM_L1) or the FLANN kd-forest, the ratio test
+    and keypoint gather, findEssentialMat(RANSAC) and recoverPose
+    (visual_odometry_v3.py:384-408 up to v3:303) in one synchronous library
+    call: one frame up, the 256-B pair record back.  With reuse_prev=True the
+    previous frame is the last call's current frame (allowed after a pair whose
+    record status is 0).  The drop-in's fused path (D8) uses it; no torch involved."""
+
+    def __init__(self, width, height, K, detector="sift", matcher="bf", hessian_threshold=400.0, trees=5, checks=50,
+                 ratio=0.75, prob=0.999, threshold=1.0, max_iters=1000, dist_thresh=50.0, ctx=None):
+        from ._native import KnnPairConfig
+        self.ctx = _ctx(ctx)
+        cfg = KnnPairConfig()
+        cfg.width, cfg.height = int(width), int(height)
+        cfg.detector = KNN_DETECTORS[detector] if isinstance(detector, str) else int(detector)
+        cfg.matcher = KNN_MATCHERS[matcher] if isinstance(matcher, str) else int(matcher)
+        cfg.hessian_threshold, cfg.trees, cfg.checks = float(hessian_threshold), int(trees), int(checks)
+        cfg.ratio = float(ratio)
+        K = np.asarray(K, np.float64).reshape(9)
+        for i in range(9):
+            cfg.K[i] = float(K[i])
+        cfg.prob, cfg.threshold, cfg.max_iters = float(prob), float(threshold), int(max_iters)
+        cfg.dist_thresh = float(dist_thresh)
+        self.h = None
+        h = ctypes.c_void_p()
+        self.ctx.check(self.ctx.lib.dvo_knn_pair_create(self.ctx.h, ctypes.byref(cfg), ctypes.byref(h)))
+        self.h = h
+        self.width, self.height = int(width), int(height)
+        self.dim = 64 if cfg.detector == 1 else 128
+        self.flann = cfg.matcher == 1
+
+    def pair(self, prev_img, cur_img, reuse_prev=False, rng_state=None):
+        """(record, theRNG state after the call); rng_state: cv::theRNG()'s state before it
+        (FLANN; default a fresh thread's)."""
+        cur = np.ascontiguousarray(cur_img, np.uint8)
+        if cur.shape != (self.height, self.width):
+            raise ValueError(f"frame shape {cur.shape} != {(self.height, self.width)}")
+        prev = None
+        if not reuse_prev:
+            prev = np.ascontiguousarray(prev_img, np.uint8)
+            if prev.shape != cur.shape:
+                raise ValueError("previous and current frames differ in shape")
+        rec = np.zeros(1, PAIR_RECORD_DTYPE)
+        st = ctypes.c_uint64(THE_RNG_SEED if rng_state is None else int(rng_state))
+        self.ctx.check(self.ctx.lib.dvo_knn_pair_run(self.h, ptr(prev), ptr(cur), self.width, int(bool(reuse_prev)),
+                                                     ctypes.byref(st), ptr(rec)))
+        return rec[0], int(st.value)
+
+    def matches(self) -> np.ndarray:
+        """The last pair's kept matches (DMATCH_DTYPE), in ascending queryIdx."""
+        m = ctypes.c_int()
+        rc = self.ctx.lib.dvo_knn_pair_get_matches(self.h, None, 0, ctypes.byref(m))
+        if rc != DVO_ECAP:
+            self.ctx.check(rc)
+        out = np.zeros(max(m.value, 1), DMATCH_DTYPE)
+        self.ctx.check(self.ctx.lib.dvo_knn_pair_get_matches(self.h, ptr(out), len(out), ctypes.byref(m)))
+        return out[:m.value].copy()
+
+    def features(self, which):
+        """(keypoints KEYPOINT_DTYPE[N], descriptors float32[N, dim]) of the last pair's
+        previous (which = 0) or current (1) frame."""
+        n = ctypes.c_int()
+        rc = self.ctx.lib.dvo_knn_pair_get_features(self.h, int(which), None, None, 0, ctypes.byref(n))
+        if rc != DVO_ECAP:
+            self.ctx.check(rc)
+        kps = np.zeros(max(n.value, 1), KEYPOINT_DTYPE)
+        desc = np.zeros((max(n.value, 1), self.dim), np.float32)
+        self.ctx.check(self.ctx.lib.dvo_knn_pair_get_features(self.h, int(which), ptr(kps), ptr(desc), len(kps),
+                                                              ctypes.byref(n)))
+        return kps[:n.value].copy(), desc[:n.value].copy()
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.dvo_knn_pair_destroy(self.h)
             self.h = None
 
     def __del__(self):

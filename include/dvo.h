@@ -312,6 +312,64 @@ int dvo_stream_retired(dvo_stream* s, void** records, int* pairs, int cap);
  * Images: w x h mono8, rows `stride` bytes apart.  Needs max_frames >= 2. */
 int dvo_stream_pair(dvo_stream* s, const uint8_t* prev_img, const uint8_t* cur_img, int stride, int reuse_prev,
                     dvo_pair_record* rec_out);
+/* One pair of HOST frames through the whole per-pair path of the k-NN modes
+ * ('knn_sift', 'surf', 'flann') in one synchronous call: the device half of
+ * visual_odometry_calculations (v3:384-408) --
+ *   detectAndCompute with SIFT or SURF (v3:373; construction v3:100, :104),
+ *   knnMatch(k = 2) through BFMatcher(NORM_L1) (v3:204, :215) or the FLANN
+ *     kd-forest (v3:206-212),
+ *   the ratio test `m.distance < ratio * n.distance` and the keypoint gather
+ *     (v3:223-238) with KeyPoint_convert (v3:355, :358), in ascending queryIdx
+ *     order, evaluated as Python does: float32 distances (for FLANN the float32
+ *     square root of its squared L2), double product, strict compare,
+ *   findEssentialMat(RANSAC, prob, threshold) (v3:297) and recoverPose (v3:303)
+ * -- returning the pair's record.  Descriptors, neighbour lists and kept points
+ * never leave the device: one frame goes up, 256 bytes come back.  E, R, t and
+ * the counts are those of the per-call operators (dvo_sift_ / dvo_surf_detect_and_compute,
+ * dvo_bf_knn_float / dvo_flann_knn, dvo_find_essential_mat, dvo_recover_pose)
+ * on the same frames.  Runs on the context's stream; synchronous at return.
+ *
+ * The handle keeps two feature slots (keypoints, descriptors, count at the
+ * detector's list capacity).  reuse_prev = 1: the previous frame is the last
+ * call's current frame (prev_img may be NULL) and only cur_img is detected.  That
+ * is allowed only after a call that returned DVO_OK with record status DVO_OK; any
+ * other call invalidates the cache and reuse_prev is then refused (DVO_EINVAL).
+ *
+ * Record: n_kp_prev / n_kp_cur are the detector counts, n_matches the kept
+ * matches.  status DVO_ENOFEAT: a frame without keypoints (knnMatch on None
+ * raises), fewer than 2 train descriptors or a query without a second
+ * neighbour (`for m, n in matches` cannot unpack, v3:223); DVO_EFEWPTS: fewer
+ * than 5 kept matches; the geometry's statuses otherwise.  The call returns
+ * DVO_ECAP when a detector list overflowed.
+ * rng_state (FLANN): cv::theRNG()'s state, in/out as in dvo_flann_knn; it
+ * advances (trees * (2 n_kp_cur - 1) draws) only when the forest was built and
+ * the call returned DVO_OK.  With DVO_MATCH_BF_L1 it may be NULL.
+ * DVO_EINVAL (create, before any allocation): width / height outside 1..4095,
+ * unknown detector or matcher, ratio not finite or <= 0, hessian_threshold < 0,
+ * trees outside 1..64, checks < 1, and prob / threshold / max_iters /
+ * dist_thresh as in dvo_find_essential_mat / dvo_recover_pose. */
+typedef struct dvo_knn_pair dvo_knn_pair;
+#define DVO_DETECT_SIFT 0
+#define DVO_DETECT_SURF 1
+#define DVO_MATCH_BF_L1 0
+#define DVO_MATCH_FLANN 1
+typedef struct {
+    int32_t width, height;
+    int32_t detector, matcher;
+    double hessian_threshold;   /* SURF, 400 */
+    int32_t trees, checks;      /* FLANN, 5 / 50 */
+    double ratio;               /* 0.75 */
+    double K[9];
+    double prob, threshold; int32_t max_iters; double dist_thresh;
+} dvo_knn_pair_config;
+int dvo_knn_pair_create(dvo_ctx* ctx, const dvo_knn_pair_config* cfg, dvo_knn_pair** out);
+void dvo_knn_pair_destroy(dvo_knn_pair* p);
+int dvo_knn_pair_run(dvo_knn_pair* p, const uint8_t* prev_img, const uint8_t* cur_img, int stride, int reuse_prev,
+                     uint64_t* rng_state /* FLANN: in/out as dvo_flann_knn; else may be NULL */, dvo_pair_record* rec_out);
+/* The last pair's kept matches (queryIdx, trainIdx, 0, distance), ascending queryIdx; *m = count (DVO_ECAP if > cap). */
+int dvo_knn_pair_get_matches(dvo_knn_pair* p, dvo_dmatch* out, int cap, int* m);
+/* The last pair's features: which 0 previous, 1 current frame; desc n x 128 (SIFT) or n x 64 (SURF) floats. */
+int dvo_knn_pair_get_features(dvo_knn_pair* p, int which, dvo_keypoint* kps, float* desc, int cap, int* n);
 /* dvo_stream_process on undistorted frames: the n raw frames are remapped by u
  * into the stream's own frame slab first (same HIP stream), as the reference
  * undistorts every frame before detection (v3:120, v3:135). */
@@ -535,6 +593,15 @@ int dvo_test_five_point(dvo_ctx* ctx, const double* q1, const double* q2, double
  * exact[i] = the f64 test (computeError, err <= t). */
 int dvo_test_sampson(dvo_ctx* ctx, const double* E, const double* pts, int n, float t, int8_t* dec,
                      uint8_t* exact);
+/* The ratio test and keypoint gather of dvo_knn_pair_run (v3:223-238) on a matcher's
+ * k = 2 output: idx / dist nq x 2 (squared = 1: dist holds FLANN's squared L2), kq
+ * (nkq >= nq) and kt the query and train keypoints.  Query q is kept when
+ * (double)d0 < ratio * (double)d1.  pts: m x (x1, y1, x2, y2) floats, matches: m
+ * entries, both in ascending q (caller buffers of nq entries); *missing_second = 1
+ * when some idx[q][1] < 0. */
+int dvo_test_ratio_gather(dvo_ctx* ctx, const int32_t* idx, const float* dist, int nq, const dvo_keypoint* kq, int nkq,
+                          const dvo_keypoint* kt, int nkt, double ratio, int squared, float* pts, dvo_dmatch* matches,
+                          int* m, int* missing_second);
 
 #ifdef __cplusplus
 }
