@@ -188,6 +188,8 @@ _SIGNATURES = {
     "dvo_test_ratio_gather": ([_vp, _vp, _vp, _c, _vp, _c, _vp, _c, _d, _c, _vp, _vp, _ip, _ip], _c),
     "dvo_test_ransac_subsets": ([_vp, _c, _c, _vp], _c),
     "dvo_test_ransac_replay": ([_vp, _vp, _vp, _c, _c, _d, _c, _vp], _c),
+    "dvo_test_ransac_hypotheses": ([_vp, _vp, _vp, _c, _c, _vp, _d, _d, _c, _c, _vp, _vp, _vp, _vp, _vp, _vp, _ip,
+                                    _vp, _vp], _c),
 }
 
 _lib = None

@@ -2159,6 +2159,117 @@ int dvo_test_ransac_replay(dvo_ctx* ctx, const int32_t* nmod, const int32_t* cnt
     return DVO_OK;
 }
 
+int dvo_test_ransac_hypotheses(dvo_ctx* ctx, const double* pts, const int32_t* m, int P, int stride, const double* K,
+                               double prob, double threshold, int n_hyp, int schedule, int32_t* subsets,
+                               int32_t* nmod, double* models, int32_t* cnt, int32_t* state, int32_t* bounds,
+                               int* n_rounds, int32_t* path, int32_t* parked) {
+    if (!ctx || !pts || !m || !K || !subsets || !nmod || !models || !cnt || !state || !bounds || !n_rounds || !path ||
+        !parked)
+        return DVO_EINVAL;
+    if (P < 1 || stride < 1 || n_hyp < 1 || n_hyp > (1 << 20) || (int64_t)P * n_hyp > (1 << 24))
+        return fail(ctx, DVO_EINVAL, "bad pair or hypothesis count");
+    if (schedule != DVO_TEST_SCHED_CALL && schedule != DVO_TEST_SCHED_BATCH_ONE &&
+        schedule != DVO_TEST_SCHED_BATCH_ROUNDS)
+        return fail(ctx, DVO_EINVAL, "unknown schedule");
+    if (schedule == DVO_TEST_SCHED_CALL && P != 1) return fail(ctx, DVO_EINVAL, "the per-call schedule takes one pair");
+    if (!(prob > 0 && prob < 1) || !(threshold > 0) || !std::isfinite(threshold))
+        return fail(ctx, DVO_EINVAL, "bad prob or threshold");
+    for (int p = 0; p < P; ++p)
+        if (m[p] < 0 || m[p] > stride) return fail(ctx, DVO_EINVAL, "m[p] must be in [0, stride]");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t hc = (size_t)n_hyp, PH = (size_t)P * hc, npt = (size_t)P * stride * 4;
+    const size_t nblocks = (PH + 63) / 64 + 1, nrec = nblocks * 128 * 64;
+    const bool one = schedule != DVO_TEST_SCHED_BATCH_ROUNDS;
+    CallMem mem(ctx->call, ctx->stream);
+    GeomArgs g{};
+    double* dpts = mem.dev<double>(npt);
+    int32_t* dm = mem.dev<int32_t>(P);
+    g.pts_d = dpts;
+    g.m_arr = dm;
+    g.pts_stride = stride;
+    set_camera(g, K);
+    g.prob = prob;
+    g.threshold = threshold;
+    g.max_iters = n_hyp;
+    g.hyp_cap = n_hyp;
+    g.npts = mem.dev<double>(npt);
+    g.models = mem.dev<double>(PH * 90);
+    g.E = mem.dev<double>((size_t)P * 90);
+    g.info = mem.dev<int32_t>((size_t)P * 4);
+    g.nmod = mem.dev<int32_t>(PH);
+    g.cnt = mem.dev<int32_t>(PH * 10);
+    g.subsets = mem.dev<int32_t>(PH * 5);
+    g.rs = mem.dev<RansacState>(P);
+    g.fprec = mem.dev<double>(nrec);
+    g.dk_off = mem.dev<int32_t>((size_t)P + 1);
+    g.a_off = mem.dev<int32_t>((size_t)P + 1);
+    g.s_off = mem.dev<int32_t>((size_t)P + 1);
+    g.dk_ctl = mem.dev<int32_t>(2 + kDkMaxPasses);
+    g.dk_list = mem.dev<int32_t>((size_t)(kDkMaxPasses - 1) * PH);
+    g.dk_list_cap = (int64_t)PH;
+    HIP_TRY(mem.error());
+    HIP_TRY(mem.put(dpts, pts, npt * 8));
+    HIP_TRY(mem.put(dm, m, (size_t)P * 4));
+    // what a launch does not write stays recognisable: nmod -1 (hypothesis not evaluated), the rest 0
+    HIP_TRY(hipMemsetAsync(g.nmod, 0xFF, PH * 4, ctx->stream));
+    HIP_TRY(hipMemsetAsync(g.models, 0, PH * 90 * 8, ctx->stream));
+    HIP_TRY(hipMemsetAsync(g.cnt, 0, PH * 10 * 4, ctx->stream));
+    HIP_TRY(hipMemsetAsync(g.subsets, 0, PH * 5 * 4, ctx->stream));
+    HIP_TRY(hipMemsetAsync(g.rs, 0, (size_t)P * sizeof(RansacState), ctx->stream));
+    HIP_TRY(hipMemsetAsync(g.fprec, 0, nrec * 8, ctx->stream));
+    HIP_TRY(hipMemsetAsync(g.dk_off, 0, ((size_t)P + 1) * 4, ctx->stream));
+    HIP_TRY(hipMemsetAsync(g.dk_ctl, 0, (2 + kDkMaxPasses) * 4, ctx->stream));
+    if (schedule == DVO_TEST_SCHED_CALL) {
+        HIP_TRY(launch_geometry_args(g, 1, kStageNormalize | kStageRansac | kStageOneRound, ctx->stream));
+    } else if (schedule == DVO_TEST_SCHED_BATCH_ONE) {
+        HIP_TRY(launch_test_ransac_one_round(g, P, ctx->stream));
+    } else {
+        HIP_TRY(launch_geometry_args(g, P, kStageNormalize | kStageRansac, ctx->stream));
+    }
+    uint8_t *hsub, *hnmod, *hmodels, *hcnt, *hrs, *hrec = nullptr, *hoff = nullptr, *hctl = nullptr;
+    HIP_TRY(mem.get(g.subsets, PH * 5 * 4, &hsub));
+    HIP_TRY(mem.get(g.nmod, PH * 4, &hnmod));
+    HIP_TRY(mem.get(g.models, PH * 90 * 8, &hmodels));
+    HIP_TRY(mem.get(g.cnt, PH * 10 * 4, &hcnt));
+    HIP_TRY(mem.get(g.rs, (size_t)P * sizeof(RansacState), &hrs));
+    if (one) {
+        HIP_TRY(mem.get(g.fprec, nrec * 8, &hrec));
+        HIP_TRY(mem.get(g.dk_off, ((size_t)P + 1) * 4, &hoff));
+        HIP_TRY(mem.get(g.dk_ctl, (2 + kDkMaxPasses) * 4, &hctl));
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    std::memcpy(subsets, hsub, PH * 5 * 4);
+    std::memcpy(nmod, hnmod, PH * 4);
+    std::memcpy(models, hmodels, PH * 90 * 8);
+    std::memcpy(cnt, hcnt, PH * 10 * 4);
+    for (int p = 0; p < P; ++p) {
+        RansacState S;
+        std::memcpy(&S, hrs + (size_t)p * sizeof(S), sizeof(S));
+        const int32_t st[5] = {S.iter, S.niters, S.maxgood, S.best_h, S.best_i};
+        std::memcpy(state + 5 * p, st, sizeof(st));
+    }
+    if (one) {
+        *n_rounds = 1;
+        bounds[0] = 1 << 30;
+        // the one round's records: hypothesis h of pair p is work item dk_off[p] + h (h0 = 0)
+        const double* rec = reinterpret_cast<const double*>(hrec);
+        const int32_t* off = reinterpret_cast<const int32_t*>(hoff);
+        for (int p = 0; p < P; ++p)
+            for (size_t h = 0; h < hc; ++h) {
+                const size_t o = (size_t)p * hc + h;
+                const int64_t item = (int64_t)off[p] + (int64_t)h;
+                path[o] = nmod[o] < 0 || item >= off[p + 1] ? -1 : (int32_t)rec[test_record_generic_offset(item)];
+            }
+        std::memcpy(parked, hctl + 2 * 4, kDkMaxPasses * 4);
+    } else {
+        *n_rounds = kRansacRounds;
+        for (int r = 0; r < kRansacRounds; ++r) bounds[r] = kRansacBounds[r];
+        for (size_t o = 0; o < PH; ++o) path[o] = -1;
+        for (int k = 0; k < kDkMaxPasses; ++k) parked[k] = -1;
+    }
+    return DVO_OK;
+}
+
 int dvo_test_five_point(dvo_ctx* ctx, const double* q1, const double* q2, double* models, int* n) {
     if (!ctx || !q1 || !q2 || !models || !n) return DVO_EINVAL;
     HIP_TRY(hipSetDevice(ctx->device));

@@ -462,6 +462,8 @@ hipError_t launch_test_update_num_iters(double p, const double* d_ep, int n, int
                                         int32_t* d_out, hipStream_t s);
 hipError_t launch_test_ransac_sample(const GeomArgs& g, hipStream_t s);
 hipError_t launch_test_ransac_replay(const GeomArgs& g, hipStream_t s);
+hipError_t launch_test_ransac_one_round(const GeomArgs& g, int pairs, hipStream_t s);
+int64_t test_record_generic_offset(int64_t item);
 hipError_t launch_test_five_point(const double* d_q, double* d_models, int* d_n, hipStream_t s);
 hipError_t launch_test_sampson(const double* d_E, const double* d_pts, int n, float t, int8_t* d_dec, uint8_t* d_ex,
                                hipStream_t s);

@@ -2640,6 +2640,23 @@ hipError_t launch_test_ransac_replay(const GeomArgs& g, hipStream_t s) {
     return hipGetLastError();
 }
 
+// dvo_test_ransac_hypotheses' BATCH_ONE schedule: the batch kernels over every hypothesis up to
+// the cap as one round (normalize, then launch_round as a stream's round 0 with no bound).
+hipError_t launch_test_ransac_one_round(const GeomArgs& g, int pairs, hipStream_t s) {
+    RoundSpec sp{};
+    sp.nsets = 1;
+    sp.F = pairs;
+    sp.npairs[0] = pairs;
+    sp.round[0] = 0;
+    sp.bound[0] = 1 << 30;
+    hipLaunchKernelGGL(normalize_kernel, dim3(4, pairs), dim3(256), 0, s, g);
+    return launch_round(g, sp, false, s);
+}
+// Where work item `item` keeps its kRecGeneric flag in a host copy of GeomArgs::fprec (item_record's layout).
+int64_t test_record_generic_offset(int64_t item) {
+    return ((item >> 6) * kRecDoubles) * 64 + (item & 63) + (int64_t)kRecGeneric * 64;
+}
+
 hipError_t launch_test_update_num_iters(double p, const double* d_ep, int n, int model_points, int max_iters,
                                         int32_t* d_out, hipStream_t s) {
     hipLaunchKernelGGL(test_update_num_iters_kernel, dim3((n + 255) / 256), dim3(256), 0, s, p, d_ep, n, model_points,

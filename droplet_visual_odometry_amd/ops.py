@@ -254,6 +254,45 @@ def test_ransac_replay(nmod, cnt, m, prob=0.999, max_iters=1000, ctx=None):
     return tuple(int(v) for v in out)
 
 
+RANSAC_SCHEDULES = {"CALL": 0, "BATCH_ONE": 1, "BATCH_ROUNDS": 2}  # include/dvo.h DVO_TEST_SCHED_*
+
+
+def test_ransac_hypotheses(sets, K, n_hyp, schedule, threshold=1.0, prob=0.999, ctx=None):
+    """Everything the production RANSAC kernels computed for the first n_hyp hypotheses of each
+    point set of `sets` (a list of (p1, p2), m x 2 pixel coordinates each, m may be 0), launched
+    together under `schedule` ("CALL": the per-call findEssentialMat, one set; "BATCH_ONE": the
+    batch kernels as one round; "BATCH_ROUNDS": the stream's round schedule).  Returns a dict:
+    subsets (P, n, 5), nmod (P, n) (-1: not evaluated), models (P, n, 10, 9), cnt (P, n, 10),
+    state (P, 5) (iterations, niters, max good, best h, best model), bounds (the round bounds),
+    and for the one-round schedules path (P, n) and parked (4,), else None."""
+    c = _ctx(ctx)
+    P = len(sets)
+    ms = np.array([len(np.asarray(p1).reshape(-1, 2)) for p1, _ in sets], np.int32)
+    stride = max(int(ms.max()) if P else 0, 1)
+    pts = np.zeros((max(P, 1), stride, 4), np.float64)
+    for k, (p1, p2) in enumerate(sets):
+        pts[k, :ms[k], :2] = np.asarray(p1, np.float64).reshape(-1, 2)
+        pts[k, :ms[k], 2:] = np.asarray(p2, np.float64).reshape(-1, 2)
+    K = np.ascontiguousarray(K, np.float64).reshape(9)
+    n = int(n_hyp)
+    out = {"subsets": np.zeros((P, n, 5), np.int32), "nmod": np.zeros((P, n), np.int32),
+           "models": np.zeros((P, n, 10, 9), np.float64), "cnt": np.zeros((P, n, 10), np.int32),
+           "state": np.zeros((P, 5), np.int32)}
+    bounds = np.zeros(8, np.int32)
+    nr = ctypes.c_int()
+    path = np.zeros((P, n), np.int32)
+    parked = np.zeros(4, np.int32)
+    c.check(c.lib.dvo_test_ransac_hypotheses(c.h, ptr(pts), ptr(ms), P, stride, ptr(K), float(prob), float(threshold),
+                                             n, RANSAC_SCHEDULES[schedule], ptr(out["subsets"]), ptr(out["nmod"]),
+                                             ptr(out["models"]), ptr(out["cnt"]), ptr(out["state"]), ptr(bounds),
+                                             ctypes.byref(nr), ptr(path), ptr(parked)))
+    out["bounds"] = bounds[:nr.value].copy()
+    one = schedule != "BATCH_ROUNDS"
+    out["path"] = path if one else None
+    out["parked"] = parked if one else None
+    return out
+
+
 def test_five_point(q1, q2, ctx=None):
     c = _ctx(ctx)
     q1 = np.ascontiguousarray(q1, np.float64).reshape(10)

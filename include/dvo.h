@@ -585,6 +585,28 @@ int dvo_test_ransac_subsets(dvo_ctx* ctx, int m, int n, int32_t* idx);
  * best hypothesis, best model}. */
 int dvo_test_ransac_replay(dvo_ctx* ctx, const int32_t* nmod, const int32_t* cnt, int n, int m, double prob,
                            int max_iters, int32_t* out);
+/* Everything findEssentialMat's RANSAC kernels compute for the first n_hyp hypotheses
+ * (hyp_cap = max_iters = n_hyp) of P >= 1 point sets, under one of the production schedules:
+ *   DVO_TEST_SCHED_CALL          what dvo_find_essential_mat launches (one round, 16-lane
+ *                                Durand-Kerner, stage C by rows, small score blocks); P = 1
+ *   DVO_TEST_SCHED_BATCH_ONE     the stream batch kernels over [0, n_hyp) as one round
+ *   DVO_TEST_SCHED_BATCH_ROUNDS  the stream batch schedule, round after round
+ * pts: P x stride x {x1, y1, x2, y2} pixel coordinates, m: P counts (0 <= m[p] <= stride).
+ * Per pair and hypothesis, copied from the kernels' arrays: subsets (x 5), nmod (-1: the
+ * hypothesis was not evaluated), models (x 10 x 9) and cnt (x 10; a model that cannot exceed
+ * max(4, the best count when its round started) may hold a partial count).  state: P x
+ * {iterations, niters, max good, best hypothesis, best model}.  bounds: the *n_rounds round bounds
+ * used (up to 8).  The one-round schedules also report path (P x n_hyp: 0 the fast Durand-Kerner
+ * kernel's roots, 1 the trimmed-degree solver, 2 coincident roots redone in stage C, -1 not
+ * evaluated) and parked (4: polynomials parked after Durand-Kerner pass k); BATCH_ROUNDS sets
+ * both to -1 (its hypothesis records are round-local). */
+#define DVO_TEST_SCHED_CALL 0
+#define DVO_TEST_SCHED_BATCH_ONE 1
+#define DVO_TEST_SCHED_BATCH_ROUNDS 2
+int dvo_test_ransac_hypotheses(dvo_ctx* ctx, const double* pts, const int32_t* m, int P, int stride, const double* K,
+                               double prob, double threshold, int n_hyp, int schedule, int32_t* subsets,
+                               int32_t* nmod, double* models, int32_t* cnt, int32_t* state, int32_t* bounds,
+                               int* n_rounds, int32_t* path, int32_t* parked);
 /* 5-point kernel on one sample of 5 normalised correspondences. */
 int dvo_test_five_point(dvo_ctx* ctx, const double* q1, const double* q2, double* models, int* n);
 /* The batched RANSAC score's single-precision Sampson decision on one model E

@@ -254,12 +254,17 @@ int solve_cubic(const double* c, double* x) {
 // (OpenCV leaves them as uninitialised buffer contents).
 // trace (analysis only, tools/dk_cycle_stats.py): a 64-bit hash of the roots' bits after each
 // sweep, trace[max_iters] = the sweeps run (the maxDiff <= 0 exit or max_iters).
+// t_last_path: the branch this thread's last solve_poly took (ora_ransac_hypotheses): 1 the
+// degree was trimmed, 2 a sweep met num_same_root > 1 at the full degree, 0 neither.
+thread_local int t_last_path;
+
 int solve_poly(const double* rc, int n0, int max_iters, Cx* roots, uint64_t* trace = nullptr) {
     std::vector<Cx> coeffs(n0 + 1);
     for (int i = 0; i <= n0; i++) coeffs[i] = Cx{rc[i], 0};
     int n = n0;
     for (; n > 1; n--)
         if (std::fabs(coeffs[n].re) + std::fabs(coeffs[n].im) > DBL_EPSILON) break;
+    t_last_path = n < n0 ? 1 : 0;
     Cx p{1, 0}, r{1, 1};
     for (int i = 0; i < n; i++) {
         roots[i] = p;
@@ -282,6 +287,7 @@ int solve_poly(const double* rc, int n0, int max_iters, Cx* roots, uint64_t* tra
             }
             num = cdiv(num, denom);
             if (num_same_root > 1) {
+                if (t_last_path == 0) t_last_path = 2;
                 double ore = num.re, oim = num.im;
                 int sq_times = num_same_root % 2 == 0 ? num_same_root / 2 : num_same_root / 2 - 1;
                 for (int j = 0; j < sq_times; j++) {
@@ -725,6 +731,35 @@ int ora_ransac_subsets(int m, int n, int32_t* idx) {
                 if (j == i) break;
             }
         }
+    return 0;
+}
+
+// The loop body of ora_find_essential for each of the first n hypotheses, with no niters and no
+// early stop: the subset, five_point's models and find_inliers' count of every model (the same
+// normalised points and t), and solve_poly's branch (t_last_path).  models / cnt rows past
+// nmod[h] are left as the caller set them.
+int ora_ransac_hypotheses(const double* p1, const double* p2, int m, const double* K, double threshold, int n,
+                          int32_t* subsets, int32_t* nmod, double* models, int32_t* cnt, int32_t* path) {
+    if (ora_ransac_subsets(m, n, subsets)) return -1;
+    std::vector<double> n1(2 * m), n2(2 * m);
+    normalize_points(p1, m, K, n1.data());
+    normalize_points(p2, m, K, n2.data());
+    const double thr = threshold / ((K[0] + K[4]) / 2);
+    const float t = (float)(thr * thr);
+    double s1[10], s2[10];
+    for (int h = 0; h < n; ++h) {
+        for (int i = 0; i < 5; ++i) {
+            const int j = subsets[h * 5 + i];
+            s1[2 * i] = n1[2 * j];
+            s1[2 * i + 1] = n1[2 * j + 1];
+            s2[2 * i] = n2[2 * j];
+            s2[2 * i + 1] = n2[2 * j + 1];
+        }
+        nmod[h] = five_point(s1, s2, models + (size_t)h * 90);
+        path[h] = t_last_path;
+        for (int i = 0; i < nmod[h]; ++i)
+            cnt[h * 10 + i] = find_inliers(models + (size_t)h * 90 + 9 * i, n1.data(), n2.data(), m, t, nullptr);
+    }
     return 0;
 }
 

@@ -105,6 +105,11 @@ int ora_ransac_update_num_iters(double p, double ep, int model_points, int max_i
 // out = {iterations, niters, max good, best hypothesis, best model}.
 int ora_ransac_subsets(int m, int n, int32_t* idx);
 int ora_ransac_replay(const int32_t* nmod, const int32_t* cnt, int n, int m, double prob, int max_iters, int32_t* out);
+// The first n hypotheses of ora_find_essential's loop (m >= 6), none skipped and no early stop:
+// subsets n x 5, nmod n, models n x 10 x 9, cnt n x 10 (rows past nmod[h] untouched), path n
+// (solvePoly's branch: 1 degree trimmed, 2 a sweep met coincident roots, 0 neither).
+int ora_ransac_hypotheses(const double* p1, const double* p2, int m, const double* K, double threshold, int n,
+                          int32_t* subsets, int32_t* nmod, double* models, int32_t* cnt, int32_t* path);
 
 // ---- SIFT_create().detectAndCompute (sift.cpp; the 'sift' / 'knn_sift' /
 // 'flann' modes, visual_odometry_v3.py:99-103, :373).  kps sorted as

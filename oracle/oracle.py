@@ -101,6 +101,7 @@ def lib():
             "ora_ransac_update_num_iters": [_d, _d, _c, _c],
             "ora_ransac_subsets": [_c, _c, _i32p],
             "ora_ransac_replay": [_i32p, _i32p, _c, _c, _d, _c, _i32p],
+            "ora_ransac_hypotheses": [_f64p, _f64p, _c, _f64p, _d, _c, _i32p, _i32p, _f64p, _i32p, _i32p],
             "ora_sift_detect_and_compute": [_u8p, _c, _c, _c, _kpp, _f32p, _c, _ip],
             "ora_surf_detect_and_compute": [_u8p, _c, _c, _c, ctypes.c_double, _kpp, _f32p, _c, _ip],
             "ora_get_optimal_new_camera_matrix": [_f64p, _f64p, _c, _c, _c, _d, _c, _c, _f64p],
@@ -334,6 +335,23 @@ def ransac_replay(nmod, cnt, m, prob=0.999, max_iters=1000):
     out = np.zeros(5, np.int32)
     lib().ora_ransac_replay(nmod, cnt, len(nmod), m, prob, max_iters, out)
     return tuple(int(v) for v in out)
+
+
+def ransac_hypotheses(p1, p2, K, threshold=1.0, n=1000):
+    """The first n hypotheses of find_essential's loop, every one evaluated (no niters, no early
+    stop): dict of subsets (n, 5), nmod (n,), models (n, 10, 9), cnt (n, 10) -- rows past nmod[h]
+    zero -- and path (n,): solvePoly's branch, 1 degree trimmed / 2 coincident roots / 0."""
+    p1 = np.ascontiguousarray(p1, np.float64).reshape(-1)
+    p2 = np.ascontiguousarray(p2, np.float64).reshape(-1)
+    m = len(p1) // 2
+    out = {"subsets": np.zeros((n, 5), np.int32), "nmod": np.zeros(n, np.int32),
+           "models": np.zeros((n, 10, 9), np.float64), "cnt": np.zeros((n, 10), np.int32),
+           "path": np.zeros(n, np.int32)}
+    rc = lib().ora_ransac_hypotheses(p1, p2, m, np.ascontiguousarray(K, np.float64).reshape(-1), threshold, n,
+                                     out["subsets"], out["nmod"], out["models"], out["cnt"], out["path"])
+    if rc != 0:
+        raise ValueError("ransac_hypotheses needs m >= 6 and n >= 0")
+    return out
 
 
 def keypoints_to_points(kps):

@@ -128,6 +128,18 @@ int main() {
         for (auto& c : cnt) c = (int)(rng() % 200);
         ora_ransac_replay(nmod.data(), cnt.data(), 4096, 200, 0.999, 4096, out.data());
         ora_ransac_replay(nmod.data(), cnt.data(), 0, 200, 0.999, 1000, out.data());
+        // the per-hypothesis loop: every output row written inside its array, m < 6 refused
+        if (m > 5) {
+            const int nh = 70;
+            std::vector<int32_t> hs(nh * 5), hn(nh), hc(nh * 10), hp(nh);
+            std::vector<double> hm(nh * 90);
+            EXPECT(ora_ransac_hypotheses(p1.data(), p2.data(), m, K, 1.0, nh, hs.data(), hn.data(), hm.data(), hc.data(),
+                                         hp.data()) == 0);
+            EXPECT(ora_ransac_hypotheses(p1.data(), p2.data(), m, K, 1.0, 0, hs.data(), hn.data(), hm.data(), hc.data(),
+                                         hp.data()) == 0);
+        }
+        EXPECT(ora_ransac_hypotheses(p1.data(), p2.data(), 5, K, 1.0, 1, sub.data(), nmod.data(), E.data(), cnt.data(),
+                                     out.data()) != 0);
     }
 
     // SURF, textured, a cap below the count and a tiny frame
