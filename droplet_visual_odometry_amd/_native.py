@@ -171,6 +171,11 @@ _SIGNATURES = {
     "dvo_stream_process_jpeg": ([_vp, _vp, _vp, _vp, _vp, _c, _vp], _c),
     "dvo_stream_submit_jpeg": ([_vp, _vp, _vp, _vp, _vp, _c, _vp], _c),
     "dvo_jpeg_get_coefficients": ([_vp, _c, _vp, _i64, ctypes.POINTER(_i64)], _c),
+    "dvo_jpeg_entropy_split_host": ([_vp, _i64, _c, _vp, _i64, _ip, _ip], _c),
+    "dvo_jpeg_set_split": ([_vp, _c], _c),
+    "dvo_jpeg_get_split": ([_vp, _ip], _c),
+    "dvo_jpeg_set_stream_entropy": ([_vp, _c], _c),
+    "dvo_jpeg_get_split_info": ([_vp, _ip, _ip, _ip], _c),
     "dvo_stream_share_pose": ([_vp, _vp], _c),
     "dvo_stream_pose_tail": ([_vp, _vp, _vp, _c, _d, _vp, _vp], _c),
     "dvo_pose_tail_records": ([_vp, _vp, _c, _vp, _vp, _vp, _c, _d, _vp, _vp, _vp, _vp], _c),

@@ -15,6 +15,7 @@
 #include "device_mem.h"
 #include "dvo_internal.h"
 #include "jpeg_entropy.h"
+#include "jpeg_split.h"
 
 using namespace dvo;
 
@@ -2671,7 +2672,7 @@ int dvo_stream_submit_bgr(dvo_stream* s, dvo_undistort* u, const uint8_t* d_fram
 
 // ---------------------------------------------------------------------------
 // JPEG frames: cv.imdecode (v3:127) of baseline JPEGs.  Parser in jpeg_parse.cpp, the entropy
-// decoder (host and device) in jpeg_entropy.h, kernels in jpeg.hip.
+// decoder (host and device) in jpeg_entropy.h, its many-lane form in jpeg_split.h, kernels in jpeg.hip.
 // ---------------------------------------------------------------------------
 struct dvo_jpeg {
     dvo_ctx* ctx = nullptr;
@@ -2702,6 +2703,10 @@ struct dvo_jpeg {
     uint8_t* d_planes = nullptr;
     uint8_t* d_gray = nullptr;  // a group of gray frames (decode -> undistort)
     int32_t* d_status = nullptr;
+    int split_bytes = DVO_JPEG_SPLIT_BYTES_DEFAULT;
+    int stream_entropy = DVO_JPEG_ENTROPY_DEVICE;  // what dvo_stream_*_jpeg decode with
+    int32_t* d_split_info = nullptr;  // [3] of the last split call: most passes, segments split, fallbacks
+    std::vector<jpeg::Segment> split_segs;  // a group's segments for the split kernel
     std::vector<int> host_status;  // per frame of the last call: what the host found
     std::vector<jpeg::Parsed> parsed;
     std::vector<int64_t> last_base, last_count;  // the last group's frames in d_coef
@@ -2715,6 +2720,11 @@ struct dvo_jpeg {
 };
 
 namespace {
+
+// Runs of split_bytes from which a segment gets a workgroup of its own.  A split segment costs its
+// wave about 2 + passes walks of one run (guess, passes, write) where its one lane costs as many as
+// it has runs, and up to 11 passes were seen at 128 to 256 bytes per run ("JPEG input").
+constexpr uint32_t kSplitMinRuns = 16;
 
 void fill_layout(const jpeg::Parsed& P, dvo_jpeg_layout* L) {
     const jpeg::FramePlan& p = P.plan;
@@ -2748,8 +2758,8 @@ int jpeg_decode_impl(dvo_jpeg* j, const uint8_t* const* bufs, const int64_t* len
     if (n < 0 || n > dvo_jpeg::kMaxCall) return fail(ctx, DVO_EINVAL, "frame count out of range (0..65536)");
     if (out_channels != 1 && out_channels != 3 && out_channels != 4)
         return fail(ctx, DVO_EINVAL, "out_channels must be 1, 3 or 4");
-    if (entropy != DVO_JPEG_ENTROPY_HOST && entropy != DVO_JPEG_ENTROPY_DEVICE)
-        return fail(ctx, DVO_EINVAL, "entropy must be DVO_JPEG_ENTROPY_HOST or DVO_JPEG_ENTROPY_DEVICE");
+    if (entropy != DVO_JPEG_ENTROPY_HOST && entropy != DVO_JPEG_ENTROPY_DEVICE && entropy != DVO_JPEG_ENTROPY_DEVICE_SPLIT)
+        return fail(ctx, DVO_EINVAL, "entropy must be DVO_JPEG_ENTROPY_HOST, _DEVICE or _DEVICE_SPLIT");
     if (n > 0 && (!bufs || !lens || !d_dst)) return fail(ctx, DVO_EINVAL, "null buffer");
     j->host_status.assign((size_t)n, DVO_OK);
     j->last_base.clear();
@@ -2777,15 +2787,20 @@ int jpeg_decode_impl(dvo_jpeg* j, const uint8_t* const* bufs, const int64_t* len
     if (u && (out_channels != 1 || u->U.w != need_w || u->U.h != need_h))
         return fail(ctx, DVO_EINVAL, "undistort size != frame size");
     HIP_TRY(hipSetDevice(ctx->device));
-    const bool on_host = entropy == DVO_JPEG_ENTROPY_HOST;
+    const bool on_host = entropy == DVO_JPEG_ENTROPY_HOST, split = entropy == DVO_JPEG_ENTROPY_DEVICE_SPLIT;
+    // a segment of at least kSplitMinRuns runs of split_bytes goes to the split kernel, a shorter one keeps its lane
+    const uint32_t split_from = split ? (uint32_t)j->split_bytes * kSplitMinRuns : 0;
     j->last_stream = st;
     HIP_TRY(hipMemsetAsync(j->d_status, 0, (size_t)n * sizeof(int32_t), st));
+    if (split) HIP_TRY(hipMemsetAsync(j->d_split_info, 0, 3 * sizeof(int32_t), st));
     for (int f0 = 0; f0 < n;) {
         const int k = j->half;
         j->half ^= 1;
         if (j->ev_used[k]) HIP_TRY(hipEventSynchronize(j->ev[k]));
         // the group: up to `group` frames whose scans fit the staging half
         int nf = 0, nseg = 0, max_nblk = 0;
+        uint32_t longest = 0;
+        j->split_segs.clear();
         size_t bytes = 0;
         int64_t elems = 0;
         j->last_base.clear();
@@ -2794,15 +2809,21 @@ int jpeg_decode_impl(dvo_jpeg* j, const uint8_t* const* bufs, const int64_t* len
             jpeg::Parsed& P = j->parsed[(size_t)(f0 + nf)];
             const size_t sb = P.scan_end - P.scan_begin;
             if (bytes + align_up(sb, 16) > j->stage_cap || (size_t)elems + (size_t)P.plan.nblk * 64 > j->coef_cap ||
-                (size_t)nseg + P.segs.size() > (size_t)0x7FFFFFFF)
+                (size_t)nseg + j->split_segs.size() + P.segs.size() > (size_t)0x7FFFFFFF)
                 break;
             P.plan.base = elems;
             j->h_plans[k][nf] = P.plan;
             if (!on_host) {
                 std::memcpy(j->h_bytes[k] + bytes, bufs[f0 + nf] + P.scan_begin, sb);
-                for (const jpeg::Segment& sg : P.segs)
-                    j->h_segs[k][nseg++] =
-                        jpeg::Segment{nf, (uint32_t)(bytes + (sg.offset - P.scan_begin)), sg.length, sg.mcu0, sg.nmcu};
+                for (const jpeg::Segment& sg : P.segs) {
+                    const jpeg::Segment g{nf, (uint32_t)(bytes + (sg.offset - P.scan_begin)), sg.length, sg.mcu0, sg.nmcu};
+                    if (split && sg.length >= split_from) {
+                        j->split_segs.push_back(g);
+                        longest = std::max(longest, sg.length);
+                    } else {
+                        j->h_segs[k][nseg++] = g;
+                    }
+                }
             }
             j->last_base.push_back(elems);
             j->last_count.push_back((int64_t)P.plan.nblk * 64);
@@ -2825,14 +2846,22 @@ int jpeg_decode_impl(dvo_jpeg* j, const uint8_t* const* bufs, const int64_t* len
         } else {
             HIP_TRY(hipMemsetAsync(j->d_coef, 0, (size_t)elems * sizeof(int16_t), st));
             if (bytes) HIP_TRY(hipMemcpyAsync(j->d_bytes, j->h_bytes[k], bytes, hipMemcpyHostToDevice, st));
-            if (nseg)
-                HIP_TRY(hipMemcpyAsync(j->d_segs, j->h_segs[k], (size_t)nseg * sizeof(jpeg::Segment), hipMemcpyHostToDevice,
-                                       st));
+            // one list: the one-lane segments, then the split ones
+            const int nsplit = (int)j->split_segs.size();
+            if (nsplit) std::memcpy(j->h_segs[k] + nseg, j->split_segs.data(), (size_t)nsplit * sizeof(jpeg::Segment));
+            if (nseg + nsplit)
+                HIP_TRY(hipMemcpyAsync(j->d_segs, j->h_segs[k], (size_t)(nseg + nsplit) * sizeof(jpeg::Segment),
+                                       hipMemcpyHostToDevice, st));
         }
         HIP_TRY(hipEventRecord(j->ev[k], st));
         j->ev_used[k] = true;
-        if (!on_host)
+        if (!on_host) {
             HIP_TRY(launch_jpeg_entropy(j->d_plans, j->d_segs, nseg, j->d_bytes, j->d_coef, j->d_status + f0, st));
+            if (!j->split_segs.empty())
+                HIP_TRY(launch_jpeg_entropy_split(j->d_plans, j->d_segs + nseg, (int)j->split_segs.size(), j->split_bytes,
+                                                  (int)jpeg::split_count(longest, (uint32_t)j->split_bytes), j->d_bytes,
+                                                  j->d_coef, j->d_status + f0, j->d_split_info, st));
+        }
         HIP_TRY(launch_jpeg_idct(j->d_plans, nf, max_nblk, j->d_coef, j->d_planes, st));
         uint8_t* dst = d_dst + (int64_t)f0 * dst_fstride;
         if (u) {
@@ -2870,7 +2899,7 @@ int run_stream_jpeg(dvo_stream* s, dvo_jpeg* j, dvo_undistort* u, const uint8_t*
     HIP_TRY(hipSetDevice(ctx->device));
     const int pw = frame_pitch(s);
     const int64_t fs = (int64_t)pw * s->cfg.height;
-    const int rc = jpeg_decode_impl(j, bufs, lens, n, 1, s->d_frames, fs, pw, DVO_JPEG_ENTROPY_DEVICE, s->hs, u,
+    const int rc = jpeg_decode_impl(j, bufs, lens, n, 1, s->d_frames, fs, pw, j->stream_entropy, s->hs, u,
                                     s->cfg.width, s->cfg.height);
     if (rc) return fail(ctx, rc, j->ctx->err);
     return run_stream(s, s->d_frames, n, fs, pw, d_records, false, 1, drain);
@@ -2902,6 +2931,27 @@ int dvo_jpeg_entropy_host(const uint8_t* buf, int64_t len, dvo_jpeg_layout* layo
     std::memset(coef, 0, (size_t)layout->coef_count * sizeof(int16_t));
     const int st = entropy_host(P, buf, coef);
     if (status) *status = st;
+    return DVO_OK;
+}
+
+int dvo_jpeg_entropy_split_host(const uint8_t* buf, int64_t len, int split_bytes, int16_t* coef, int64_t cap, int* status,
+                                int* passes) {
+    if (!buf || len < 0 || !coef || !jpeg::split_bytes_ok(split_bytes)) return DVO_EINVAL;
+    jpeg::Parsed P;
+    const int rc = jpeg::parse(buf, (size_t)len, &P);
+    if (rc) return rc;
+    const int64_t count = (int64_t)P.plan.nblk * 64;
+    if (cap < count) return DVO_ECAP;
+    std::memset(coef, 0, (size_t)count * sizeof(int16_t));
+    int st = P.scan_status, most = 0;
+    for (const jpeg::Segment& sg : P.segs) {
+        int np = 0;
+        if (jpeg::decode_segment_split(P.plan, buf + sg.offset, sg.length, sg.mcu0, sg.nmcu, coef, (uint32_t)split_bytes, &np))
+            st = jpeg::kCorrupt;
+        most = std::max(most, np);
+    }
+    if (status) *status = st;
+    if (passes) *passes = most;
     return DVO_OK;
 }
 
@@ -2939,6 +2989,7 @@ int dvo_jpeg_create(dvo_ctx* ctx, int max_w, int max_h, int group_frames, dvo_jp
     dev(&j->d_planes, j->coef_cap);
     dev(&j->d_gray, G * pw * (size_t)max_h);
     dev(&j->d_status, (size_t)dvo_jpeg::kMaxCall * sizeof(int32_t));
+    dev(&j->d_split_info, 3 * sizeof(int32_t));
     for (int k = 0; k < 2; ++k) {
         pinned(&j->h_bytes[k], j->stage_cap);
         pinned(&j->h_plans[k], G * sizeof(jpeg::FramePlan));
@@ -2950,6 +3001,7 @@ int dvo_jpeg_create(dvo_ctx* ctx, int max_w, int max_h, int group_frames, dvo_jp
     if (e == hipSuccess) e = hipEventCreateWithFlags(&j->ev_coef, hipEventDisableTiming);
     if (e != hipSuccess) return fail(ctx, DVO_EHIP, std::string("JPEG decoder buffers: ") + hipGetErrorString(e));
     std::memset(j->h_status, 0, (size_t)dvo_jpeg::kMaxCall * sizeof(int32_t));
+    HIP_TRY(hipMemset(j->d_split_info, 0, 3 * sizeof(int32_t)));
     *out = j.release();
     return DVO_OK;
 }
@@ -2965,6 +3017,40 @@ int dvo_jpeg_decode(dvo_jpeg* j, const uint8_t* const* bufs, const int64_t* lens
     if (!j) return DVO_EINVAL;
     return jpeg_decode_impl(j, bufs, lens, n, out_channels, d_dst, dst_frame_stride, dst_pitch, entropy,
                             hip_stream ? (hipStream_t)hip_stream : j->ctx->stream, nullptr, 0, 0);
+}
+
+int dvo_jpeg_set_split(dvo_jpeg* j, int split_bytes) {
+    if (!j) return DVO_EINVAL;
+    if (!jpeg::split_bytes_ok(split_bytes)) return fail(j->ctx, DVO_EINVAL, "split_bytes must be a power of two in 16..4096");
+    j->split_bytes = split_bytes;
+    return DVO_OK;
+}
+
+int dvo_jpeg_get_split(dvo_jpeg* j, int* split_bytes) {
+    if (!j || !split_bytes) return DVO_EINVAL;
+    *split_bytes = j->split_bytes;
+    return DVO_OK;
+}
+
+int dvo_jpeg_set_stream_entropy(dvo_jpeg* j, int entropy) {
+    if (!j) return DVO_EINVAL;
+    if (entropy != DVO_JPEG_ENTROPY_DEVICE && entropy != DVO_JPEG_ENTROPY_DEVICE_SPLIT)
+        return fail(j->ctx, DVO_EINVAL, "the stream decodes with DVO_JPEG_ENTROPY_DEVICE or _DEVICE_SPLIT");
+    j->stream_entropy = entropy;
+    return DVO_OK;
+}
+
+int dvo_jpeg_get_split_info(dvo_jpeg* j, int* max_passes, int* segments, int* fallbacks) {
+    if (!j) return DVO_EINVAL;
+    dvo_ctx* ctx = j->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (j->last_stream) HIP_TRY(hipStreamSynchronize(j->last_stream));
+    int32_t v[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpy(v, j->d_split_info, sizeof(v), hipMemcpyDeviceToHost));
+    if (max_passes) *max_passes = v[0];
+    if (segments) *segments = v[1];
+    if (fallbacks) *fallbacks = v[2];
+    return DVO_OK;
 }
 
 int dvo_jpeg_status(dvo_jpeg* j, int* st, int n) {

@@ -363,6 +363,12 @@ struct Segment;
 }  // namespace jpeg
 hipError_t launch_jpeg_entropy(const jpeg::FramePlan* d_plans, const jpeg::Segment* d_segs, int nseg,
                                const uint8_t* d_bytes, int16_t* d_coef, int32_t* d_status, hipStream_t s);
+// The segments of a group that are long enough to be split (jpeg_split.h): one workgroup each, lane i
+// on the i-th run of split_bytes bytes; max_runs: the most runs a segment of the list has.  d_info:
+// 3 counters (most synchronisation passes, segments, one-lane fallbacks), or null.
+hipError_t launch_jpeg_entropy_split(const jpeg::FramePlan* d_plans, const jpeg::Segment* d_segs, int nseg, int split_bytes,
+                                     int max_runs, const uint8_t* d_bytes, int16_t* d_coef, int32_t* d_status,
+                                     int32_t* d_info, hipStream_t s);
 hipError_t launch_jpeg_idct(const jpeg::FramePlan* d_plans, int nframes, int max_nblk, const int16_t* d_coef,
                             uint8_t* d_planes, hipStream_t s);
 hipError_t launch_jpeg_color(const GrayCoef& c, const jpeg::FramePlan* d_plans, int nframes, int w, int h,

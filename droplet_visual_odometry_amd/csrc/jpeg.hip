@@ -8,6 +8,12 @@
 //   has a wave of its own and no lane waits for a neighbour's branches; a group with more segments
 //   than the launch has lanes (64 x 16,384) is decoded in rounds.  A wave whose segments are
 //   all of one frame decodes from a copy of that frame's plan (its Huffman tables) in LDS.
+// jpeg_entropy_split_kernel: one workgroup of up to 1,024 lanes decodes one long segment by the
+//   schedule of jpeg_split.h, lane i taking the i-th run of split_bytes bytes: guessed entry states,
+//   synchronisation passes until no exit state changes, a scan of block counts and DC sums, a
+//   write pass.  States and scan live in LDS; a segment of more runs than lanes is walked in chunks.
+//   The workgroup (LANES: 64 .. 1,024) is the smallest that holds the longest segment of the launch:
+//   what a workgroup keeps in LDS grows with it, and with it falls the number a CU runs at a time.
 // jpeg_idct_kernel: 8 lanes per block.  Lane j fetches row j of the block as one 16-byte load and
 //   dequantises it into LDS, reads back column j and runs pass 1 (jidctint.c, descale 11), writes
 //   the column back, reads row j, runs pass 2 (descale 18), and stores 8 samples of the component's
@@ -21,6 +27,7 @@
 
 #include "dvo_internal.h"
 #include "jpeg_entropy.h"
+#include "jpeg_split.h"
 
 namespace dvo {
 namespace {
@@ -65,6 +72,116 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const FramePlan* __res
             if (bad) status[sg.frame] = jpeg::kCorrupt;
         }
         __syncthreads();  // before the next round's plan replaces this one
+    }
+}
+
+// exclusive sum of v over the workgroup's lanes (whole waves); tot: one word per wave
+__device__ __forceinline__ uint32_t block_exclusive_sum(uint32_t v, uint32_t* tot) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(inc, d);
+        if (lane >= d) inc += t;
+    }
+    if (lane == 63) tot[wave] = inc;
+    __syncthreads();
+    uint32_t before = 0;
+    for (int w = 0; w < wave; ++w) before += tot[w];
+    return before + inc - v;
+}
+
+// info: [0] most synchronisation passes of a segment, [1] segments decoded here, [2] of them by the one-lane fallback
+template <int LANES>
+__global__ __launch_bounds__(LANES) void jpeg_entropy_split_kernel(
+    const FramePlan* __restrict__ plans, const Segment* __restrict__ segs, int nseg, uint32_t split_bytes,
+    const uint8_t* __restrict__ bytes, int16_t* __restrict__ coef, int32_t* __restrict__ status,
+    int32_t* __restrict__ info) {
+    __shared__ FramePlan lp;
+    static_assert(LANES % 64 == 0 && LANES <= jpeg::kSplitLanes, "whole waves, at most the model's chunk");
+    __shared__ uint64_t s_exit[LANES];
+    __shared__ uint32_t s_tot[4][LANES / 64];
+    __shared__ uint64_t c_state, c_ord;
+    __shared__ uint32_t c_dc[3];
+    if ((int)blockIdx.x >= nseg) return;
+    const Segment sg = segs[blockIdx.x];
+    const int t = threadIdx.x, L = LANES;
+    {
+        const uint4* src = reinterpret_cast<const uint4*>(plans + sg.frame);
+        uint4* dst = reinterpret_cast<uint4*>(&lp);
+        for (int k = t; k < (int)(sizeof(FramePlan) / sizeof(uint4)); k += L) dst[k] = src[k];
+    }
+    if (t == 0) {
+        c_state = jpeg::pack_state(0, 0, 0);
+        c_ord = 0;
+        c_dc[0] = c_dc[1] = c_dc[2] = 0;
+    }
+    __syncthreads();
+    const uint8_t* data = bytes + sg.offset;
+    const uint32_t len = sg.length, S = split_bytes;
+    const uint32_t n = jpeg::split_count(len, S);
+    int16_t* fcoef = coef + lp.base;
+    // (the host sends segments of at least two runs; decode_segment refuses a bad MCU range itself)
+    if (n < 2 || sg.mcu0 < 0 || sg.nmcu < 0 || (int64_t)sg.mcu0 + sg.nmcu > (int64_t)lp.mcux * lp.mcuy) {
+        if (t == 0 && jpeg::decode_segment(lp, data, len, sg.mcu0, sg.nmcu, fcoef)) status[sg.frame] = jpeg::kCorrupt;
+        return;
+    }
+    const uint64_t total = (uint64_t)sg.nmcu * (uint64_t)jpeg::blocks_per_mcu(lp);
+    int bad = 0, np = 0;
+    for (uint32_t c0 = 0; c0 < n; c0 += (uint32_t)L) {
+        const int nl = (int)min(n - c0, (uint32_t)L);
+        const bool on = t < nl;
+        const uint32_t g = c0 + (uint32_t)t;
+        const uint64_t end_bit = on ? jpeg::split_end(len, S, g) : 0;
+        uint64_t entry = jpeg::kDead;
+        if (on) entry = t == 0 ? c_state : jpeg::split_guess(data, len, S, g);
+        jpeg::LaneResult res{jpeg::kDead, 0, {0, 0, 0}, -1};
+        // Pass 0 from the guesses, then passes while an exit state changed: lane i's entry is final
+        // after pass i (jpeg_split.h), so pass nl - 1 is the last there can be, whatever the bytes.
+        bool need = on;
+        for (int pass = 0;; ++pass) {
+            int changed = 0;
+            if (need) {
+                const jpeg::LaneResult r = jpeg::run(lp, data, len, entry, end_bit, nullptr);
+                if (pass == 0 || r.exit != res.exit) {
+                    changed = 1;
+                    s_exit[t] = r.exit;
+                }
+                res = r;
+            }
+            const int any = __syncthreads_or(changed);  // the exits of this pass are written
+            if (pass > 0) ++np;
+            if ((pass > 0 && !any) || pass + 1 >= nl) break;
+            const uint64_t e = on && t > 0 ? s_exit[t - 1] : entry;
+            need = on && t > 0 && e != entry;
+            entry = e;
+            __syncthreads();  // ... and read, before the next pass writes
+        }
+        const uint32_t b0 = block_exclusive_sum(on ? res.blocks : 0u, s_tot[0]);
+        const uint32_t d0 = block_exclusive_sum(on ? res.dc[0] : 0u, s_tot[1]);
+        const uint32_t d1 = block_exclusive_sum(on ? res.dc[1] : 0u, s_tot[2]);
+        const uint32_t d2 = block_exclusive_sum(on ? res.dc[2] : 0u, s_tot[3]);
+        jpeg::CoefSink sink{fcoef, c_ord + b0, total, sg.mcu0, {c_dc[0] + d0, c_dc[1] + d1, c_dc[2] + d2}};
+        const int err = on && res.err_block >= 0 && sink.first + (uint64_t)res.err_block < total;
+        bad = __syncthreads_or(err);  // every lane has read the carried values
+        if (bad) break;
+        if (on) jpeg::run(lp, data, len, entry, end_bit, &sink);
+        if (t == nl - 1) {
+            c_state = res.exit;
+            c_ord = sink.first + res.blocks;
+            for (int c = 0; c < 3; ++c) c_dc[c] = sink.pred[c] + res.dc[c];
+        }
+        __syncthreads();
+    }
+    if (t != 0) return;
+    if (!bad && c_ord < total) bad = 1;  // the data ended between two blocks
+    // A corrupt segment is decode_segment's business: the blocks before the first bad one, that one
+    // in part.  Chunks already written hold only what it writes to the same places.
+    if (bad && jpeg::decode_segment(lp, data, len, sg.mcu0, sg.nmcu, fcoef)) status[sg.frame] = jpeg::kCorrupt;
+    if (info) {
+        atomicMax(&info[0], np);
+        atomicAdd(&info[1], 1);
+        if (bad) atomicAdd(&info[2], 1);
     }
 }
 
@@ -249,6 +366,28 @@ hipError_t launch_jpeg_entropy(const jpeg::FramePlan* d_plans, const jpeg::Segme
     const int nwaves = std::min(nseg, kEntropyWaves);
     hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(nwaves), dim3(64), 0, s, d_plans, d_segs, nseg, nwaves, d_bytes, d_coef,
                        d_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_jpeg_entropy_split(const jpeg::FramePlan* d_plans, const jpeg::Segment* d_segs, int nseg, int split_bytes,
+                                     int max_runs, const uint8_t* d_bytes, int16_t* d_coef, int32_t* d_status,
+                                     int32_t* d_info, hipStream_t s) {
+    if (nseg <= 0) return hipSuccess;
+    if (!jpeg::split_bytes_ok(split_bytes)) return hipErrorInvalidValue;
+#define DVO_SPLIT_LAUNCH(LANES)                                                                                  \
+    hipLaunchKernelGGL(jpeg_entropy_split_kernel<LANES>, dim3(nseg), dim3(LANES), 0, s, d_plans, d_segs, nseg, \
+                       (uint32_t)split_bytes, d_bytes, d_coef, d_status, d_info)
+    if (max_runs <= 64)
+        DVO_SPLIT_LAUNCH(64);
+    else if (max_runs <= 128)
+        DVO_SPLIT_LAUNCH(128);
+    else if (max_runs <= 256)
+        DVO_SPLIT_LAUNCH(256);
+    else if (max_runs <= 512)
+        DVO_SPLIT_LAUNCH(512);
+    else
+        DVO_SPLIT_LAUNCH(1024);
+#undef DVO_SPLIT_LAUNCH
     return hipGetLastError();
 }
 

@@ -66,8 +66,9 @@ DVO_HD inline void refill(BitReader& r) {
     }
 }
 
-// the next symbol, or -1 if no code matches
-DVO_HD inline int huff_decode(BitReader& r, const HuffTable& T) {
+// the next symbol, or -1 if no code matches (Reader: BitReader, or jpeg_split.h's SplitReader)
+template <class Reader>
+DVO_HD inline int huff_decode(Reader& r, const HuffTable& T) {
     refill(r);
     const uint32_t top = (uint32_t)(r.acc >> (r.nbits - 16)) & 0xFFFFu;
     const uint32_t e = T.look[top >> 8];
@@ -88,7 +89,8 @@ DVO_HD inline int huff_decode(BitReader& r, const HuffTable& T) {
 }
 
 // s <= 15 bits as a signed value of category s
-DVO_HD inline int receive_extend(BitReader& r, int s) {
+template <class Reader>
+DVO_HD inline int receive_extend(Reader& r, int s) {
     if (s == 0) return 0;
     refill(r);
     const int v = (int)((r.acc >> (r.nbits - s)) & ((1u << s) - 1u));

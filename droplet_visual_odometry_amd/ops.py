@@ -18,7 +18,7 @@ mirrors its argument meaning, output layout and failure points:
                        cv::getOptimalNewCameraMatrix, cv::undistort  v3:117, v3:120
   bgr2gray, bgr2gray_device
                        cv::cvtColor(COLOR_BGR2GRAY)       visual_odometry_v3.py:132
-  JpegDecoder, jpeg_probe, jpeg_entropy_host
+  JpegDecoder, jpeg_probe, jpeg_entropy_host, jpeg_entropy_split_host
                        cv::imdecode(IMREAD_COLOR) of baseline JPEGs  visual_odometry_v3.py:127
 """
 from __future__ import annotations
@@ -490,9 +490,10 @@ class Undistorter:
 
 # ---- JPEG frames: cv.imdecode(np_arr, IMREAD_COLOR) (v3:127) of baseline JPEGs ----
 JPEG_COLORS = {"gray": 1, "bgr": 3, "bgra": 4}
-JPEG_ENTROPY = {"host": 0, "device": 1}
+JPEG_ENTROPY = {"host": 0, "device": 1, "device_split": 2}
 # the faster of the two at 256 frames of 1280x720 4:2:0 without restart markers (tools/time_jpeg.py)
 JPEG_DEFAULT_ENTROPY = "device"
+JPEG_SPLIT_BYTES_DEFAULT = 256  # include/dvo.h's DVO_JPEG_SPLIT_BYTES_DEFAULT: scan bytes per lane of "device_split"
 
 
 def jpeg_blobs(blobs, max_frames=None):
@@ -567,20 +568,42 @@ def jpeg_entropy_host(blob):
     return lay, coef, st.value
 
 
+def jpeg_entropy_split_host(blob, split_bytes):
+    """The host model of entropy="device_split" (dvo_jpeg_entropy_split_host): jpeg_entropy_host's
+    coefficients and status by the split kernel's functions and schedule with `split_bytes`
+    scan bytes per lane, and the most synchronisation passes a segment took."""
+    from ._native import JpegLayout
+    lib = load_library()
+    a = _jpeg_bytes(blob)
+    lay = JpegLayout()
+    rc = lib.dvo_jpeg_entropy_host(ptr(a), a.size, ctypes.byref(lay), None, 0, None)
+    if rc != DVO_OK:
+        raise _jpeg_error(rc)
+    coef = np.zeros(lay.coef_count, np.int16)
+    st, passes = ctypes.c_int(), ctypes.c_int()
+    rc = lib.dvo_jpeg_entropy_split_host(ptr(a), a.size, int(split_bytes), ptr(coef), coef.size, ctypes.byref(st),
+                                         ctypes.byref(passes))
+    if rc != DVO_OK:
+        raise DVOError(rc, "dvo_jpeg_entropy_split_host failed")
+    return coef, st.value, passes.value
+
+
 class JpegDecoder:
     """cv.imdecode(buf, IMREAD_COLOR) (v3:127) of baseline JPEGs on the GPU, byte for
     byte libjpeg-turbo's default decode, for batches of frames of one size up to
     max_w x max_h.  Scratch (about 7 device and 5 pinned host bytes per pixel of a frame) is sized here for one
     group of `group_frames` frames; a batch runs group after group.  The device entropy
     decoder takes a group's restart segments one lane each: files without restart
-    markers decode `group_frames` at a time, which is what the default is for."""
+    markers decode `group_frames` at a time, which is what the default is for.
+    entropy="device_split" gives a long segment a workgroup instead, one lane per
+    `split_bytes` bytes of it (a power of two in 16..4096; None: the library's default)."""
 
     @staticmethod
     def default_group_frames(max_w: int, max_h: int) -> int:
         """256 frames, fewer where that would take more than 2 GiB of device memory."""
         return max(1, min(256, (2 << 30) // (7 * int(max_w) * int(max_h))))
 
-    def __init__(self, max_w: int, max_h: int, group_frames: int | None = None, ctx=None):
+    def __init__(self, max_w: int, max_h: int, group_frames: int | None = None, ctx=None, split_bytes=None):
         self.ctx = _ctx(ctx)
         if group_frames is None:
             group_frames = self.default_group_frames(max_w, max_h)
@@ -590,15 +613,41 @@ class JpegDecoder:
                                                     ctypes.byref(h)))
         self.h_ = h
         self._n = 0
+        if split_bytes is not None:
+            self.split_bytes = split_bytes
 
     probe = staticmethod(jpeg_probe)
+
+    @property
+    def split_bytes(self) -> int:
+        """Scan bytes per lane of entropy="device_split"."""
+        v = ctypes.c_int()
+        self.ctx.check(self.ctx.lib.dvo_jpeg_get_split(self.h_, ctypes.byref(v)))
+        return v.value
+
+    @split_bytes.setter
+    def split_bytes(self, v):
+        self.ctx.check(self.ctx.lib.dvo_jpeg_set_split(self.h_, int(v)))
+
+    def set_stream_entropy(self, entropy):
+        """The mode FrameStream.process_jpeg / submit_jpeg decode with: "device" or "device_split"."""
+        if entropy not in JPEG_ENTROPY:
+            raise ValueError(f"entropy must be one of {sorted(JPEG_ENTROPY)}")
+        self.ctx.check(self.ctx.lib.dvo_jpeg_set_stream_entropy(self.h_, JPEG_ENTROPY[entropy]))
+
+    def split_info(self):
+        """Test hook, of the last "device_split" call: (most synchronisation passes of a
+        segment, segments the split kernel took, of them decoded again by one lane)."""
+        v = [ctypes.c_int() for _ in range(3)]
+        self.ctx.check(self.ctx.lib.dvo_jpeg_get_split_info(self.h_, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
     def decode(self, blobs, color="gray", entropy=None, out=None, stream=None):
         """n JPEG files of one size -> a uint8 device tensor [n, H, W] (gray:
         cvtColor(BGR2GRAY) of the decoded bytes) or [n, H, W, 3 | 4] (bgr, bgra),
         asynchronously on `stream` (a hipStream_t handle; default: ordered with torch's
-        current stream).  entropy: "device" or "host" Huffman decoding (default
-        JPEG_DEFAULT_ENTROPY).  status() tells which frames were corrupt."""
+        current stream).  entropy: "device", "device_split" or "host" Huffman decoding
+        (default JPEG_DEFAULT_ENTROPY).  status() tells which frames were corrupt."""
         import torch
         if color not in JPEG_COLORS:
             raise ValueError(f"color must be one of {sorted(JPEG_COLORS)}")

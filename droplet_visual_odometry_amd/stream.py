@@ -205,13 +205,17 @@ class FrameStream:
             self._jpeg = JpegDecoder(self.width, self.height, group_frames=group, ctx=self.ctx)
         return self._jpeg
 
-    def process_jpeg(self, blobs, records: torch.Tensor | None = None, undistort=None) -> torch.Tensor:
+    def process_jpeg(self, blobs, records: torch.Tensor | None = None, undistort=None, entropy=None) -> torch.Tensor:
         """process() of a list of JPEG files (bytes-like) of the stream's size: decoded to
         gray on the device, and remapped by `undistort` (ops.Undistorter) if given, into
-        the stream's slab; from there exactly process() of colour frames."""
+        the stream's slab; from there exactly process() of colour frames.  entropy:
+        "device" or "device_split" (ops.JpegDecoder.decode), kept for the calls that
+        follow; None: as it is ("device" at first)."""
         arrs, ptrs, lens = self._check_jpeg(blobs, undistort, 1)
         n = len(arrs)
         dec = self.jpeg_decoder
+        if entropy is not None:
+            dec.set_stream_entropy(entropy)
         if records is None:
             records = self.new_records(n - 1)
         self._after_torch()
@@ -226,13 +230,15 @@ class FrameStream:
         self._hold(records)
         return records
 
-    def submit_jpeg(self, blobs, records: torch.Tensor, undistort=None) -> list:
+    def submit_jpeg(self, blobs, records: torch.Tensor, undistort=None, entropy=None) -> list:
         """submit() of a list of JPEG files (see process_jpeg)."""
         arrs, ptrs, lens = self._check_jpeg(blobs, undistort, 2)
         n = len(arrs)
         if not isinstance(records, torch.Tensor) or records.numel() < (n - 1) * PAIR_RECORD_DTYPE.itemsize:
             raise ValueError("records too small")
         dec = self.jpeg_decoder
+        if entropy is not None:
+            dec.set_stream_entropy(entropy)
         self._after_torch()
         self.ctx.check(self.ctx.lib.dvo_stream_submit_jpeg(
             self.h, dec.h_, undistort.h_ if undistort is not None else None, ptrs, lens, n, records.data_ptr()))

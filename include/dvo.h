@@ -514,11 +514,37 @@ int dvo_jpeg_entropy_host(const uint8_t* buf, int64_t len, dvo_jpeg_layout* layo
  * entropy decoder works on one group's segments at a time, one lane each, so frames
  * without restart markers decode as many at a time as the group holds.  A decoder
  * serves one HIP stream at a time. */
+/* The host model of DVO_JPEG_ENTROPY_DEVICE_SPLIT (ctx-free): dvo_jpeg_entropy_host by the
+ * split kernel's functions and schedule, the lanes taken one after the other.  Every
+ * segment of at least two runs of split_bytes bytes is split.  coef: coef_count
+ * coefficients in dvo_jpeg_entropy_host's layout (DVO_ECAP if cap is smaller), equal to
+ * its output, as is *status; *passes: the most synchronisation passes a segment took. */
+int dvo_jpeg_entropy_split_host(const uint8_t* buf, int64_t len, int split_bytes, int16_t* coef, int64_t cap, int* status,
+                                int* passes);
+
 int dvo_jpeg_create(dvo_ctx* ctx, int max_w, int max_h, int group_frames, dvo_jpeg** out);
 void dvo_jpeg_destroy(dvo_jpeg* j);
 
 #define DVO_JPEG_ENTROPY_HOST 0   /* Huffman decoding on the calling thread     */
 #define DVO_JPEG_ENTROPY_DEVICE 1 /* one GPU lane per restart segment (default) */
+/* Long segments (at least 16 runs of split_bytes bytes) by one workgroup each, lane i on
+ * the i-th run: lanes start from guessed decoder states and take over their left
+ * neighbour's exit state until none changes (self-synchronising Huffman decoding), at
+ * most as many passes as the segment has runs; shorter segments as under _DEVICE.  The
+ * output is _DEVICE's on every input; a corrupt segment is decoded again by one lane. */
+#define DVO_JPEG_ENTROPY_DEVICE_SPLIT 2
+
+/* Scan bytes per lane under DVO_JPEG_ENTROPY_DEVICE_SPLIT: a power of two in 16..4096
+ * (a symbol is at most 31 bits, so none jumps over 16 bytes), else DVO_EINVAL.
+ * The default, DVO_JPEG_SPLIT_BYTES_DEFAULT, is the fastest of 32, 64, 128, 256 and 512
+ * on 256 restart-free 1280x720 frames per group (tools/time_jpeg.py; DESIGN.md, "JPEG input"). */
+#define DVO_JPEG_SPLIT_BYTES_DEFAULT 256
+int dvo_jpeg_set_split(dvo_jpeg* j, int split_bytes);
+int dvo_jpeg_get_split(dvo_jpeg* j, int* split_bytes);
+/* The mode dvo_stream_process_jpeg / dvo_stream_submit_jpeg decode with:
+ * DVO_JPEG_ENTROPY_DEVICE (initially) or DVO_JPEG_ENTROPY_DEVICE_SPLIT; the host mode is
+ * not used on that path: DVO_EINVAL. */
+int dvo_jpeg_set_stream_entropy(dvo_jpeg* j, int entropy);
 
 /* n JPEGs of one size w x h <= max (sampling, tables and restart interval may differ
  * per frame) -> n device frames of out_channels bytes per pixel: 1 gray
@@ -550,6 +576,10 @@ int dvo_stream_submit_jpeg(dvo_stream* s, dvo_jpeg* j, dvo_undistort* u, const u
  * (dvo_jpeg_entropy_host's layout); *n_out is their count, DVO_ECAP if cap is
  * smaller; synchronises. */
 int dvo_jpeg_get_coefficients(dvo_jpeg* j, int frame, int16_t* out, int64_t cap, int64_t* n_out);
+/* Test hook: of the last DVO_JPEG_ENTROPY_DEVICE_SPLIT call, the most synchronisation
+ * passes a segment took, the segments the split kernel decoded and how many of them
+ * it gave to the one-lane decoder as corrupt; synchronises. */
+int dvo_jpeg_get_split_info(dvo_jpeg* j, int* max_passes, int* segments, int* fallbacks);
 
 /* Per-stage device time via HIP events recorded on the stream's HIP stream
  * around each kernel group (0 pyramid, 1 blur, 2 fast, 3 select+harris,

@@ -1,5 +1,6 @@
-"""What JPEG input costs: ops.JpegDecoder alone with device and with host
-entropy decoding, today's route (Pillow on one core -> colour frames -> FrameStream.submit) on
+"""What JPEG input costs: ops.JpegDecoder alone with device, with split device
+(`--split`: one leg per split_bytes, and the restart-per-row files once at the default) and with
+host entropy decoding, today's route (Pillow on one core -> colour frames -> FrameStream.submit) on
 the same files, and FrameStream.submit_jpeg against submit on the resident mono8 frames.
 
 Frames: `--distinct` frames of the synthetic scene with three different channels, encoded by
@@ -8,7 +9,10 @@ repeated to `--batch` frames per call.  Method (bench.py's): one warm-up call, t
 runs with a device synchronise on both sides, on the host clock; the value is the median run
 and every run is printed.  Needs Pillow (it makes the files).  Prints one JSON line.
 
-usage: python tools/time_jpeg.py [--width 1280 --height 720 --nfeatures 2000 --batch 256 --quality 80]"""
+`--decode-only` leaves out the stream comparisons.
+
+usage: python tools/time_jpeg.py [--width 1280 --height 720 --nfeatures 2000 --batch 256 --quality 80]
+                                 [--split 32,64,128,256,512] [--decode-only]"""
 import argparse
 import io
 import json
@@ -38,6 +42,8 @@ def main():
     ap.add_argument("--group", type=int, default=256, help="the decoder's group_frames")
     ap.add_argument("--steps", type=int, default=2, help="calls per timed run of the stream comparisons")
     ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--split", default="32,64,128,256,512", help="split_bytes of the device_split legs ('' for none)")
+    ap.add_argument("--decode-only", action="store_true", help="no stream comparisons")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("time_jpeg.py measures on the GPU; none is visible")
@@ -79,6 +85,45 @@ def main():
     same_rows = bool(torch.equal(out, mono))
     t_host = timed(lambda: dec.decode(plain, "gray", "host", out=out, stream=st))
     same_host = bool(torch.equal(out, mono))
+    split_res = {}
+    same_split = True
+    for sb in [int(v) for v in a.split.split(",") if v]:
+        dec.split_bytes = sb
+        ts = timed(lambda: dec.decode(plain, "gray", "device_split", out=out, stream=st))
+        same_split = same_split and bool(torch.equal(out, mono))
+        passes, segments, fallbacks = dec.split_info()
+        split_res[f"decode_split_{sb}_frames_per_s"] = round(B / med(ts), 1)
+        split_res[f"decode_split_{sb}_runs_s"] = [round(t, 5) for t in ts]
+        split_res[f"decode_split_{sb}_max_passes"] = passes
+        assert fallbacks == 0 and segments > 0
+    if a.split:
+        dec.split_bytes = ops.JPEG_SPLIT_BYTES_DEFAULT
+        ts = timed(lambda: dec.decode(rows, "gray", "device_split", out=out, stream=st))
+        same_split = same_split and bool(torch.equal(out, mono))
+        split_res["decode_split_default_restart_rows_frames_per_s"] = round(B / med(ts), 1)
+        split_res["decode_split_default_restart_rows_runs_s"] = [round(t, 5) for t in ts]
+        split_res["split_bytes_default"] = ops.JPEG_SPLIT_BYTES_DEFAULT
+        # the legs before, once more after the split ones (the legs alternate in one process)
+        ts = timed(lambda: dec.decode(plain, "gray", "device", out=out, stream=st))
+        split_res["decode_device_again_frames_per_s"] = round(B / med(ts), 1)
+        split_res["decode_device_again_runs_s"] = [round(t, 5) for t in ts]
+        ts = timed(lambda: dec.decode(rows, "gray", "device", out=out, stream=st))
+        split_res["decode_device_restart_rows_again_frames_per_s"] = round(B / med(ts), 1)
+        split_res["decode_device_restart_rows_again_runs_s"] = [round(t, 5) for t in ts]
+        split_res["split_decodes_equal"] = same_split
+    if a.decode_only:
+        dec.close()
+        print(json.dumps({
+            "source_hash": build.source_hash(), "device": torch.cuda.get_device_name(0), "width": W, "height": H,
+            "batch": B, "distinct": a.distinct, "quality": a.quality, "sampling": "4:2:0", "group_frames": a.group,
+            "runs": a.runs, "jpeg_bytes_per_frame": round(float(np.mean([len(b) for b in plain])), 1),
+            "decode_device_frames_per_s": round(B / med(t_dev), 1), "decode_device_runs_s": [round(t, 5) for t in t_dev],
+            "decode_device_restart_rows_frames_per_s": round(B / med(t_dev_rows), 1),
+            "decode_device_restart_rows_runs_s": [round(t, 5) for t in t_dev_rows],
+            "decode_host_frames_per_s": round(B / med(t_host), 1), "decode_host_runs_s": [round(t, 5) for t in t_host],
+            "decodes_equal": same_rows and same_host, **split_res,
+            "note": "one machine, one run; host clock around work that ends in a device synchronise"}))
+        return
 
     fs = FrameStream(W, H, scene.K, nfeatures=a.nfeatures, max_frames=B, ctx=ctx)
     depth = FrameStream.pipeline_depth()
@@ -137,7 +182,7 @@ def main():
         "submit_mono_frames_per_s": fps(t_mono, B * a.steps), "submit_mono_runs_s": r5(t_mono),
         "submit_jpeg_frames_per_s": fps(t_jpeg, B * a.steps), "submit_jpeg_runs_s": r5(t_jpeg),
         "pil_then_submit_frames_per_s": fps(t_pil, B * a.steps), "pil_then_submit_runs_s": r5(t_pil),
-        "records_equal": same_rec,
+        "records_equal": same_rec, **split_res,
         "note": "one machine, one run; host clock around work that ends in a device synchronise",
     }
     print(json.dumps(res))
