@@ -76,6 +76,14 @@ class KnnPairConfig(ctypes.Structure):
                 ("dist_thresh", ctypes.c_double)]
 
 
+class KnnStreamConfig(ctypes.Structure):
+    """dvo_knn_stream_config: the k-NN modes' batched device-resident stream (dvo_knn_stream_process)."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("max_frames", ctypes.c_int32),
+                ("detector", ctypes.c_int32), ("feat_cap", ctypes.c_int32), ("hessian_threshold", ctypes.c_double),
+                ("ratio", ctypes.c_double), ("K", ctypes.c_double * 9), ("prob", ctypes.c_double),
+                ("threshold", ctypes.c_double), ("max_iters", ctypes.c_int32), ("dist_thresh", ctypes.c_double)]
+
+
 class JpegLayout(ctypes.Structure):
     """dvo_jpeg_layout: what dvo_jpeg_entropy_host produces for one image."""
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("components", ctypes.c_int32),
@@ -144,6 +152,15 @@ _SIGNATURES = {
     "dvo_knn_pair_run": ([_vp, _vp, _vp, _c, _c, ctypes.POINTER(ctypes.c_uint64), _vp], _c),
     "dvo_knn_pair_get_matches": ([_vp, _vp, _c, _ip], _c),
     "dvo_knn_pair_get_features": ([_vp, _c, _vp, _vp, _c, _ip], _c),
+    "dvo_knn_stream_create": ([_vp, ctypes.POINTER(KnnStreamConfig), ctypes.POINTER(_vp)], _c),
+    "dvo_knn_stream_destroy": ([_vp], None),
+    "dvo_knn_stream_process": ([_vp, _vp, _c, _i64, _c, _vp], _c),
+    "dvo_knn_stream_sync": ([_vp], _c),
+    "dvo_knn_stream_hip_stream": ([_vp], _vp),
+    "dvo_knn_stream_get_features": ([_vp, _c, _vp, _vp, _c, _ip], _c),
+    "dvo_knn_stream_get_matches": ([_vp, _c, _vp, _c, _ip], _c),
+    "dvo_knn_stream_set_profiling": ([_vp, _c], _c),
+    "dvo_knn_stream_stage_times": ([_vp, _vp], _c),
     "dvo_stream_hip_stream": ([_vp], _vp),
     "dvo_stream_set_profiling": ([_vp, _c], _c),
     "dvo_stream_reset_pose": ([_vp, _vp, _vp], _c),
@@ -191,6 +208,7 @@ _SIGNATURES = {
     "dvo_test_five_point": ([_vp, _vp, _vp, _vp, _ip], _c),
     "dvo_test_sampson": ([_vp, _vp, _vp, _c, ctypes.c_float, _vp, _vp], _c),
     "dvo_test_ratio_gather": ([_vp, _vp, _vp, _c, _vp, _c, _vp, _c, _d, _c, _vp, _vp, _ip, _ip], _c),
+    "dvo_test_knn_batch": ([_vp, _vp, _vp, _vp, _c, _c, _c, _c, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ip], _c),
     "dvo_test_ransac_subsets": ([_vp, _c, _c, _vp], _c),
     "dvo_test_ransac_replay": ([_vp, _vp, _vp, _c, _c, _d, _c, _vp], _c),
     "dvo_test_ransac_hypotheses": ([_vp, _vp, _vp, _c, _c, _vp, _d, _d, _c, _c, _vp, _vp, _vp, _vp, _vp, _vp, _ip,

@@ -1346,6 +1346,10 @@ int dvo_flann_knn(dvo_ctx* ctx, const float* dq, int nq, const float* dt, int nt
 }
 
 namespace {
+// Keypoint list capacity of the detectors' plans (SiftArgs / SurfArgs::kp_cap).
+constexpr int kSiftKpCap = 1 << 16;
+int surf_kp_cap(int w, int h) { return std::max(4096, (w * h) / 64); }
+
 // getGaussianKernel(ksize = cvRound(sigma * 8 + 1) | 1, sigma, CV_32F), as oracle/sift.cpp gauss_kernel
 std::vector<float> sift_gauss_taps(double sigma) {
     const int n = (int)std::nearbyint(sigma * 4 * 2 + 1) | 1;
@@ -1385,7 +1389,7 @@ int sift_plan(dvo_ctx* ctx, int w, int h) {
         dg += 5 * px;
     }
     A.cand_cap = 1 << 18;
-    A.kp_cap = 1 << 16;
+    A.kp_cap = kSiftKpCap;
     std::vector<float> taps;
     const double sig0 = std::sqrt(std::max(1.6f * 1.6f - 0.5f * 0.5f * 4, 0.01f));
     std::vector<double> sig(6);
@@ -1499,7 +1503,7 @@ int surf_plan(dvo_ctx* ctx, int w, int h) {
             }
     A.nori = (int)aptw.size();
     for (int i = 0; i < 20; ++i) A.gdesc[i] = gd[i];
-    A.kp_cap = std::max(4096, (w * h) / 64);
+    A.kp_cap = surf_kp_cap(w, h);
     int order_n = 1;
     while (order_n < A.kp_cap) order_n <<= 1;
     auto A_ = [&](auto*& p, size_t bytes) { return P.mem.alloc(&p, bytes ? bytes : 16) == hipSuccess; };
@@ -2056,6 +2060,356 @@ int dvo_test_ratio_gather(dvo_ctx* ctx, const int32_t* idx, const float* dist, i
         std::memcpy(pts, hp, (size_t)words[0] * 16);
         std::memcpy(matches, hm, (size_t)words[0] * sizeof(dvo_dmatch));
     }
+    return DVO_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The k-NN modes' batched stream (dvo_knn_stream): dvo_knn_pair_run's path for many device-resident
+// frames per call, nothing read back on the way.
+extern "C++" {  // KnnBatch has a member template
+namespace {
+// Frame slots and per-pair match arrays of the batched k-NN path: what dvo_knn_pair_run keeps in
+// its two slots and takes from CallMem, for F frames and F - 1 pairs.
+struct KnnBatch {
+    int F = 0, cap = 0, dim = 0, cus = 0;
+    int fixed_ranges = 0;    // > 0: every call runs this many train ranges (the test hook)
+    size_t part_lists = 0;   // (pair, range) partial lists pdist / pidx hold
+    dvo_keypoint* kps = nullptr;  // [F][cap]
+    float* desc = nullptr;        // [F][cap][dim]
+    int32_t* n = nullptr;         // [F][2] detector count, flags (feature_copy_kernel)
+    int32_t* fstate = nullptr;    // [F][2] features brought to the pairs, marked
+    uint32_t* bytes = nullptr;    // SIFT: [F][cap][dim / 4]
+    uint32_t* norms = nullptr;    // SIFT: [F][cap]
+    int32_t* rejected = nullptr;  // SIFT: [F]
+    float* dist = nullptr;        // [P][cap][2]
+    int32_t* idx = nullptr;
+    float* pdist = nullptr;       // [part_lists][cap][2]
+    int32_t* pidx = nullptr;
+    dvo_dmatch* matches = nullptr;  // [P][cap]
+    int32_t* missing = nullptr;     // [P]
+
+    int ranges_of(int pairs) const { return fixed_ranges > 0 ? fixed_ranges : knn_batch_ranges(cap, pairs, cus); }
+
+    // take(pointer, bytes) per array; false from take stops the walk
+    template <class Take>
+    bool layout(int F_, int cap_, int dim_, int cus_, int fixed_ranges_, Take&& take) {
+        F = F_, cap = cap_, dim = dim_, cus = cus_, fixed_ranges = fixed_ranges_;
+        const size_t P = (size_t)std::max(F - 1, 1), C = (size_t)cap;
+        part_lists = 0;
+        for (int p = 1; p < F; ++p) {
+            const size_t r = (size_t)ranges_of(p);
+            if (r > 1) part_lists = std::max(part_lists, r * p);
+        }
+        const size_t L = std::max<size_t>(part_lists, 1);
+        bool ok = take(kps, F * C * sizeof(dvo_keypoint)) && take(desc, F * C * dim * 4) && take(n, (size_t)F * 8) &&
+                  take(fstate, (size_t)F * 8) && take(dist, P * C * 8) && take(idx, P * C * 8) &&
+                  take(pdist, L * C * 8) && take(pidx, L * C * 8) && take(matches, P * C * sizeof(dvo_dmatch)) &&
+                  take(missing, P * 4);
+        if (ok && dim == 128)  // SURF rows are never byte-valued: neither the pack nor the byte kernel runs
+            ok = take(bytes, F * C * dim) && take(norms, F * C * 4) && take(rejected, (size_t)F * 4);
+        return ok;
+    }
+
+    // Steps 2 to 4 of a call over `frames` slots: frame state, pack + k-NN (+ merge), ratio test and gather.
+    hipError_t match(int frames, double ratio, float* pts, int32_t* nmatch, PairHeader* hdr, hipStream_t s) const {
+        hipError_t e = launch_knn_frame_state(n, frames, cap, fstate, s);
+        if (e != hipSuccess || frames < 2) return e;
+        const KnnBatchArgs ka{desc, fstate, bytes, norms, rejected, cap, dim, dist, idx, pdist, pidx};
+        if ((e = launch_knn_batch(ka, frames, ranges_of(frames - 1), s)) != hipSuccess) return e;
+        const RatioBatchArgs ra{idx, dist, kps, n, fstate, cap, ratio, pts, matches, nmatch, hdr, missing};
+        return launch_ratio_gather_batch(ra, frames - 1, s);
+    }
+};
+
+constexpr int kKnnStreamMaxFrames = 65536;  // pairs ride a grid's y / z dimension
+}  // namespace
+}  // extern "C++"
+
+struct dvo_knn_stream {
+    dvo_ctx* ctx = nullptr;
+    dvo_knn_stream_config cfg{};
+    KnnBatch b;
+    PairSets pairs;    // one set of max_frames - 1 pairs: pairs.all.g is the stream's GeomArgs
+    DeviceAllocs mem;  // the frame slots, the match arrays and the round-local geometry arrays
+    int last_frames = 0;
+    bool profiling = false, timed = false;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+
+    ~dvo_knn_stream() {
+        for (auto e : ev)
+            if (e) hipEventDestroy(e);
+    }
+};
+
+namespace {
+int knn_stream_plan(dvo_knn_stream* s) {
+    return s->cfg.detector == DVO_DETECT_SIFT ? sift_plan(s->ctx, s->cfg.width, s->cfg.height)
+                                              : surf_plan(s->ctx, s->cfg.width, s->cfg.height);
+}
+}  // namespace
+
+int dvo_knn_stream_create(dvo_ctx* ctx, const dvo_knn_stream_config* cfg, dvo_knn_stream** out) {
+    if (!ctx || !cfg || !out) return DVO_EINVAL;
+    *out = nullptr;
+    dvo_knn_pair_config pc{};
+    pc.width = cfg->width, pc.height = cfg->height;
+    pc.detector = cfg->detector, pc.matcher = DVO_MATCH_BF_L1;
+    pc.hessian_threshold = cfg->hessian_threshold;
+    pc.ratio = cfg->ratio;
+    pc.prob = cfg->prob, pc.threshold = cfg->threshold, pc.max_iters = cfg->max_iters, pc.dist_thresh = cfg->dist_thresh;
+    int rc = check_knn_pair_config(ctx, &pc);
+    if (rc) return rc;
+    if (cfg->max_frames < 2 || cfg->max_frames > kKnnStreamMaxFrames)
+        return fail(ctx, DVO_EINVAL, "max_frames out of range (2..65536)");
+    const bool sift = cfg->detector == DVO_DETECT_SIFT;
+    const int det_cap = sift ? kSiftKpCap : surf_kp_cap(cfg->width, cfg->height);
+    if (cfg->feat_cap != 0 && (cfg->feat_cap < 2 || cfg->feat_cap > det_cap))
+        return fail(ctx, DVO_EINVAL, "feat_cap must be 0 or 2..the detector's list capacity");
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::unique_ptr<dvo_knn_stream> s(new dvo_knn_stream);
+    s->ctx = ctx;
+    s->cfg = *cfg;
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    if ((rc = knn_stream_plan(s.get()))) return rc;
+    const int F = cfg->max_frames, P = F - 1, cap = cfg->feat_cap ? cfg->feat_cap : det_cap;
+    hipError_t he = hipSuccess;
+    s->b.layout(F, cap, sift ? 128 : 64, cus, 0, [&](auto*& p, size_t bytes) {
+        he = s->mem.alloc(&p, bytes);
+        return he == hipSuccess;
+    });
+    HIP_TRY(he);
+    // the geometry as a dvo_stream allocates it (stream_alloc): the per-pair arrays from PairSets,
+    // the round-local ones sized for the largest round of P pairs
+    const size_t hc = (size_t)cfg->max_iters;
+    GeomArgs& g = s->pairs.all.g;
+    g.pts_stride = cap;
+    set_camera(g, cfg->K);
+    g.prob = cfg->prob;
+    g.threshold = cfg->threshold;
+    g.max_iters = cfg->max_iters;
+    g.dist_thresh = cfg->dist_thresh;
+    g.hyp_cap = (int)hc;
+    g.dk_list_cap = std::max<int64_t>(round_items_bound(P, (int)hc), (int64_t)hc);
+    s->pairs.stream = ctx->stream;
+    HIP_TRY(s->pairs.ensure(1, P, cap, hc));
+    const size_t blocks = (size_t)std::max<int64_t>(round_blocks_bound(P, (int)hc), (int64_t)(hc + 63) / 64);
+    HIP_TRY(s->mem.alloc(&g.fprec, blocks * 128 * 64 * sizeof(double) + 256));
+    HIP_TRY(s->mem.alloc(&g.dk_ctl, (size_t)(2 + kDkMaxPasses) * sizeof(int32_t) + 256));
+    HIP_TRY(s->mem.alloc(&g.dk_list, (size_t)(kDkMaxPasses - 1) * g.dk_list_cap * sizeof(int32_t) + 256));
+    *out = s.release();
+    return DVO_OK;
+}
+
+void dvo_knn_stream_destroy(dvo_knn_stream* s) {
+    if (!s) return;
+    hipSetDevice(s->ctx->device);
+    hipStreamSynchronize(s->ctx->stream);
+    delete s;
+}
+
+int dvo_knn_stream_process(dvo_knn_stream* st, const uint8_t* d_frames, int n_frames, int64_t frame_stride, int stride,
+                           dvo_pair_record* d_records) {
+    if (!st) return DVO_EINVAL;
+    dvo_ctx* ctx = st->ctx;
+    const dvo_knn_stream_config& c = st->cfg;
+    const int w = c.width, h = c.height;
+    if (n_frames < 1 || n_frames > c.max_frames) return fail(ctx, DVO_EINVAL, "n_frames out of range (1..max_frames)");
+    if (!d_frames || stride < w || (n_frames > 1 && !d_records)) return fail(ctx, DVO_EINVAL, "bad frame or record buffer");
+    HIP_TRY(hipSetDevice(ctx->device));
+    int rc = knn_stream_plan(st);  // another size may have taken the context's plan since
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    const KnnBatch& b = st->b;
+    const bool sift = c.detector == DVO_DETECT_SIFT;
+    hipEvent_t* ev = st->profiling ? st->ev : nullptr;
+    st->last_frames = 0;
+    st->timed = false;
+    if (ev) HIP_TRY(hipEventRecord(ev[0], s));
+    // detection, frame by frame (the plan's scratch is single), in place on the caller's frames
+    for (int f = 0; f < n_frames; ++f) {
+        const uint8_t* img = d_frames + (int64_t)f * frame_stride;
+        dvo_keypoint* kps = b.kps + (size_t)f * b.cap;
+        float* desc = b.desc + (size_t)f * b.cap * b.dim;
+        int32_t* dn = b.n + 2 * (size_t)f;
+        if (sift) {
+            SiftPlanDev& D = ctx->sift;
+            HIP_TRY(hipMemsetAsync(D.a.ncand, 0, 16, s));
+            HIP_TRY(launch_sift(D.a, img, w, h, stride, D.taps, D.tap_off, D.tap_n, s));
+            HIP_TRY(launch_feature_copy(D.a.kps, D.a.desc, D.a.nkp, D.a.flags, b.cap, 128, kps, desc, dn, s));
+        } else {
+            SurfPlanDev& D = ctx->surf;
+            D.a.thr = (float)c.hessian_threshold;
+            HIP_TRY(hipMemsetAsync(D.a.nraw, 0, 16, s));
+            const int64_t cells = D.a.off[kSurfTot - 1] + (int64_t)D.a.rows[kSurfOct - 1] * D.a.cols[kSurfOct - 1];
+            HIP_TRY(hipMemsetAsync(D.a.det, 0, (size_t)cells * 4, s));
+            HIP_TRY(hipMemsetAsync(D.a.trace, 0, (size_t)cells * 4, s));
+            SurfArgs a = D.a;
+            a.img = img;
+            a.pitch = stride;
+            HIP_TRY(launch_surf(a, s));
+            HIP_TRY(launch_feature_copy(D.a.out, D.a.desc, D.a.nout, D.a.flags, b.cap, 64, kps, desc, dn, s));
+        }
+    }
+    if (ev) HIP_TRY(hipEventRecord(ev[1], s));
+    const int pairs = n_frames - 1;
+    const PairArrays& v = st->pairs.all;
+    HIP_TRY(b.match(n_frames, c.ratio, v.pts, v.nmatch, v.hdr, s));
+    if (ev) HIP_TRY(hipEventRecord(ev[2], s));
+    if (pairs >= 1) {
+        // the stream's round schedule (not kStageOneRound): a record does not depend on the split into calls
+        HIP_TRY(launch_geometry_args(v.g, pairs, kStageNormalize | kStageRansac, s));
+        HIP_TRY(launch_retire(v.g, pairs, v.hdr, d_records, s));
+        HIP_TRY(launch_knn_status(b.n, b.fstate, b.missing, pairs, d_records, s));
+    }
+    if (ev) {
+        HIP_TRY(hipEventRecord(ev[3], s));
+        st->timed = true;
+    }
+    st->last_frames = n_frames;
+    return DVO_OK;
+}
+
+int dvo_knn_stream_sync(dvo_knn_stream* s) {
+    if (!s) return DVO_EINVAL;
+    dvo_ctx* ctx = s->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipGetLastError());
+    return DVO_OK;
+}
+
+void* dvo_knn_stream_hip_stream(dvo_knn_stream* s) { return s ? (void*)s->ctx->stream : nullptr; }
+
+int dvo_knn_stream_set_profiling(dvo_knn_stream* s, int enable) {
+    if (!s) return DVO_EINVAL;
+    dvo_ctx* ctx = s->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (enable)
+        for (auto& e : s->ev)
+            if (!e) HIP_TRY(hipEventCreate(&e));
+    s->profiling = enable != 0;
+    s->timed = false;
+    return DVO_OK;
+}
+
+int dvo_knn_stream_stage_times(dvo_knn_stream* s, double* ms) {
+    if (!s || !ms) return DVO_EINVAL;
+    dvo_ctx* ctx = s->ctx;
+    if (!s->timed) return fail(ctx, DVO_EINVAL, "no profiled dvo_knn_stream_process call");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipEventSynchronize(s->ev[3]));
+    for (int k = 0; k < 3; ++k) {
+        float t = 0.f;
+        HIP_TRY(hipEventElapsedTime(&t, s->ev[k], s->ev[k + 1]));
+        ms[k] = t;
+    }
+    return DVO_OK;
+}
+
+int dvo_knn_stream_get_features(dvo_knn_stream* s, int frame, dvo_keypoint* kps, float* desc, int cap, int* n) {
+    if (!s || !n) return DVO_EINVAL;
+    dvo_ctx* ctx = s->ctx;
+    *n = 0;
+    if (frame < 0 || frame >= s->last_frames) return fail(ctx, DVO_EINVAL, "frame outside the last call");
+    const KnnBatch& b = s->b;
+    HIP_TRY(hipSetDevice(ctx->device));
+    int32_t cf[2];
+    HIP_TRY(hipMemcpyAsync(cf, b.n + 2 * (size_t)frame, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *n = cf[0];
+    if (cf[1] || cf[0] > b.cap) return fail(ctx, DVO_ECAP, "the frame has more features than the stream keeps (feat_cap)");
+    if (cf[0] > cap) return fail(ctx, DVO_ECAP, "caller capacity too small");
+    if (cf[0] <= 0) return DVO_OK;
+    if (kps)
+        HIP_TRY(hipMemcpyAsync(kps, b.kps + (size_t)frame * b.cap, (size_t)cf[0] * sizeof(dvo_keypoint), hipMemcpyDeviceToHost,
+                               ctx->stream));
+    if (desc)
+        HIP_TRY(hipMemcpyAsync(desc, b.desc + (size_t)frame * b.cap * b.dim, (size_t)cf[0] * b.dim * 4, hipMemcpyDeviceToHost,
+                               ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return DVO_OK;
+}
+
+int dvo_knn_stream_get_matches(dvo_knn_stream* s, int pair, dvo_dmatch* out, int cap, int* m) {
+    if (!s || !m) return DVO_EINVAL;
+    dvo_ctx* ctx = s->ctx;
+    *m = 0;
+    if (pair < 0 || pair >= s->last_frames - 1) return fail(ctx, DVO_EINVAL, "pair outside the last call");
+    HIP_TRY(hipSetDevice(ctx->device));
+    int32_t nm = 0;
+    HIP_TRY(hipMemcpyAsync(&nm, s->pairs.all.nmatch + pair, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *m = nm;
+    if (nm > cap) return fail(ctx, DVO_ECAP, "caller capacity too small");
+    if (nm <= 0) return DVO_OK;
+    if (!out) return fail(ctx, DVO_EINVAL, "null buffer");
+    HIP_TRY(hipMemcpyAsync(out, s->b.matches + (size_t)pair * s->b.cap, (size_t)nm * sizeof(dvo_dmatch),
+                           hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return DVO_OK;
+}
+
+// Test hook: the matching stages of dvo_knn_stream_process on host arrays.
+int dvo_test_knn_batch(dvo_ctx* ctx, const float* desc, const dvo_keypoint* kps, const int32_t* counts, int frames,
+                       int cap, int dim, int ranges, double ratio, int32_t* idx, float* dist, int32_t* nmatch,
+                       dvo_dmatch* matches, float* pts, int32_t* hdr, int32_t* missing, int* ranges_used) {
+    if (!ctx || !desc || !kps || !counts || !idx || !dist || !nmatch || !matches || !pts || !hdr || !missing ||
+        !ranges_used)
+        return DVO_EINVAL;
+    if (frames < 2 || frames > 4096 || cap < 2 || cap > (1 << 16) || (dim != 128 && dim != 64) || ranges < 0 ||
+        ranges > cap)
+        return fail(ctx, DVO_EINVAL, "frames 2..4096, cap 2..65536, dim 64 or 128, ranges 0..cap");
+    if (!std::isfinite(ratio) || !(ratio > 0)) return fail(ctx, DVO_EINVAL, "ratio must be finite and > 0");
+    for (int f = 0; f < frames; ++f)
+        if (counts[f] < 0) return fail(ctx, DVO_EINVAL, "negative count");
+    HIP_TRY(hipSetDevice(ctx->device));
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    hipStream_t s = ctx->stream;
+    CallMem mem(ctx->call, s);
+    KnnBatch b;
+    b.layout(frames, cap, dim, cus, ranges, [&](auto*& p, size_t bytes) {
+        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(mem.dev<uint8_t>(bytes));
+        return true;
+    });
+    const size_t P = (size_t)frames - 1, C = (size_t)cap;
+    float* d_pts = mem.dev<float>(P * C * 4);
+    int32_t* d_nmatch = mem.dev<int32_t>(P);
+    PairHeader* d_hdr = mem.dev<PairHeader>(P);
+    HIP_TRY(mem.error());
+    std::vector<int32_t> n2(2 * (size_t)frames, 0);
+    for (int f = 0; f < frames; ++f) n2[2 * (size_t)f] = counts[f];
+    *ranges_used = b.ranges_of(frames - 1);
+    uint8_t *hi, *hd, *hn, *hm, *hp, *hh, *hs;
+    // after the first upload an error drains the stream before returning (the copies use the
+    // context's pinned buffers, which the next per-call entry point rewrites)
+    auto body = [&]() -> int {
+        HIP_TRY(mem.put(b.desc, desc, (size_t)frames * C * dim * 4));
+        HIP_TRY(mem.put(b.kps, kps, (size_t)frames * C * sizeof(dvo_keypoint)));
+        HIP_TRY(mem.put(b.n, n2.data(), n2.size() * 4));
+        HIP_TRY(b.match(frames, ratio, d_pts, d_nmatch, d_hdr, s));
+        HIP_TRY(mem.get(b.idx, P * C * 8, &hi));
+        HIP_TRY(mem.get(b.dist, P * C * 8, &hd));
+        HIP_TRY(mem.get(d_nmatch, P * 4, &hn));
+        HIP_TRY(mem.get(b.matches, P * C * sizeof(dvo_dmatch), &hm));
+        HIP_TRY(mem.get(d_pts, P * C * 16, &hp));
+        HIP_TRY(mem.get(d_hdr, P * sizeof(PairHeader), &hh));
+        HIP_TRY(mem.get(b.missing, P * 4, &hs));
+        HIP_TRY(hipStreamSynchronize(s));
+        return DVO_OK;
+    };
+    if (int rc = body()) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    std::memcpy(idx, hi, P * C * 8);
+    std::memcpy(dist, hd, P * C * 8);
+    std::memcpy(nmatch, hn, P * 4);
+    std::memcpy(matches, hm, P * C * sizeof(dvo_dmatch));
+    std::memcpy(pts, hp, P * C * 16);
+    std::memcpy(hdr, hh, P * sizeof(PairHeader));
+    std::memcpy(missing, hs, P * 4);
     return DVO_OK;
 }
 

@@ -462,6 +462,48 @@ hipError_t launch_ratio_gather(const RatioArgs& a, hipStream_t s);
 // feature slot, dn = {*cnt, *flags}
 hipError_t launch_feature_copy(const dvo_keypoint* skps, const float* sdesc, const int32_t* cnt, const int32_t* flags,
                                int kp_cap, int dim, dvo_keypoint* dkps, float* ddesc, int32_t* dn, hipStream_t s);
+// ---- the batched k-NN path (dvo_knn_stream): many pairs per launch, counts read on the device ----
+// Frame slots hold `cap` features each; pair p is frames p (queries) and p + 1 (trains).
+// fstate[f] = {features the frame brings to its pairs, marked}: a frame whose detector count
+// exceeds cap or whose detector flagged an overflow is marked and brings 0 features.
+hipError_t launch_knn_frame_state(const int32_t* d_n /*[F][2] count, flags*/, int frames, int cap,
+                                  int32_t* d_fstate /*[F][2]*/, hipStream_t s);
+struct KnnBatchArgs {
+    const float* desc;        // [F][cap][dim]
+    const int32_t* fstate;    // [F][2]
+    uint32_t* bytes;          // [F][cap][dim / 4] byte-packed rows (dim 128 only; null: no byte path)
+    uint32_t* norms;          // [F][cap] squared norms of the packed rows
+    int32_t* rejected;        // [F] 1: the frame holds a value that is not an integer in [0, 255]
+    int cap, dim;
+    float* dist;              // [P][cap][2] the k = 2 lists
+    int32_t* idx;
+    float* pdist;             // [P][ranges][cap][2] partial lists (ranges > 1)
+    int32_t* pidx;
+};
+// Train ranges of a batch launch: about two rounds of resident workgroups over all pairs.
+int knn_batch_ranges(int cap, int pairs, int cus);
+// BFMatcher(NORM_L1).knnMatch(k = 2) of `pairs` pairs: pack (dim 128), byte / float scan, merge.
+hipError_t launch_knn_batch(const KnnBatchArgs& a, int frames, int ranges, hipStream_t s);
+struct RatioBatchArgs {
+    const int32_t* idx;       // [P][cap][2]
+    const float* dist;
+    const dvo_keypoint* kps;  // [F][cap]
+    const int32_t* n;         // [F][2] detector count, flags
+    const int32_t* fstate;    // [F][2]
+    int cap;
+    double ratio;
+    float* pts;               // [P][cap][4]
+    dvo_dmatch* matches;      // [P][cap]
+    int32_t* nmatch;          // [P]
+    PairHeader* hdr;          // [P] {detector counts, marked(prev) | marked(cur), 0}
+    int32_t* missing;         // [P]
+};
+hipError_t launch_ratio_gather_batch(const RatioBatchArgs& a, int pairs, hipStream_t s);
+// The records of pairs the reference raises on before findEssentialMat (no query, fewer than 2
+// trains, a query without a second neighbour): status DVO_ENOFEAT, the counts, zeros elsewhere.
+// Pairs of a marked frame keep records_kernel's DVO_ECAP.
+hipError_t launch_knn_status(const int32_t* d_n, const int32_t* d_fstate, const int32_t* d_missing, int pairs,
+                             dvo_pair_record* records, hipStream_t s);
 hipError_t launch_test_retain_best(float* d_resp, uint32_t* d_payload, int32_t* d_tmp, int n, int n_points, int depth,
                                    int semantics, int* d_k, hipStream_t s);
 hipError_t launch_test_update_num_iters(double p, const double* d_ep, int n, int model_points, int max_iters,

@@ -817,6 +817,270 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const float* __restrict_
     }
 }
 
+// ---- many pairs per launch, counts read on the device (dvo_knn_stream) -------
+// The twins of the four kernels above for a batch of frame slots of `cap` rows: pair p = blockIdx.z
+// (.y in the merge) takes its queries from frame p and its trains from frame p + 1, nq and nt from
+// fstate (a marked frame brings 0), k = 2, NORM_L1.  The grids are sized from cap alone, so a
+// workgroup whose first query is at or past nq returns before it loads a descriptor (nq = 0
+// included: the clamp qs = nq - 1 is never formed then).  Rows are packed once per frame with a
+// per-frame flag; a pair takes the byte kernel iff both its frames' flags are 0, uniformly per
+// workgroup.  Train range c = [c range, (c + 1) range) is fixed for the launch from cap; one that
+// starts at or past nt writes nothing and the merge skips it, so every partial slot the merge
+// reads was written in this launch sequence.  With one range the scan kernels write the lists
+// themselves, and nt = 0 leaves (-1, FLT_MAX) for the live queries.  The distance arithmetic and
+// the list order are dist_group / knn_insert / knn_merge2, as in the single-pair kernels: the
+// lists are bit for bit launch_knn_float's on the pair's descriptors.
+__global__ __launch_bounds__(256) void knn_pack_u8_batch_kernel(KnnBatchArgs a) {
+    const int f = blockIdx.y;
+    const int n = a.fstate[2 * f];
+    const int wpr = a.dim / 4;  // 32: divides 64
+    const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x, words = (int64_t)n * wpr;
+    if ((int64_t)blockIdx.x * 256 >= words) return;  // block-uniform
+    const bool in = id < words;
+    const float4* __restrict__ x = reinterpret_cast<const float4*>(a.desc + (size_t)f * a.cap * a.dim);
+    const float4 v = in ? x[id] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float e[4] = {v.x, v.y, v.z, v.w};
+    uint32_t word = 0, ss = 0;
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        ok &= e[c] >= 0.f && e[c] <= 255.f && e[c] == __builtin_rintf(e[c]);  // NaN fails
+        const uint32_t b = e[c] >= 0.f && e[c] <= 255.f ? (uint32_t)e[c] : 0u;
+        word |= b << (8 * c);
+        ss += b * b;
+    }
+    for (int o = 1; o < wpr; o <<= 1) ss += __shfl_xor(ss, o);
+    if (in) {
+        a.bytes[(size_t)f * a.cap * wpr + id] = word;
+        if ((id & (wpr - 1)) == 0) a.norms[(size_t)f * a.cap + id / wpr] = ss;
+    }
+    if (__ballot(!ok) != 0 && (threadIdx.x & 63) == 0) atomicOr(a.rejected + f, 1);
+}
+
+// The list slots of (pair p, range c): the lists themselves when the launch has one range.
+__device__ __forceinline__ size_t knn_batch_slot(const KnnBatchArgs& a, int p, int ranges, int c) {
+    return (ranges == 1 ? (size_t)p : (size_t)p * ranges + c) * a.cap * 2;
+}
+
+template <int D>
+__global__ __launch_bounds__(kKnnQ) void knn_float_batch_kernel(KnnBatchArgs a, int range) {
+    constexpr int K = 2, R = D / 4;
+    static_assert(R % kKnnG == 0, "pipeline depth must divide the row");
+    __shared__ float4 st[kKnnTC * R];
+    const int p = blockIdx.z, ranges = gridDim.y;
+    const int nq = a.fstate[2 * p], nt = a.fstate[2 * p + 2];
+    if ((int)(blockIdx.x * kKnnQ) >= nq) return;                                // no live query (nq = 0 too)
+    if (a.rejected && (a.rejected[p] | a.rejected[p + 1]) == 0) return;         // knn_u8_batch_kernel serves the pair
+    const int qi = blockIdx.x * kKnnQ + threadIdx.x;
+    const size_t o = knn_batch_slot(a, p, ranges, blockIdx.y) + (size_t)qi * K;
+    float* __restrict__ odist = ranges == 1 ? a.dist : a.pdist;
+    int32_t* __restrict__ oidx = ranges == 1 ? a.idx : a.pidx;
+    const int r0 = blockIdx.y * range, r1 = min(nt, r0 + range);
+    if (r0 >= nt) {  // an empty range: the merge skips it; alone (nt = 0) it leaves empty lists
+        if (ranges == 1 && qi < nq) {
+#pragma unroll
+            for (int s = 0; s < K; ++s) {
+                odist[o + s] = FLT_MAX;
+                oidx[o + s] = -1;
+            }
+        }
+        return;
+    }
+    const float* __restrict__ q = a.desc + (size_t)p * a.cap * D;
+    const float* __restrict__ t = q + (size_t)a.cap * D;
+    const int qs = qi < nq ? qi : nq - 1;  // clamped: spare lanes compute, never store
+    float qv[D];
+    const float4* q4 = reinterpret_cast<const float4*>(q + (size_t)qs * D);
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+        const float4 v = q4[i];
+        qv[4 * i] = v.x;
+        qv[4 * i + 1] = v.y;
+        qv[4 * i + 2] = v.z;
+        qv[4 * i + 3] = v.w;
+    }
+    float bd[K];
+    int bi[K];
+#pragma unroll
+    for (int s = 0; s < K; ++s) {
+        bd[s] = FLT_MAX;
+        bi[s] = -1;
+    }
+    for (int j0 = r0; j0 < r1; j0 += kKnnTC) {
+        const int nj = min(r1 - j0, kKnnTC);
+        const float4* src = reinterpret_cast<const float4*>(t + (size_t)j0 * D);
+        if (j0 != r0) __syncthreads();  // previous stage fully read
+        for (int i = threadIdx.x; i < nj * R; i += kKnnQ) st[i] = src[i];
+        __syncthreads();
+        float4 cur[kKnnG];
+#pragma unroll
+        for (int e = 0; e < kKnnG; ++e) cur[e] = st[e];
+        for (int j = 0; j < nj; ++j) {
+            const float4* row = st + j * R;
+            const float4* nrow = st + min(j + 1, nj - 1) * R;
+            float s = 0.f;
+#pragma unroll
+            for (int g = 0; g < R; g += kKnnG) {
+                float4 nxt[kKnnG];
+                const float4* pf = g + kKnnG < R ? row + g + kKnnG : nrow;
+#pragma unroll
+                for (int e = 0; e < kKnnG; ++e) nxt[e] = pf[e];
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int e = 0; e < kKnnG; ++e) {
+                    const int i = 4 * (g + e);
+                    dist_group<0>(s, qv[i], qv[i + 1], qv[i + 2], qv[i + 3], cur[e]);
+                }
+#pragma unroll
+                for (int e = 0; e < kKnnG; ++e) cur[e] = nxt[e];
+            }
+            knn_insert<K>(bd, bi, s, j0 + j);
+        }
+    }
+    if (qi < nq) {
+#pragma unroll
+        for (int s = 0; s < K; ++s) {
+            odist[o + s] = bd[s];
+            oidx[o + s] = bi[s];
+        }
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void knn_u8_batch_kernel(KnnBatchArgs a, int range) {
+    constexpr int K = 2, W = D / 16;  // uint4 per row
+    __shared__ uint4 st[kKnnTC * W];
+    const int p = blockIdx.z, ranges = gridDim.y;
+    const int nq = a.fstate[2 * p], nt = a.fstate[2 * p + 2];
+    if ((int)(blockIdx.x * (256 * kKnnU8Q)) >= nq) return;       // no live query (nq = 0 too)
+    if ((a.rejected[p] | a.rejected[p + 1]) != 0) return;        // knn_float_batch_kernel serves the pair
+    const size_t ob = knn_batch_slot(a, p, ranges, blockIdx.y);
+    float* __restrict__ odist = ranges == 1 ? a.dist : a.pdist;
+    int32_t* __restrict__ oidx = ranges == 1 ? a.idx : a.pidx;
+    int qi[kKnnU8Q];
+#pragma unroll
+    for (int u = 0; u < kKnnU8Q; ++u) qi[u] = blockIdx.x * (256 * kKnnU8Q) + 256 * u + threadIdx.x;
+    const int r0 = blockIdx.y * range, r1 = min(nt, r0 + range);
+    if (r0 >= nt) {
+        if (ranges == 1) {
+#pragma unroll
+            for (int u = 0; u < kKnnU8Q; ++u)
+                if (qi[u] < nq) {
+#pragma unroll
+                    for (int s2 = 0; s2 < K; ++s2) {
+                        odist[ob + (size_t)qi[u] * K + s2] = FLT_MAX;
+                        oidx[ob + (size_t)qi[u] * K + s2] = -1;
+                    }
+                }
+        }
+        return;
+    }
+    const uint32_t* __restrict__ q = a.bytes + (size_t)p * a.cap * (D / 4);
+    const uint32_t* __restrict__ t = q + (size_t)a.cap * (D / 4);
+    uint4 qv[kKnnU8Q][W];
+    float bd[kKnnU8Q][K];
+    int bi[kKnnU8Q][K];
+#pragma unroll
+    for (int u = 0; u < kKnnU8Q; ++u) {
+        const int qs = qi[u] < nq ? qi[u] : nq - 1;
+        const uint4* q4 = reinterpret_cast<const uint4*>(q + (size_t)qs * (D / 4));
+#pragma unroll
+        for (int g = 0; g < W; ++g) qv[u][g] = q4[g];
+#pragma unroll
+        for (int s2 = 0; s2 < K; ++s2) {
+            bd[u][s2] = FLT_MAX;
+            bi[u][s2] = -1;
+        }
+    }
+    for (int j0 = r0; j0 < r1; j0 += kKnnTC) {
+        const int nj = min(r1 - j0, kKnnTC);
+        const uint4* src = reinterpret_cast<const uint4*>(t + (size_t)j0 * (D / 4));
+        if (j0 != r0) __syncthreads();
+        for (int i = threadIdx.x; i < nj * W; i += 256) st[i] = src[i];
+        __syncthreads();
+        uint4 cur[W];
+#pragma unroll
+        for (int g = 0; g < W; ++g) cur[g] = st[g];
+        for (int j = 0; j < nj; ++j) {
+            uint4 nxt[W];
+            const uint4* nrow = st + min(j + 1, nj - 1) * W;
+#pragma unroll
+            for (int g = 0; g < W; ++g) nxt[g] = nrow[g];
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < kKnnU8Q; ++u) {
+                uint32_t acc = 0;
+#pragma unroll
+                for (int g = 0; g < W; ++g) {
+                    acc = __builtin_amdgcn_sad_u8(qv[u][g].x, cur[g].x, acc);
+                    acc = __builtin_amdgcn_sad_u8(qv[u][g].y, cur[g].y, acc);
+                    acc = __builtin_amdgcn_sad_u8(qv[u][g].z, cur[g].z, acc);
+                    acc = __builtin_amdgcn_sad_u8(qv[u][g].w, cur[g].w, acc);
+                }
+                knn_insert<K>(bd[u], bi[u], (float)acc, j0 + j);  // exact: < 2^24
+            }
+#pragma unroll
+            for (int g = 0; g < W; ++g) cur[g] = nxt[g];
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < kKnnU8Q; ++u)
+        if (qi[u] < nq) {
+#pragma unroll
+            for (int s2 = 0; s2 < K; ++s2) {
+                odist[ob + (size_t)qi[u] * K + s2] = bd[u][s2];
+                oidx[ob + (size_t)qi[u] * K + s2] = bi[u][s2];
+            }
+        }
+}
+
+// one wave per (pair, query), as knn_merge_kernel; ranges that start at or past nt were not written
+__global__ __launch_bounds__(256) void knn_merge_batch_kernel(KnnBatchArgs a, int ranges, int range) {
+    constexpr int K = 2;
+    const int p = blockIdx.y;
+    const int nq = a.fstate[2 * p], nt = a.fstate[2 * p + 2];
+    const int qi = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (qi >= nq) return;  // wave-uniform
+    const size_t pb = (size_t)p * ranges * a.cap * K;
+    float bd[K];
+    int bi[K];
+#pragma unroll
+    for (int s = 0; s < K; ++s) {
+        bd[s] = FLT_MAX;
+        bi[s] = INT_MAX;
+    }
+    for (int c = lane; c < ranges && c * range < nt; c += 64) {
+        const size_t o = pb + ((size_t)c * a.cap + qi) * K;
+        float cd[K];
+        int ci[K];
+#pragma unroll
+        for (int s = 0; s < K; ++s) {
+            const int i = a.pidx[o + s];
+            cd[s] = i >= 0 ? a.pdist[o + s] : FLT_MAX;
+            ci[s] = i >= 0 ? i : INT_MAX;
+        }
+        knn_merge2<K>(bd, bi, cd, ci);
+    }
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        float od[K];
+        int oi[K];
+#pragma unroll
+        for (int s = 0; s < K; ++s) {
+            od[s] = __shfl_xor(bd[s], m, 64);
+            oi[s] = __shfl_xor(bi[s], m, 64);
+        }
+        knn_merge2<K>(bd, bi, od, oi);
+    }
+    if (lane < K) {
+        const float d = lane == 0 ? bd[0] : bd[1];
+        const int i = lane == 0 ? bi[0] : bi[1];
+        const size_t o = ((size_t)p * a.cap + qi) * K + lane;
+        a.dist[o] = i == INT_MAX ? FLT_MAX : d;
+        a.idx[o] = i == INT_MAX ? -1 : i;
+    }
+}
+
 template <int D, int NORM, int K>
 hipError_t launch_knn_t(const float* d_q, int nq, const float* d_t, int nt, int ranges, const KnnBytes& u8,
                         float* d_part, int32_t* d_pidx, float* d_dist, int32_t* d_idx, hipStream_t s) {
@@ -860,6 +1124,42 @@ int knn_ranges(int nq, int nt, int cus) {
     ranges = std::max(ranges, 1);
     const int range = (nt + ranges - 1) / ranges;
     return (nt + range - 1) / range;  // no empty trailing range
+}
+
+int knn_batch_ranges(int cap, int pairs, int cus) {
+    // knn_ranges' rule over the launch's whole grid: every pair has cap / kKnnRangeQB query blocks
+    // (the counts stay on the device), so many pairs take one range and no merge launch
+    const int64_t qblocks = (int64_t)((cap + kKnnRangeQB - 1) / kKnnRangeQB) * std::max(pairs, 1);
+    int ranges = (int)std::min<int64_t>((cus * kKnnWgPerCu * 2) / qblocks, (cap + 15) / 16);
+    ranges = std::max(ranges, 1);
+    const int range = (cap + ranges - 1) / ranges;
+    return (cap + range - 1) / range;  // no empty trailing range
+}
+
+hipError_t launch_knn_batch(const KnnBatchArgs& a, int frames, int ranges, hipStream_t s) {
+    const int pairs = frames - 1;
+    if (pairs < 1) return hipSuccess;
+    if ((a.dim != 128 && a.dim != 64) || a.cap < 1 || ranges < 1 || ranges > a.cap) return hipErrorInvalidValue;
+    const int range = (a.cap + ranges - 1) / ranges;
+    const bool bytes = a.dim == 128 && a.bytes != nullptr;
+    const dim3 fgrid((a.cap + kKnnQ - 1) / kKnnQ, ranges, pairs);
+    if (bytes) {
+        hipError_t e = hipMemsetAsync(a.rejected, 0, sizeof(int32_t) * (size_t)frames, s);
+        if (e != hipSuccess) return e;
+        const int wblocks = (int)(((int64_t)a.cap * (a.dim / 4) + 255) / 256);
+        hipLaunchKernelGGL(knn_pack_u8_batch_kernel, dim3(wblocks, frames), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(knn_u8_batch_kernel<128>, dim3((a.cap + 256 * kKnnU8Q - 1) / (256 * kKnnU8Q), ranges, pairs),
+                           dim3(256), 0, s, a, range);
+        hipLaunchKernelGGL(knn_float_batch_kernel<128>, fgrid, dim3(kKnnQ), 0, s, a, range);
+    } else {
+        KnnBatchArgs f = a;
+        f.rejected = nullptr;  // the float kernel serves every pair
+        if (a.dim == 128) hipLaunchKernelGGL(knn_float_batch_kernel<128>, fgrid, dim3(kKnnQ), 0, s, f, range);
+        else hipLaunchKernelGGL(knn_float_batch_kernel<64>, fgrid, dim3(kKnnQ), 0, s, f, range);
+    }
+    if (ranges > 1)
+        hipLaunchKernelGGL(knn_merge_batch_kernel, dim3((a.cap + 3) / 4, pairs), dim3(256), 0, s, a, ranges, range);
+    return hipGetLastError();
 }
 
 size_t knn_bytes_size(int nq, int nt, int dim) { return (size_t)(nq + nt) * dim + 4 * (size_t)(nq + nt) + 16; }

@@ -7,6 +7,11 @@
 // DMatch list, the count and the pair's PairHeader.  The order is part of the result: RANSAC's
 // subsets index into the point list, so the slots come from a ballot / prefix scan, never from
 // atomics.
+//
+// ratio_gather_batch_kernel runs the same body for every pair of a dvo_knn_stream batch in one
+// launch (a workgroup per pair, the counts read from the frame slots); knn_frame_state_kernel and
+// knn_status_kernel are that path's bookkeeping: which frames overflow their slot, and the records
+// of the pairs the reference raises on before findEssentialMat.
 #include "dvo_internal.h"
 
 namespace dvo {
@@ -16,8 +21,9 @@ namespace {
 constexpr int kRatioNT = 1024;  // one workgroup: 16 waves walk the queries 1024 at a time, in order
 
 // Python's test on the float32 values DMatch.distance holds: the product and the compare are
-// double (a float32 product 0.75f * d1 rounds and keeps a different set).
-__global__ __launch_bounds__(kRatioNT) void ratio_gather_kernel(RatioArgs a) {
+// double (a float32 product 0.75f * d1 rounds and keeps a different set).  One workgroup of
+// kRatioNT lanes runs one pair; h is the header it leaves.
+__device__ __forceinline__ void ratio_gather_pair(const RatioArgs& a, const PairHeader h) {
     __shared__ int wtot[kRatioNT / 64];
     __shared__ int wmiss[kRatioNT / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -71,9 +77,25 @@ __global__ __launch_bounds__(kRatioNT) void ratio_gather_kernel(RatioArgs a) {
         int any = 0;
         for (int w = 0; w < kRatioNT / 64; ++w) any |= wmiss[w];
         *a.nmatch = base;
-        *a.hdr = PairHeader{a.nkq, a.nkt, 0, 0};
+        *a.hdr = h;
         *a.missing = any;
     }
+}
+
+__global__ __launch_bounds__(kRatioNT) void ratio_gather_kernel(RatioArgs a) {
+    ratio_gather_pair(a, PairHeader{a.nkq, a.nkt, 0, 0});
+}
+
+// The same for pair blockIdx.x of a batch of frame slots (dvo_knn_stream): the counts come from
+// the slots, and every pair gets its count, flag and header, the empty ones too (RANSAC reads
+// m_arr of all of them).  The header carries the detector's counts and whether a frame is marked.
+__global__ __launch_bounds__(kRatioNT) void ratio_gather_batch_kernel(RatioBatchArgs b) {
+    const int p = blockIdx.x;
+    const int nq = b.fstate[2 * p], nt = b.fstate[2 * p + 2];
+    const size_t o = (size_t)p * b.cap;
+    const RatioArgs a{b.idx + o * 2, b.dist + o * 2, b.kps + o, b.kps + o + b.cap, nq, nq, nt, b.ratio, 0,
+                      b.pts + o * 4, b.matches + o, b.nmatch + p, b.hdr + p, b.missing + p};
+    ratio_gather_pair(a, PairHeader{b.n[2 * p], b.n[2 * p + 2], b.fstate[2 * p + 1] | b.fstate[2 * p + 3], 0});
 }
 
 // The first min(*cnt, kp_cap) keypoints and descriptors of a detection into a feature slot, the
@@ -92,6 +114,30 @@ __global__ __launch_bounds__(256) void feature_copy_kernel(const uint32_t* skps,
     }
 }
 
+// A frame whose detector count exceeds the slot or whose detector flagged an overflow is marked:
+// it brings no feature to its pairs, and their records say DVO_ECAP.
+__global__ __launch_bounds__(64) void knn_frame_state_kernel(const int32_t* n, int frames, int cap, int32_t* fstate) {
+    const int f = blockIdx.x * 64 + threadIdx.x;
+    if (f >= frames) return;
+    const int c = n[2 * f];
+    const int marked = n[2 * f + 1] != 0 || c > cap;
+    fstate[2 * f] = marked ? 0 : max(c, 0);
+    fstate[2 * f + 1] = marked;
+}
+
+__global__ __launch_bounds__(64) void knn_status_kernel(const int32_t* n, const int32_t* fstate, const int32_t* missing,
+                                                        int pairs, dvo_pair_record* rec) {
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= pairs) return;
+    if (fstate[2 * p + 1] | fstate[2 * p + 3]) return;  // DVO_ECAP stands
+    if (fstate[2 * p] != 0 && fstate[2 * p + 2] >= 2 && missing[p] == 0) return;
+    dvo_pair_record r{};
+    r.n_kp_prev = n[2 * p];
+    r.n_kp_cur = n[2 * p + 2];
+    r.status = DVO_ENOFEAT;
+    rec[p] = r;
+}
+
 }  // namespace
 
 hipError_t launch_ratio_gather(const RatioArgs& a, hipStream_t s) {
@@ -104,6 +150,26 @@ hipError_t launch_feature_copy(const dvo_keypoint* skps, const float* sdesc, con
     hipLaunchKernelGGL(feature_copy_kernel, dim3(512), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(skps),
                        reinterpret_cast<const uint4*>(sdesc), cnt, flags, kp_cap, dim, reinterpret_cast<uint32_t*>(dkps),
                        reinterpret_cast<uint4*>(ddesc), dn);
+    return hipGetLastError();
+}
+
+hipError_t launch_ratio_gather_batch(const RatioBatchArgs& a, int pairs, hipStream_t s) {
+    if (pairs < 1) return hipSuccess;
+    hipLaunchKernelGGL(ratio_gather_batch_kernel, dim3(pairs), dim3(kRatioNT), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_knn_frame_state(const int32_t* d_n, int frames, int cap, int32_t* d_fstate, hipStream_t s) {
+    if (frames < 1) return hipSuccess;
+    hipLaunchKernelGGL(knn_frame_state_kernel, dim3((frames + 63) / 64), dim3(64), 0, s, d_n, frames, cap, d_fstate);
+    return hipGetLastError();
+}
+
+hipError_t launch_knn_status(const int32_t* d_n, const int32_t* d_fstate, const int32_t* d_missing, int pairs,
+                             dvo_pair_record* records, hipStream_t s) {
+    if (pairs < 1) return hipSuccess;
+    hipLaunchKernelGGL(knn_status_kernel, dim3((pairs + 63) / 64), dim3(64), 0, s, d_n, d_fstate, d_missing, pairs,
+                       records);
     return hipGetLastError();
 }
 

@@ -794,6 +794,33 @@ def test_ratio_gather(idx, dist, kq, kt, ratio=0.75, squared=False, ctx=None):
     return pts[:m.value].copy(), matches[:m.value].copy(), bool(miss.value)
 
 
+def test_knn_batch(desc, kps, counts, ranges=0, ratio=0.75, ctx=None):
+    """The matching stages of dvo_knn_stream_process (frame state, byte pack, batched k-NN, batched
+    ratio test and gather) on host arrays: desc float32[F, cap, dim] frame slots, kps
+    KEYPOINT_DTYPE[F, cap], counts int[F]; pair p is frames p, p + 1; ranges = train ranges (0: the
+    library's choice).  Returns a dict of per-pair arrays: idx int32[P, cap, 2], dist float32[P, cap, 2]
+    (rows < nq of a pair are written), nmatch int32[P], matches DMATCH_DTYPE[P, cap], pts
+    float32[P, cap, 4] (entries < nmatch), hdr int32[P, 4] (counts, flags, 0), missing int32[P], and
+    ranges_used."""
+    c = _ctx(ctx)
+    desc = np.ascontiguousarray(desc, np.float32)
+    kps = np.ascontiguousarray(kps, KEYPOINT_DTYPE)
+    counts = np.ascontiguousarray(counts, np.int32)
+    if desc.ndim != 3 or kps.shape != desc.shape[:2] or counts.shape != desc.shape[:1]:
+        raise DVOError(-1, "desc float32[F, cap, dim], kps [F, cap] and counts [F] must agree")
+    F, cap, dim = desc.shape
+    P = max(F - 1, 1)
+    out = dict(idx=np.zeros((P, cap, 2), np.int32), dist=np.zeros((P, cap, 2), np.float32),
+               nmatch=np.zeros(P, np.int32), matches=np.zeros((P, cap), DMATCH_DTYPE),
+               pts=np.zeros((P, cap, 4), np.float32), hdr=np.zeros((P, 4), np.int32), missing=np.zeros(P, np.int32))
+    used = ctypes.c_int()
+    c.check(c.lib.dvo_test_knn_batch(c.h, ptr(desc), ptr(kps), ptr(counts), F, cap, dim, int(ranges), float(ratio),
+                                     ptr(out["idx"]), ptr(out["dist"]), ptr(out["nmatch"]), ptr(out["matches"]),
+                                     ptr(out["pts"]), ptr(out["hdr"]), ptr(out["missing"]), ctypes.byref(used)))
+    out["ranges_used"] = used.value
+    return out
+
+
 KNN_DETECTORS = {"sift": 0, "surf": 1}
 KNN_MATCHERS = {"bf": 0, "flann": 1}
 

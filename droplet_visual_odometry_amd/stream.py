@@ -6,6 +6,9 @@ A call with n frames runs ORB on every frame once, matches each consecutive
 pair, runs findEssentialMat(RANSAC) + recoverPose per pair and writes n-1
 256-byte pair records (PAIR_RECORD_DTYPE) to device memory.  Torch tensors are
 only containers for device memory; all compute is in libdvo_hip.so.
+
+KnnFrameStream is the same for the k-NN modes 'knn_sift' and 'surf' (SIFT / SURF,
+BFMatcher(NORM_L1).knnMatch(k=2), the ratio test): dvo_knn_stream_process.
 """
 from __future__ import annotations
 
@@ -443,6 +446,138 @@ class FrameStream:
                 self._held.clear()
             self._last = ()
             self._pending = {}
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class KnnFrameStream:
+    """The batched frame stream of the k-NN modes 'knn_sift' and 'surf' (dvo_knn_stream_process):
+    n device-resident frames per call are detected once each (SIFT or SURF), every consecutive
+    pair goes through BFMatcher(NORM_L1).knnMatch(k=2), the ratio test and keypoint gather,
+    findEssentialMat(RANSAC) and recoverPose, and n - 1 pair records (PAIR_RECORD_DTYPE) land in
+    device memory; nothing is read back on the way.  The records equal ops.KnnPairStream.pair's
+    on the same frames (n_hypotheses aside) and feed stream.PoseTail.run as they are.
+
+    feat_cap: features kept per frame (None: the detector's list capacity, 65536 for SIFT, which
+    costs 44 MB per frame slot: give the count you expect).  A frame with more features marks its
+    two pairs DVO_ECAP.  The calls run on the context's HIP stream, asynchronously; sync() waits."""
+
+    def __init__(self, width: int, height: int, K, max_frames: int, detector="sift", feat_cap: int | None = None,
+                 hessian_threshold: float = 400.0, ratio: float = 0.75, prob: float = 0.999, threshold: float = 1.0,
+                 max_iters: int = 1000, dist_thresh: float = 50.0, ctx: Context | None = None):
+        from ._native import KnnStreamConfig
+        from .ops import KNN_DETECTORS
+        self.h = None
+        self.ctx = ctx if ctx is not None else Context.default()
+        self.device = torch.device("cuda", self.ctx.device)
+        cfg = KnnStreamConfig()
+        cfg.width, cfg.height, cfg.max_frames = int(width), int(height), int(max_frames)
+        cfg.detector = KNN_DETECTORS[detector] if isinstance(detector, str) else int(detector)
+        cfg.feat_cap = 0 if feat_cap is None else int(feat_cap)
+        cfg.hessian_threshold, cfg.ratio = float(hessian_threshold), float(ratio)
+        K = np.asarray(K, np.float64).reshape(9)
+        for i in range(9):
+            cfg.K[i] = float(K[i])
+        cfg.prob, cfg.threshold, cfg.max_iters = float(prob), float(threshold), int(max_iters)
+        cfg.dist_thresh = float(dist_thresh)
+        h = _vp()
+        self.ctx.check(self.ctx.lib.dvo_knn_stream_create(self.ctx.h, ctypes.byref(cfg), ctypes.byref(h)))
+        self.h = h
+        self._ext = torch.cuda.ExternalStream(self.hip_stream, device=self.device)
+        self._held = collections.deque()  # (event, tensors) in flight on the library's stream
+        self.width, self.height, self.max_frames = int(width), int(height), int(max_frames)
+        self.dim = 64 if cfg.detector == 1 else 128
+        self.K = K.reshape(3, 3)
+
+    @property
+    def hip_stream(self) -> int:
+        return self.ctx.lib.dvo_knn_stream_hip_stream(self.h) or 0
+
+    def new_records(self, n_pairs: int) -> torch.Tensor:
+        return torch.zeros(max(n_pairs, 1) * PAIR_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+
+    def process(self, frames, records: torch.Tensor | None = None, wait_torch: bool = True) -> torch.Tensor:
+        """Enqueue the batch (asynchronous).  frames: a uint8 [n, H, W] device tensor (rows contiguous,
+        any row pitch) or a numpy array, which is uploaded first.  With wait_torch the batch is
+        ordered after work queued on torch's current stream; pass False for frames already resident."""
+        if isinstance(frames, np.ndarray):
+            if frames.dtype != np.uint8 or frames.ndim != 3:
+                raise ValueError("frames must be uint8 [n, H, W]")
+            frames = torch.from_numpy(np.ascontiguousarray(frames)).to(self.device)
+            wait_torch = True
+        if frames.dtype != torch.uint8 or frames.dim() != 3 or not frames.is_cuda:
+            raise ValueError("frames must be a uint8 [n, H, W] device tensor or numpy array")
+        n, h, w = frames.shape
+        if (h, w) != (self.height, self.width):
+            raise ValueError(f"frame size {w}x{h} != stream {self.width}x{self.height}")
+        if n and (frames.stride(2) != 1 or frames.stride(1) < w):
+            raise ValueError("frames rows must be contiguous")
+        if records is None:
+            records = self.new_records(n - 1)
+            wait_torch = True  # the zero-fill runs on torch's stream: order the library's writes after it
+        if wait_torch:
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.device))
+            self._ext.wait_event(ev)
+        self.ctx.check(self.ctx.lib.dvo_knn_stream_process(self.h, frames.data_ptr() if n else None, n,
+                                                           frames.stride(0), frames.stride(1),
+                                                           records.data_ptr() if n > 1 else None))
+        ev = torch.cuda.Event()  # keep the tensors alive until the library's stream is past them
+        ev.record(self._ext)
+        self._held.append((ev, (frames, records)))
+        while self._held and self._held[0][0].query():
+            self._held.popleft()
+        return records
+
+    def sync(self):
+        self.ctx.check(self.ctx.lib.dvo_knn_stream_sync(self.h))
+        self._held.clear()
+
+    records_numpy = staticmethod(FrameStream.records_numpy)
+
+    def features(self, frame: int):
+        """(keypoints KEYPOINT_DTYPE[N], descriptors float32[N, dim]) of frame `frame` of the last call."""
+        from ._native import DVO_ECAP
+        n = ctypes.c_int()
+        rc = self.ctx.lib.dvo_knn_stream_get_features(self.h, int(frame), None, None, 0, ctypes.byref(n))
+        if rc != DVO_ECAP:
+            self.ctx.check(rc)
+        kps = np.zeros(max(n.value, 1), KEYPOINT_DTYPE)
+        desc = np.zeros((max(n.value, 1), self.dim), np.float32)
+        self.ctx.check(self.ctx.lib.dvo_knn_stream_get_features(self.h, int(frame), ptr(kps), ptr(desc), len(kps),
+                                                                ctypes.byref(n)))
+        return kps[:n.value].copy(), desc[:n.value].copy()
+
+    def matches(self, pair: int) -> np.ndarray:
+        """Pair `pair`'s kept matches of the last call (DMATCH_DTYPE), in ascending queryIdx."""
+        from ._native import DVO_ECAP
+        m = ctypes.c_int()
+        rc = self.ctx.lib.dvo_knn_stream_get_matches(self.h, int(pair), None, 0, ctypes.byref(m))
+        if rc != DVO_ECAP:
+            self.ctx.check(rc)
+        out = np.zeros(max(m.value, 1), DMATCH_DTYPE)
+        self.ctx.check(self.ctx.lib.dvo_knn_stream_get_matches(self.h, int(pair), ptr(out), len(out), ctypes.byref(m)))
+        return out[:m.value].copy()
+
+    def set_profiling(self, enable: bool = True):
+        self.ctx.check(self.ctx.lib.dvo_knn_stream_set_profiling(self.h, int(enable)))
+
+    def stage_times(self):
+        """Device ms of the last profiled call: detection, matching + ratio test, geometry + records."""
+        ms = np.zeros(3, np.float64)
+        self.ctx.check(self.ctx.lib.dvo_knn_stream_stage_times(self.h, ptr(ms)))
+        return dict(zip(("detect", "match", "geometry"), ms.tolist()))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.dvo_knn_stream_destroy(self.h)  # synchronises the stream first
+            self.h = None
+            if getattr(self, "_held", None):
+                self._held.clear()
 
     def __del__(self):
         try:

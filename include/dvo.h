@@ -370,6 +370,70 @@ int dvo_knn_pair_run(dvo_knn_pair* p, const uint8_t* prev_img, const uint8_t* cu
 int dvo_knn_pair_get_matches(dvo_knn_pair* p, dvo_dmatch* out, int cap, int* m);
 /* The last pair's features: which 0 previous, 1 current frame; desc n x 128 (SIFT) or n x 64 (SURF) floats. */
 int dvo_knn_pair_get_features(dvo_knn_pair* p, int which, dvo_keypoint* kps, float* desc, int cap, int* n);
+/* The same per-pair path for a batch of DEVICE-resident frames in modes 'knn_sift' and
+ * 'surf' (BFMatcher(NORM_L1); FLANN is not batched): n_frames w x h mono8 frames, laid
+ * out as for dvo_stream_process, give n_frames - 1 records on the device; pair p is
+ * frames p (query, previous) and p + 1 (train, current), each frame detected once.
+ * dvo_knn_stream_process is asynchronous on the context's stream (the detector's plan
+ * and scratch belong to the context): it makes no host synchronisation and no
+ * device-to-host copy, and its launch shapes depend on feat_cap, max_iters and n_frames
+ * only; wait with dvo_knn_stream_sync.
+ *
+ * One call: the frames are detected one after another (SIFT / SURF as dvo_knn_pair_run,
+ * in place on the caller's frames) into frame slots of feat_cap features; one launch
+ * packs every frame's SIFT descriptors to bytes; the k-NN, ratio-test and gather
+ * kernels take every pair in one launch each, with the counts read on the device;
+ * findEssentialMat runs the stream's round schedule and recoverPose follows, so a
+ * record does not depend on how the frames are split into calls.  Every field of a
+ * record equals dvo_knn_pair_run's on the same two frames, except n_hypotheses
+ * (the per-call path solves one round).
+ *
+ * Record status: as dvo_knn_pair_run (DVO_ENOFEAT: a frame without keypoints or
+ * fewer than 2 train descriptors, with the counts and zeros elsewhere), and DVO_ECAP
+ * for both pairs of a frame that has more features than feat_cap or whose detector
+ * list overflowed (the call itself returns DVO_OK; such a frame brings no feature).
+ *
+ * Memory, all allocated at create (F = max_frames, P = F - 1, C = feat_cap, D = 128
+ * SIFT / 64 SURF, H = max_iters), in bytes:
+ *   frame slots  F (28 C + 4 D C + 16), SIFT also F (D C + 4 C + 4) (packed rows, norms, flag)
+ *   match        P (48 C + 4) (neighbour lists, matches, point quads) + 16 C L, L the most
+ *                (pair, range) partial lists a call can have (0 when no call splits the trains)
+ *   geometry     P (32 C + 784 H + 1.5 K) (a dvo_stream's per-pair arrays)
+ *                + 64 K per five-point block of the largest round + 12 per its hypotheses.
+ * feat_cap = 0 takes the detector's list capacity (65536 SIFT, max(4096, w h / 64) SURF):
+ * 44 MB per SIFT frame slot, so give the count you expect.
+ *
+ * DVO_EINVAL (create, before any allocation): as dvo_knn_pair_create, max_frames < 2 or
+ * > 65536, feat_cap not 0 and outside 2..the detector's list capacity.  process:
+ * n_frames outside 1..max_frames, stride < width, a null buffer.  n_frames == 1 detects
+ * the frame and writes no record. */
+typedef struct dvo_knn_stream dvo_knn_stream;
+typedef struct {
+    int32_t width, height, max_frames;
+    int32_t detector;            /* DVO_DETECT_SIFT | DVO_DETECT_SURF */
+    int32_t feat_cap;            /* features kept per frame; 0 = the detector's list capacity */
+    double hessian_threshold;    /* SURF, 400 */
+    double ratio;                /* 0.75 */
+    double K[9];
+    double prob, threshold; int32_t max_iters; double dist_thresh;
+} dvo_knn_stream_config;
+int dvo_knn_stream_create(dvo_ctx* ctx, const dvo_knn_stream_config* cfg, dvo_knn_stream** out);
+void dvo_knn_stream_destroy(dvo_knn_stream* s);
+int dvo_knn_stream_process(dvo_knn_stream* s, const uint8_t* d_frames, int n_frames, int64_t frame_stride, int stride,
+                           dvo_pair_record* d_records);
+int dvo_knn_stream_sync(dvo_knn_stream* s);
+/* The HIP stream the calls run on (the context's). */
+void* dvo_knn_stream_hip_stream(dvo_knn_stream* s);
+/* After the last process call (these synchronise): frame `frame`'s features, desc n x 128 (SIFT)
+ * or n x 64 (SURF) floats, *n = the detector's count (DVO_ECAP if > cap or the frame is marked);
+ * pair `pair`'s kept matches in ascending queryIdx, *m = count (DVO_ECAP if > cap). */
+int dvo_knn_stream_get_features(dvo_knn_stream* s, int frame, dvo_keypoint* kps, float* desc, int cap, int* n);
+int dvo_knn_stream_get_matches(dvo_knn_stream* s, int pair, dvo_dmatch* out, int cap, int* m);
+/* Device time of the last process call's stages, for tools: enable = 1 records events on the
+ * stream from the next call on; ms[3] = detection, matching + ratio test, geometry + records
+ * (synchronises; DVO_EINVAL before a profiled call). */
+int dvo_knn_stream_set_profiling(dvo_knn_stream* s, int enable);
+int dvo_knn_stream_stage_times(dvo_knn_stream* s, double* ms);
 /* dvo_stream_process on undistorted frames: the n raw frames are remapped by u
  * into the stream's own frame slab first (same HIP stream), as the reference
  * undistorts every frame before detection (v3:120, v3:135). */
@@ -654,6 +718,19 @@ int dvo_test_sampson(dvo_ctx* ctx, const double* E, const double* pts, int n, fl
 int dvo_test_ratio_gather(dvo_ctx* ctx, const int32_t* idx, const float* dist, int nq, const dvo_keypoint* kq, int nkq,
                           const dvo_keypoint* kt, int nkt, double ratio, int squared, float* pts, dvo_dmatch* matches,
                           int* m, int* missing_second);
+/* The matching stages of dvo_knn_stream_process (frame state, byte pack, batched k-NN,
+ * batched ratio test and gather) through the production launches, on host arrays:
+ * `frames` frame slots of cap rows, desc [frames][cap][dim] (dim 128 or 64), kps
+ * [frames][cap], counts [frames] (a count above cap marks the frame), ranges = train ranges
+ * (0: the library's choice for frames - 1 pairs).  Per pair p = frames p, p + 1:
+ * idx / dist [P][cap][2] (the first nq rows of a pair are written), nmatch [P], matches
+ * [P][cap], pts [P][cap][4], hdr [P][4] (PairHeader: counts, flags, 0), missing [P];
+ * *ranges_used = the ranges the launch ran with.  The arrays come back whole from the
+ * context's reused device buffers: rows past a pair's nq (idx / dist) or nmatch (matches,
+ * pts) hold whatever an earlier call left there. */
+int dvo_test_knn_batch(dvo_ctx* ctx, const float* desc, const dvo_keypoint* kps, const int32_t* counts, int frames,
+                       int cap, int dim, int ranges, double ratio, int32_t* idx, float* dist, int32_t* nmatch,
+                       dvo_dmatch* matches, float* pts, int32_t* hdr, int32_t* missing, int* ranges_used);
 
 #ifdef __cplusplus
 }
