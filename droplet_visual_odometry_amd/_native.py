@@ -131,6 +131,11 @@ _SIGNATURES = {
     "dvo_bf_knn_float": ([_vp, _vp, _c, _vp, _c, _c, _c, _c, _vp, _vp], _c),
     "dvo_flann_knn": ([_vp, _vp, _c, _vp, _c, _c, _c, _c, _c, ctypes.POINTER(ctypes.c_uint64), _vp, _vp], _c),
     "dvo_sift_detect_and_compute": ([_vp, _vp, _c, _c, _c, _vp, _vp, _c, _ip], _c),
+    "dvo_sift_batch_bytes": ([_c, _c, _c], _i64),
+    "dvo_sift_batch_create": ([_vp, _c, _c, _c, ctypes.POINTER(_vp)], _c),
+    "dvo_sift_batch_destroy": ([_vp], None),
+    "dvo_sift_batch_detect": ([_vp, _vp, _c, _i64, _c, _c, _vp, _vp, _vp], _c),
+    "dvo_sift_batch_hip_stream": ([_vp], _vp),
     "dvo_surf_detect_and_compute": ([_vp, _vp, _c, _c, _c, ctypes.c_double, _vp, _vp, _c, _ip], _c),
     "dvo_find_essential_mat": ([_vp, _vp, _vp, _c, _vp, _d, _d, _c, _vp, _ip, _vp], _c),
     "dvo_recover_pose": ([_vp, _vp, _c, _vp, _vp, _c, _vp, _d, _vp, _vp, _vp, _vp, _ip], _c),
@@ -157,6 +162,7 @@ _SIGNATURES = {
     "dvo_knn_stream_process": ([_vp, _vp, _c, _i64, _c, _vp], _c),
     "dvo_knn_stream_sync": ([_vp], _c),
     "dvo_knn_stream_hip_stream": ([_vp], _vp),
+    "dvo_knn_stream_set_detect_group": ([_vp, _c], _c),
     "dvo_knn_stream_get_features": ([_vp, _c, _vp, _vp, _c, _ip], _c),
     "dvo_knn_stream_get_matches": ([_vp, _c, _vp, _c, _ip], _c),
     "dvo_knn_stream_set_profiling": ([_vp, _c], _c),

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -26,6 +27,17 @@ struct SiftPlanDev {  // per-size device buffers of dvo_sift_detect_and_compute
     int tap_off[6] = {0}, tap_n[6] = {0};
     uint8_t* img = nullptr;
     int pitch = 0;
+    DeviceAllocs mem;
+};
+
+// Scratch of the group SIFT detector (launch_sift_group): `group` copies of what sift_plan
+// allocates per frame, kps / desc / the image copy aside (the results go to the caller's slots,
+// the frames are read in place), and one taps table.  Allocated whole by sift_group_alloc.
+struct SiftGroupDev {
+    int w = 0, h = 0, group = 0;
+    SiftGroupArgs g{};
+    float* taps = nullptr;
+    int tap_off[6] = {0}, tap_n[6] = {0};
     DeviceAllocs mem;
 };
 
@@ -1366,11 +1378,10 @@ std::vector<float> sift_gauss_taps(double sigma) {
     return k;
 }
 
-int sift_plan(dvo_ctx* ctx, int w, int h) {
-    SiftPlanDev& P = ctx->sift;
-    if (P.w == w && P.h == h) return DVO_OK;
-    P = SiftPlanDev{};
-    SiftArgs& A = P.a;
+// The octave layout of a w x h image and the list capacities: what sift_plan and the group
+// detector's scratch (sift_group_alloc, dvo_sift_batch_bytes) both size their buffers from.
+// *gp_floats / *dog_floats: the pyramid's and the DoG's floats (6 S and 5 S, S the octaves' pixels).
+void sift_layout(int w, int h, SiftLayout& A, int64_t* gp_floats, int64_t* dog_floats) {
     const int W = 2 * w, H = 2 * h;  // firstOctave = -1
     A.noct = (int)std::nearbyint(std::log((double)std::min(W, H)) / std::log(2.) - 2) + 1;
     A.noct = std::max(1, std::min(A.noct, kSiftMaxOct));
@@ -1390,6 +1401,18 @@ int sift_plan(dvo_ctx* ctx, int w, int h) {
     }
     A.cand_cap = 1 << 18;
     A.kp_cap = kSiftKpCap;
+    *gp_floats = gp;
+    *dog_floats = dg;
+}
+
+int sift_order_n(int kp_cap) {  // the sort scratch: the next power of two >= kp_cap
+    int order_n = 1;
+    while (order_n < kp_cap) order_n <<= 1;
+    return order_n;
+}
+
+// The 6 Gaussian kernels (initial blur, layers 1..5) back to back.
+std::vector<float> sift_taps(int* tap_off, int* tap_n) {
     std::vector<float> taps;
     const double sig0 = std::sqrt(std::max(1.6f * 1.6f - 0.5f * 0.5f * 4, 0.01f));
     std::vector<double> sig(6);
@@ -1403,14 +1426,25 @@ int sift_plan(dvo_ctx* ctx, int w, int h) {
     }
     for (int i = 0; i < 6; ++i) {
         const std::vector<float> t = sift_gauss_taps(i == 0 ? (double)(float)sig0 : sig[i]);
-        P.tap_off[i] = (int)taps.size();
-        P.tap_n[i] = (int)t.size();
+        tap_off[i] = (int)taps.size();
+        tap_n[i] = (int)t.size();
         taps.insert(taps.end(), t.begin(), t.end());
     }
+    return taps;
+}
+
+int sift_plan(dvo_ctx* ctx, int w, int h) {
+    SiftPlanDev& P = ctx->sift;
+    if (P.w == w && P.h == h) return DVO_OK;
+    P = SiftPlanDev{};
+    SiftArgs& A = P.a;
+    const int W = 2 * w, H = 2 * h;
+    int64_t gp = 0, dg = 0;
+    sift_layout(w, h, A, &gp, &dg);
+    const std::vector<float> taps = sift_taps(P.tap_off, P.tap_n);
     P.pitch = (w + 255) & ~255;
     auto A_ = [&](auto*& p, size_t bytes) { return P.mem.alloc(&p, bytes ? bytes : 16) == hipSuccess; };
-    int order_n = 1;
-    while (order_n < A.kp_cap) order_n <<= 1;
+    const int order_n = sift_order_n(A.kp_cap);
     int* counters = nullptr;
     if (!A_(A.gp, (size_t)gp * 4) || !A_(A.dog, (size_t)dg * 4) || !A_(A.tmp, (size_t)W * H * 4) ||
         !A_(A.cand, (size_t)A.cand_cap * sizeof(int4)) || !A_(A.raw, (size_t)A.kp_cap * sizeof(dvo_keypoint)) ||
@@ -1430,7 +1464,139 @@ int sift_plan(dvo_ctx* ctx, int w, int h) {
     P.h = h;
     return DVO_OK;
 }
+
+// One frame's share of a group's scratch, array by array (bytes).
+struct SiftGroupBytes {
+    int64_t gp, dog, tmp, cand, raw, order, counters;
+    int64_t frame() const { return gp + dog + tmp + cand + raw + order + counters; }
+};
+SiftGroupBytes sift_group_bytes(int w, int h, SiftLayout& L) {
+    int64_t gp = 0, dg = 0;
+    sift_layout(w, h, L, &gp, &dg);
+    SiftGroupBytes b;
+    b.gp = gp * 4;
+    b.dog = dg * 4;
+    b.tmp = (int64_t)4 * w * h * 4;
+    b.cand = (int64_t)L.cand_cap * (int64_t)sizeof(int4);
+    b.raw = (int64_t)L.kp_cap * (int64_t)sizeof(dvo_keypoint);
+    b.order = (int64_t)sift_order_n(L.kp_cap) * 4;
+    b.counters = 16;
+    return b;
+}
+
+constexpr int kSiftGroupMax = 64;
+
+// Allocates a group's whole scratch and uploads the taps, after waiting for the context's stream
+// (nothing is allocated later, inside a detect / process call).  D is empty on failure.
+int sift_group_alloc(dvo_ctx* ctx, int w, int h, int group, SiftGroupDev& D) {
+    D = SiftGroupDev{};
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    SiftGroupArgs& g = D.g;
+    const SiftGroupBytes b = sift_group_bytes(w, h, g.l);
+    const std::vector<float> taps = sift_taps(D.tap_off, D.tap_n);
+    const int64_t G = group;
+    int* counters = nullptr;
+    hipError_t e = hipSuccess;
+    auto A_ = [&](auto*& p, int64_t bytes) {
+        if (e == hipSuccess) e = D.mem.alloc(&p, (size_t)bytes);
+    };
+    A_(g.b.gp, G * b.gp);
+    A_(g.b.dog, G * b.dog);
+    A_(g.b.tmp, G * b.tmp);
+    A_(g.b.cand, G * b.cand);
+    A_(g.b.raw, G * b.raw);
+    A_(g.b.order, G * b.order);
+    A_(counters, G * b.counters);
+    A_(D.taps, (int64_t)taps.size() * 4);
+    if (e == hipSuccess) e = hipMemcpy(D.taps, taps.data(), taps.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        D = SiftGroupDev{};
+        return fail(ctx, DVO_EHIP, std::string("SIFT group buffers: ") + hipGetErrorString(e));
+    }
+    g.b.ncand = counters;
+    g.b.nraw = counters + 1;
+    g.b.nkp = counters + 2;
+    g.b.flags = counters + 3;
+    g.gp_stride = b.gp / 4;
+    g.dog_stride = b.dog / 4;
+    g.tmp_stride = b.tmp / 4;
+    g.order_stride = b.order / 4;
+    // DVO_SIFT_FUSED_BLUR=0 (read here, when the scratch is made) keeps the two-pass blurs: the A/B of
+    // tools/time_sift_batch.py.  The results are the same either way.
+    const char* fb = std::getenv("DVO_SIFT_FUSED_BLUR");
+    g.fused_blur = !(fb && fb[0] == '0');
+    D.w = w;
+    D.h = h;
+    D.group = group;
+    return DVO_OK;
+}
+
+// n frames through the group detector, in chunks of D.group on stream s: frame f's keypoints and
+// descriptors go to kps + f * feat_cap and desc + f * feat_cap * 128, its (count, flags) to counts + 2 f.
+int sift_group_detect(dvo_ctx* ctx, const SiftGroupDev& D, const uint8_t* d_frames, int n, int64_t frame_stride, int stride,
+                      int feat_cap, dvo_keypoint* kps, float* desc, int32_t* counts, hipStream_t s) {
+    for (int f0 = 0; f0 < n; f0 += D.group) {
+        const int frames = std::min(D.group, n - f0);
+        SiftGroupArgs g = D.g;
+        g.out_kps = kps + (size_t)f0 * feat_cap;
+        g.out_desc = desc + (size_t)f0 * feat_cap * 128;
+        g.out_n = counts + 2 * (size_t)f0;
+        g.feat_cap = feat_cap;
+        HIP_TRY(hipMemsetAsync(g.b.ncand, 0, (size_t)frames * 16, s));  // the chunk's counters, all four per frame
+        HIP_TRY(launch_sift_group(g, frames, d_frames + (int64_t)f0 * frame_stride, frame_stride, D.w, D.h, stride, D.taps,
+                                  D.tap_off, D.tap_n, s));
+    }
+    return DVO_OK;
+}
 }  // namespace
+
+struct dvo_sift_batch {
+    dvo_ctx* ctx = nullptr;
+    SiftGroupDev d;
+};
+
+int64_t dvo_sift_batch_bytes(int w, int h, int group) {
+    if (w < 1 || h < 1 || w >= kMaxW || h >= kMaxW || group < 1 || group > kSiftGroupMax) return DVO_EINVAL;
+    SiftLayout L{};
+    int off[6], n[6];
+    return group * sift_group_bytes(w, h, L).frame() + (int64_t)sift_taps(off, n).size() * 4;
+}
+
+int dvo_sift_batch_create(dvo_ctx* ctx, int w, int h, int group, dvo_sift_batch** out) {
+    if (!ctx || !out) return DVO_EINVAL;
+    *out = nullptr;
+    if (w < 1 || h < 1 || w >= kMaxW || h >= kMaxW) return fail(ctx, DVO_EINVAL, "image size out of range (1..4095)");
+    if (group < 1 || group > kSiftGroupMax) return fail(ctx, DVO_EINVAL, "group out of range (1..64)");
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::unique_ptr<dvo_sift_batch> b(new dvo_sift_batch);
+    b->ctx = ctx;
+    const int rc = sift_group_alloc(ctx, w, h, group, b->d);
+    if (rc) return rc;
+    *out = b.release();
+    return DVO_OK;
+}
+
+void dvo_sift_batch_destroy(dvo_sift_batch* b) {
+    if (!b) return;
+    hipSetDevice(b->ctx->device);
+    hipStreamSynchronize(b->ctx->stream);
+    delete b;
+}
+
+void* dvo_sift_batch_hip_stream(dvo_sift_batch* b) { return b ? (void*)b->ctx->stream : nullptr; }
+
+int dvo_sift_batch_detect(dvo_sift_batch* b, const uint8_t* d_frames, int n_frames, int64_t frame_stride, int stride,
+                          int feat_cap, dvo_keypoint* d_kps, float* d_desc, int32_t* d_counts) {
+    if (!b) return DVO_EINVAL;
+    dvo_ctx* ctx = b->ctx;
+    if (n_frames < 1) return fail(ctx, DVO_EINVAL, "n_frames must be >= 1");
+    if (!d_frames || !d_kps || !d_desc || !d_counts || stride < b->d.w)
+        return fail(ctx, DVO_EINVAL, "bad frame or output buffer");
+    if (feat_cap < 1 || feat_cap > kSiftKpCap) return fail(ctx, DVO_EINVAL, "feat_cap out of range (1..65536)");
+    HIP_TRY(hipSetDevice(ctx->device));
+    return sift_group_detect(ctx, b->d, d_frames, n_frames, frame_stride, stride, feat_cap, d_kps, d_desc, d_counts,
+                             ctx->stream);
+}
 
 namespace {
 // getGaussianKernel(n, sigma, CV_32F) as oracle/surf.cpp restates it
@@ -2131,6 +2297,7 @@ struct dvo_knn_stream {
     KnnBatch b;
     PairSets pairs;    // one set of max_frames - 1 pairs: pairs.all.g is the stream's GeomArgs
     DeviceAllocs mem;  // the frame slots, the match arrays and the round-local geometry arrays
+    SiftGroupDev grp;  // dvo_knn_stream_set_detect_group: grp.group > 0 detects through launch_sift_group
     int last_frames = 0;
     bool profiling = false, timed = false;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -2217,7 +2384,8 @@ int dvo_knn_stream_process(dvo_knn_stream* st, const uint8_t* d_frames, int n_fr
     if (n_frames < 1 || n_frames > c.max_frames) return fail(ctx, DVO_EINVAL, "n_frames out of range (1..max_frames)");
     if (!d_frames || stride < w || (n_frames > 1 && !d_records)) return fail(ctx, DVO_EINVAL, "bad frame or record buffer");
     HIP_TRY(hipSetDevice(ctx->device));
-    int rc = knn_stream_plan(st);  // another size may have taken the context's plan since
+    const bool grouped = st->grp.group > 0;  // the group detector has its own scratch: the context's plan is not used
+    int rc = grouped ? DVO_OK : knn_stream_plan(st);  // another size may have taken the context's plan since
     if (rc) return rc;
     hipStream_t s = ctx->stream;
     const KnnBatch& b = st->b;
@@ -2226,8 +2394,11 @@ int dvo_knn_stream_process(dvo_knn_stream* st, const uint8_t* d_frames, int n_fr
     st->last_frames = 0;
     st->timed = false;
     if (ev) HIP_TRY(hipEventRecord(ev[0], s));
-    // detection, frame by frame (the plan's scratch is single), in place on the caller's frames
-    for (int f = 0; f < n_frames; ++f) {
+    // detection in place on the caller's frames: a group of frames per launch straight into the
+    // frame slots, or frame by frame on the plan's single scratch
+    if (grouped) rc = sift_group_detect(ctx, st->grp, d_frames, n_frames, frame_stride, stride, b.cap, b.kps, b.desc, b.n, s);
+    if (rc) return rc;
+    for (int f = 0; f < n_frames && !grouped; ++f) {
         const uint8_t* img = d_frames + (int64_t)f * frame_stride;
         dvo_keypoint* kps = b.kps + (size_t)f * b.cap;
         float* desc = b.desc + (size_t)f * b.cap * b.dim;
@@ -2280,6 +2451,18 @@ int dvo_knn_stream_sync(dvo_knn_stream* s) {
 }
 
 void* dvo_knn_stream_hip_stream(dvo_knn_stream* s) { return s ? (void*)s->ctx->stream : nullptr; }
+
+int dvo_knn_stream_set_detect_group(dvo_knn_stream* s, int group) {
+    if (!s) return DVO_EINVAL;
+    dvo_ctx* ctx = s->ctx;
+    if (s->cfg.detector != DVO_DETECT_SIFT) return fail(ctx, DVO_EINVAL, "the group detector is SIFT only");
+    if (group < 0 || group > kSiftGroupMax) return fail(ctx, DVO_EINVAL, "group out of range (0..64)");
+    if (group == s->grp.group) return DVO_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // the old scratch may be in use
+    s->grp = SiftGroupDev{};
+    return group ? sift_group_alloc(ctx, s->cfg.width, s->cfg.height, group, s->grp) : DVO_OK;
+}
 
 int dvo_knn_stream_set_profiling(dvo_knn_stream* s, int enable) {
     if (!s) return DVO_EINVAL;

@@ -235,25 +235,44 @@ constexpr int kStageOneRound = 8;
 // (0..5) starts at gp + gp_off[o * 6 + l] and DoG layer l (0..4) at
 // dog + dog_off[o * 5 + l] (floats, rows of ow[o]).
 constexpr int kSiftMaxOct = 16;
-struct SiftArgs {
-    float* gp;
-    float* dog;
-    float* tmp;             // row-pass buffer, ow[0] * oh[0]
+struct SiftLayout {         // what depends on the image size only
     int64_t gp_off[kSiftMaxOct * 6];
     int64_t dog_off[kSiftMaxOct * 5];
     int ow[kSiftMaxOct], oh[kSiftMaxOct];
     int noct;
+    int cand_cap;
+    int kp_cap;
+};
+struct SiftBufs {           // one frame's scratch and lists
+    float* gp;
+    float* dog;
+    float* tmp;             // row-pass buffer, ow[0] * oh[0]
     int4* cand;             // (octave, layer, row, col) extrema
     int* ncand;
-    int cand_cap;
     dvo_keypoint* raw;      // refined, oriented keypoints (unsorted)
     int* nraw;
-    int kp_cap;
     int32_t* order;         // sort scratch, next power of two >= kp_cap
     dvo_keypoint* kps;      // final keypoints (sorted, deduplicated, input-image units)
     int* nkp;
     float* desc;            // kp_cap x 128
     int* flags;             // 1: candidate overflow, 2: keypoint overflow
+};
+struct SiftArgs : SiftLayout, SiftBufs {};
+
+// The same for a group of frames of one size (launch_sift_group): b is frame 0's scratch, frame f's
+// is b's pointers advanced by f strides (in elements; cand by cand_cap, raw by kp_cap, the four
+// counters ncand / nraw / nkp / flags by 4).  b.kps and b.desc are unused: the final keypoints and
+// descriptors go to the caller's slots, frame f's at out_kps + f * feat_cap and out_desc +
+// f * feat_cap * 128 (entries below feat_cap only), its (count, flags) to out_n + 2 f.
+struct SiftGroupArgs {
+    SiftLayout l;
+    SiftBufs b;
+    int64_t gp_stride, dog_stride, tmp_stride, order_stride;
+    dvo_keypoint* out_kps;
+    float* out_desc;
+    int32_t* out_n;
+    int feat_cap;
+    int fused_blur;  // the blurs of layers 1..5 in one launch each (blur_fused_group_kernel), not a row and a column pass
 };
 
 // SURF_create(hessianThreshold).detectAndCompute (surf.hip): nOctaves 4,
@@ -404,6 +423,12 @@ size_t match_pair_work_size(int nq, int nt);
 // d_taps: the 6 Gaussian kernels (initial blur, layers 1..5) back to back.
 hipError_t launch_sift(const SiftArgs& A, const uint8_t* d_img, int w, int h, int stride, const float* d_taps,
                        const int* tap_off, const int* tap_n, hipStream_t s);
+// The same stages for `frames` frames (<= the frames G's scratch holds), one launch per stage with
+// the frame as a grid dimension; frame f's image is d_frames + f * frame_stride.  The caller has
+// cleared the frames' counters.
+hipError_t launch_sift_group(const SiftGroupArgs& G, int frames, const uint8_t* d_frames, int64_t frame_stride, int w,
+                             int h, int stride, const float* d_taps, const int* tap_off, const int* tap_n,
+                             hipStream_t s);
 hipError_t launch_surf(const SurfArgs& a, hipStream_t s);
 hipError_t launch_match_pair(const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int cross_check, void* d_work,
                              dvo_dmatch* d_out, int* d_m, hipStream_t s);

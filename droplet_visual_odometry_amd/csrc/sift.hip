@@ -19,6 +19,13 @@
 //                      firstOctave = -1 rescale (one workgroup, bitonic network)
 //   descriptor_kernel  one wave per keypoint: calcSIFTDescriptor, the 360-bin
 //                      trilinear histogram filled in sample order, normalised
+//
+// For a group of frames of one size (launch_sift_group) every stage is one launch
+// with the frame as a grid dimension (*_group_kernel): the stage bodies below are
+// shared by both, a group kernel only picks its frame's buffers (frame_bufs) and
+// walks the frame's items with a grid stride.  Where a blur's launch has enough
+// tiles, its row and column pass run fused through LDS (blur_fused_group_kernel).
+#include <algorithm>
 #include <cfloat>
 #include <climits>
 
@@ -83,13 +90,35 @@ __device__ __forceinline__ float atan2_deg(float y, float x) {  // cv::fastAtan2
     return a;
 }
 
-__device__ __forceinline__ const float* layer(const SiftArgs& A, int o, int l) { return A.gp + A.gp_off[o * 6 + l]; }
-__device__ __forceinline__ const float* dogl(const SiftArgs& A, int o, int l) { return A.dog + A.dog_off[o * 5 + l]; }
+__device__ __forceinline__ const float* layer(const SiftLayout& L, const SiftBufs& B, int o, int l) {
+    return B.gp + L.gp_off[o * 6 + l];
+}
+__device__ __forceinline__ const float* dogl(const SiftLayout& L, const SiftBufs& B, int o, int l) {
+    return B.dog + L.dog_off[o * 5 + l];
+}
 
-__global__ __launch_bounds__(256) void up2_kernel(const uint8_t* src, int w, int h, int stride, float* dst) {
-    const int W = 2 * w, H = 2 * h;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= W * H) return;
+// Frame f's buffers in a group's scratch; kps / desc are the caller's slots of feat_cap features.
+__device__ __forceinline__ SiftBufs frame_bufs(const SiftGroupArgs& G, int f) {
+    const int64_t F = f;
+    SiftBufs b = G.b;
+    b.gp += F * G.gp_stride;
+    b.dog += F * G.dog_stride;
+    b.tmp += F * G.tmp_stride;
+    b.cand += F * G.l.cand_cap;
+    b.raw += F * G.l.kp_cap;
+    b.order += F * G.order_stride;
+    b.ncand += F * 4;
+    b.nraw += F * 4;
+    b.nkp += F * 4;
+    b.flags += F * 4;
+    b.kps = G.out_kps + F * G.feat_cap;
+    b.desc = G.out_desc + F * G.feat_cap * 128;
+    return b;
+}
+
+// pixel i of the 2w x 2h upscaled image
+__device__ __forceinline__ void up2_px(const uint8_t* src, int w, int h, int stride, float* dst, int i) {
+    const int W = 2 * w;
     const int dy = i / W, dx = i - dy * W;
     float fx = (float)((dx + 0.5) * 0.5 - 0.5);
     int sx = (int)floorf(fx);
@@ -108,9 +137,21 @@ __global__ __launch_bounds__(256) void up2_kernel(const uint8_t* src, int w, int
     dst[i] = hrow(sy) * (1.f - fy) + hrow(sy1) * fy;
 }
 
-__global__ __launch_bounds__(256) void blur_rows_kernel(const float* src, float* dst, int w, int h, const float* k, int n) {
+__global__ __launch_bounds__(256) void up2_kernel(const uint8_t* src, int w, int h, int stride, float* dst) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= w * h) return;
+    if (i >= 4 * w * h) return;
+    up2_px(src, w, h, stride, dst, i);
+}
+
+__global__ __launch_bounds__(256) void up2_group_kernel(const uint8_t* src, int64_t frame_stride, int w, int h, int stride,
+                                                        float* dst, int64_t dst_stride) {
+    src += (int64_t)blockIdx.y * frame_stride;
+    dst += (int64_t)blockIdx.y * dst_stride;
+    const int n = 4 * w * h, step = gridDim.x * 256;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += step) up2_px(src, w, h, stride, dst, i);
+}
+
+__device__ __forceinline__ void blur_rows_px(const float* src, float* dst, int w, const float* k, int n, int i) {
     const int y = i / w, x = i - y * w, r = n / 2;
     const float* s = src + (int64_t)y * w;
     float acc = k[0] * s[refl101(x - r, w)];
@@ -118,9 +159,7 @@ __global__ __launch_bounds__(256) void blur_rows_kernel(const float* src, float*
     dst[i] = acc;
 }
 
-__global__ __launch_bounds__(256) void blur_cols_kernel(const float* src, float* dst, int w, int h, const float* k, int n) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= w * h) return;
+__device__ __forceinline__ void blur_cols_px(const float* src, float* dst, int w, int h, const float* k, int n, int i) {
     const int y = i / w, x = i - y * w, r = n / 2;
     float acc = k[r] * src[i] + 0.f;
     for (int t = 1; t <= r; ++t)
@@ -128,31 +167,123 @@ __global__ __launch_bounds__(256) void blur_cols_kernel(const float* src, float*
     dst[i] = acc;
 }
 
+__global__ __launch_bounds__(256) void blur_rows_kernel(const float* src, float* dst, int w, int h, const float* k, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= w * h) return;
+    blur_rows_px(src, dst, w, k, n, i);
+}
+
+__global__ __launch_bounds__(256) void blur_cols_kernel(const float* src, float* dst, int w, int h, const float* k, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= w * h) return;
+    blur_cols_px(src, dst, w, h, k, n, i);
+}
+
+// src / dst: frame 0's image; frame blockIdx.y's is src_stride / dst_stride floats further per frame
+__global__ __launch_bounds__(256) void blur_rows_group_kernel(const float* src, int64_t src_stride, float* dst,
+                                                              int64_t dst_stride, int w, int h, const float* k, int n) {
+    src += (int64_t)blockIdx.y * src_stride;
+    dst += (int64_t)blockIdx.y * dst_stride;
+    const int npx = w * h, step = gridDim.x * 256;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < npx; i += step) blur_rows_px(src, dst, w, k, n, i);
+}
+
+__global__ __launch_bounds__(256) void blur_cols_group_kernel(const float* src, int64_t src_stride, float* dst,
+                                                              int64_t dst_stride, int w, int h, const float* k, int n) {
+    src += (int64_t)blockIdx.y * src_stride;
+    dst += (int64_t)blockIdx.y * dst_stride;
+    const int npx = w * h, step = gridDim.x * 256;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < npx; i += step) blur_cols_px(src, dst, w, h, k, n, i);
+}
+
+// Both passes of a blur in one launch: a workgroup takes a kFuseTW x kFuseTH tile of the output,
+// stages the source pixels it needs (r more on every side, REFLECT_101 applied once per pixel) in
+// LDS, runs the row pass of the tile's kFuseTH + 2r rows into LDS and the column pass from there.
+// The row pass is neither written to nor re-read from global memory.  Each sum is blur_rows_px's /
+// blur_cols_px's, term for term in the same order, over the same values.  src and dst must differ
+// (a tile reads its neighbours' source pixels); n <= 2 kFuseMaxR + 1 taps.
+constexpr int kFuseTW = 64, kFuseTH = 32, kFuseMaxR = 13;
+constexpr int kFuseMinTiles = 1024;  // launch_sift_group: tiles in a launch below which the two passes run
+__global__ __launch_bounds__(256) void blur_fused_group_kernel(const float* src, float* dst, int64_t stride, int w, int h,
+                                                               const float* k, int n) {
+    __shared__ float s_in[(kFuseTH + 2 * kFuseMaxR) * (kFuseTW + 2 * kFuseMaxR)];
+    __shared__ float s_row[(kFuseTH + 2 * kFuseMaxR) * kFuseTW];
+    src += (int64_t)blockIdx.y * stride;
+    dst += (int64_t)blockIdx.y * stride;
+    const int r = n / 2, iw = kFuseTW + 2 * r, ih = kFuseTH + 2 * r;
+    const int tx = (w + kFuseTW - 1) / kFuseTW, ty = (h + kFuseTH - 1) / kFuseTH;
+    for (int tile = blockIdx.x; tile < tx * ty; tile += gridDim.x) {
+        const int x0 = (tile % tx) * kFuseTW, y0 = (tile / tx) * kFuseTH;
+        for (int q = threadIdx.x; q < iw * ih; q += 256) {
+            const int j = q / iw, c = q - j * iw;
+            s_in[q] = src[(int64_t)refl101(y0 - r + j, h) * w + refl101(x0 - r + c, w)];
+        }
+        __syncthreads();
+        for (int q = threadIdx.x; q < ih * kFuseTW; q += 256) {  // the row pass of source row refl101(y0 - r + j)
+            const int j = q / kFuseTW, x = q % kFuseTW;
+            const float* s = s_in + j * iw + x;
+            float acc = k[0] * s[0];
+            for (int t = 1; t < n; ++t) acc += k[t] * s[t];
+            s_row[q] = acc;
+        }
+        __syncthreads();
+        for (int q = threadIdx.x; q < kFuseTH * kFuseTW; q += 256) {
+            const int y = q / kFuseTW, x = q % kFuseTW;
+            if (y0 + y < h && x0 + x < w) {
+                const float* c = s_row + (y + r) * kFuseTW + x;
+                float acc = k[r] * c[0] + 0.f;
+                for (int t = 1; t <= r; ++t) acc += k[r + t] * (c[t * kFuseTW] + c[-t * kFuseTW]);
+                dst[(int64_t)(y0 + y) * w + x0 + x] = acc;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+__device__ __forceinline__ void down2_px(const float* src, int sw, float* dst, int w, int i) {
+    const int y = i / w, x = i - y * w;
+    dst[i] = src[(int64_t)(2 * y) * sw + 2 * x];
+}
+
 __global__ __launch_bounds__(256) void down2_kernel(const float* src, int sw, float* dst, int w, int h) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= w * h) return;
-    const int y = i / w, x = i - y * w;
-    dst[i] = src[(int64_t)(2 * y) * sw + 2 * x];
+    down2_px(src, sw, dst, w, i);
+}
+
+// src, dst: both in the pyramid, stride floats per frame
+__global__ __launch_bounds__(256) void down2_group_kernel(const float* src, int sw, float* dst, int64_t stride, int w, int h) {
+    src += (int64_t)blockIdx.y * stride;
+    dst += (int64_t)blockIdx.y * stride;
+    const int npx = w * h, step = gridDim.x * 256;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < npx; i += step) down2_px(src, sw, dst, w, i);
+}
+
+__device__ __forceinline__ void dog_px(const SiftLayout& L, const SiftBufs& B, int o, int l, int i) {
+    B.dog[L.dog_off[o * 5 + l] + i] = layer(L, B, o, l + 1)[i] - layer(L, B, o, l)[i];
 }
 
 __global__ __launch_bounds__(256) void dog_kernel(SiftArgs A, int o) {
     const int n = A.ow[o] * A.oh[o];
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const int l = blockIdx.y;
-    A.dog[A.dog_off[o * 5 + l] + i] = layer(A, o, l + 1)[i] - layer(A, o, l)[i];
+    dog_px(A, A, o, blockIdx.y, i);
 }
 
-__global__ __launch_bounds__(256) void extrema_kernel(SiftArgs A, int o, int threshold) {
-    const int w = A.ow[o], h = A.oh[o];
-    const int iw = w - 2 * kBorderS, ih = h - 2 * kBorderS;
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    const int l = 1 + blockIdx.y;
-    if (iw <= 0 || ih <= 0 || t >= iw * ih) return;
+__global__ __launch_bounds__(256) void dog_group_kernel(SiftGroupArgs G, int o) {
+    const SiftBufs B = frame_bufs(G, blockIdx.z);
+    const int n = G.l.ow[o] * G.l.oh[o], step = gridDim.x * 256;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += step) dog_px(G.l, B, o, blockIdx.y, i);
+}
+
+// interior pixel t of DoG layer l of octave o
+__device__ __forceinline__ void extrema_px(const SiftLayout& A, const SiftBufs& B, int o, int l, int threshold, int t) {
+    const int w = A.ow[o];
+    const int iw = w - 2 * kBorderS;
     const int r = kBorderS + t / iw, c = kBorderS + t % iw;
-    const float* cur = dogl(A, o, l);
-    const float* prv = dogl(A, o, l - 1);
-    const float* nxt = dogl(A, o, l + 1);
+    const float* cur = dogl(A, B, o, l);
+    const float* prv = dogl(A, B, o, l - 1);
+    const float* nxt = dogl(A, B, o, l + 1);
     const float val = cur[r * w + c];
     if (!(fabsf(val) > (float)threshold)) return;
     bool ext = val != 0;
@@ -165,22 +296,37 @@ __global__ __launch_bounds__(256) void extrema_kernel(SiftArgs A, int o, int thr
             else ext &= val <= cur[q] && val <= prv[q] && val <= nxt[q];
         }
     if (!ext) return;
-    const int slot = atomicAdd(A.ncand, 1);
-    if (slot < A.cand_cap) A.cand[slot] = make_int4(o, l, r, c);
-    else atomicOr(A.flags, 1);
+    const int slot = atomicAdd(B.ncand, 1);
+    if (slot < A.cand_cap) B.cand[slot] = make_int4(o, l, r, c);
+    else atomicOr(B.flags, 1);
+}
+
+__global__ __launch_bounds__(256) void extrema_kernel(SiftArgs A, int o, int threshold) {
+    const int iw = A.ow[o] - 2 * kBorderS, ih = A.oh[o] - 2 * kBorderS;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (iw <= 0 || ih <= 0 || t >= iw * ih) return;
+    extrema_px(A, A, o, 1 + blockIdx.y, threshold, t);
+}
+
+__global__ __launch_bounds__(256) void extrema_group_kernel(SiftGroupArgs G, int o, int threshold) {
+    const SiftBufs B = frame_bufs(G, blockIdx.z);
+    const int iw = G.l.ow[o] - 2 * kBorderS, ih = G.l.oh[o] - 2 * kBorderS;
+    if (iw <= 0 || ih <= 0) return;
+    const int n = iw * ih, step = gridDim.x * 256;
+    for (int t = blockIdx.x * 256 + threadIdx.x; t < n; t += step) extrema_px(G.l, B, o, 1 + blockIdx.y, threshold, t);
 }
 
 // adjustLocalExtrema (oracle/sift.cpp adjust); wave-uniform scalar code
-__device__ bool adjust(const SiftArgs& A, dvo_keypoint& kpt, int octv, int& lay, int& r, int& c) {
+__device__ bool adjust(const SiftLayout& A, const SiftBufs& B, dvo_keypoint& kpt, int octv, int& lay, int& r, int& c) {
     const float img_scale = 1.f / 255;
     const float deriv_scale = img_scale * 0.5f, second = img_scale, cross = img_scale * 0.25f;
     const int w = A.ow[octv], h = A.oh[octv];
     float xi = 0, xr = 0, xc = 0, contr = 0;
     int i = 0;
     for (; i < kMaxInterp; i++) {
-        const float* img = dogl(A, octv, lay);
-        const float* prev = dogl(A, octv, lay - 1);
-        const float* next = dogl(A, octv, lay + 1);
+        const float* img = dogl(A, B, octv, lay);
+        const float* prev = dogl(A, B, octv, lay - 1);
+        const float* next = dogl(A, B, octv, lay + 1);
         auto I = [&](const float* p, int y, int x) { return p[y * w + x]; };
         const float dD0 = (I(img, r, c + 1) - I(img, r, c - 1)) * deriv_scale;
         const float dD1 = (I(img, r + 1, c) - I(img, r - 1, c)) * deriv_scale;
@@ -214,9 +360,9 @@ __device__ bool adjust(const SiftArgs& A, dvo_keypoint& kpt, int octv, int& lay,
     }
     if (i >= kMaxInterp) return false;
     {
-        const float* img = dogl(A, octv, lay);
-        const float* prev = dogl(A, octv, lay - 1);
-        const float* next = dogl(A, octv, lay + 1);
+        const float* img = dogl(A, B, octv, lay);
+        const float* prev = dogl(A, B, octv, lay - 1);
+        const float* next = dogl(A, B, octv, lay + 1);
         auto I = [&](const float* p, int y, int x) { return p[y * w + x]; };
         const float dD0 = (I(img, r, c + 1) - I(img, r, c - 1)) * deriv_scale;
         const float dD1 = (I(img, r + 1, c) - I(img, r - 1, c)) * deriv_scale;
@@ -241,22 +387,22 @@ __device__ bool adjust(const SiftArgs& A, dvo_keypoint& kpt, int octv, int& lay,
     return true;
 }
 
-// One wave per candidate (grid-stride over the candidate list).
-__global__ __launch_bounds__(64) void refine_kernel(SiftArgs A) {
+// One wave per candidate: candidates first, first + step, ... of the frame's list.
+__device__ __forceinline__ void refine_body(const SiftLayout& A, const SiftBufs& B, int first, int step) {
     const int lane = threadIdx.x;
-    const int ncand = min(*A.ncand, A.cand_cap);
-    for (int e = blockIdx.x; e < ncand; e += gridDim.x) {
-        const int4 cd = A.cand[e];
+    const int ncand = min(*B.ncand, A.cand_cap);
+    for (int e = first; e < ncand; e += step) {
+        const int4 cd = B.cand[e];
         const int o = cd.x;
         int lay = cd.y, r = cd.z, c = cd.w;
         dvo_keypoint kpt;
-        if (!adjust(A, kpt, o, lay, r, c)) continue;
+        if (!adjust(A, B, kpt, o, lay, r, c)) continue;
         // calcOrientationHist on the Gaussian layer, centre (c, r)
         const float scl_octv = kpt.size * 0.5f / (float)(1 << o);
         const int radius = rnd(kOriRadius * scl_octv);
         const float sigma = kOriSigFctr * scl_octv;
         const float expf_scale = -1.f / (2.f * sigma * sigma);
-        const float* img = layer(A, o, lay);
+        const float* img = layer(A, B, o, lay);
         const int w = A.ow[o], h = A.oh[o];
         const int side = 2 * radius + 1, total = side * side;
         float th = 0.f;  // lane b < 36 holds temphist[b]
@@ -304,11 +450,17 @@ __global__ __launch_bounds__(64) void refine_kernel(SiftArgs A) {
             dvo_keypoint q = kpt;
             q.angle = 360.f - (360.f / kOriBins) * bn;
             if (fabsf(q.angle - 360.f) < FLT_EPSILON) q.angle = 0.f;
-            const int slot = atomicAdd(A.nraw, 1);
-            if (slot < A.kp_cap) A.raw[slot] = q;
-            else atomicOr(A.flags, 2);
+            const int slot = atomicAdd(B.nraw, 1);
+            if (slot < A.kp_cap) B.raw[slot] = q;
+            else atomicOr(B.flags, 2);
         }
     }
+}
+
+__global__ __launch_bounds__(64) void refine_kernel(SiftArgs A) { refine_body(A, A, blockIdx.x, gridDim.x); }
+
+__global__ __launch_bounds__(64) void refine_group_kernel(SiftGroupArgs G) {
+    refine_body(G.l, frame_bufs(G, blockIdx.y), blockIdx.x, gridDim.x);
 }
 
 __device__ __forceinline__ bool kp_less(const dvo_keypoint& a, const dvo_keypoint& b) {  // KeyPoint12_LessThan
@@ -320,10 +472,11 @@ __device__ __forceinline__ bool kp_less(const dvo_keypoint& a, const dvo_keypoin
     return a.octave > b.octave;
 }
 
-// removeDuplicatedSorted + the firstOctave = -1 rescale, one workgroup.
+// removeDuplicatedSorted + the firstOctave = -1 rescale, one workgroup per frame.  The keypoints
+// below out_cap go to B.kps; dn, if given, takes (count, flags) as feature_copy_kernel writes them.
 constexpr int kSortNT = 1024;
-__global__ __launch_bounds__(kSortNT) void sort_kernel(SiftArgs A) {
-    const int n = min(*A.nraw, A.kp_cap);
+__device__ __forceinline__ void sort_body(const SiftLayout& L, const SiftBufs& A, int out_cap, int32_t* dn) {
+    const int n = min(*A.nraw, L.kp_cap);
     int n2 = 1;
     while (n2 < n) n2 <<= 1;
     int32_t* idx = A.order;
@@ -366,6 +519,10 @@ __global__ __launch_bounds__(kSortNT) void sort_kernel(SiftArgs A) {
             acc += v;
         }
         *A.nkp = acc;
+        if (dn) {
+            dn[0] = acc;
+            dn[1] = *A.flags;
+        }
     }
     __syncthreads();
     int pos = s_part[threadIdx.x];
@@ -376,21 +533,27 @@ __global__ __launch_bounds__(kSortNT) void sort_kernel(SiftArgs A) {
             q.y = q.y * 0.5f;
             q.size = q.size * 0.5f;
             q.octave = (q.octave & ~255) | ((q.octave - 1) & 255);
-            A.kps[pos++] = q;
+            if (pos < out_cap) A.kps[pos] = q;
+            ++pos;
         }
 }
 
-// calcSIFTDescriptor, one wave per keypoint (grid-stride).
-__global__ __launch_bounds__(64) void descriptor_kernel(SiftArgs A) {
+__global__ __launch_bounds__(kSortNT) void sort_kernel(SiftArgs A) { sort_body(A, A, A.kp_cap, nullptr); }
+
+__global__ __launch_bounds__(kSortNT) void sort_group_kernel(SiftGroupArgs G) {
+    sort_body(G.l, frame_bufs(G, blockIdx.x), G.feat_cap, G.out_n + 2 * (int64_t)blockIdx.x);
+}
+
+// calcSIFTDescriptor, one wave per keypoint: keypoints first, first + step, ... below nk of B.kps.
+__device__ __forceinline__ void descriptor_body(const SiftLayout& A, const SiftBufs& B, int nk, int first, int step) {
     __shared__ float hist[kHistN];
     __shared__ int s_idx[64];
     __shared__ float s_v[64][8];
     const int lane = threadIdx.x;
-    const int nk = *A.nkp;
     constexpr int d = kDW, n = kDB;
     const int off[8] = {0, 1, n + 2, n + 3, (d + 2) * (n + 2), (d + 2) * (n + 2) + 1, (d + 3) * (n + 2), (d + 3) * (n + 2) + 1};
-    for (int e = blockIdx.x; e < nk; e += gridDim.x) {
-        const dvo_keypoint kp = A.kps[e];
+    for (int e = first; e < nk; e += step) {
+        const dvo_keypoint kp = B.kps[e];
         const int ob = kp.octave & 255, lay = (kp.octave >> 8) & 255;
         const int octv = ob < 128 ? ob : (-128 | ob);
         const float scale = octv >= 0 ? 1.f / (float)(1 << octv) : (float)(1 << -octv);
@@ -400,7 +563,7 @@ __global__ __launch_bounds__(64) void descriptor_kernel(SiftArgs A) {
         if (fabsf(ori - 360.f) < FLT_EPSILON) ori = 0.f;
         const float scl = size * 0.5f;
         const int o = octv + 1;
-        const float* img = layer(A, o, lay);
+        const float* img = layer(A, B, o, lay);
         const int w = A.ow[o], h = A.oh[o];
         const int px = rnd(ptx), py = rnd(pty);
         const float ang = ori * (float)(M_PI / 180);
@@ -501,10 +664,17 @@ __global__ __launch_bounds__(64) void descriptor_kernel(SiftArgs A) {
         for (int k = lane; k < d * d * n; k += 64) {
             const float v = fminf(raw[k], s_scale[0]);
             const int q = rnd(v * s_scale[1]);
-            A.desc[(int64_t)e * 128 + k] = (float)min(max(q, 0), 255);
+            B.desc[(int64_t)e * 128 + k] = (float)min(max(q, 0), 255);
         }
         __syncthreads();
     }
+}
+
+__global__ __launch_bounds__(64) void descriptor_kernel(SiftArgs A) { descriptor_body(A, A, *A.nkp, blockIdx.x, gridDim.x); }
+
+__global__ __launch_bounds__(64) void descriptor_group_kernel(SiftGroupArgs G) {
+    const SiftBufs B = frame_bufs(G, blockIdx.y);
+    descriptor_body(G.l, B, min(*B.nkp, G.feat_cap), blockIdx.x, gridDim.x);
 }
 
 }  // namespace
@@ -542,6 +712,58 @@ hipError_t launch_sift(const SiftArgs& A, const uint8_t* d_img, int w, int h, in
     hipLaunchKernelGGL(refine_kernel, dim3(4096), dim3(64), 0, s, A);
     hipLaunchKernelGGL(sort_kernel, dim3(1), dim3(kSortNT), 0, s, A);
     hipLaunchKernelGGL(descriptor_kernel, dim3(4096), dim3(64), 0, s, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_sift_group(const SiftGroupArgs& G, int frames, const uint8_t* d_frames, int64_t frame_stride, int w,
+                             int h, int stride, const float* d_taps, const int* tap_off, const int* tap_n,
+                             hipStream_t s) {
+    const SiftLayout& L = G.l;
+    const unsigned F = (unsigned)frames;
+    // memory-bound stages: about kBlocks workgroups per launch, the frame's items grid-strided
+    constexpr int64_t kBlocks = 4096;
+    const int64_t per_frame = std::max<int64_t>(1, kBlocks / frames);
+    auto grid = [&](int64_t n, unsigned y, unsigned z) {
+        return dim3((unsigned)std::min<int64_t>((n + 255) / 256, per_frame), y, z);
+    };
+    float* base = G.b.gp + L.gp_off[0];
+    hipLaunchKernelGGL(up2_group_kernel, grid((int64_t)L.ow[0] * L.oh[0], F, 1), dim3(256), 0, s, d_frames, frame_stride, w, h,
+                       stride, base, G.gp_stride);
+    auto blur = [&](const float* src, float* dst, int o, int which) {
+        // fused where its tiles fill the card (4 workgroups of its LDS size per CU), two passes elsewhere:
+        // a small octave has few tiles, and a tile is far more work than a two-pass workgroup
+        const int64_t tiles = (int64_t)((L.ow[o] + kFuseTW - 1) / kFuseTW) * ((L.oh[o] + kFuseTH - 1) / kFuseTH);
+        if (G.fused_blur && src != dst && tap_n[which] / 2 <= kFuseMaxR && tiles * frames >= kFuseMinTiles) {
+            hipLaunchKernelGGL(blur_fused_group_kernel, dim3((unsigned)std::min(tiles, per_frame), F), dim3(256), 0, s, src, dst,
+                               G.gp_stride, L.ow[o], L.oh[o], d_taps + tap_off[which], tap_n[which]);
+            return;
+        }
+        const dim3 g = grid((int64_t)L.ow[o] * L.oh[o], F, 1);
+        hipLaunchKernelGGL(blur_rows_group_kernel, g, dim3(256), 0, s, src, G.gp_stride, G.b.tmp, G.tmp_stride, L.ow[o],
+                           L.oh[o], d_taps + tap_off[which], tap_n[which]);
+        hipLaunchKernelGGL(blur_cols_group_kernel, g, dim3(256), 0, s, (const float*)G.b.tmp, G.tmp_stride, dst, G.gp_stride,
+                           L.ow[o], L.oh[o], d_taps + tap_off[which], tap_n[which]);
+    };
+    blur(base, base, 0, 0);
+    for (int o = 0; o < L.noct; ++o) {
+        if (o > 0)
+            hipLaunchKernelGGL(down2_group_kernel, grid((int64_t)L.ow[o] * L.oh[o], F, 1), dim3(256), 0, s,
+                               (const float*)(G.b.gp + L.gp_off[(o - 1) * 6 + 3]), L.ow[o - 1], G.b.gp + L.gp_off[o * 6],
+                               G.gp_stride, L.ow[o], L.oh[o]);
+        for (int l = 1; l < 6; ++l) blur(G.b.gp + L.gp_off[o * 6 + l - 1], G.b.gp + L.gp_off[o * 6 + l], o, l);
+        hipLaunchKernelGGL(dog_group_kernel, grid((int64_t)L.ow[o] * L.oh[o], 5, F), dim3(256), 0, s, G, o);
+    }
+    const int threshold = (int)floor(0.5 * kContrast / kLayers * 255);
+    for (int o = 0; o < L.noct; ++o) {
+        const int iw = L.ow[o] - 2 * kBorderS, ih = L.oh[o] - 2 * kBorderS;
+        if (iw <= 0 || ih <= 0) continue;
+        hipLaunchKernelGGL(extrema_group_kernel, grid((int64_t)iw * ih, kLayers, F), dim3(256), 0, s, G, o, threshold);
+    }
+    // one wave per item: 4096 waves a frame as launch_sift, fewer as the group fills the card
+    const unsigned waves = (unsigned)std::min(4096, std::max(128, 8192 / frames));
+    hipLaunchKernelGGL(refine_group_kernel, dim3(waves, F), dim3(64), 0, s, G);
+    hipLaunchKernelGGL(sort_group_kernel, dim3(F), dim3(kSortNT), 0, s, G);
+    hipLaunchKernelGGL(descriptor_group_kernel, dim3(waves, F), dim3(64), 0, s, G);
     return hipGetLastError();
 }
 

@@ -464,11 +464,16 @@ class KnnFrameStream:
 
     feat_cap: features kept per frame (None: the detector's list capacity, 65536 for SIFT, which
     costs 44 MB per frame slot: give the count you expect).  A frame with more features marks its
-    two pairs DVO_ECAP.  The calls run on the context's HIP stream, asynchronously; sync() waits."""
+    two pairs DVO_ECAP.  The calls run on the context's HIP stream, asynchronously; sync() waits.
+
+    detect_group (SIFT only): 0 detects frame by frame; G >= 1 detects G frames per launch
+    (dvo_knn_stream_set_detect_group, the detector of ops.SiftBatch) straight into the frame slots,
+    for ops.SiftBatch.scratch_bytes(width, height, G) more device memory.  Same records either way."""
 
     def __init__(self, width: int, height: int, K, max_frames: int, detector="sift", feat_cap: int | None = None,
                  hessian_threshold: float = 400.0, ratio: float = 0.75, prob: float = 0.999, threshold: float = 1.0,
-                 max_iters: int = 1000, dist_thresh: float = 50.0, ctx: Context | None = None):
+                 max_iters: int = 1000, dist_thresh: float = 50.0, ctx: Context | None = None, *,
+                 detect_group: int = 0):
         from ._native import KnnStreamConfig
         from .ops import KNN_DETECTORS
         self.h = None
@@ -487,6 +492,9 @@ class KnnFrameStream:
         h = _vp()
         self.ctx.check(self.ctx.lib.dvo_knn_stream_create(self.ctx.h, ctypes.byref(cfg), ctypes.byref(h)))
         self.h = h
+        self.detect_group = 0
+        if detect_group:
+            self.set_detect_group(detect_group)
         self._ext = torch.cuda.ExternalStream(self.hip_stream, device=self.device)
         self._held = collections.deque()  # (event, tensors) in flight on the library's stream
         self.width, self.height, self.max_frames = int(width), int(height), int(max_frames)
@@ -499,6 +507,12 @@ class KnnFrameStream:
 
     def new_records(self, n_pairs: int) -> torch.Tensor:
         return torch.zeros(max(n_pairs, 1) * PAIR_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+
+    def set_detect_group(self, group: int):
+        """SIFT frames per detection launch from the next process() on (0: frame by frame).  Waits
+        for the stream and allocates or frees the group's scratch; DVOError(DVO_EINVAL) on a SURF stream."""
+        self.ctx.check(self.ctx.lib.dvo_knn_stream_set_detect_group(self.h, int(group)))
+        self.detect_group = int(group)
 
     def process(self, frames, records: torch.Tensor | None = None, wait_torch: bool = True) -> torch.Tensor:
         """Enqueue the batch (asynchronous).  frames: a uint8 [n, H, W] device tensor (rows contiguous,

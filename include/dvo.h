@@ -132,6 +132,47 @@ int dvo_flann_knn(dvo_ctx* ctx, const float* dq, int nq, const float* dt, int nt
 int dvo_sift_detect_and_compute(dvo_ctx* ctx, const uint8_t* img, int w, int h, int stride, dvo_keypoint* kps,
                                 float* desc, int cap, int* n_out);
 
+/* The same SIFT_create().detectAndCompute (visual_odometry_v3.py:373) for DEVICE-resident
+ * frames of one size, a group of frames per launch: every stage of the detector (upscale, the
+ * blurs, downsample, DoG, extrema, refine, sort, descriptor) is one launch over `group` frames,
+ * the frame a grid dimension (a blur is one launch, row and column pass fused through LDS,
+ * where the octave and the group are large enough to fill the card with its tiles, else two).
+ * Keypoints and descriptors of every frame are bit-identical to dvo_sift_detect_and_compute's
+ * whatever the group.
+ *
+ * dvo_sift_batch_create allocates the whole scratch (after synchronising the context's stream);
+ * a detect call allocates nothing.  Bytes, which dvo_sift_batch_bytes returns (host only: no
+ * context, no device; DVO_EINVAL for arguments create would reject), with S the sum over the
+ * octaves of their pixels (octave 0 is 2w x 2h, each next one half of it, truncated; the octave
+ * count is cvRound(log2(min(2w, 2h)) - 2) + 1, ended early where a side reaches 0):
+ *   group * (4 * (6 S + 5 S + 2w * 2h)    Gaussian pyramid, DoG, row-pass buffer (floats)
+ *            + 16 * 262144                candidate list (2^18 extrema)
+ *            + 28 * 65536                 raw keypoint list
+ *            + 4 * 65536                  sort scratch
+ *            + 16)                        the frame's four counters
+ *   + 400                                 one table of the 6 Gaussian kernels (11 + 11 + 13 + 17 + 21 + 27 taps)
+ * which is 83.3 MB per frame of the group at 640 x 480 and 237.3 MB at 1280 x 720.
+ *
+ * dvo_sift_batch_detect: n_frames >= 1 mono8 frames on the device, frame f at d_frames +
+ * f * frame_stride, rows `stride` >= w bytes apart, read in place.  Asynchronous on the context's
+ * stream, nothing is read back; more frames than `group` run in chunks of `group` on that stream,
+ * and the results do not depend on the group.  Frame f's keypoints go to d_kps + f * feat_cap
+ * (removeDuplicatedSorted order), its descriptors to d_desc + f * feat_cap * 128, entries below
+ * feat_cap only; d_counts[2 f] is the detector's count even where it exceeds feat_cap and
+ * d_counts[2 f + 1] the detector's flags (1: more than 2^18 extrema, 2: more than 65536 raw
+ * keypoints; a frame is complete when the flags are 0 and the count <= feat_cap).
+ *
+ * DVO_EINVAL, before any allocation: a side outside 1..4095, group outside 1..64; detect:
+ * n_frames < 1, stride < w, feat_cap outside 1..65536, a null buffer. */
+typedef struct dvo_sift_batch dvo_sift_batch;
+int64_t dvo_sift_batch_bytes(int w, int h, int group);
+int dvo_sift_batch_create(dvo_ctx* ctx, int w, int h, int group, dvo_sift_batch** out);
+void dvo_sift_batch_destroy(dvo_sift_batch* b);
+int dvo_sift_batch_detect(dvo_sift_batch* b, const uint8_t* d_frames, int n_frames, int64_t frame_stride, int stride,
+                          int feat_cap, dvo_keypoint* d_kps, float* d_desc, int32_t* d_counts);
+/* The HIP stream the detect calls run on (the context's). */
+void* dvo_sift_batch_hip_stream(dvo_sift_batch* b);
+
 /* Replaces cv::xfeatures2d::SURF_create(hessianThreshold).detectAndCompute(img,
  * None) — the detector of the 'surf' mode, visual_odometry_v3.py:104
  * (SURF_create(400)) and :373 (call).  Other parameters at their defaults
@@ -424,6 +465,13 @@ int dvo_knn_stream_process(dvo_knn_stream* s, const uint8_t* d_frames, int n_fra
 int dvo_knn_stream_sync(dvo_knn_stream* s);
 /* The HIP stream the calls run on (the context's). */
 void* dvo_knn_stream_hip_stream(dvo_knn_stream* s);
+/* SIFT detection (v3:373) of the process calls that follow through the group detector
+ * (dvo_sift_batch_detect's path): `group` frames per launch, written straight into the stream's
+ * frame slots.  0 (the default) keeps the frame-by-frame detection.  Records, features and
+ * matches are the same either way.  The setter synchronises the context's stream and allocates
+ * (or frees) the group's scratch, dvo_sift_batch_bytes(width, height, group) bytes; process
+ * allocates nothing.  DVO_EINVAL: a SURF stream, group outside 0..64. */
+int dvo_knn_stream_set_detect_group(dvo_knn_stream* s, int group);
 /* After the last process call (these synchronise): frame `frame`'s features, desc n x 128 (SIFT)
  * or n x 64 (SURF) floats, *n = the detector's count (DVO_ECAP if > cap or the frame is marked);
  * pair `pair`'s kept matches in ascending queryIdx, *m = count (DVO_ECAP if > cap). */
