@@ -136,6 +136,11 @@ _SIGNATURES = {
     "dvo_sift_batch_destroy": ([_vp], None),
     "dvo_sift_batch_detect": ([_vp, _vp, _c, _i64, _c, _c, _vp, _vp, _vp], _c),
     "dvo_sift_batch_hip_stream": ([_vp], _vp),
+    "dvo_surf_batch_bytes": ([_c, _c, _c], _i64),
+    "dvo_surf_batch_create": ([_vp, _c, _c, _c, ctypes.POINTER(_vp)], _c),
+    "dvo_surf_batch_destroy": ([_vp], None),
+    "dvo_surf_batch_detect": ([_vp, _vp, _c, _i64, _c, ctypes.c_double, _c, _vp, _vp, _vp], _c),
+    "dvo_surf_batch_hip_stream": ([_vp], _vp),
     "dvo_surf_detect_and_compute": ([_vp, _vp, _c, _c, _c, ctypes.c_double, _vp, _vp, _c, _ip], _c),
     "dvo_find_essential_mat": ([_vp, _vp, _vp, _c, _vp, _d, _d, _c, _vp, _ip, _vp], _c),
     "dvo_recover_pose": ([_vp, _vp, _c, _vp, _vp, _c, _vp, _d, _vp, _vp, _vp, _vp, _ip], _c),
@@ -163,6 +168,7 @@ _SIGNATURES = {
     "dvo_knn_stream_sync": ([_vp], _c),
     "dvo_knn_stream_hip_stream": ([_vp], _vp),
     "dvo_knn_stream_set_detect_group": ([_vp, _c], _c),
+    "dvo_knn_stream_set_surf_group": ([_vp, _c], _c),
     "dvo_knn_stream_get_features": ([_vp, _c, _vp, _vp, _c, _ip], _c),
     "dvo_knn_stream_get_matches": ([_vp, _c, _vp, _c, _ip], _c),
     "dvo_knn_stream_set_profiling": ([_vp, _c], _c),

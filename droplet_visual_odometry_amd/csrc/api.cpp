@@ -48,6 +48,16 @@ struct SurfPlanDev {  // per-size device buffers of dvo_surf_detect_and_compute
     DeviceAllocs mem;
 };
 
+// Scratch of the group SURF detector (launch_surf_group): `group` copies of what surf_plan
+// allocates per frame, out / desc / the image copy aside (the results go to the caller's slots,
+// the frames are read in place), det and trace of a frame adjacent, and one set of the Haar and
+// orientation tables.  Allocated whole by surf_group_alloc.
+struct SurfGroupDev {
+    int w = 0, h = 0, group = 0;
+    SurfGroupArgs g{};
+    DeviceAllocs mem;
+};
+
 struct dvo_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -1628,19 +1638,25 @@ void surf_haar(const int src[][5], SurfHaar* dst, int n, int old_size, int new_s
     }
 }
 
-int surf_plan(dvo_ctx* ctx, int w, int h) {
-    SurfPlanDev& P = ctx->surf;
-    if (P.w == w && P.h == h) return DVO_OK;
-    P = SurfPlanDev{};
-    SurfArgs& A = P.a;
+// The host tables of a w x h image: the layer geometry in A (w, h, off, size, rows, cols, nori,
+// gdesc, kp_cap; pitch, thr and the table pointers are the caller's) and the three device tables'
+// contents.  What surf_plan and the group detector's scratch (surf_group_alloc) both start from.
+struct SurfTables {
+    std::vector<SurfHaar> haar;
+    std::vector<int8_t> apt;
+    std::vector<float> aptw;
+    int64_t cells = 0;  // floats of det (and of trace): all 20 layers
+};
+SurfTables surf_tables(int w, int h, SurfLayout& A) {
+    SurfTables T;
     A.w = w;
     A.h = h;
-    A.pitch = (w + 255) & ~255;
     const int sw = w + 1;
     static const int dx_s[3][5] = {{0, 2, 3, 7, 1}, {3, 2, 6, 7, -2}, {6, 2, 9, 7, 1}};
     static const int dy_s[3][5] = {{2, 0, 7, 3, 1}, {2, 3, 7, 6, -2}, {2, 6, 7, 9, 1}};
     static const int dxy_s[4][5] = {{1, 1, 4, 4, 1}, {5, 1, 8, 4, -1}, {1, 5, 4, 8, -1}, {5, 5, 8, 8, 1}};
-    std::vector<SurfHaar> haar((size_t)kSurfTot * 10);
+    std::vector<SurfHaar>& haar = T.haar;
+    haar.resize((size_t)kSurfTot * 10);
     int64_t cells = 0;
     for (int o = 0; o < kSurfOct; ++o) {
         const int step = 1 << o;
@@ -1658,20 +1674,39 @@ int surf_plan(dvo_ctx* ctx, int w, int h) {
     }
     // SURF_ORI_SIGMA 2.5f, SURF_DESC_SIGMA 3.3f: float constants widened to double
     const std::vector<float> go = surf_gauss(13, (double)2.5f), gd = surf_gauss(20, (double)3.3f);
-    std::vector<int8_t> apt;
-    std::vector<float> aptw;
     for (int i = -6; i <= 6; ++i)
         for (int j = -6; j <= 6; ++j)
             if (i * i + j * j <= 36) {
-                apt.push_back((int8_t)i);
-                apt.push_back((int8_t)j);
-                aptw.push_back(go[i + 6] * go[j + 6]);
+                T.apt.push_back((int8_t)i);
+                T.apt.push_back((int8_t)j);
+                T.aptw.push_back(go[i + 6] * go[j + 6]);
             }
-    A.nori = (int)aptw.size();
+    A.nori = (int)T.aptw.size();
     for (int i = 0; i < 20; ++i) A.gdesc[i] = gd[i];
     A.kp_cap = surf_kp_cap(w, h);
+    T.cells = cells;
+    return T;
+}
+
+int surf_order_n(int kp_cap) {  // the sort scratch: the next power of two >= kp_cap
     int order_n = 1;
-    while (order_n < A.kp_cap) order_n <<= 1;
+    while (order_n < kp_cap) order_n <<= 1;
+    return order_n;
+}
+
+int surf_plan(dvo_ctx* ctx, int w, int h) {
+    SurfPlanDev& P = ctx->surf;
+    if (P.w == w && P.h == h) return DVO_OK;
+    P = SurfPlanDev{};
+    SurfArgs& A = P.a;
+    A.pitch = (w + 255) & ~255;
+    const int sw = w + 1;
+    const SurfTables T = surf_tables(w, h, A);
+    const std::vector<SurfHaar>& haar = T.haar;
+    const std::vector<int8_t>& apt = T.apt;
+    const std::vector<float>& aptw = T.aptw;
+    const int64_t cells = T.cells;
+    const int order_n = surf_order_n(A.kp_cap);
     auto A_ = [&](auto*& p, size_t bytes) { return P.mem.alloc(&p, bytes ? bytes : 16) == hipSuccess; };
     int* counters = nullptr;
     SurfHaar* d_haar = nullptr;
@@ -1701,7 +1736,156 @@ int surf_plan(dvo_ctx* ctx, int w, int h) {
     P.h = h;
     return DVO_OK;
 }
+
+// One frame's share of a group's scratch, array by array (bytes), and the tables the group shares.
+struct SurfGroupBytes {
+    int64_t sum, cells, raw, kps, dtmp, order, counters, tables;
+    int64_t frame() const { return sum + cells + raw + kps + dtmp + order + counters; }
+};
+SurfGroupBytes surf_group_bytes(int w, int h) {
+    const int64_t kp_cap = surf_kp_cap(w, h);
+    int64_t cells = 0;
+    for (int o = 0; o < kSurfOct; ++o) cells += (int64_t)kSurfLayers * (h >> o) * (w >> o);
+    SurfGroupBytes b;
+    b.sum = (int64_t)4 * (w + 1) * (h + 1);
+    b.cells = 8 * cells;  // det and trace
+    b.raw = kp_cap * (int64_t)sizeof(dvo_keypoint);
+    b.kps = b.raw;
+    b.dtmp = kp_cap * 64 * 4;
+    b.order = (int64_t)surf_order_n((int)kp_cap) * 4;
+    b.counters = 16;
+    b.tables = (int64_t)kSurfTot * 10 * (int64_t)sizeof(SurfHaar) + 113 * 2 + 113 * 4;
+    return b;
+}
+
+constexpr int kSurfGroupMax = 64;
+
+// Allocates a group's whole scratch and uploads the tables, after waiting for the context's stream
+// (nothing is allocated later, inside a detect / process call).  D is empty on failure.
+int surf_group_alloc(dvo_ctx* ctx, int w, int h, int group, SurfGroupDev& D) {
+    D = SurfGroupDev{};
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    SurfGroupArgs& g = D.g;
+    const SurfTables T = surf_tables(w, h, g.l);
+    const SurfGroupBytes b = surf_group_bytes(w, h);
+    const int64_t G = group;
+    int* counters = nullptr;
+    SurfHaar* d_haar = nullptr;
+    int8_t* d_apt = nullptr;
+    float* d_aptw = nullptr;
+    hipError_t e = hipSuccess;
+    auto A_ = [&](auto*& p, int64_t bytes) {
+        if (e == hipSuccess) e = D.mem.alloc(&p, (size_t)bytes);
+    };
+    A_(g.b.sum, G * b.sum);
+    A_(g.b.det, G * b.cells);  // frame f: its det, then its trace (one clear covers a chunk's both)
+    A_(g.b.raw, G * b.raw);
+    A_(g.b.kps, G * b.kps);
+    A_(g.b.dtmp, G * b.dtmp);
+    A_(g.b.order, G * b.order);
+    A_(counters, G * b.counters);
+    A_(d_haar, (int64_t)(T.haar.size() * sizeof(SurfHaar)));
+    A_(d_apt, (int64_t)T.apt.size());
+    A_(d_aptw, (int64_t)T.aptw.size() * 4);
+    if (e == hipSuccess) e = hipMemcpy(d_haar, T.haar.data(), T.haar.size() * sizeof(SurfHaar), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_apt, T.apt.data(), T.apt.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_aptw, T.aptw.data(), T.aptw.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        D = SurfGroupDev{};
+        return fail(ctx, DVO_EHIP, std::string("SURF group buffers: ") + hipGetErrorString(e));
+    }
+    g.b.trace = g.b.det + T.cells;
+    g.b.nraw = counters;
+    g.b.nout = counters + 1;
+    g.b.flags = counters + 2;
+    g.l.haar = d_haar;
+    g.l.apt = d_apt;
+    g.l.aptw = d_aptw;
+    g.sum_stride = b.sum / 4;
+    g.cell_stride = 2 * T.cells;
+    g.order_stride = b.order / 4;
+    // DVO_SURF_LARGE_FIRST=0 (read here, when the scratch is made) keeps describe's plain stride over
+    // each frame's list: the A/B of tools/time_surf_batch.py.  The results are the same either way.
+    const char* lf = std::getenv("DVO_SURF_LARGE_FIRST");
+    g.large_first = !(lf && lf[0] == '0');
+    D.w = w;
+    D.h = h;
+    D.group = group;
+    return DVO_OK;
+}
+
+// n frames through the group detector, in chunks of D.group on stream s: frame f's keypoints and
+// descriptors go to kps + f * feat_cap and desc + f * feat_cap * 64, its (count, flags) to counts + 2 f.
+int surf_group_detect(dvo_ctx* ctx, const SurfGroupDev& D, const uint8_t* d_frames, int n, int64_t frame_stride, int stride,
+                      double hessian_threshold, int feat_cap, dvo_keypoint* kps, float* desc, int32_t* counts,
+                      hipStream_t s) {
+    for (int f0 = 0; f0 < n; f0 += D.group) {
+        const int frames = std::min(D.group, n - f0);
+        SurfGroupArgs g = D.g;
+        g.l.pitch = stride;
+        g.l.thr = (float)hessian_threshold;
+        g.b.img = d_frames + (int64_t)f0 * frame_stride;
+        g.frame_stride = frame_stride;
+        g.out_kps = kps + (size_t)f0 * feat_cap;
+        g.out_desc = desc + (size_t)f0 * feat_cap * 64;
+        g.out_n = counts + 2 * (size_t)f0;
+        g.feat_cap = feat_cap;
+        HIP_TRY(hipMemsetAsync(g.b.nraw, 0, (size_t)frames * 16, s));  // the chunk's counters
+        HIP_TRY(hipMemsetAsync(g.b.det, 0, (size_t)frames * (size_t)g.cell_stride * 4, s));  // its det and trace
+        HIP_TRY(launch_surf_group(g, frames, s));
+    }
+    return DVO_OK;
+}
 }  // namespace
+
+struct dvo_surf_batch {
+    dvo_ctx* ctx = nullptr;
+    SurfGroupDev d;
+};
+
+int64_t dvo_surf_batch_bytes(int w, int h, int group) {
+    if (w < 1 || h < 1 || w >= kMaxW || h >= kMaxW || group < 1 || group > kSurfGroupMax) return DVO_EINVAL;
+    const SurfGroupBytes b = surf_group_bytes(w, h);
+    return group * b.frame() + b.tables;
+}
+
+int dvo_surf_batch_create(dvo_ctx* ctx, int w, int h, int group, dvo_surf_batch** out) {
+    if (!ctx || !out) return DVO_EINVAL;
+    *out = nullptr;
+    if (w < 1 || h < 1 || w >= kMaxW || h >= kMaxW) return fail(ctx, DVO_EINVAL, "image size out of range (1..4095)");
+    if (group < 1 || group > kSurfGroupMax) return fail(ctx, DVO_EINVAL, "group out of range (1..64)");
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::unique_ptr<dvo_surf_batch> b(new dvo_surf_batch);
+    b->ctx = ctx;
+    const int rc = surf_group_alloc(ctx, w, h, group, b->d);
+    if (rc) return rc;
+    *out = b.release();
+    return DVO_OK;
+}
+
+void dvo_surf_batch_destroy(dvo_surf_batch* b) {
+    if (!b) return;
+    hipSetDevice(b->ctx->device);
+    hipStreamSynchronize(b->ctx->stream);
+    delete b;
+}
+
+void* dvo_surf_batch_hip_stream(dvo_surf_batch* b) { return b ? (void*)b->ctx->stream : nullptr; }
+
+int dvo_surf_batch_detect(dvo_surf_batch* b, const uint8_t* d_frames, int n_frames, int64_t frame_stride, int stride,
+                          double hessian_threshold, int feat_cap, dvo_keypoint* d_kps, float* d_desc, int32_t* d_counts) {
+    if (!b) return DVO_EINVAL;
+    dvo_ctx* ctx = b->ctx;
+    if (n_frames < 1) return fail(ctx, DVO_EINVAL, "n_frames must be >= 1");
+    if (!d_frames || !d_kps || !d_desc || !d_counts || stride < b->d.w)
+        return fail(ctx, DVO_EINVAL, "bad frame or output buffer");
+    if (feat_cap < 1 || feat_cap > surf_kp_cap(b->d.w, b->d.h))
+        return fail(ctx, DVO_EINVAL, "feat_cap out of range (1..the detector's list capacity)");
+    if (!(hessian_threshold >= 0)) return fail(ctx, DVO_EINVAL, "hessianThreshold must be >= 0");
+    HIP_TRY(hipSetDevice(ctx->device));
+    return surf_group_detect(ctx, b->d, d_frames, n_frames, frame_stride, stride, hessian_threshold, feat_cap, d_kps,
+                             d_desc, d_counts, ctx->stream);
+}
 
 int dvo_surf_detect_and_compute(dvo_ctx* ctx, const uint8_t* img, int w, int h, int stride, double hessian_threshold,
                                 dvo_keypoint* kps, float* desc, int cap, int* n_out) {
@@ -2298,6 +2482,7 @@ struct dvo_knn_stream {
     PairSets pairs;    // one set of max_frames - 1 pairs: pairs.all.g is the stream's GeomArgs
     DeviceAllocs mem;  // the frame slots, the match arrays and the round-local geometry arrays
     SiftGroupDev grp;  // dvo_knn_stream_set_detect_group: grp.group > 0 detects through launch_sift_group
+    SurfGroupDev sgrp;  // dvo_knn_stream_set_surf_group: sgrp.group > 0 detects through launch_surf_group
     int last_frames = 0;
     bool profiling = false, timed = false;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -2384,7 +2569,8 @@ int dvo_knn_stream_process(dvo_knn_stream* st, const uint8_t* d_frames, int n_fr
     if (n_frames < 1 || n_frames > c.max_frames) return fail(ctx, DVO_EINVAL, "n_frames out of range (1..max_frames)");
     if (!d_frames || stride < w || (n_frames > 1 && !d_records)) return fail(ctx, DVO_EINVAL, "bad frame or record buffer");
     HIP_TRY(hipSetDevice(ctx->device));
-    const bool grouped = st->grp.group > 0;  // the group detector has its own scratch: the context's plan is not used
+    // a group detector has its own scratch: the context's plan is not used
+    const bool grouped = st->grp.group > 0 || st->sgrp.group > 0;
     int rc = grouped ? DVO_OK : knn_stream_plan(st);  // another size may have taken the context's plan since
     if (rc) return rc;
     hipStream_t s = ctx->stream;
@@ -2396,7 +2582,11 @@ int dvo_knn_stream_process(dvo_knn_stream* st, const uint8_t* d_frames, int n_fr
     if (ev) HIP_TRY(hipEventRecord(ev[0], s));
     // detection in place on the caller's frames: a group of frames per launch straight into the
     // frame slots, or frame by frame on the plan's single scratch
-    if (grouped) rc = sift_group_detect(ctx, st->grp, d_frames, n_frames, frame_stride, stride, b.cap, b.kps, b.desc, b.n, s);
+    if (st->grp.group > 0)
+        rc = sift_group_detect(ctx, st->grp, d_frames, n_frames, frame_stride, stride, b.cap, b.kps, b.desc, b.n, s);
+    else if (st->sgrp.group > 0)
+        rc = surf_group_detect(ctx, st->sgrp, d_frames, n_frames, frame_stride, stride, c.hessian_threshold, b.cap, b.kps,
+                               b.desc, b.n, s);
     if (rc) return rc;
     for (int f = 0; f < n_frames && !grouped; ++f) {
         const uint8_t* img = d_frames + (int64_t)f * frame_stride;
@@ -2462,6 +2652,18 @@ int dvo_knn_stream_set_detect_group(dvo_knn_stream* s, int group) {
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // the old scratch may be in use
     s->grp = SiftGroupDev{};
     return group ? sift_group_alloc(ctx, s->cfg.width, s->cfg.height, group, s->grp) : DVO_OK;
+}
+
+int dvo_knn_stream_set_surf_group(dvo_knn_stream* s, int group) {
+    if (!s) return DVO_EINVAL;
+    dvo_ctx* ctx = s->ctx;
+    if (s->cfg.detector != DVO_DETECT_SURF) return fail(ctx, DVO_EINVAL, "the group SURF detector needs a SURF stream");
+    if (group < 0 || group > kSurfGroupMax) return fail(ctx, DVO_EINVAL, "group out of range (0..64)");
+    if (group == s->sgrp.group) return DVO_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // the old scratch may be in use
+    s->sgrp = SurfGroupDev{};
+    return group ? surf_group_alloc(ctx, s->cfg.width, s->cfg.height, group, s->sgrp) : DVO_OK;
 }
 
 int dvo_knn_stream_set_profiling(dvo_knn_stream* s, int enable) {

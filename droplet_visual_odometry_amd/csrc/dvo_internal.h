@@ -282,12 +282,8 @@ struct SurfHaar {  // resizeHaarPattern output: 4 corner offsets + weight (host-
     int p0, p1, p2, p3;
     float w;
 };
-struct SurfArgs {
-    const uint8_t* img;     // device copy of the image (pitch)
-    int w, h, pitch;
-    int32_t* sum;           // integral image, (h + 1) x (w + 1)
-    float* det;             // per layer: rows x cols of the layer's octave
-    float* trace;
+struct SurfLayout {         // what depends on the image size only (and the call's threshold)
+    int w, h, pitch;        // pitch: row pitch of img
     int64_t off[kSurfTot];  // element offset of each layer in det / trace
     int size[kSurfTot];     // (9 + 6 layer) << octave
     int rows[kSurfOct], cols[kSurfOct];
@@ -295,18 +291,42 @@ struct SurfArgs {
     const int8_t* apt;      // 113 x (i, j): the orientation disc, apt[n] = Point(i, j)
     const float* aptw;      // 113 weights gori[i + 6] * gori[j + 6]
     float thr;              // hessianThreshold
+    int kp_cap;
+    int nori;               // samples in the orientation disc (113)
+    float gdesc[20];        // getGaussianKernel(20, 3.3)
+};
+struct SurfBufs {           // one frame's image, scratch and lists
+    const uint8_t* img;     // the image on the device (rows SurfLayout::pitch apart)
+    int32_t* sum;           // integral image, (h + 1) x (w + 1)
+    float* det;             // per layer: rows x cols of the layer's octave
+    float* trace;
     dvo_keypoint* raw;      // extrema after interpolation (unsorted)
     int* nraw;
-    int kp_cap;
     int32_t* order;         // sort scratch, next power of two >= kp_cap
     dvo_keypoint* kps;      // sorted (KeypointGreater), then oriented; size -1 = dropped
     float* dtmp;            // kp_cap x 64, descriptors in sorted order
     dvo_keypoint* out;      // compacted keypoints
     float* desc;            // compacted descriptors
     int* nout;
-    int* flags;             // 2: keypoint overflow
-    int nori;               // samples in the orientation disc (113)
-    float gdesc[20];        // getGaussianKernel(20, 3.3)
+    int* flags;             // 2: keypoint overflow, 4: a descriptor window above 768
+};
+struct SurfArgs : SurfBufs, SurfLayout {};
+
+// The same for a group of frames of one size (launch_surf_group): b is frame 0's scratch, frame f's
+// is b's pointers advanced by f strides (in elements; raw and kps by kp_cap, dtmp by kp_cap * 64,
+// the counters nraw / nout / flags by 4) and b.img the first frame of the chunk, frame f's image
+// frame_stride bytes further per frame.  b.out and b.desc are unused: the kept keypoints and
+// descriptors go to the caller's slots, frame f's at out_kps + f * feat_cap and out_desc +
+// f * feat_cap * 64 (entries below feat_cap only), its (count, flags) to out_n + 2 f.
+struct SurfGroupArgs {
+    SurfLayout l;
+    SurfBufs b;
+    int64_t frame_stride, sum_stride, cell_stride, order_stride;  // cell_stride: det and trace
+    dvo_keypoint* out_kps;
+    float* out_desc;
+    int32_t* out_n;
+    int feat_cap;
+    int large_first;  // describe serves the chunk's large windows (octaves 2 and 3) first, from per-frame queues
 };
 
 // ---- host entry points of the kernels (implemented in the .hip files) -------
@@ -430,6 +450,9 @@ hipError_t launch_sift_group(const SiftGroupArgs& G, int frames, const uint8_t* 
                              int h, int stride, const float* d_taps, const int* tap_off, const int* tap_n,
                              hipStream_t s);
 hipError_t launch_surf(const SurfArgs& a, hipStream_t s);
+// The same stages for `frames` frames (<= the frames G's scratch holds), one launch per stage with
+// the frame as a grid dimension.  The caller has cleared the frames' counters, det and trace.
+hipError_t launch_surf_group(const SurfGroupArgs& G, int frames, hipStream_t s);
 hipError_t launch_match_pair(const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int cross_check, void* d_work,
                              dvo_dmatch* d_out, int* d_m, hipStream_t s);
 // FLANN randomized kd-tree k-NN (flann.hip; the 'flann' mode's FlannBasedMatcher).

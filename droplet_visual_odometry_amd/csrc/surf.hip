@@ -21,6 +21,13 @@
 //                         the rows combined per output row in ytab order; then
 //                         the 4x4x4 sums
 //   compact_kernel        drop the keypoints marked size -1, in order
+//
+// For a group of frames of one size (launch_surf_group) every stage is one launch
+// with the frame as a grid dimension (*_group_kernel): the stage bodies below are
+// shared by both, a group kernel only picks its frame's buffers (frame_bufs) and
+// loops.  The group's compact stage writes straight into the caller's per-frame
+// slots with the (count, flags) pair, so that path has no copy launch.
+#include <algorithm>
 #include <cfloat>
 
 #include "dvo_internal.h"
@@ -77,16 +84,35 @@ __device__ __forceinline__ void resize_haar(const int (&src)[2][5], SurfHaar* ds
     }
 }
 
+// Frame f's buffers in a group's scratch; out / desc are the caller's slots of feat_cap features.
+__device__ __forceinline__ SurfBufs frame_bufs(const SurfGroupArgs& G, int f) {
+    const int64_t F = f;
+    SurfBufs b = G.b;
+    b.img += F * G.frame_stride;
+    b.sum += F * G.sum_stride;
+    b.det += F * G.cell_stride;
+    b.trace += F * G.cell_stride;
+    b.raw += F * G.l.kp_cap;
+    b.order += F * G.order_stride;
+    b.kps += F * G.l.kp_cap;
+    b.dtmp += F * G.l.kp_cap * 64;
+    b.nraw += F * 4;
+    b.nout += F * 4;
+    b.flags += F * 4;
+    b.out = G.out_kps + F * G.feat_cap;
+    b.desc = G.out_desc + F * G.feat_cap * 64;
+    return b;
+}
+
 // ---- integral image -------------------------------------------------------------
-__global__ __launch_bounds__(256) void row_scan_kernel(SurfArgs a) {
-    const int y = blockIdx.x;
-    if (y >= a.h) return;
-    const int sw = a.w + 1, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+__device__ __forceinline__ void row_scan_body(const SurfLayout& L, const SurfBufs& B, int y) {
+    if (y >= L.h) return;
+    const int sw = L.w + 1, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     __shared__ int s_w[4];
     int carry = 0;
-    for (int x0 = 0; x0 < a.w; x0 += 256) {
+    for (int x0 = 0; x0 < L.w; x0 += 256) {
         const int x = x0 + threadIdx.x;
-        const int v = x < a.w ? a.img[(size_t)y * a.pitch + x] : 0;
+        const int v = x < L.w ? B.img[(size_t)y * L.pitch + x] : 0;
         int incl = v;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -101,69 +127,94 @@ __global__ __launch_bounds__(256) void row_scan_kernel(SurfArgs a) {
             before += k < wid ? s_w[k] : 0;
             tot += s_w[k];
         }
-        if (x < a.w) a.sum[(size_t)(y + 1) * sw + x + 1] = carry + before + incl;
+        if (x < L.w) B.sum[(size_t)(y + 1) * sw + x + 1] = carry + before + incl;
         carry += tot;
         __syncthreads();
     }
-    if (threadIdx.x == 0) a.sum[(size_t)(y + 1) * sw] = 0;
+    if (threadIdx.x == 0) B.sum[(size_t)(y + 1) * sw] = 0;
 }
 
-__global__ __launch_bounds__(256) void col_scan_kernel(SurfArgs a) {
-    const int x = blockIdx.x * 256 + threadIdx.x;
-    const int sw = a.w + 1;
-    if (x > a.w) return;
-    a.sum[x] = 0;
+__global__ __launch_bounds__(256) void row_scan_kernel(SurfArgs a) { row_scan_body(a, a, blockIdx.x); }
+
+__global__ __launch_bounds__(256) void row_scan_group_kernel(SurfGroupArgs G) {
+    row_scan_body(G.l, frame_bufs(G, blockIdx.y), blockIdx.x);
+}
+
+__device__ __forceinline__ void col_scan_body(const SurfLayout& L, const SurfBufs& B, int x) {
+    const int sw = L.w + 1;
+    if (x > L.w) return;
+    B.sum[x] = 0;
     int acc = 0, y = 1;
-    for (; y + 8 <= a.h + 1; y += 8) {  // 8 rows of loads in flight, then the sequential sums
+    for (; y + 8 <= L.h + 1; y += 8) {  // 8 rows of loads in flight, then the sequential sums
         int v[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = a.sum[(size_t)(y + k) * sw + x];
+        for (int k = 0; k < 8; ++k) v[k] = B.sum[(size_t)(y + k) * sw + x];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             acc += v[k];
-            a.sum[(size_t)(y + k) * sw + x] = acc;
+            B.sum[(size_t)(y + k) * sw + x] = acc;
         }
     }
-    for (; y <= a.h; ++y) {
-        acc += a.sum[(size_t)y * sw + x];
-        a.sum[(size_t)y * sw + x] = acc;
+    for (; y <= L.h; ++y) {
+        acc += B.sum[(size_t)y * sw + x];
+        B.sum[(size_t)y * sw + x] = acc;
     }
+}
+
+__global__ __launch_bounds__(256) void col_scan_kernel(SurfArgs a) { col_scan_body(a, a, blockIdx.x * 256 + threadIdx.x); }
+
+__global__ __launch_bounds__(256) void col_scan_group_kernel(SurfGroupArgs G) {
+    col_scan_body(G.l, frame_bufs(G, blockIdx.y), blockIdx.x * 256 + threadIdx.x);
 }
 
 // ---- calcLayerDetAndTrace -------------------------------------------------------
-__global__ __launch_bounds__(256) void hessian_kernel(SurfArgs a) {
-    const int L = blockIdx.y, o = L / kSurfLayers;
-    const int size = a.size[L], step = 1 << o;
-    const int sw = a.w + 1, sh = a.h + 1;
+// sample t of layer ly
+__device__ __forceinline__ void hessian_body(const SurfLayout& L, const SurfBufs& B, int ly, int64_t t) {
+    const int o = ly / kSurfLayers;
+    const int size = L.size[ly], step = 1 << o;
+    const int sw = L.w + 1, sh = L.h + 1;
     if (size > sh - 1 || size > sw - 1) return;
     const int si = 1 + (sh - 1 - size) / step, sj = 1 + (sw - 1 - size) / step;
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= (int64_t)si * sj) return;
     const int i = (int)(t / sj), j = (int)(t - (int64_t)i * sj);
     const int margin = (size / 2) / step;
-    const int32_t* sp = a.sum + (size_t)(i * step) * sw + j * step;
-    const SurfHaar* H = a.haar + L * 10;
+    const int32_t* sp = B.sum + (size_t)(i * step) * sw + j * step;
+    const SurfHaar* H = L.haar + ly * 10;
     const float dx = haar(sp, H, 3), dy = haar(sp, H + 3, 3), dxy = haar(sp, H + 6, 4);
-    const int64_t off = a.off[L] + (int64_t)(i + margin) * a.cols[o] + (j + margin);
-    a.det[off] = dx * dy - 0.81f * dxy * dxy;
-    a.trace[off] = dx + dy;
+    const int64_t off = L.off[ly] + (int64_t)(i + margin) * L.cols[o] + (j + margin);
+    B.det[off] = dx * dy - 0.81f * dxy * dxy;
+    B.trace[off] = dx + dy;
+}
+
+__global__ __launch_bounds__(256) void hessian_kernel(SurfArgs a) {
+    hessian_body(a, a, blockIdx.y, (int64_t)blockIdx.x * 256 + threadIdx.x);
+}
+
+// grid (blocks, layer, frame): the layer's samples grid-strided
+__global__ __launch_bounds__(256) void hessian_group_kernel(SurfGroupArgs G) {
+    const int ly = blockIdx.y, step = 1 << (ly / kSurfLayers), size = G.l.size[ly];
+    if (size > G.l.h || size > G.l.w) return;
+    const int64_t n = (int64_t)(1 + (G.l.h - size) / step) * (1 + (G.l.w - size) / step);
+    const SurfBufs B = frame_bufs(G, blockIdx.z);
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)gridDim.x * 256)
+        hessian_body(G.l, B, ly, t);
 }
 
 // ---- findMaximaInLayer + interpolateKeypoint -------------------------------------
-__global__ __launch_bounds__(256) void extrema_kernel(SurfArgs a) {
-    const int m = blockIdx.y, o = m / 3, Li = o * kSurfLayers + m % 3 + 1;
-    const int step = 1 << o, size = a.size[Li];
-    const int rows = a.h / step, cols = a.w / step, C = a.cols[o];
-    const int margin = (a.size[Li + 1] / 2) / step + 1;
+// sample t of middle layer m (0..11)
+__device__ __forceinline__ void extrema_body(const SurfLayout& L, const SurfBufs& B, int m, int64_t t) {
+    const int o = m / 3, Li = o * kSurfLayers + m % 3 + 1;
+    const int step = 1 << o, size = L.size[Li];
+    const int rows = L.h / step, cols = L.w / step, C = L.cols[o];
+    const int margin = (L.size[Li + 1] / 2) / step + 1;
     const int ni = rows - 2 * margin, nj = cols - 2 * margin;
     if (ni <= 0 || nj <= 0) return;
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= (int64_t)ni * nj) return;
     const int i = margin + (int)(t / nj), j = margin + (int)(t % nj);
-    const float* d2 = a.det + a.off[Li];
+    const float* d2 = B.det + L.off[Li];
     const float v = d2[(int64_t)i * C + j];
-    if (!(v > a.thr)) return;
-    const float* Ls[3] = {a.det + a.off[Li - 1], d2, a.det + a.off[Li + 1]};
+    if (!(v > L.thr)) return;
+    const float* Ls[3] = {B.det + L.off[Li - 1], d2, B.det + L.off[Li + 1]};
     float N9[3][9];
 #pragma unroll
     for (int q = 0; q < 3; ++q)
@@ -179,7 +230,7 @@ __global__ __launch_bounds__(256) void extrema_kernel(SurfArgs a) {
             if (!(q == 1 && k == 4)) mx = mx && v > N9[q][k];
     if (!mx) return;
     const int sum_i = step * (i - (size / 2) / step), sum_j = step * (j - (size / 2) / step);
-    const float tr = a.trace[a.off[Li] + (int64_t)i * C + j];
+    const float tr = B.trace[L.off[Li] + (int64_t)i * C + j];
     dvo_keypoint kp;
     kp.x = sum_j + (size - 1) * 0.5f;
     kp.y = sum_i + (size - 1) * 0.5f;
@@ -189,7 +240,7 @@ __global__ __launch_bounds__(256) void extrema_kernel(SurfArgs a) {
     kp.octave = o;
     kp.class_id = (tr > 0) - (tr < 0);
     // interpolateKeypoint: Matx33f(A).solve(b, DECOMP_LU) = Matx_FastSolveOp<3, 1>
-    const int ds = size - a.size[Li - 1];
+    const int ds = size - L.size[Li - 1];
     const float b0 = -(N9[1][5] - N9[1][3]) / 2, b1 = -(N9[1][7] - N9[1][1]) / 2, b2 = -(N9[2][4] - N9[0][4]) / 2;
     const float a00 = N9[1][3] - 2 * N9[1][4] + N9[1][5];
     const float a01 = (N9[1][8] - N9[1][6] - N9[1][2] + N9[1][0]) / 4;
@@ -212,9 +263,26 @@ __global__ __launch_bounds__(256) void extrema_kernel(SurfArgs a) {
     kp.x += x0 * step;
     kp.y += x1 * step;
     kp.size = (float)cv_round_f(kp.size + x2 * ds);
-    const int slot = atomicAdd(a.nraw, 1);
-    if (slot < a.kp_cap) a.raw[slot] = kp;
-    else atomicOr(a.flags, 2);
+    const int slot = atomicAdd(B.nraw, 1);
+    if (slot < L.kp_cap) B.raw[slot] = kp;
+    else atomicOr(B.flags, 2);
+}
+
+__global__ __launch_bounds__(256) void extrema_kernel(SurfArgs a) {
+    extrema_body(a, a, blockIdx.y, (int64_t)blockIdx.x * 256 + threadIdx.x);
+}
+
+// grid (blocks, middle layer, frame): the layer's samples grid-strided.  The slots the atomicAdd
+// hands out only fill the raw list: the sort orders it whatever the arrival order.
+__global__ __launch_bounds__(256) void extrema_group_kernel(SurfGroupArgs G) {
+    const int m = blockIdx.y, o = m / 3, step = 1 << o;
+    const int margin = (G.l.size[o * kSurfLayers + m % 3 + 2] / 2) / step + 1;
+    const int ni = G.l.h / step - 2 * margin, nj = G.l.w / step - 2 * margin;
+    if (ni <= 0 || nj <= 0) return;
+    const int64_t n = (int64_t)ni * nj;
+    const SurfBufs B = frame_bufs(G, blockIdx.z);
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)gridDim.x * 256)
+        extrema_body(G.l, B, m, t);
 }
 
 // ---- std::sort(KeypointGreater) ---------------------------------------------------
@@ -230,11 +298,21 @@ __device__ __forceinline__ bool kp_greater(const dvo_keypoint& a, const dvo_keyp
     return a.x < b.x;
 }
 
-__global__ __launch_bounds__(kSortNT) void sort_kernel(SurfArgs a) {
-    const int n = min(*a.nraw, a.kp_cap);
+// A group's large-window queue (describe_group_kernel<true>): the sorted-list indices of a frame's
+// keypoints of octave >= kLargeOct, octave 3 first, kept in B.order between the sort and compact
+// (free then), their count in large_count(B); describe hands them out by large_ticket(B).  The two
+// are the frame's counters 1 and 3, which the group path does not use otherwise (compact writes
+// the caller's count, not nout) and which the chunk's clear zeroes.
+constexpr int kLargeOct = 2;
+__device__ __forceinline__ int* large_count(const SurfBufs& B) { return B.nout; }
+__device__ __forceinline__ int* large_ticket(const SurfBufs& B) { return B.nraw + 3; }
+
+// queue: build the frame's large-window queue after the sort
+__device__ __forceinline__ void sort_body(const SurfLayout& L, const SurfBufs& B, bool queue) {
+    const int n = min(*B.nraw, L.kp_cap);
     int n2 = 1;
     while (n2 < n) n2 <<= 1;
-    int32_t* idx = a.order;
+    int32_t* idx = B.order;
     for (int i = threadIdx.x; i < n2; i += kSortNT) idx[i] = i < n ? i : -1;
     __syncthreads();
     for (int k = 2; k <= n2; k <<= 1)
@@ -244,7 +322,7 @@ __global__ __launch_bounds__(kSortNT) void sort_kernel(SurfArgs a) {
                 if (ixj > i) {
                     const int p = idx[i], q = idx[ixj];
                     // q belongs before p (padding -1 sorts last)
-                    const bool q_first = p < 0 ? q >= 0 : (q >= 0 && kp_greater(a.raw[q], a.raw[p]));
+                    const bool q_first = p < 0 ? q >= 0 : (q >= 0 && kp_greater(B.raw[q], B.raw[p]));
                     if (q_first == ((i & k) == 0)) {
                         idx[i] = q;
                         idx[ixj] = p;
@@ -253,7 +331,19 @@ __global__ __launch_bounds__(kSortNT) void sort_kernel(SurfArgs a) {
             }
             __syncthreads();
         }
-    for (int i = threadIdx.x; i < n; i += kSortNT) a.kps[i] = a.raw[idx[i]];
+    for (int i = threadIdx.x; i < n; i += kSortNT) B.kps[i] = B.raw[idx[i]];
+    if (!queue) return;
+    for (int o = kSurfOct - 1; o >= kLargeOct; --o) {
+        __syncthreads();  // idx is read no more; the octave above is queued
+        for (int i = threadIdx.x; i < n; i += kSortNT)
+            if (B.kps[i].octave == o) idx[atomicAdd(large_count(B), 1)] = i;
+    }
+}
+
+__global__ __launch_bounds__(kSortNT) void sort_kernel(SurfArgs a) { sort_body(a, a, false); }
+
+__global__ __launch_bounds__(kSortNT) void sort_group_kernel(SurfGroupArgs G) {
+    sort_body(G.l, frame_bufs(G, blockIdx.x), G.large_first != 0);
 }
 
 // ---- SURFInvoker: orientation + 64-d descriptor, one wave per keypoint ------------
@@ -262,19 +352,24 @@ struct AreaCell {
     float al, af, ar;
 };
 
-__device__ __forceinline__ uint8_t win_sample(const SurfArgs& a, double px, double py) {
+__device__ __forceinline__ uint8_t win_sample(const SurfLayout& L, const SurfBufs& B, double px, double py) {
     const int ix = cv_floor_d(px), iy = cv_floor_d(py);
-    if ((unsigned)ix < (unsigned)(a.w - 1) && (unsigned)iy < (unsigned)(a.h - 1)) {
+    if ((unsigned)ix < (unsigned)(L.w - 1) && (unsigned)iy < (unsigned)(L.h - 1)) {
         const float fa = (float)(px - ix), fb = (float)(py - iy);
-        const uint8_t* q = a.img + (size_t)iy * a.pitch + ix;
-        return (uint8_t)cv_round_f(q[0] * (1.f - fa) * (1.f - fb) + q[1] * fa * (1.f - fb) + q[a.pitch] * (1.f - fa) * fb +
-                                   q[a.pitch + 1] * fa * fb);
+        const uint8_t* q = B.img + (size_t)iy * L.pitch + ix;
+        return (uint8_t)cv_round_f(q[0] * (1.f - fa) * (1.f - fb) + q[1] * fa * (1.f - fb) + q[L.pitch] * (1.f - fa) * fb +
+                                   q[L.pitch + 1] * fa * fb);
     }
-    const int x = min(max(cv_round_d(px), 0), a.w - 1), y = min(max(cv_round_d(py), 0), a.h - 1);
-    return a.img[(size_t)y * a.pitch + x];
+    const int x = min(max(cv_round_d(px), 0), L.w - 1), y = min(max(cv_round_d(py), 0), L.h - 1);
+    return B.img[(size_t)y * L.pitch + x];
 }
 
-__global__ __launch_bounds__(64) void describe_kernel(SurfArgs a) {
+// Keypoints k0, k0 + kstep, ... of frame fown's sorted list, one wave (the workgroup) each;
+// frame(f) gives a frame's buffers.  kQueue: before them, large-window keypoints of frame fq's queue
+// for as long as a ticket yields one, and the stride then skips the large ones.  Which wave
+// describes a keypoint changes nothing in what it computes.
+template <bool kQueue, class Frame>
+__device__ __forceinline__ void describe_body(const SurfLayout& L, Frame frame, int fown, int fq, int k0, int kstep) {
     __shared__ float s_X[128], s_Y[128];
     __shared__ int s_A[128];
     __shared__ float s_sx[kMaxWin], s_sy[kMaxWin];        // window row starts
@@ -289,16 +384,33 @@ __global__ __launch_bounds__(64) void describe_kernel(SurfArgs a) {
     __shared__ float s_DX[kPatch * kPatch], s_DY[kPatch * kPatch];
     __shared__ float s_vec[64];
     const int lane = threadIdx.x;
-    const int n_kp = min(*a.nraw, a.kp_cap);
-    const int sw = a.w + 1, sh = a.h + 1;
+    const int sw = L.w + 1, sh = L.h + 1;
     const int gx_s[2][5] = {{0, 0, 2, 4, -1}, {2, 0, 4, 4, 1}};
     const int gy_s[2][5] = {{0, 0, 4, 2, 1}, {0, 2, 4, 4, -1}};
-    for (int k = blockIdx.x; k < n_kp; k += gridDim.x) {
-        dvo_keypoint kp = a.kps[k];
+    bool queue = kQueue;
+    for (int ks = k0 - kstep;;) {
+        int k;
+        if (queue) {  // the queue's next keypoint, by ticket
+            int t = 0;
+            if (lane == 0) t = atomicAdd(large_ticket(frame(fq)), 1);
+            t = __shfl(t, 0);
+            if (t >= *large_count(frame(fq))) {
+                queue = false;
+                continue;
+            }
+            k = frame(fq).order[t];
+        } else {  // the next keypoint of this wave's stride
+            ks += kstep;
+            if (ks >= min(*frame(fown).nraw, L.kp_cap)) break;
+            if (kQueue && frame(fown).kps[ks].octave >= kLargeOct) continue;
+            k = ks;
+        }
+        const SurfBufs& B = frame(queue ? fq : fown);
+        dvo_keypoint kp = B.kps[k];
         const float s = kp.size * 1.2f / 9.0f;
         const int gws = 2 * cv_round_f(2 * s);
         if (sh < gws || sw < gws) {
-            if (lane == 0) a.kps[k].size = -1;
+            if (lane == 0) B.kps[k].size = -1;
             continue;
         }
         // ---- orientation: the disc's Haar responses, compacted in sample order
@@ -306,19 +418,19 @@ __global__ __launch_bounds__(64) void describe_kernel(SurfArgs a) {
         resize_haar(gx_s, gx, 4, gws, sw);
         resize_haar(gy_s, gy, 4, gws, sw);
         int nang = 0;
-        for (int t0 = 0; t0 < a.nori; t0 += 64) {
+        for (int t0 = 0; t0 < L.nori; t0 += 64) {
             const int t = t0 + lane;
             bool valid = false;
             float X = 0, Y = 0;
-            if (t < a.nori) {
-                const int x = cv_round_f(kp.x + a.apt[2 * t] * s - (float)(gws - 1) / 2);
-                const int y = cv_round_f(kp.y + a.apt[2 * t + 1] * s - (float)(gws - 1) / 2);
+            if (t < L.nori) {
+                const int x = cv_round_f(kp.x + L.apt[2 * t] * s - (float)(gws - 1) / 2);
+                const int y = cv_round_f(kp.y + L.apt[2 * t + 1] * s - (float)(gws - 1) / 2);
                 valid = !(y < 0 || y >= sh - gws || x < 0 || x >= sw - gws);
                 if (valid) {
-                    const int32_t* p = a.sum + (size_t)y * sw + x;
+                    const int32_t* p = B.sum + (size_t)y * sw + x;
                     const float vx = haar(p, gx, 2), vy = haar(p, gy, 2);
-                    X = vx * a.aptw[t];
-                    Y = vy * a.aptw[t];
+                    X = vx * L.aptw[t];
+                    Y = vy * L.aptw[t];
                 }
             }
             const unsigned long long bal = __ballot(valid);
@@ -333,7 +445,7 @@ __global__ __launch_bounds__(64) void describe_kernel(SurfArgs a) {
         }
         __syncthreads();
         if (nang == 0) {
-            if (lane == 0) a.kps[k].size = -1;
+            if (lane == 0) B.kps[k].size = -1;
             __syncthreads();
             continue;
         }
@@ -378,8 +490,8 @@ __global__ __launch_bounds__(64) void describe_kernel(SurfArgs a) {
         const int n = (int)((kPatch + 1) * s);
         if (n > kMaxWin) {
             if (lane == 0) {
-                a.kps[k].size = -1;
-                atomicOr(a.flags, 4);
+                B.kps[k].size = -1;
+                atomicOr(B.flags, 4);
             }
             __syncthreads();
             continue;
@@ -478,7 +590,7 @@ __global__ __launch_bounds__(64) void describe_kernel(SurfArgs a) {
                     uint8_t v[8];
 #pragma unroll
                     for (int q = 0; q < 8; ++q) {
-                        v[q] = x0 + q < n ? win_sample(a, px, py) : 0;
+                        v[q] = x0 + q < n ? win_sample(L, B, px, py) : 0;
                         px += cos_dir;  // the reference's per-pixel accumulation (done for the
                         py -= sin_dir;  // padding samples too: they are never read back)
                     }
@@ -534,7 +646,7 @@ __global__ __launch_bounds__(64) void describe_kernel(SurfArgs a) {
         // ---- gradients with wavelets of size 2s, Gaussian weighted; the 4x4x4 sums
         for (int c = lane; c < kPatch * kPatch; c += 64) {
             const int i = c / kPatch, j = c - i * kPatch;
-            const float dw = a.gdesc[i] * a.gdesc[j];
+            const float dw = L.gdesc[i] * L.gdesc[j];
             s_DX[c] = (s_P[i][j + 1] - s_P[i][j] + s_P[i + 1][j + 1] - s_P[i + 1][j]) * dw;
             s_DY[c] = (s_P[i + 1][j] - s_P[i][j] + s_P[i + 1][j + 1] - s_P[i][j + 1]) * dw;
         }
@@ -559,20 +671,36 @@ __global__ __launch_bounds__(64) void describe_kernel(SurfArgs a) {
         double mag = 0;
         for (int q = 0; q < 64; ++q) mag += (double)(s_vec[q] * s_vec[q]);  // every lane: the same sequence
         const float sc = (float)(1. / (sqrt(mag) + FLT_EPSILON));
-        a.dtmp[(size_t)k * 64 + lane] = s_vec[lane] * sc;
-        if (lane == 0) a.kps[k].angle = kp.angle;
+        B.dtmp[(size_t)k * 64 + lane] = s_vec[lane] * sc;
+        if (lane == 0) B.kps[k].angle = kp.angle;
         __syncthreads();
     }
 }
 
+__global__ __launch_bounds__(64) void describe_kernel(SurfArgs a) { 
+    describe_body<false>(a, [&](int) -> const SurfBufs& { return a; }, 0, 0, blockIdx.x, gridDim.x);
+}
+
+// grid (waves, frame): each wave strides over its own frame's list.  kQueue: first it serves a large-
+// window queue, workgroup i (in launch order) frame i mod frames's, so that the workgroups that
+// start first take the chunk's longest walks whichever frame they are of.
+template <bool kQueue>
+__global__ __launch_bounds__(64) void describe_group_kernel(SurfGroupArgs G) {
+    const int i = blockIdx.y * gridDim.x + blockIdx.x;
+    describe_body<kQueue>(G.l, [&](int f) { return frame_bufs(G, f); }, blockIdx.y, i % gridDim.y, blockIdx.x, gridDim.x);
+}
+
 // ---- drop the keypoints marked size -1 (in order) ----------------------------------
-__global__ __launch_bounds__(kSortNT) void compact_kernel(SurfArgs a) {
-    const int n = min(*a.nraw, a.kp_cap);
+// kSlot: B.out / B.desc are a caller's slot of out_cap features: only entries below out_cap are
+// written, and dn takes (count, flags) as feature_copy_kernel writes them, the count the true one.
+template <bool kSlot>
+__device__ __forceinline__ void compact_body(const SurfLayout& L, const SurfBufs& B, int out_cap, int32_t* dn) {
+    const int n = min(*B.nraw, L.kp_cap);
     __shared__ int s_part[kSortNT];
     const int per = (n + kSortNT - 1) / kSortNT;
     const int i0 = min(n, (int)threadIdx.x * per), i1 = min(n, i0 + per);
     int cnt = 0;
-    for (int i = i0; i < i1; ++i) cnt += a.kps[i].size > 0;
+    for (int i = i0; i < i1; ++i) cnt += B.kps[i].size > 0;
     s_part[threadIdx.x] = cnt;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -582,20 +710,38 @@ __global__ __launch_bounds__(kSortNT) void compact_kernel(SurfArgs a) {
             s_part[t] = acc;
             acc += v;
         }
-        *a.nout = acc;
+        if (kSlot) {
+            dn[0] = acc;
+            dn[1] = *B.flags;
+        } else {
+            *B.nout = acc;
+        }
     }
     __syncthreads();
     int pos = s_part[threadIdx.x];
-    for (int i = i0; i < i1; ++i) {  // destination of each kept keypoint (order: a.order, free after the sort)
-        const bool keep = a.kps[i].size > 0;
-        a.order[i] = keep ? pos : -1;
-        if (keep) a.out[pos++] = a.kps[i];
+    for (int i = i0; i < i1; ++i) {  // destination of each kept keypoint (order: B.order, free after the sort)
+        const bool keep = B.kps[i].size > 0;
+        if (kSlot) {
+            const bool put = keep && pos < out_cap;
+            B.order[i] = put ? pos : -1;
+            if (put) B.out[pos] = B.kps[i];
+            pos += keep;
+        } else {
+            B.order[i] = keep ? pos : -1;
+            if (keep) B.out[pos++] = B.kps[i];
+        }
     }
     __syncthreads();
     for (int e = threadIdx.x; e < n * 64; e += kSortNT) {  // descriptors: flat, coalesced
-        const int i = e >> 6, d = a.order[i];
-        if (d >= 0) a.desc[(size_t)d * 64 + (e & 63)] = a.dtmp[e];
+        const int i = e >> 6, d = B.order[i];
+        if (d >= 0) B.desc[(size_t)d * 64 + (e & 63)] = B.dtmp[e];
     }
+}
+
+__global__ __launch_bounds__(kSortNT) void compact_kernel(SurfArgs a) { compact_body<false>(a, a, 0, nullptr); }
+
+__global__ __launch_bounds__(kSortNT) void compact_group_kernel(SurfGroupArgs G) {
+    compact_body<true>(G.l, frame_bufs(G, blockIdx.x), G.feat_cap, G.out_n + 2 * (int64_t)blockIdx.x);
 }
 
 }  // namespace
@@ -609,6 +755,29 @@ hipError_t launch_surf(const SurfArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(sort_kernel, dim3(1), dim3(kSortNT), 0, s, a);
     hipLaunchKernelGGL(describe_kernel, dim3(4096), dim3(64), 0, s, a);
     hipLaunchKernelGGL(compact_kernel, dim3(1), dim3(kSortNT), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_surf_group(const SurfGroupArgs& G, int frames, hipStream_t s) {
+    const SurfLayout& L = G.l;
+    const unsigned F = (unsigned)frames;
+    hipLaunchKernelGGL(row_scan_group_kernel, dim3(L.h, F), dim3(256), 0, s, G);
+    hipLaunchKernelGGL(col_scan_group_kernel, dim3((L.w + 1 + 255) / 256, F), dim3(256), 0, s, G);
+    // the pixel stages: about kBlocks workgroups per launch over layers and frames, a layer's samples
+    // grid-strided; a workgroup past its layer's samples (the upper octaves) ends at once
+    constexpr int64_t kBlocks = 16384;
+    const int64_t blocks0 = ((int64_t)L.h * L.w + 255) / 256;
+    auto bx = [&](int layers) {
+        return (unsigned)std::min<int64_t>(blocks0, std::max<int64_t>(64, kBlocks / ((int64_t)layers * frames)));
+    };
+    hipLaunchKernelGGL(hessian_group_kernel, dim3(bx(kSurfTot), kSurfTot, F), dim3(256), 0, s, G);
+    hipLaunchKernelGGL(extrema_group_kernel, dim3(bx(kSurfOct * 3), kSurfOct * 3, F), dim3(256), 0, s, G);
+    hipLaunchKernelGGL(sort_group_kernel, dim3(F), dim3(kSortNT), 0, s, G);
+    // one wave per keypoint: 4096 waves a frame as launch_surf, fewer as the group fills the card
+    const unsigned waves = (unsigned)std::min(4096, std::max(128, 8192 / frames));
+    if (G.large_first) hipLaunchKernelGGL(describe_group_kernel<true>, dim3(waves, F), dim3(64), 0, s, G);
+    else hipLaunchKernelGGL(describe_group_kernel<false>, dim3(waves, F), dim3(64), 0, s, G);
+    hipLaunchKernelGGL(compact_group_kernel, dim3(F), dim3(kSortNT), 0, s, G);
     return hipGetLastError();
 }
 

@@ -7,6 +7,8 @@ mirrors its argument meaning, output layout and failure points:
   sift_detect_and_compute  cv::SIFT::detectAndCompute    visual_odometry_v3.py:100, :373
   SiftBatch            cv::SIFT::detectAndCompute of device-resident frames, a group per launch
                                                           visual_odometry_v3.py:373
+  surf_detect_and_compute  xfeatures2d::SURF::detectAndCompute  visual_odometry_v3.py:104, :373
+  SurfBatch            the same of device-resident frames, a group per launch
   bf_match             cv::BFMatcher(NORM_HAMMING).match  visual_odometry_v3.py:75, :219
   bf_knn_float         cv::BFMatcher(NORM_L1).knnMatch / .match, FLANN knnMatch
                                                           visual_odometry_v3.py:99-106, :200-215
@@ -209,6 +211,113 @@ def surf_detect_and_compute(img: np.ndarray, hessian_threshold: float = 400.0, c
             continue
         c.check(rc)
         return kps[:n.value].copy(), desc[:n.value].copy()
+
+
+class SurfBatch:
+    """SURF_create(hessian_threshold).detectAndCompute (visual_odometry_v3.py:104, :373) of
+    device-resident frames of one size, `group` frames per launch (dvo_surf_batch_detect): every
+    stage of the detector runs once over the group.  Every frame's features are bit-identical to
+    surf_detect_and_compute's, whatever the group.  The scratch (scratch_bytes: about 19 MB per
+    frame of the group at 640x480) is allocated here, none in detect.  The threshold belongs to
+    the call."""
+
+    def __init__(self, width: int, height: int, group: int, ctx=None):
+        self.h = None
+        self.ctx = _ctx(ctx)
+        h = ctypes.c_void_p()
+        self.ctx.check(self.ctx.lib.dvo_surf_batch_create(self.ctx.h, int(width), int(height), int(group),
+                                                          ctypes.byref(h)))
+        self.h = h
+        self.width, self.height, self.group = int(width), int(height), int(group)
+        self.list_cap = max(4096, self.width * self.height // 64)  # the detector's keypoint list
+        self._ext = None
+
+    @staticmethod
+    def scratch_bytes(width: int, height: int, group: int) -> int:
+        """dvo_surf_batch_bytes: the device bytes a SurfBatch of this size and group allocates
+        (host arithmetic only; raises ValueError for arguments the constructor would reject)."""
+        b = int(load_library().dvo_surf_batch_bytes(int(width), int(height), int(group)))
+        if b < 0:
+            raise ValueError("sides must be 1..4095 and group 1..64")
+        return b
+
+    def detect_device(self, frames, feat_cap: int, hessian_threshold: float = 400.0, out=None):
+        """The device form: frames uint8 [n, H, W] on the device (rows contiguous, any row pitch and
+        frame stride) or a numpy array, which is uploaded.  Returns device tensors (keypoints uint8
+        [n, feat_cap, 28] (KEYPOINT_DTYPE records), descriptors float32 [n, feat_cap, 64], counts
+        int32 [n, 2]): frame f holds min(counts[f, 0], feat_cap) features, counts[f, 0] is the
+        detector's count and counts[f, 1] its flags (2: list overflow, 4: a window above 768).
+        Entries past a frame's count are not written.  out: contiguous tensors of at least those
+        sizes to write into.  Nothing is read back; the work is ordered after torch's current
+        stream, and torch's current stream after it."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        if isinstance(frames, np.ndarray):
+            if frames.dtype != np.uint8 or frames.ndim != 3:
+                raise ValueError("frames must be uint8 [n, H, W]")
+            frames = torch.from_numpy(np.ascontiguousarray(frames)).to(dev)
+        if frames.dtype != torch.uint8 or frames.dim() != 3 or not frames.is_cuda:
+            raise ValueError("frames must be a uint8 [n, H, W] device tensor or numpy array")
+        n, h, w = frames.shape
+        if (h, w) != (self.height, self.width):
+            raise ValueError(f"frame size {w}x{h} != detector {self.width}x{self.height}")
+        if n and (frames.stride(2) != 1 or frames.stride(1) < w):
+            raise ValueError("frames rows must be contiguous")
+        cap = int(feat_cap)
+        if out is None:
+            slots = max(cap, 0)  # a bad feat_cap is the library's to reject
+            out = (torch.empty((n, slots, KEYPOINT_DTYPE.itemsize), dtype=torch.uint8, device=dev),
+                   torch.empty((n, slots, 64), dtype=torch.float32, device=dev),
+                   torch.empty((n, 2), dtype=torch.int32, device=dev))
+        kps, desc, counts = out
+        for t, dt, need in ((kps, torch.uint8, n * cap * KEYPOINT_DTYPE.itemsize), (desc, torch.float32, n * cap * 64),
+                            (counts, torch.int32, n * 2)):
+            if t.dtype != dt or not t.is_cuda or not t.is_contiguous() or t.numel() < need:
+                raise ValueError("out must hold contiguous device tensors: uint8 keypoints, float32 descriptors, "
+                                 "int32 counts of at least n * feat_cap entries")
+        if self._ext is None:
+            self._ext = torch.cuda.ExternalStream(self.ctx.lib.dvo_surf_batch_hip_stream(self.h) or 0, device=dev)
+        cur = torch.cuda.current_stream(dev)
+        ev = torch.cuda.Event()
+        ev.record(cur)
+        self._ext.wait_event(ev)
+        self.ctx.check(self.ctx.lib.dvo_surf_batch_detect(self.h, frames.data_ptr() if n else None, n, frames.stride(0),
+                                                          frames.stride(1), float(hessian_threshold), cap,
+                                                          kps.data_ptr(), desc.data_ptr(), counts.data_ptr()))
+        cur.wait_stream(self._ext)
+        return kps, desc, counts
+
+    def detect(self, frames, hessian_threshold: float = 400.0, feat_cap: int | None = None):
+        """A list of (keypoints KEYPOINT_DTYPE[N], descriptors float32[N, 64]), one per frame.
+        feat_cap: features kept per frame; a frame with more raises DVOError(DVO_ECAP), as
+        KnnFrameStream.features does.  None: 8192, grown to the largest count if a frame has more."""
+        cap = min(8192 if feat_cap is None else int(feat_cap), self.list_cap)
+        while True:
+            kps, desc, counts = self.detect_device(frames, cap, hessian_threshold)
+            c = counts.cpu().numpy()
+            if c[:, 1].any():
+                raise DVOError(DVO_ECAP, "SURF: more keypoints than the device lists hold")
+            if c[:, 0].max() <= cap:
+                break
+            if feat_cap is not None:
+                raise DVOError(DVO_ECAP, "a frame has more features than feat_cap")
+            cap = int(c[:, 0].max())
+        res = []
+        for f, n in enumerate(c[:, 0].tolist()):
+            k = kps[f, :n].cpu().numpy().reshape(-1).view(KEYPOINT_DTYPE).copy()
+            res.append((k, desc[f, :n].cpu().numpy().copy()))
+        return res
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.dvo_surf_batch_destroy(self.h)  # synchronises the stream first
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def bf_match(dq: np.ndarray, dt: np.ndarray, cross_check: int = 1, ctx=None) -> np.ndarray:

@@ -468,12 +468,16 @@ class KnnFrameStream:
 
     detect_group (SIFT only): 0 detects frame by frame; G >= 1 detects G frames per launch
     (dvo_knn_stream_set_detect_group, the detector of ops.SiftBatch) straight into the frame slots,
-    for ops.SiftBatch.scratch_bytes(width, height, G) more device memory.  Same records either way."""
+    for ops.SiftBatch.scratch_bytes(width, height, G) more device memory.  Same records either way.
+
+    surf_group (SURF only): the same for detector="surf" (dvo_knn_stream_set_surf_group, the detector
+    of ops.SurfBatch with the stream's hessian_threshold), for ops.SurfBatch.scratch_bytes(width,
+    height, G) more device memory.  Same records either way."""
 
     def __init__(self, width: int, height: int, K, max_frames: int, detector="sift", feat_cap: int | None = None,
                  hessian_threshold: float = 400.0, ratio: float = 0.75, prob: float = 0.999, threshold: float = 1.0,
                  max_iters: int = 1000, dist_thresh: float = 50.0, ctx: Context | None = None, *,
-                 detect_group: int = 0):
+                 detect_group: int = 0, surf_group: int = 0):
         from ._native import KnnStreamConfig
         from .ops import KNN_DETECTORS
         self.h = None
@@ -495,6 +499,9 @@ class KnnFrameStream:
         self.detect_group = 0
         if detect_group:
             self.set_detect_group(detect_group)
+        self.surf_group = 0
+        if surf_group:
+            self.set_surf_group(surf_group)
         self._ext = torch.cuda.ExternalStream(self.hip_stream, device=self.device)
         self._held = collections.deque()  # (event, tensors) in flight on the library's stream
         self.width, self.height, self.max_frames = int(width), int(height), int(max_frames)
@@ -513,6 +520,12 @@ class KnnFrameStream:
         for the stream and allocates or frees the group's scratch; DVOError(DVO_EINVAL) on a SURF stream."""
         self.ctx.check(self.ctx.lib.dvo_knn_stream_set_detect_group(self.h, int(group)))
         self.detect_group = int(group)
+
+    def set_surf_group(self, group: int):
+        """SURF frames per detection launch from the next process() on (0: frame by frame).  Waits
+        for the stream and allocates or frees the group's scratch; DVOError(DVO_EINVAL) on a SIFT stream."""
+        self.ctx.check(self.ctx.lib.dvo_knn_stream_set_surf_group(self.h, int(group)))
+        self.surf_group = int(group)
 
     def process(self, frames, records: torch.Tensor | None = None, wait_torch: bool = True) -> torch.Tensor:
         """Enqueue the batch (asynchronous).  frames: a uint8 [n, H, W] device tensor (rows contiguous,

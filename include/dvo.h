@@ -184,6 +184,51 @@ void* dvo_sift_batch_hip_stream(dvo_sift_batch* b);
 int dvo_surf_detect_and_compute(dvo_ctx* ctx, const uint8_t* img, int w, int h, int stride, double hessian_threshold,
                                 dvo_keypoint* kps, float* desc, int cap, int* n_out);
 
+/* The same SURF_create(hessianThreshold).detectAndCompute (visual_odometry_v3.py:104, :373) for
+ * DEVICE-resident frames of one size, a group of frames per launch: every stage of the detector
+ * (the integral image's row and column scan, the Hessian layers, the extrema, the sort, the
+ * descriptors, the compaction) is one launch over `group` frames, the frame a grid dimension.
+ * Keypoints and descriptors of every frame are bit-identical to dvo_surf_detect_and_compute's
+ * whatever the group.
+ *
+ * dvo_surf_batch_create allocates the whole scratch (after synchronising the context's stream);
+ * a detect call allocates nothing.  Bytes, which dvo_surf_batch_bytes returns (host only: no
+ * context, no device; DVO_EINVAL for arguments create would reject), with
+ * cells = 5 * sum over o < 4 of (h >> o) * (w >> o), kp_cap = max(4096, w * h / 64) and n2 the
+ * power of two >= kp_cap:
+ *   group * (4 * (w + 1) * (h + 1)        integral image
+ *            + 8 * cells                  det and trace of the 20 layers (floats), adjacent
+ *            + 2 * 28 * kp_cap            raw and sorted keypoint lists
+ *            + 256 * kp_cap               descriptors in sorted order
+ *            + 4 * n2                     sort scratch
+ *            + 16)                        the frame's counters
+ *   + 4000 + 226 + 452                    one set of tables: 200 Haar boxes of 20 bytes, the 113
+ *                                         orientation samples (2 bytes each) and their weights
+ * which is 19.1 MB per frame of the group at 640 x 480 and 57.2 MB at 1280 x 720.
+ *
+ * dvo_surf_batch_detect: n_frames >= 1 mono8 frames on the device, frame f at d_frames +
+ * f * frame_stride, rows `stride` >= w bytes apart, read in place.  hessian_threshold belongs to
+ * the call, not to the handle.  Asynchronous on the context's stream, nothing is read back; more
+ * frames than `group` run in chunks of `group` on that stream, and the results do not depend on
+ * the group.  Frame f's keypoints go to d_kps + f * feat_cap (KeypointGreater order), its
+ * descriptors to d_desc + f * feat_cap * 64, entries below feat_cap only; d_counts[2 f] is the
+ * detector's count even where it exceeds feat_cap and d_counts[2 f + 1] the detector's flags
+ * (2: more than kp_cap extrema, 4: a descriptor window above 768 pixels; a frame is complete
+ * when the flags are 0 and the count <= feat_cap).
+ *
+ * DVO_EINVAL, before any allocation: a side outside 1..4095, group outside 1..64; detect:
+ * n_frames < 1, stride < w, feat_cap outside 1..kp_cap, hessian_threshold not >= 0, a null
+ * buffer or handle. */
+typedef struct dvo_surf_batch dvo_surf_batch;
+int64_t dvo_surf_batch_bytes(int w, int h, int group);
+int dvo_surf_batch_create(dvo_ctx* ctx, int w, int h, int group, dvo_surf_batch** out);
+void dvo_surf_batch_destroy(dvo_surf_batch* b);
+int dvo_surf_batch_detect(dvo_surf_batch* b, const uint8_t* d_frames, int n_frames, int64_t frame_stride, int stride,
+                          double hessian_threshold, int feat_cap, dvo_keypoint* d_kps, float* d_desc,
+                          int32_t* d_counts);
+/* The HIP stream the detect calls run on (the context's). */
+void* dvo_surf_batch_hip_stream(dvo_surf_batch* b);
+
 /* Replaces cv::findEssentialMat(points1, points2, K, RANSAC, prob, threshold,
  * maxIters) — visual_odometry_v3.py:297-300.  p1/p2: m x 2 doubles (pixel
  * coords, the float32 KeyPoint_convert output widened).  E receives 3 rows
@@ -472,6 +517,12 @@ void* dvo_knn_stream_hip_stream(dvo_knn_stream* s);
  * (or frees) the group's scratch, dvo_sift_batch_bytes(width, height, group) bytes; process
  * allocates nothing.  DVO_EINVAL: a SURF stream, group outside 0..64. */
 int dvo_knn_stream_set_detect_group(dvo_knn_stream* s, int group);
+/* The same for a SURF stream (dvo_surf_batch_detect's path, with the stream's hessian_threshold):
+ * `group` frames per launch straight into the frame slots, 0 (the default) frame by frame on the
+ * context's plan, which a grouped process call does not touch.  Same records, features and
+ * matches either way.  The setter synchronises the context's stream and allocates (or frees)
+ * dvo_surf_batch_bytes(width, height, group) bytes.  DVO_EINVAL: a SIFT stream, group outside 0..64. */
+int dvo_knn_stream_set_surf_group(dvo_knn_stream* s, int group);
 /* After the last process call (these synchronise): frame `frame`'s features, desc n x 128 (SIFT)
  * or n x 64 (SURF) floats, *n = the detector's count (DVO_ECAP if > cap or the frame is marked);
  * pair `pair`'s kept matches in ascending queryIdx, *m = count (DVO_ECAP if > cap). */
