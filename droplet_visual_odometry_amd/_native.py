@@ -169,6 +169,11 @@ _SIGNATURES = {
     "dvo_knn_stream_hip_stream": ([_vp], _vp),
     "dvo_knn_stream_set_detect_group": ([_vp, _c], _c),
     "dvo_knn_stream_set_surf_group": ([_vp, _c], _c),
+    "dvo_knn_stream_set_flann": ([_vp, _c, _c], _c),
+    "dvo_knn_stream_set_rng_state": ([_vp, ctypes.c_uint64], _c),
+    "dvo_knn_stream_get_rng_state": ([_vp, ctypes.POINTER(ctypes.c_uint64)], _c),
+    "dvo_knn_stream_flann_bytes": ([_c, _c, _c], ctypes.c_size_t),
+    "dvo_flann_rng_plan_host": ([ctypes.c_uint64, _vp, _c, _c, _c, _vp, ctypes.POINTER(ctypes.c_uint64)], _c),
     "dvo_knn_stream_get_features": ([_vp, _c, _vp, _vp, _c, _ip], _c),
     "dvo_knn_stream_get_matches": ([_vp, _c, _vp, _c, _ip], _c),
     "dvo_knn_stream_set_profiling": ([_vp, _c], _c),
@@ -221,6 +226,8 @@ _SIGNATURES = {
     "dvo_test_sampson": ([_vp, _vp, _vp, _c, ctypes.c_float, _vp, _vp], _c),
     "dvo_test_ratio_gather": ([_vp, _vp, _vp, _c, _vp, _c, _vp, _c, _d, _c, _vp, _vp, _ip, _ip], _c),
     "dvo_test_knn_batch": ([_vp, _vp, _vp, _vp, _c, _c, _c, _c, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ip], _c),
+    "dvo_test_flann_batch": ([_vp, _vp, _vp, _c, _c, _c, _c, _c, ctypes.c_uint64, _c, _vp, _vp, _vp,
+                              ctypes.POINTER(ctypes.c_uint64), _ip, _ip], _c),
     "dvo_test_ransac_subsets": ([_vp, _c, _c, _vp], _c),
     "dvo_test_ransac_replay": ([_vp, _vp, _vp, _c, _c, _d, _c, _vp], _c),
     "dvo_test_ransac_hypotheses": ([_vp, _vp, _vp, _c, _c, _vp, _d, _d, _c, _c, _vp, _vp, _vp, _vp, _vp, _vp, _ip,

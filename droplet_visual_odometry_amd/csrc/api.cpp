@@ -2461,12 +2461,22 @@ struct KnnBatch {
     }
 
     // Steps 2 to 4 of a call over `frames` slots: frame state, pack + k-NN (+ merge), ratio test and gather.
-    hipError_t match(int frames, double ratio, float* pts, int32_t* nmatch, PairHeader* hdr, hipStream_t s) const {
+    // fl (the FLANN mode's scratch): the kd-forests and their search take the k-NN's place, and
+    // the lists hold squared L2.
+    hipError_t match(int frames, double ratio, float* pts, int32_t* nmatch, PairHeader* hdr, hipStream_t s,
+                     const FlannBatchArgs* fl = nullptr, int levels = 0) const {
         hipError_t e = launch_knn_frame_state(n, frames, cap, fstate, s);
         if (e != hipSuccess || frames < 2) return e;
-        const KnnBatchArgs ka{desc, fstate, bytes, norms, rejected, cap, dim, dist, idx, pdist, pidx};
-        if ((e = launch_knn_batch(ka, frames, ranges_of(frames - 1), s)) != hipSuccess) return e;
-        const RatioBatchArgs ra{idx, dist, kps, n, fstate, cap, ratio, pts, matches, nmatch, hdr, missing};
+        if (fl) {
+            FlannBatchArgs fa = *fl;
+            fa.desc = desc, fa.fstate = fstate, fa.cap = cap, fa.dim = dim, fa.idx = idx, fa.dist = dist;
+            e = launch_flann_batch(fa, frames, levels, s);
+        } else {
+            const KnnBatchArgs ka{desc, fstate, bytes, norms, rejected, cap, dim, dist, idx, pdist, pidx};
+            e = launch_knn_batch(ka, frames, ranges_of(frames - 1), s);
+        }
+        if (e != hipSuccess) return e;
+        const RatioBatchArgs ra{idx, dist, kps, n, fstate, cap, ratio, pts, matches, nmatch, hdr, missing, fl ? 1 : 0};
         return launch_ratio_gather_batch(ra, frames - 1, s);
     }
 };
@@ -2483,6 +2493,8 @@ struct dvo_knn_stream {
     DeviceAllocs mem;  // the frame slots, the match arrays and the round-local geometry arrays
     SiftGroupDev grp;  // dvo_knn_stream_set_detect_group: grp.group > 0 detects through launch_sift_group
     SurfGroupDev sgrp;  // dvo_knn_stream_set_surf_group: sgrp.group > 0 detects through launch_surf_group
+    FlannBatchArgs fl{};  // dvo_knn_stream_set_flann: fl.trees > 0 matches through launch_flann_batch
+    DeviceAllocs fl_mem;  // its scratch and the theRNG state word
     int last_frames = 0;
     bool profiling = false, timed = false;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -2615,7 +2627,7 @@ int dvo_knn_stream_process(dvo_knn_stream* st, const uint8_t* d_frames, int n_fr
     if (ev) HIP_TRY(hipEventRecord(ev[1], s));
     const int pairs = n_frames - 1;
     const PairArrays& v = st->pairs.all;
-    HIP_TRY(b.match(n_frames, c.ratio, v.pts, v.nmatch, v.hdr, s));
+    HIP_TRY(b.match(n_frames, c.ratio, v.pts, v.nmatch, v.hdr, s, st->fl.trees > 0 ? &st->fl : nullptr));
     if (ev) HIP_TRY(hipEventRecord(ev[2], s));
     if (pairs >= 1) {
         // the stream's round schedule (not kStageOneRound): a record does not depend on the split into calls
@@ -2664,6 +2676,68 @@ int dvo_knn_stream_set_surf_group(dvo_knn_stream* s, int group) {
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // the old scratch may be in use
     s->sgrp = SurfGroupDev{};
     return group ? surf_group_alloc(ctx, s->cfg.width, s->cfg.height, group, s->sgrp) : DVO_OK;
+}
+
+int dvo_knn_stream_set_flann(dvo_knn_stream* s, int trees, int checks) {
+    if (!s) return DVO_EINVAL;
+    dvo_ctx* ctx = s->ctx;
+    if (trees < 0 || trees > 64) return fail(ctx, DVO_EINVAL, "trees out of range (0..64)");
+    if (trees > 0 && checks < 1) return fail(ctx, DVO_EINVAL, "checks must be >= 1");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // the old scratch may be in use
+    if (trees != s->fl.trees) {
+        s->fl = FlannBatchArgs{};
+        s->fl_mem.release();
+        if (trees == 0) return DVO_OK;
+        FlannBatchArgs a{};
+        hipError_t he = hipSuccess;
+        flann_batch_layout(a, s->b.F - 1, s->b.cap, trees, [&](auto*& p, size_t bytes) {
+            he = s->fl_mem.alloc(&p, bytes);
+            return he == hipSuccess;
+        });
+        if (he != hipSuccess) s->fl_mem.release();
+        HIP_TRY(he);
+        a.trees = trees;
+        s->fl = a;
+    }
+    if (trees == 0) return DVO_OK;
+    s->fl.checks = checks;
+    HIP_TRY(launch_flann_set_state(s->fl.state, 0xFFFFFFFFull, ctx->stream));  // cv::theRNG() of a fresh thread
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return DVO_OK;
+}
+
+int dvo_knn_stream_set_rng_state(dvo_knn_stream* s, uint64_t state) {
+    if (!s) return DVO_EINVAL;
+    dvo_ctx* ctx = s->ctx;
+    if (s->fl.trees == 0) return fail(ctx, DVO_EINVAL, "the stream matches with BFMatcher: no theRNG state");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(launch_flann_set_state(s->fl.state, state, ctx->stream));
+    return DVO_OK;
+}
+
+int dvo_knn_stream_get_rng_state(dvo_knn_stream* s, uint64_t* state) {
+    if (!s || !state) return DVO_EINVAL;
+    dvo_ctx* ctx = s->ctx;
+    if (s->fl.trees == 0) return fail(ctx, DVO_EINVAL, "the stream matches with BFMatcher: no theRNG state");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(state, s->fl.state, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return DVO_OK;
+}
+
+size_t dvo_knn_stream_flann_bytes(int max_frames, int feat_cap, int trees) {
+    if (max_frames < 2 || max_frames > kKnnStreamMaxFrames || feat_cap < 2 || feat_cap > (1 << 16) || trees < 1 || trees > 64)
+        return 0;
+    return flann_batch_bytes(max_frames - 1, feat_cap, trees);
+}
+
+int dvo_flann_rng_plan_host(uint64_t state, const int32_t* counts, int frames, int cap, int trees, uint64_t* starts,
+                            uint64_t* state_out) {
+    if (!counts || !state_out || frames < 1 || cap < 1 || trees < 1 || trees > 64 || (frames > 1 && !starts))
+        return DVO_EINVAL;
+    flann_rng_plan_host(state, counts, frames, cap, trees, starts, state_out);
+    return DVO_OK;
 }
 
 int dvo_knn_stream_set_profiling(dvo_knn_stream* s, int enable) {
@@ -2795,6 +2869,65 @@ int dvo_test_knn_batch(dvo_ctx* ctx, const float* desc, const dvo_keypoint* kps,
     std::memcpy(pts, hp, P * C * 16);
     std::memcpy(hdr, hh, P * sizeof(PairHeader));
     std::memcpy(missing, hs, P * 4);
+    return DVO_OK;
+}
+
+// Test hook: the batched kd-forest build and search of dvo_knn_stream_process's FLANN mode on host arrays.
+int dvo_test_flann_batch(dvo_ctx* ctx, const float* desc, const int32_t* counts, int frames, int cap, int dim, int trees,
+                         int checks, uint64_t state, int levels, int32_t* idx, float* dist, uint64_t* starts,
+                         uint64_t* state_out, int* n_global, int* depth) {
+    if (!ctx || !desc || !counts || !idx || !dist || !starts || !state_out || !n_global || !depth) return DVO_EINVAL;
+    if (frames < 2 || frames > 4096 || cap < 2 || cap > (1 << 16) || (dim != 128 && dim != 64) || trees < 1 || trees > 64 ||
+        checks < 1 || levels < 0 || levels > 1024)
+        return fail(ctx, DVO_EINVAL, "frames 2..4096, cap 2..65536, dim 64 or 128, trees 1..64, checks >= 1, levels 0..1024");
+    for (int f = 0; f < frames; ++f)
+        if (counts[f] < 0) return fail(ctx, DVO_EINVAL, "negative count");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    CallMem mem(ctx->call, s);
+    const size_t P = (size_t)frames - 1, C = (size_t)cap;
+    FlannBatchArgs a{};
+    a.desc = mem.dev<float>((size_t)frames * C * dim);
+    int32_t* d_n = mem.dev<int32_t>(2 * (size_t)frames);
+    int32_t* d_fstate = mem.dev<int32_t>(2 * (size_t)frames);
+    a.fstate = d_fstate;
+    a.cap = cap, a.dim = dim, a.trees = trees, a.checks = checks;
+    a.idx = mem.dev<int32_t>(P * C * 2);
+    a.dist = mem.dev<float>(P * C * 2);
+    flann_batch_layout(a, frames - 1, cap, trees, [&](auto*& p, size_t bytes) {
+        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(mem.dev<uint8_t>(bytes));
+        return true;
+    });
+    HIP_TRY(mem.error());
+    std::vector<int32_t> n2(2 * (size_t)frames, 0);
+    for (int f = 0; f < frames; ++f) n2[2 * (size_t)f] = counts[f];
+    uint8_t *hi, *hd, *hs, *hst, *hc;
+    auto body = [&]() -> int {
+        HIP_TRY(mem.put(const_cast<float*>(a.desc), desc, (size_t)frames * C * dim * 4));
+        HIP_TRY(mem.put(d_n, n2.data(), n2.size() * 4));
+        HIP_TRY(launch_flann_set_state(a.state, state, s));
+        HIP_TRY(launch_knn_frame_state(d_n, frames, cap, d_fstate, s));
+        HIP_TRY(launch_flann_batch(a, frames, levels, s));
+        HIP_TRY(mem.get(a.idx, P * C * 8, &hi));
+        HIP_TRY(mem.get(a.dist, P * C * 8, &hd));
+        HIP_TRY(mem.get(a.starts, P * 8, &hs));
+        HIP_TRY(mem.get(a.state, 8, &hst));
+        HIP_TRY(mem.get(a.ctl, 16, &hc));
+        HIP_TRY(hipStreamSynchronize(s));
+        return DVO_OK;
+    };
+    if (int rc = body()) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    std::memcpy(idx, hi, P * C * 8);
+    std::memcpy(dist, hd, P * C * 8);
+    std::memcpy(starts, hs, P * 8);
+    std::memcpy(state_out, hst, 8);
+    int32_t ctl[4];
+    std::memcpy(ctl, hc, 16);
+    *n_global = ctl[0];
+    *depth = ctl[1];
     return DVO_OK;
 }
 

@@ -488,6 +488,61 @@ hipError_t launch_flann_search(const FlannSearchArgs& a, hipStream_t s);
 hipError_t launch_flann_redo_list(const int32_t* d_flag, int nq, int32_t* d_list, int32_t* d_count, hipStream_t s);
 hipError_t launch_flann_search_global(const FlannSearchArgs& a, const int32_t* d_list, int count, float* d_heap_d,
                                       int32_t* d_heap_n, hipStream_t s);
+// ---- the batched kd-forest (dvo_knn_stream's FLANN mode): every pair's forest and search per launch ----
+// Pair p is frame slots p (queries) and p + 1 (trains) of `cap` rows; its forest is built iff
+// fstate gives it nq >= 1 and nt >= 2.  Nothing is read back: the theRNG state lives in *state,
+// and the launch shapes depend on cap, frames, trees and the level count only.
+constexpr int kFlannChunks = 64;    // draw chunks per tree (as flann_knn_device)
+constexpr int kFlannLevels = 24;    // divideTree level launches per tree; the tail kernel runs what is left
+constexpr int kFlannRedoPool = 64;  // workgroups of the global-heap pass, a heap of cap entries each
+struct FlannBatchArgs {
+    const float* desc;      // [F][cap][dim]
+    const int32_t* fstate;  // [F][2]
+    int cap, dim, trees, checks;
+    int32_t* idx;           // [P][cap][2]
+    float* dist;            // [P][cap][2] squared L2
+    uint64_t* state;        // [1] theRNG state: read, and advanced past the built forests, by every launch
+    int32_t* ctl;           // [4] {queries sent to the global-heap pass, deepest level + 1, 0, 0} of the last launch
+    uint64_t* starts;       // [P] the state pair p's forest starts from
+    uint64_t* cs;           // [P][trees][kFlannChunks] chunk start states
+    uint32_t* R;            // [P][2 cap] the current tree's draws
+    int* bcnt;              // [P][cap] shuffle buckets: count, fill, list, and offsets [P][cap + 1]
+    int* bfill;
+    int* blist;
+    int* boff;
+    int* ind;               // [P][cap] the point order, ping-pong between trees
+    int* ind2;
+    float* xv;              // [P][cap]
+    int* sl;                // [P][cap]
+    int* sr;                // [P][cap]
+    int4* nodes;            // [P][trees][2 cap] (tree t of a pair at t (2 nt - 1))
+    int4* open;             // [P][2][cap] open nodes, even / odd levels
+    int* lev;               // [P][cap + 2] open nodes per level
+    uint32_t* redo;         // [P cap] pair * cap + query of the queries whose heap outgrew LDS
+    float* gheap_d;         // [kFlannRedoPool][cap]
+    int32_t* gheap_n;
+};
+// The scratch arrays of P pairs (everything but desc, fstate, idx, dist): take(pointer, bytes)
+// per array, false from take stops the walk.  flann_batch_bytes sums the same sizes.
+template <class Take>
+bool flann_batch_layout(FlannBatchArgs& a, int P_, int cap, int trees, Take&& take) {
+    const size_t P = (size_t)P_, C = (size_t)cap, T = (size_t)trees;
+    return take(a.state, 8) && take(a.ctl, 16) && take(a.starts, P * 8) && take(a.cs, P * T * kFlannChunks * 8) &&
+           take(a.R, P * C * 8) && take(a.bcnt, P * C * 4) && take(a.bfill, P * C * 4) && take(a.blist, P * C * 4) &&
+           take(a.boff, P * (C + 1) * 4) && take(a.ind, P * C * 4) && take(a.ind2, P * C * 4) && take(a.xv, P * C * 4) &&
+           take(a.sl, P * C * 4) && take(a.sr, P * C * 4) && take(a.nodes, P * T * C * 32) && take(a.open, P * C * 32) &&
+           take(a.lev, P * (C + 2) * 4) && take(a.redo, P * C * 4) && take(a.gheap_d, kFlannRedoPool * C * 4) &&
+           take(a.gheap_n, kFlannRedoPool * C * 4);
+}
+size_t flann_batch_bytes(int pairs, int cap, int trees);
+// RNG plan, then per tree draws / shuffle / root / `levels` level launches / tail, then the search
+// and the global-heap pass of frames - 1 pairs: 3 + trees (levels + 8) launches.
+hipError_t launch_flann_batch(const FlannBatchArgs& a, int frames, int levels, hipStream_t s);
+hipError_t launch_flann_set_state(uint64_t* d_state, uint64_t value, hipStream_t s);
+// The RNG plan's arithmetic on the host (the kernel's __host__ __device__ text): counts are
+// detector counts (one above cap marks the frame), starts[frames - 1], *state_out after the call.
+void flann_rng_plan_host(uint64_t state, const int32_t* counts, int frames, int cap, int trees, uint64_t* starts,
+                         uint64_t* state_out);
 // The k-NN modes' ratio test, ordered compaction and keypoint gather (ratio.hip): query q of the
 // matcher's k = 2 output is kept when (double)d0 < ratio * (double)d1, d the float32 values
 // DMatch.distance holds (squared: sqrtf of FLANN's squared L2).  Kept matches in ascending q.
@@ -545,6 +600,7 @@ struct RatioBatchArgs {
     int32_t* nmatch;          // [P]
     PairHeader* hdr;          // [P] {detector counts, marked(prev) | marked(cur), 0}
     int32_t* missing;         // [P]
+    int squared = 0;          // 1: dist holds FLANN's squared L2 (RatioArgs::squared)
 };
 hipError_t launch_ratio_gather_batch(const RatioBatchArgs& a, int pairs, hipStream_t s);
 // The records of pairs the reference raises on before findEssentialMat (no query, fewer than 2

@@ -31,10 +31,17 @@
 //              added in order; a KNNUniqueResultSet of (distance, index).
 //              A query whose heap outgrows LDS is flagged and redone with its
 //              heap in global memory (the heap holds up to n entries).
+//
+// Every step is a __device__ body with two kernels around it: the single-pair kernel that
+// dvo_flann_knn / dvo_knn_pair_run drive from the host, and a batch twin for dvo_knn_stream's
+// FLANN mode (the second half of this file), which takes the pair from the grid and the counts
+// from the frame slots, so the arithmetic of both paths is the same text.
+#include <algorithm>
 #include <cfloat>
 #include <climits>
 
 #include "dvo_internal.h"
+#include "mwc.h"
 
 namespace dvo {
 namespace {
@@ -44,8 +51,7 @@ constexpr int kFlNT = 256;         // build kernels
 constexpr int kFlSample = 101;     // SAMPLE_MEAN + 1
 constexpr int kFlHeapLds = 1024;   // heap entries per query wave in LDS
 
-__global__ void flann_draws_kernel(const uint64_t* chunk_state, int nchunk, int total, uint32_t* R) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void flann_draws_body(const uint64_t* chunk_state, int nchunk, int total, uint32_t* R, int c) {
     if (c >= nchunk) return;
     const int b = (int)((int64_t)total * c / nchunk), e = (int)((int64_t)total * (c + 1) / nchunk);
     uint64_t st = chunk_state[c];
@@ -55,13 +61,20 @@ __global__ void flann_draws_kernel(const uint64_t* chunk_state, int nchunk, int 
     }
 }
 
-__global__ void flann_bucket_count_kernel(const uint32_t* R, int n, int* cnt) {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+__global__ void flann_draws_kernel(const uint64_t* chunk_state, int nchunk, int total, uint32_t* R) {
+    flann_draws_body(chunk_state, nchunk, total, R, blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+__device__ __forceinline__ void flann_bucket_count_body(const uint32_t* R, int n, int* cnt, int s) {
     if (s < n) atomicAdd(&cnt[R[s] % (uint32_t)n], 1);
 }
 
-// exclusive scan of cnt[0..n) into off[0..n], one workgroup (n <= 2^16)
-__global__ __launch_bounds__(1024) void flann_bucket_scan_kernel(const int* cnt, int n, int* off, int* fill) {
+__global__ void flann_bucket_count_kernel(const uint32_t* R, int n, int* cnt) {
+    flann_bucket_count_body(R, n, cnt, blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// exclusive scan of cnt[0..n) into off[0..n], one workgroup of 1024 (n <= 2^16)
+__device__ __forceinline__ void flann_bucket_scan_body(const int* cnt, int n, int* off, int* fill) {
     __shared__ int part[1024];
     const int per = (n + 1023) / 1024, b = threadIdx.x * per, e = min(n, b + per);
     int s = 0;
@@ -83,17 +96,24 @@ __global__ __launch_bounds__(1024) void flann_bucket_scan_kernel(const int* cnt,
     if (threadIdx.x == 1023) off[n] = part[1023];
 }
 
-__global__ void flann_bucket_fill_kernel(const uint32_t* R, int n, const int* off, int* fill, int* list) {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+__global__ __launch_bounds__(1024) void flann_bucket_scan_kernel(const int* cnt, int n, int* off, int* fill) {
+    flann_bucket_scan_body(cnt, n, off, fill);
+}
+
+__device__ __forceinline__ void flann_bucket_fill_body(const uint32_t* R, int n, const int* off, int* fill, int* list,
+                                                       int s) {
     if (s >= n) return;
     const int v = (int)(R[s] % (uint32_t)n);
     list[off[v] + atomicAdd(&fill[v], 1)] = s;  // bucket order is irrelevant: the trace takes a maximum
 }
 
+__global__ void flann_bucket_fill_kernel(const uint32_t* R, int n, const int* off, int* fill, int* list) {
+    flann_bucket_fill_body(R, n, off, fill, list, blockIdx.x * blockDim.x + threadIdx.x);
+}
+
 // new_ind[p] = ind[pos], pos = the position whose value the n transpositions move into p
-__global__ void flann_shuffle_trace_kernel(const uint32_t* R, int n, const int* off, const int* list,
-                                           const int* ind, int* new_ind) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void flann_shuffle_trace_body(const uint32_t* R, int n, const int* off, const int* list,
+                                                         const int* ind, int* new_ind, int p) {
     if (p >= n) return;
     int pos = p, s = n - 1;
     while (s >= 0) {
@@ -116,6 +136,11 @@ __global__ void flann_shuffle_trace_kernel(const uint32_t* R, int n, const int* 
     new_ind[p] = ind[pos];
 }
 
+__global__ void flann_shuffle_trace_kernel(const uint32_t* R, int n, const int* off, const int* list,
+                                           const int* ind, int* new_ind) {
+    flann_shuffle_trace_body(R, n, off, list, ind, new_ind, blockIdx.x * blockDim.x + threadIdx.x);
+}
+
 struct FlannBuild {
     const float* data;
     int n, dim;
@@ -128,6 +153,9 @@ struct FlannBuild {
     int4* open[2];       // open nodes {segment start, count, node id, preorder internal index}
     int* cnt;            // [levels] open nodes per level
 };
+
+// the open list of a level (a select, not an index: B may live in registers)
+__device__ __forceinline__ int4* open_list(const FlannBuild& B, int level) { return (level & 1) ? B.open[1] : B.open[0]; }
 
 __device__ __forceinline__ int block_scan_excl(int v, int& total, int* sh) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -187,9 +215,9 @@ __device__ __forceinline__ bool var_better(float va, int ia, float vb, int ib) {
     return va > vb || (va == vb && ia < ib);
 }
 
-__global__ __launch_bounds__(kFlNT) void flann_level_kernel(FlannBuild B, int level) {
-    if ((int)blockIdx.x >= B.cnt[level]) return;
-    const int4 e = B.open[level & 1][blockIdx.x];
+// One open node e = {segment start, count, node id, preorder internal index} of `level`: one
+// workgroup of kFlNT.  Its children go to the next level's open list, or become leaves.
+__device__ __forceinline__ void flann_level_body(const FlannBuild& B, int level, const int4 e) {
     const int a = e.x, c = e.y, id = e.z, pre = e.w;
     __shared__ int s_ind[kFlSample];
     __shared__ float s_mean[256], s_var[256];
@@ -289,13 +317,18 @@ __global__ __launch_bounds__(kFlNT) void flann_level_kernel(FlannBuild B, int le
                 B.nodes[ci[h]] = make_int4(B.ind[ca[h]], 0, -1, -1);
             } else {
                 const int slot = atomicAdd(&B.cnt[level + 1], 1);
-                B.open[(level + 1) & 1][slot] = make_int4(ca[h], cc[h], ci[h], cp[h]);
+                open_list(B, level + 1)[slot] = make_int4(ca[h], cc[h], ci[h], cp[h]);
             }
         }
     }
 }
 
-__global__ void flann_root_kernel(FlannBuild B) {
+__global__ __launch_bounds__(kFlNT) void flann_level_kernel(FlannBuild B, int level) {
+    if ((int)blockIdx.x >= B.cnt[level]) return;
+    flann_level_body(B, level, open_list(B, level)[blockIdx.x]);
+}
+
+__device__ __forceinline__ void flann_root_body(const FlannBuild& B) {
     if (threadIdx.x != 0) return;
     if (B.n == 1) {
         B.nodes[0] = make_int4(B.ind[0], 0, -1, -1);
@@ -305,6 +338,8 @@ __global__ void flann_root_kernel(FlannBuild B) {
         B.cnt[0] = 1;
     }
 }
+
+__global__ void flann_root_kernel(FlannBuild B) { flann_root_body(B); }
 
 // ---- search ------------------------------------------------------------------
 struct FlannSearch {
@@ -320,17 +355,12 @@ struct FlannSearch {
     int32_t* gheap_n;
 };
 
-template <bool kGlobalHeap>
-__global__ __launch_bounds__(64) void flann_search_kernel(FlannSearch S) {
-    extern __shared__ uint32_t smem[];
-    const int qi = kGlobalHeap ? S.redo[blockIdx.x] : (int)blockIdx.x;
-    if (qi >= S.nq) return;
+// Query qi of S, one wave: `checked` holds (S.n + 31) / 32 words of LDS, hd / hn a heap of hcap
+// entries.  Writes the query's k results unless the heap outgrew hcap, which it returns.
+__device__ __forceinline__ bool flann_search_body(const FlannSearch& S, int qi, uint32_t* checked, float* hd, int* hn,
+                                                  int hcap) {
     const int lane = threadIdx.x;
     const int nwords = (S.n + 31) >> 5;
-    uint32_t* checked = smem;
-    float* hd = kGlobalHeap ? S.gheap_d + (int64_t)blockIdx.x * S.n : reinterpret_cast<float*>(smem + nwords);
-    int* hn = kGlobalHeap ? S.gheap_n + (int64_t)blockIdx.x * S.n : reinterpret_cast<int*>(smem + nwords + kFlHeapLds);
-    const int hcap = kGlobalHeap ? S.n : min(S.n, kFlHeapLds);
     for (int w = lane; w < nwords; w += 64) checked[w] = 0;
     const int ng = S.dim >> 2;  // groups of 4 (dim % 4 == 0)
     const float4 qv = lane < ng ? *reinterpret_cast<const float4*>(S.q + (int64_t)qi * S.dim + 4 * lane)
@@ -480,19 +510,242 @@ __global__ __launch_bounds__(64) void flann_search_kernel(FlannSearch S) {
         const int tr = gnode / S.nodes_per_tree;
         descend(tr, gnode - tr * S.nodes_per_tree, md);
     }
-    if (lane == 0) {
-        if (!kGlobalHeap) S.flag[qi] = overflow ? 1 : 0;
-        if (!overflow)
-            for (int j = 0; j < S.k; ++j) {
-                S.idx[(int64_t)qi * S.k + j] = j < rsize ? ri[j] : -1;
-                S.dist[(int64_t)qi * S.k + j] = j < rsize ? rd[j] : FLT_MAX;
-            }
-    }
+    if (lane == 0 && !overflow)
+        for (int j = 0; j < S.k; ++j) {
+            S.idx[(int64_t)qi * S.k + j] = j < rsize ? ri[j] : -1;
+            S.dist[(int64_t)qi * S.k + j] = j < rsize ? rd[j] : FLT_MAX;
+        }
+    return overflow;
+}
+
+template <bool kGlobalHeap>
+__global__ __launch_bounds__(64) void flann_search_kernel(FlannSearch S) {
+    extern __shared__ uint32_t smem[];
+    const int qi = kGlobalHeap ? S.redo[blockIdx.x] : (int)blockIdx.x;
+    if (qi >= S.nq) return;
+    const int nwords = (S.n + 31) >> 5;
+    float* hd = kGlobalHeap ? S.gheap_d + (int64_t)blockIdx.x * S.n : reinterpret_cast<float*>(smem + nwords);
+    int* hn = kGlobalHeap ? S.gheap_n + (int64_t)blockIdx.x * S.n : reinterpret_cast<int*>(smem + nwords + kFlHeapLds);
+    const bool overflow = flann_search_body(S, qi, smem, hd, hn, kGlobalHeap ? S.n : min(S.n, kFlHeapLds));
+    if (!kGlobalHeap && threadIdx.x == 0) S.flag[qi] = overflow ? 1 : 0;
 }
 
 __global__ void flann_redo_list_kernel(const int32_t* flag, int nq, int32_t* list, int32_t* count) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < nq && flag[i]) list[atomicAdd(count, 1)] = i;
+}
+
+
+// ---- the batch twins (dvo_knn_stream's FLANN mode) -------------------------------------------
+// The pair is a grid dimension and nq / nt come from fstate, so no count crosses to the host.  A
+// workgroup of a pair that builds nothing (nq == 0 or nt < 2: an empty or marked frame, a single
+// train) returns before its first descriptor load.  fstate counts never exceed cap
+// (knn_frame_state_kernel), which bounds every index below: rows < nt <= cap, nodes < 2 nt - 1.
+
+// the draws of a pair's forest: the theRNG state advances by them only when the forest is built
+__host__ __device__ inline uint64_t flann_pair_draws(int nq, int nt, int trees) {
+    return nq >= 1 && nt >= 2 ? (uint64_t)trees * (uint64_t)(2 * nt - 1) : 0;
+}
+
+__device__ __forceinline__ bool flann_pair(const FlannBatchArgs& a, int p, int& nq, int& nt) {
+    nq = a.fstate[2 * p];
+    nt = a.fstate[2 * p + 2];
+    return nq >= 1 && nt >= 2;
+}
+
+// tree `tree` of pair p: it shuffles the order the tree before it left (ind and ind2 take turns)
+__device__ __forceinline__ FlannBuild flann_pair_build(const FlannBatchArgs& a, int p, int nt, int tree) {
+    const size_t C = (size_t)a.cap, o = (size_t)p * C;
+    return FlannBuild{a.desc + (size_t)(p + 1) * C * a.dim, nt, a.dim, ((tree & 1) ? a.ind : a.ind2) + o, a.xv + o,
+                      a.sl + o, a.sr + o, a.R + 2 * o, a.nodes + (size_t)p * a.trees * 2 * C + (size_t)tree * (2 * nt - 1),
+                      {a.open + 2 * o, a.open + 2 * o + C}, a.lev + (size_t)p * (C + 2)};
+}
+
+__device__ __forceinline__ FlannSearch flann_pair_search(const FlannBatchArgs& a, int p, int nq, int nt) {
+    const size_t C = (size_t)a.cap, o = (size_t)p * C;
+    return FlannSearch{a.desc + o * a.dim, a.desc + (o + C) * a.dim, a.nodes + (size_t)p * a.trees * 2 * C,
+                       nq, nt, a.dim, 2, a.trees, a.checks, 2 * nt - 1, a.idx + 2 * o, a.dist + 2 * o,
+                       nullptr, nullptr, nullptr, nullptr};
+}
+
+// RNG plan, one workgroup: pair p's forest starts after the draws of the built pairs before it
+// (an exclusive scan of their draw counts, then a jump by that count), every (pair, tree, chunk)
+// start follows from the pair's, and the stream's state moves past the whole call.
+__global__ __launch_bounds__(1024) void flann_rng_plan_kernel(FlannBatchArgs a, int pairs) {
+    __shared__ uint64_t part[1024];
+    const int tid = threadIdx.x;
+    const int per = (pairs + 1023) / 1024, b = min(pairs, tid * per), e = min(pairs, b + per);
+    uint64_t sum = 0;
+    for (int p = b; p < e; ++p) sum += flann_pair_draws(a.fstate[2 * p], a.fstate[2 * p + 2], a.trees);
+    part[tid] = sum;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {  // Hillis-Steele inclusive scan of the per-thread sums
+        const uint64_t v = tid >= o ? part[tid - o] : 0;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    const uint64_t st0 = *a.state;
+    uint64_t run = part[tid] - sum;
+    for (int p = b; p < e; ++p) {
+        a.starts[p] = mwc_jump_by(st0, run);
+        run += flann_pair_draws(a.fstate[2 * p], a.fstate[2 * p + 2], a.trees);
+    }
+    __syncthreads();  // every thread has read the state, and the starts are written
+    if (tid == 0) {
+        *a.state = mwc_jump_by(st0, part[1023]);
+        a.ctl[0] = 0;
+        a.ctl[1] = 0;
+    }
+    const int per_pair = a.trees * kFlannChunks;
+    for (int64_t i = tid; i < (int64_t)pairs * per_pair; i += 1024) {
+        const int p = (int)(i / per_pair), r = (int)(i - (int64_t)p * per_pair), t = r / kFlannChunks, c = r % kFlannChunks;
+        int nq, nt;
+        if (!flann_pair(a, p, nq, nt)) continue;
+        const int draws = 2 * nt - 1;
+        a.cs[i] = mwc_jump_by(a.starts[p], (uint64_t)t * draws + (uint64_t)((int64_t)draws * c / kFlannChunks));
+    }
+}
+
+__global__ void flann_set_state_kernel(uint64_t* state, uint64_t value) { *state = value; }
+
+// before tree `tree`: empty shuffle buckets and level counts; the first tree shuffles 0..nt-1
+__global__ __launch_bounds__(256) void flann_prep_batch_kernel(FlannBatchArgs a, int tree) {
+    const int p = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    int nq, nt;
+    if (!flann_pair(a, p, nq, nt)) return;
+    const size_t C = (size_t)a.cap, o = (size_t)p * C;
+    if (i < nt) {
+        a.bcnt[o + i] = 0;
+        if (tree == 0) a.ind[o + i] = i;
+    }
+    if (i < nt + 2) a.lev[(size_t)p * (C + 2) + i] = 0;
+}
+
+__global__ __launch_bounds__(kFlannChunks) void flann_draws_batch_kernel(FlannBatchArgs a, int tree) {
+    const int p = blockIdx.y;
+    int nq, nt;
+    if (!flann_pair(a, p, nq, nt)) return;
+    flann_draws_body(a.cs + ((size_t)p * a.trees + tree) * kFlannChunks, kFlannChunks, 2 * nt - 1,
+                     a.R + 2 * (size_t)p * a.cap, threadIdx.x);
+}
+
+__global__ __launch_bounds__(256) void flann_bucket_count_batch_kernel(FlannBatchArgs a) {
+    const int p = blockIdx.y;
+    int nq, nt;
+    if (!flann_pair(a, p, nq, nt)) return;
+    const size_t o = (size_t)p * a.cap;
+    flann_bucket_count_body(a.R + 2 * o, nt, a.bcnt + o, blockIdx.x * 256 + threadIdx.x);
+}
+
+__global__ __launch_bounds__(1024) void flann_bucket_scan_batch_kernel(FlannBatchArgs a) {
+    const int p = blockIdx.x;
+    int nq, nt;
+    if (!flann_pair(a, p, nq, nt)) return;
+    const size_t o = (size_t)p * a.cap;
+    flann_bucket_scan_body(a.bcnt + o, nt, a.boff + o + p, a.bfill + o);
+}
+
+__global__ __launch_bounds__(256) void flann_bucket_fill_batch_kernel(FlannBatchArgs a) {
+    const int p = blockIdx.y;
+    int nq, nt;
+    if (!flann_pair(a, p, nq, nt)) return;
+    const size_t o = (size_t)p * a.cap;
+    flann_bucket_fill_body(a.R + 2 * o, nt, a.boff + o + p, a.bfill + o, a.blist + o, blockIdx.x * 256 + threadIdx.x);
+}
+
+__global__ __launch_bounds__(256) void flann_shuffle_trace_batch_kernel(FlannBatchArgs a, int tree) {
+    const int p = blockIdx.y;
+    int nq, nt;
+    if (!flann_pair(a, p, nq, nt)) return;
+    const size_t o = (size_t)p * a.cap;
+    flann_shuffle_trace_body(a.R + 2 * o, nt, a.boff + o + p, a.blist + o, ((tree & 1) ? a.ind2 : a.ind) + o,
+                             ((tree & 1) ? a.ind : a.ind2) + o, blockIdx.x * 256 + threadIdx.x);
+}
+
+__global__ __launch_bounds__(64) void flann_root_batch_kernel(FlannBatchArgs a, int tree) {
+    const int p = blockIdx.x;
+    int nq, nt;
+    if (!flann_pair(a, p, nq, nt)) return;
+    flann_root_body(flann_pair_build(a, p, nt, tree));
+}
+
+// Level `level` of every pair's tree: workgroup x takes open nodes x, x + gridDim.x, ... of its
+// pair (the list is complete: the launch before filled it, this one fills the other).  A tree
+// over nt points has no open node at level nt - 1 or below it (every split gives both children a point).
+__global__ __launch_bounds__(kFlNT) void flann_level_batch_kernel(FlannBatchArgs a, int tree, int level) {
+    const int p = blockIdx.y;
+    int nq, nt;
+    if (!flann_pair(a, p, nq, nt) || level >= nt - 1) return;
+    const FlannBuild B = flann_pair_build(a, p, nt, tree);
+    const int c = B.cnt[level];
+    if ((int)blockIdx.x >= c) return;
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(&a.ctl[1], level + 1);
+    for (int slot = blockIdx.x; slot < c; slot += gridDim.x) {
+        flann_level_body(B, level, open_list(B, level)[slot]);
+        __syncthreads();  // the body's LDS is rewritten by the next node
+    }
+}
+
+// The levels from level0 on, a workgroup per pair: it walks the open nodes of a level one after
+// another with the level kernel's body, then the level they opened, until a level is empty.  A
+// split leaves both children at least one point, so a node at level l holds at most nt - l
+// points and no node is open at level nt - 1: the loop ends after at most nt - 1 - level0 levels.
+__global__ __launch_bounds__(kFlNT) void flann_tail_batch_kernel(FlannBatchArgs a, int tree, int level0) {
+    const int p = blockIdx.x;
+    int nq, nt;
+    if (!flann_pair(a, p, nq, nt)) return;
+    const FlannBuild B = flann_pair_build(a, p, nt, tree);
+    for (int level = level0; level < nt - 1; ++level) {
+        // the count and the list were written by this workgroup's thread 0 (or a level launch before)
+        const int c = __hip_atomic_load(&B.cnt[level], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (c == 0) break;
+        if (threadIdx.x == 0) atomicMax(&a.ctl[1], level + 1);
+        for (int slot = 0; slot < c; ++slot) {
+            flann_level_body(B, level, open_list(B, level)[slot]);
+            __syncthreads();  // the body's LDS is rewritten by the next node; its stores are visible to the workgroup
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void flann_search_batch_kernel(FlannBatchArgs a) {
+    extern __shared__ uint32_t smem[];
+    const int p = blockIdx.y, qi = blockIdx.x;
+    int nq, nt;
+    const bool built = flann_pair(a, p, nq, nt);
+    if (qi >= nq) return;
+    if (!built) {  // a single train: no forest; the ratio test sees a query without neighbours
+        if (threadIdx.x < 2) {
+            const size_t o = ((size_t)p * a.cap + qi) * 2 + threadIdx.x;
+            a.idx[o] = -1;
+            a.dist[o] = FLT_MAX;
+        }
+        return;
+    }
+    const FlannSearch S = flann_pair_search(a, p, nq, nt);
+    const int nwords = (nt + 31) >> 5;  // this pair's words only: the launch's LDS is sized for cap
+    const bool overflow = flann_search_body(S, qi, smem, reinterpret_cast<float*>(smem + nwords),
+                                            reinterpret_cast<int*>(smem + nwords + kFlHeapLds), min(nt, kFlHeapLds));
+    if (overflow && threadIdx.x == 0) a.redo[atomicAdd(&a.ctl[0], 1)] = (uint32_t)p * (uint32_t)a.cap + (uint32_t)qi;
+}
+
+// The queries whose heap outgrew LDS, all pairs' in one list (its length is read here): a fixed
+// pool of workgroups strides over it, each with a heap of cap entries in global memory.
+__global__ __launch_bounds__(64) void flann_redo_batch_kernel(FlannBatchArgs a) {
+    extern __shared__ uint32_t smem[];
+    const int count = a.ctl[0];
+    float* hd = a.gheap_d + (size_t)blockIdx.x * a.cap;
+    int* hn = a.gheap_n + (size_t)blockIdx.x * a.cap;
+    for (int i = blockIdx.x; i < count; i += gridDim.x) {
+        const uint32_t v = a.redo[i];
+        const int p = (int)(v / (uint32_t)a.cap), qi = (int)(v % (uint32_t)a.cap);
+        int nq, nt;
+        if (!flann_pair(a, p, nq, nt) || qi >= nq) continue;
+        flann_search_body(flann_pair_search(a, p, nq, nt), qi, smem, hd, hn, nt);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
 }
 
 }  // namespace
@@ -547,6 +800,61 @@ hipError_t launch_flann_search_global(const FlannSearchArgs& a, const int32_t* d
     FlannSearch S{a.q, a.t, a.nodes, a.nq, a.n, a.dim, a.k, a.trees, a.checks, 2 * a.n - 1,
                   a.idx, a.dist, a.flag, d_list, d_heap_d, d_heap_n};
     hipLaunchKernelGGL(flann_search_kernel<true>, dim3(count), dim3(64), ((size_t)(a.n + 31) / 32) * 4, s, S);
+    return hipGetLastError();
+}
+
+size_t flann_batch_bytes(int pairs, int cap, int trees) {
+    FlannBatchArgs a{};
+    size_t total = 0;
+    flann_batch_layout(a, pairs, cap, trees, [&](auto*&, size_t bytes) {
+        total += bytes;
+        return true;
+    });
+    return total;
+}
+
+hipError_t launch_flann_set_state(uint64_t* d_state, uint64_t value, hipStream_t s) {
+    hipLaunchKernelGGL(flann_set_state_kernel, dim3(1), dim3(1), 0, s, d_state, value);
+    return hipGetLastError();
+}
+
+void flann_rng_plan_host(uint64_t state, const int32_t* counts, int frames, int cap, int trees, uint64_t* starts,
+                         uint64_t* state_out) {
+    auto brings = [&](int f) { return counts[f] > cap ? 0 : std::max(counts[f], 0); };  // knn_frame_state_kernel
+    uint64_t run = 0;
+    for (int p = 0; p + 1 < frames; ++p) {
+        starts[p] = mwc_jump_by(state, run);
+        run += flann_pair_draws(brings(p), brings(p + 1), trees);
+    }
+    *state_out = mwc_jump_by(state, run);
+}
+
+hipError_t launch_flann_batch(const FlannBatchArgs& a, int frames, int levels, hipStream_t s) {
+    const int P = frames - 1;
+    if (P < 1) return hipSuccess;
+    const int L = levels > 0 ? levels : kFlannLevels, C = a.cap;
+    const dim3 rows((C + 255) / 256, P);
+    hipLaunchKernelGGL(flann_rng_plan_kernel, dim3(1), dim3(1024), 0, s, a, P);
+    for (int t = 0; t < a.trees; ++t) {  // serial: tree t shuffles the order tree t - 1 left
+        hipLaunchKernelGGL(flann_prep_batch_kernel, dim3((C + 2 + 255) / 256, P), dim3(256), 0, s, a, t);
+        hipLaunchKernelGGL(flann_draws_batch_kernel, dim3(1, P), dim3(kFlannChunks), 0, s, a, t);
+        hipLaunchKernelGGL(flann_bucket_count_batch_kernel, rows, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(flann_bucket_scan_batch_kernel, dim3(P), dim3(1024), 0, s, a);
+        hipLaunchKernelGGL(flann_bucket_fill_batch_kernel, rows, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(flann_shuffle_trace_batch_kernel, rows, dim3(256), 0, s, a, t);
+        hipLaunchKernelGGL(flann_root_batch_kernel, dim3(P), dim3(64), 0, s, a, t);
+        // a per-pair open list: level l has at most min(2^l, nt / 2) open nodes (each holds 2 points or
+        // more); a pair gets at most `wide` workgroups, which stride over its list, so that the deep,
+        // nearly empty levels do not pay for cap / 2 workgroups per pair that return at once
+        const int wide = std::max(32, 8192 / P);
+        for (int l = 0; l < L; ++l)
+            hipLaunchKernelGGL(flann_level_batch_kernel,
+                               dim3((int)std::min<int64_t>(std::min<int64_t>(int64_t(1) << std::min(l, 20), C / 2 + 1), wide), P),
+                               dim3(kFlNT), 0, s, a, t, l);
+        hipLaunchKernelGGL(flann_tail_batch_kernel, dim3(P), dim3(kFlNT), 0, s, a, t, L);
+    }
+    hipLaunchKernelGGL(flann_search_batch_kernel, dim3(C, P), dim3(64), flann_search_lds(C), s, a);
+    hipLaunchKernelGGL(flann_redo_batch_kernel, dim3(kFlannRedoPool), dim3(64), ((size_t)(C + 31) / 32) * 4, s, a);
     return hipGetLastError();
 }
 

@@ -21,6 +21,7 @@
 // Every double expression mirrors oracle/geometry.cpp operation for operation
 // (compiled with -ffp-contract=off), so E, R and t are bit-identical to it.
 #include "dvo_internal.h"
+#include "mwc.h"
 #include "sampson.h"
 
 #include <cfloat>
@@ -1025,15 +1026,8 @@ constexpr int kSampleBuf = 1024;  // MWC states staged per refill
 // the second state of a stream on (the seed ~0 is the only state >= m it
 // meets), s_{n+k} = s_n * A^k mod m exactly.  Lane j of a refill starts from
 // s_n * A^(16 j + 1), a Montgomery product (R = 2^64) with the table below,
-// and steps 15 times; the buffer equals lane 0 running the stream sequentially.
-constexpr uint64_t kMwcA = 4164903690ull;
-constexpr uint64_t kMwcM = kMwcA * (1ull << 32) - 1;
-constexpr uint64_t mwc_mprime() {  // -m^-1 mod 2^64 (Newton)
-    uint64_t inv = kMwcM;
-    for (int i = 0; i < 6; ++i) inv *= 2 - kMwcM * inv;
-    return 0 - inv;
-}
-constexpr uint64_t kMwcMp = mwc_mprime();
+// and steps 15 times; the buffer equals lane 0 running the stream sequentially.  The constants
+// and mwc_mont are in mwc.h (flann.hip jumps the same generator).
 struct MwcJump {
     uint64_t v[64];  // A^(16 j + 1) * 2^64 mod m
 };
@@ -1049,19 +1043,6 @@ constexpr MwcJump mwc_jump() {
     return t;
 }
 __constant__ MwcJump c_mwc_jump = mwc_jump();
-static_assert(kMwcM % 2 == 1 && (uint64_t)(kMwcM * (0 - kMwcMp)) == 1, "Montgomery constants");
-
-__device__ __forceinline__ uint64_t mwc_mont(uint64_t a, uint64_t bR) {  // a * b mod m, a < m, bR = b * 2^64 mod m
-    const uint64_t lo = a * bR, hi = __umul64hi(a, bR);
-    const uint64_t u = lo * kMwcMp;
-    const uint64_t uh = __umul64hi(u, kMwcM);
-    uint64_t t = hi + uh;
-    const bool c1 = t < hi;
-    const uint64_t c = lo != 0;  // lo + u * m = 0 mod 2^64, with a carry unless lo == 0
-    const uint64_t t2 = t + c;
-    const bool c2 = t2 < t;
-    return (c1 || c2 || t2 >= kMwcM) ? t2 - kMwcM : t2;
-}
 // Launch pair p belongs to set p / F, which runs round spec.round[set] (-1: idle set, its pairs
 // get an empty range); slots past the set's batch (npairs) start with m = 0 (nothing to do).
 __global__ __launch_bounds__(64) void ransac_sample_kernel(GeomArgs g, RoundSpec spec) {

@@ -93,7 +93,7 @@ __global__ __launch_bounds__(kRatioNT) void ratio_gather_batch_kernel(RatioBatch
     const int p = blockIdx.x;
     const int nq = b.fstate[2 * p], nt = b.fstate[2 * p + 2];
     const size_t o = (size_t)p * b.cap;
-    const RatioArgs a{b.idx + o * 2, b.dist + o * 2, b.kps + o, b.kps + o + b.cap, nq, nq, nt, b.ratio, 0,
+    const RatioArgs a{b.idx + o * 2, b.dist + o * 2, b.kps + o, b.kps + o + b.cap, nq, nq, nt, b.ratio, b.squared,
                       b.pts + o * 4, b.matches + o, b.nmatch + p, b.hdr + p, b.missing + p};
     ratio_gather_pair(a, PairHeader{b.n[2 * p], b.n[2 * p + 2], b.fstate[2 * p + 1] | b.fstate[2 * p + 3], 0});
 }

@@ -15,6 +15,9 @@ mirrors its argument meaning, output layout and failure points:
   flann_knn            cv::FlannBasedMatcher(KDTREE).knnMatch  visual_odometry_v3.py:206-212
   KnnPairStream        detect + knnMatch + ratio test + E + recoverPose of one pair in the
                        knn_sift / surf / flann modes      visual_odometry_v3.py:373, :204-238, :297, :303
+  stream.KnnFrameStream  the same for a batch of device-resident frames (matcher="bf" | "flann"; the
+                       FLANN forests are built on the device: test_flann_batch, flann_rng_plan_host,
+                       knn_stream_flann_bytes below)
   find_essential_mat   cv::findEssentialMat(RANSAC)       visual_odometry_v3.py:297-300
   recover_pose         cv::recoverPose                    visual_odometry_v3.py:303-306
   triangulate_points   cv::triangulatePoints              visual_odometry_v3.py:265
@@ -1036,6 +1039,54 @@ def test_knn_batch(desc, kps, counts, ranges=0, ratio=0.75, ctx=None):
                                      ptr(out["pts"]), ptr(out["hdr"]), ptr(out["missing"]), ctypes.byref(used)))
     out["ranges_used"] = used.value
     return out
+
+
+def test_flann_batch(desc, counts, trees=5, checks=50, rng_state=None, levels=0, ctx=None):
+    """The batched kd-forest build and search of dvo_knn_stream_process's FLANN mode
+    (stream.KnnFrameStream(matcher="flann")) on host arrays: desc float32[F, cap, dim] frame slots,
+    counts int[F] (a count above cap marks the frame); pair p is frames p (queries), p + 1 (trains);
+    rng_state: the incoming theRNG state (default THE_RNG_SEED); levels: level launches per tree
+    before the tail kernel (0: the library's choice).  Returns a dict: idx int32[P, cap, 2], dist
+    float32[P, cap, 2] (squared L2; rows < nq of a built pair are written), starts uint64[P] (the
+    state each pair starts from), state (after the call), n_global (queries that took the
+    global-heap pass) and depth (the deepest tree level reached, counted from 1)."""
+    c = _ctx(ctx)
+    desc = np.ascontiguousarray(desc, np.float32)
+    counts = np.ascontiguousarray(counts, np.int32)
+    if desc.ndim != 3 or counts.shape != desc.shape[:1]:
+        raise DVOError(-1, "desc float32[F, cap, dim] and counts [F] must agree")
+    F, cap, dim = desc.shape
+    P = max(F - 1, 1)
+    out = dict(idx=np.zeros((P, cap, 2), np.int32), dist=np.zeros((P, cap, 2), np.float32), starts=np.zeros(P, np.uint64))
+    st, ng, depth = ctypes.c_uint64(), ctypes.c_int(), ctypes.c_int()
+    c.check(c.lib.dvo_test_flann_batch(c.h, ptr(desc), ptr(counts), F, cap, dim, int(trees), int(checks),
+                                       ctypes.c_uint64(THE_RNG_SEED if rng_state is None else int(rng_state)),
+                                       int(levels), ptr(out["idx"]), ptr(out["dist"]), ptr(out["starts"]),
+                                       ctypes.byref(st), ctypes.byref(ng), ctypes.byref(depth)))
+    out.update(state=int(st.value), n_global=ng.value, depth=depth.value)
+    return out
+
+
+def flann_rng_plan_host(counts, cap, trees=5, rng_state=THE_RNG_SEED):
+    """The FLANN stream's RNG plan on the host (dvo_flann_rng_plan_host, the device kernel's text; no
+    GPU needed): (starts uint64[F - 1], the state after the call) for detector counts counts[F]."""
+    from ._native import load_library
+    counts = np.ascontiguousarray(counts, np.int32)
+    starts = np.zeros(max(len(counts) - 1, 1), np.uint64)
+    st = ctypes.c_uint64()
+    rc = load_library().dvo_flann_rng_plan_host(ctypes.c_uint64(int(rng_state)), ptr(counts), len(counts), int(cap),
+                                                int(trees), ptr(starts), ctypes.byref(st))
+    if rc:
+        raise DVOError(rc, "dvo_flann_rng_plan_host: bad arguments")
+    return starts[:len(counts) - 1].copy(), int(st.value)
+
+
+def knn_stream_flann_bytes(max_frames, feat_cap, trees=5) -> int:
+    """Device bytes stream.KnnFrameStream(matcher="flann") allocates beside the BF stream's
+    (dvo_knn_stream_flann_bytes): P (84 C + 32 T C + 512 T + 20) + 512 C + 24 with P = max_frames - 1,
+    C = feat_cap, T = trees; 0 for arguments out of range."""
+    from ._native import load_library
+    return int(load_library().dvo_knn_stream_flann_bytes(int(max_frames), int(feat_cap), int(trees)))
 
 
 KNN_DETECTORS = {"sift": 0, "surf": 1}

@@ -7,7 +7,7 @@ pair, runs findEssentialMat(RANSAC) + recoverPose per pair and writes n-1
 256-byte pair records (PAIR_RECORD_DTYPE) to device memory.  Torch tensors are
 only containers for device memory; all compute is in libdvo_hip.so.
 
-KnnFrameStream is the same for the k-NN modes 'knn_sift' and 'surf' (SIFT / SURF,
+KnnFrameStream is the same for the k-NN modes 'knn_sift', 'surf' and 'flann' (SIFT / SURF,
 BFMatcher(NORM_L1).knnMatch(k=2), the ratio test): dvo_knn_stream_process.
 """
 from __future__ import annotations
@@ -472,15 +472,30 @@ class KnnFrameStream:
 
     surf_group (SURF only): the same for detector="surf" (dvo_knn_stream_set_surf_group, the detector
     of ops.SurfBatch with the stream's hessian_threshold), for ops.SurfBatch.scratch_bytes(width,
-    height, G) more device memory.  Same records either way."""
+    height, G) more device memory.  Same records either way.
+
+    matcher: "bf" (the default) or "flann", the reference's 'flann' mode (dvo_knn_stream_set_flann):
+    every pair's randomized kd-forest (trees) is built and searched (checks) on the device in place
+    of BFMatcher, with no read-back, for ops.knn_stream_flann_bytes(max_frames, feat_cap, trees)
+    more device memory.  The records are ops.KnnPairStream(matcher="flann").pair's chained through
+    its returned state: the stream keeps cv::theRNG()'s state on the device (rng_state; enabling
+    sets ops.THE_RNG_SEED, rng_state=... another start), advances it by trees (2 nt - 1) draws per
+    built pair, and carries it from call to call, so the records do not depend on the split."""
 
     def __init__(self, width: int, height: int, K, max_frames: int, detector="sift", feat_cap: int | None = None,
                  hessian_threshold: float = 400.0, ratio: float = 0.75, prob: float = 0.999, threshold: float = 1.0,
                  max_iters: int = 1000, dist_thresh: float = 50.0, ctx: Context | None = None, *,
-                 detect_group: int = 0, surf_group: int = 0):
+                 detect_group: int = 0, surf_group: int = 0, matcher: str = "bf", trees: int = 5, checks: int = 50,
+                 rng_state: int | None = None):
         from ._native import KnnStreamConfig
-        from .ops import KNN_DETECTORS
+        from .ops import KNN_DETECTORS, KNN_MATCHERS
         self.h = None
+        if matcher not in KNN_MATCHERS:
+            raise ValueError(f"matcher must be one of {sorted(KNN_MATCHERS)}")
+        if matcher == "bf" and rng_state is not None:
+            raise ValueError("rng_state needs matcher='flann'")
+        if matcher == "flann" and not (1 <= int(trees) <= 64 and int(checks) >= 1):
+            raise ValueError("matcher='flann' needs trees in 1..64 and checks >= 1")
         self.ctx = ctx if ctx is not None else Context.default()
         self.device = torch.device("cuda", self.ctx.device)
         cfg = KnnStreamConfig()
@@ -502,6 +517,11 @@ class KnnFrameStream:
         self.surf_group = 0
         if surf_group:
             self.set_surf_group(surf_group)
+        self.trees = self.checks = 0
+        if matcher == "flann":
+            self.set_flann(trees, checks)
+            if rng_state is not None:
+                self.rng_state = rng_state
         self._ext = torch.cuda.ExternalStream(self.hip_stream, device=self.device)
         self._held = collections.deque()  # (event, tensors) in flight on the library's stream
         self.width, self.height, self.max_frames = int(width), int(height), int(max_frames)
@@ -526,6 +546,29 @@ class KnnFrameStream:
         for the stream and allocates or frees the group's scratch; DVOError(DVO_EINVAL) on a SIFT stream."""
         self.ctx.check(self.ctx.lib.dvo_knn_stream_set_surf_group(self.h, int(group)))
         self.surf_group = int(group)
+
+    def set_flann(self, trees: int, checks: int = 50):
+        """The FLANN kd-forest matcher from the next process() on: trees 1..64 and checks >= 1; trees
+        0 returns to BFMatcher.  Waits for the stream, allocates or frees the mode's scratch and sets
+        rng_state to ops.THE_RNG_SEED; DVOError(DVO_EINVAL) on bad arguments."""
+        self.ctx.check(self.ctx.lib.dvo_knn_stream_set_flann(self.h, int(trees), int(checks)))
+        self.trees, self.checks = int(trees), int(checks) if trees else 0
+
+    @property
+    def matcher(self) -> str:
+        return "flann" if self.trees else "bf"
+
+    @property
+    def rng_state(self) -> int:
+        """cv::theRNG()'s state after the calls enqueued so far (waits for them); setting it is ordered
+        after them.  DVOError(DVO_EINVAL) on a stream that matches with BFMatcher."""
+        st = ctypes.c_uint64()
+        self.ctx.check(self.ctx.lib.dvo_knn_stream_get_rng_state(self.h, ctypes.byref(st)))
+        return int(st.value)
+
+    @rng_state.setter
+    def rng_state(self, state: int):
+        self.ctx.check(self.ctx.lib.dvo_knn_stream_set_rng_state(self.h, ctypes.c_uint64(int(state))))
 
     def process(self, frames, records: torch.Tensor | None = None, wait_torch: bool = True) -> torch.Tensor:
         """Enqueue the batch (asynchronous).  frames: a uint8 [n, H, W] device tensor (rows contiguous,

@@ -14,6 +14,7 @@
 #ifndef DVO_H_
 #define DVO_H_
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -457,7 +458,7 @@ int dvo_knn_pair_get_matches(dvo_knn_pair* p, dvo_dmatch* out, int cap, int* m);
 /* The last pair's features: which 0 previous, 1 current frame; desc n x 128 (SIFT) or n x 64 (SURF) floats. */
 int dvo_knn_pair_get_features(dvo_knn_pair* p, int which, dvo_keypoint* kps, float* desc, int cap, int* n);
 /* The same per-pair path for a batch of DEVICE-resident frames in modes 'knn_sift' and
- * 'surf' (BFMatcher(NORM_L1); FLANN is not batched): n_frames w x h mono8 frames, laid
+ * 'surf' (BFMatcher(NORM_L1)) and, after dvo_knn_stream_set_flann, 'flann': n_frames w x h mono8 frames, laid
  * out as for dvo_stream_process, give n_frames - 1 records on the device; pair p is
  * frames p (query, previous) and p + 1 (train, current), each frame detected once.
  * dvo_knn_stream_process is asynchronous on the context's stream (the detector's plan
@@ -523,6 +524,50 @@ int dvo_knn_stream_set_detect_group(dvo_knn_stream* s, int group);
  * matches either way.  The setter synchronises the context's stream and allocates (or frees)
  * dvo_surf_batch_bytes(width, height, group) bytes.  DVO_EINVAL: a SIFT stream, group outside 0..64. */
 int dvo_knn_stream_set_surf_group(dvo_knn_stream* s, int group);
+/* The 'flann' mode in the batch (v3:207-212: FlannBasedMatcher(KDTREE, trees = 5), checks = 50):
+ * trees 1..64 with checks >= 1 makes the process calls that follow build the randomized
+ * kd-forest of every pair's train frame and search k = 2 for every query on the device, in
+ * place of BFMatcher; trees = 0 (the default) returns to BFMatcher and frees the scratch.  It
+ * works for SIFT and SURF streams and together with the group detectors.  The setter
+ * synchronises the context's stream and allocates everything the mode needs,
+ * dvo_knn_stream_flann_bytes(max_frames, feat_cap, trees) bytes; process allocates nothing,
+ * makes no host synchronisation and no device-to-host copy, and its 3 + trees (levels + 8)
+ * forest launches (levels = 24 level launches per tree, then a tail kernel that finishes
+ * deeper trees) have shapes that depend on feat_cap, n_frames and trees only.
+ *
+ * Records are dvo_knn_pair_run's with DVO_MATCH_FLANN, chained: the stream keeps cv::theRNG()'s
+ * state in device memory; enabling sets it to a fresh thread's (0xFFFFFFFF).  Pair p's forest is
+ * built iff the pair brings nq >= 1 and nt >= 2 features; it starts from the state left by the
+ * built pairs before it, in this call and in earlier ones, and advances it by trees (2 nt - 1)
+ * draws.  A marked (DVO_ECAP) or empty frame builds nothing and advances nothing.  Every record
+ * field equals the pair path's on the same frames with the same incoming state (n_hypotheses
+ * aside), whatever the split into calls; dvo_knn_stream_get_matches gives
+ * dvo_knn_pair_get_matches's list (distances sqrtf of the squared L2).  One difference: a query
+ * without a second neighbour although nt >= 2 (it needs a non-finite distance, which no detector
+ * produces) marks the pair DVO_ENOFEAT with zeros elsewhere, where the pair path keeps the
+ * geometry's fields.
+ *
+ * Scratch in bytes (P = max_frames - 1, C = feat_cap, T = trees):
+ *   P (84 C + 32 T C + 512 T + 20) + 512 C + 24
+ * (per pair: draws 8 C, shuffle buckets and point orders 24 C + 4, split scratch 12 C, nodes
+ * 32 T C, open lists 32 C, level counts 4 C + 8, overflow list 4 C, chunk states 512 T, start
+ * state 8; per stream: 64 global heaps of C entries, the state and two counters).
+ * DVO_EINVAL: a null handle, trees outside 0..64, checks < 1 with trees > 0. */
+int dvo_knn_stream_set_flann(dvo_knn_stream* s, int trees, int checks);
+/* The FLANN mode's theRNG state: the setter is ordered on the stream (the calls before it use
+ * the old state), the getter synchronises.  DVO_EINVAL on a stream that matches with BFMatcher. */
+int dvo_knn_stream_set_rng_state(dvo_knn_stream* s, uint64_t state);
+int dvo_knn_stream_get_rng_state(dvo_knn_stream* s, uint64_t* state);
+/* Host only: the bytes dvo_knn_stream_set_flann allocates (the formula above; feat_cap is the
+ * stream's effective capacity); 0 for max_frames outside 2..65536, feat_cap outside 2..65536 or
+ * trees outside 1..64. */
+size_t dvo_knn_stream_flann_bytes(int max_frames, int feat_cap, int trees);
+/* Host only: the FLANN mode's RNG plan for `frames` frames with detector counts counts[frames]
+ * (a count above cap marks the frame): starts[frames - 1] = the state each pair's forest starts
+ * from (also of pairs that build nothing), *state_out = the state after the call.  The device
+ * kernel runs the same text. */
+int dvo_flann_rng_plan_host(uint64_t state, const int32_t* counts, int frames, int cap, int trees, uint64_t* starts,
+                            uint64_t* state_out);
 /* After the last process call (these synchronise): frame `frame`'s features, desc n x 128 (SIFT)
  * or n x 64 (SURF) floats, *n = the detector's count (DVO_ECAP if > cap or the frame is marked);
  * pair `pair`'s kept matches in ascending queryIdx, *m = count (DVO_ECAP if > cap). */
@@ -830,6 +875,16 @@ int dvo_test_ratio_gather(dvo_ctx* ctx, const int32_t* idx, const float* dist, i
 int dvo_test_knn_batch(dvo_ctx* ctx, const float* desc, const dvo_keypoint* kps, const int32_t* counts, int frames,
                        int cap, int dim, int ranges, double ratio, int32_t* idx, float* dist, int32_t* nmatch,
                        dvo_dmatch* matches, float* pts, int32_t* hdr, int32_t* missing, int* ranges_used);
+/* The batched kd-forest build and search of dvo_knn_stream_process's FLANN mode through the
+ * production launches, on host arrays: desc [frames][cap][dim], counts [frames] (a count above
+ * cap marks the frame), state = the incoming theRNG state, levels = level launches per tree
+ * before the tail kernel (0: the library's 24).  idx / dist [P][cap][2] (squared L2; the first
+ * nq rows of a pair are written, other rows hold whatever an earlier call left), starts [P] the
+ * state each pair starts from, *state_out the state after the call, *n_global the queries that
+ * took the global-heap pass, *depth the deepest tree level reached, counted from 1. */
+int dvo_test_flann_batch(dvo_ctx* ctx, const float* desc, const int32_t* counts, int frames, int cap, int dim, int trees,
+                         int checks, uint64_t state, int levels, int32_t* idx, float* dist, uint64_t* starts,
+                         uint64_t* state_out, int* n_global, int* depth);
 
 #ifdef __cplusplus
 }
