@@ -116,12 +116,18 @@ int ora_ransac_hypotheses(const double* p1, const double* p2, int m, const doubl
 // removeDuplicatedSorted leaves them; desc: n x 128 floats (integer values).
 int ora_sift_detect_and_compute(const uint8_t* img, int w, int h, int stride, ora_keypoint* kps, float* desc, int cap,
                                 int* n_out);
+// Branch census of this thread's last ora_sift_detect_and_compute: how often each branch of the
+// restatement was taken (the counters and their order: oracle.py SIFT_CENSUS).  Writes min(cap, count)
+// values, returns the count.  Counting changes no result.
+int ora_sift_census(int64_t* out, int cap);
 
 // ---- SURF_create(hessian).detectAndCompute (surf.cpp; the 'surf' mode,
 // visual_odometry_v3.py:103-106, :373): nOctaves 4, nOctaveLayers 3, 64-d.
 // kps in KeypointGreater order; desc: n x 64 floats.  -5 when cap < n.
 int ora_surf_detect_and_compute(const uint8_t* img, int w, int h, int stride, double hessian_threshold,
                                 ora_keypoint* kps, float* desc, int cap, int* n_out);
+// The same census of this thread's last ora_surf_detect_and_compute (oracle.py SURF_CENSUS).
+int ora_surf_census(int64_t* out, int cap);
 
 /* Image pre-processing (undistort.cpp): cv::getOptimalNewCameraMatrix and
  * cv::undistort (striped initUndistortRectifyMap + remap INTER_LINEAR,

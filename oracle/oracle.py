@@ -104,6 +104,8 @@ def lib():
             "ora_ransac_hypotheses": [_f64p, _f64p, _c, _f64p, _d, _c, _i32p, _i32p, _f64p, _i32p, _i32p],
             "ora_sift_detect_and_compute": [_u8p, _c, _c, _c, _kpp, _f32p, _c, _ip],
             "ora_surf_detect_and_compute": [_u8p, _c, _c, _c, ctypes.c_double, _kpp, _f32p, _c, _ip],
+            "ora_sift_census": [np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS"), _c],
+            "ora_surf_census": [np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS"), _c],
             "ora_get_optimal_new_camera_matrix": [_f64p, _f64p, _c, _c, _c, _d, _c, _c, _f64p],
             "ora_undistort": [_u8p, _c, _c, _c, _f64p, _f64p, _c, ctypes.c_void_p, _u8p, _c,
                               np.ctypeslib.ndpointer(np.int16, flags="C"), np.ctypeslib.ndpointer(np.uint16, flags="C")],
@@ -217,6 +219,37 @@ def surf_detect_and_compute(img, hessian_threshold=400.0):
             continue
         assert rc == 0, rc
         return kps[:n.value].copy(), desc[:n.value].copy()
+
+
+# The census counters, in the order of the Cen enums of sift.cpp / surf.cpp.
+SIFT_CENSUS = ("candidates", "moves_iter0", "moves_iter1", "moves_iter2", "moves_iter3", "moves_iter4",
+               "moves_across_layers", "reject_out_of_bounds", "reject_5_iterations", "reject_contrast",
+               "reject_det_le_0", "reject_edge_ratio", "reject_int_max_3", "d_eq_0", "accepted", "two_or_more_orientations",
+               "peak_bin_wrap", "snap_to_0", "orientation_window_cut", "duplicates_removed", "descriptor_radius_clamp",
+               "descriptor_samples_skipped", "o0_lt_0", "o0_ge_n", "clip_0_2", "saturate_255", "octaves",
+               "octaves_too_small")
+SURF_CENSUS = ("layers_skipped", "maxima", "d_eq_0", "reject_all_zero", "reject_abs_gt_1", "accepted", "size_changed",
+               "drop_gws", "drop_nang", "orientation_samples_outside", "window_samples_clamped", "area_scale_2",
+               "area_integer_scale", "area_fractional", "equal_response_neighbours", "class_id_0")
+
+
+def _census(fn, names):
+    out = np.zeros(len(names), np.int64)
+    n = fn(out, len(out))
+    assert n == len(names), (n, len(names))
+    return dict(zip(names, out.tolist()))
+
+
+def sift_census(img):
+    """How often the SIFT restatement takes each of its branches on img (SIFT_CENSUS -> count)."""
+    sift_detect_and_compute(img)
+    return _census(lib().ora_sift_census, SIFT_CENSUS)
+
+
+def surf_census(img, thr=400.0):
+    """How often the SURF restatement takes each of its branches on img at threshold thr (SURF_CENSUS -> count)."""
+    surf_detect_and_compute(img, thr)
+    return _census(lib().ora_surf_census, SURF_CENSUS)
 
 
 def bf_match(dq, dt, mode=1):

@@ -15,6 +15,9 @@
 //   - exp32f = its scalar table path (data/sift_exp_tab.inc);
 //   - cos/sin/pow of a float argument = double libm result rounded to float.
 // Parity against OpenCV itself is unpinned (OpenCV is absent).
+// What is pinned: first-principles anchors on Gaussian blobs (blob position, size and orientation:
+// tests/test_detector_anchors.py), and which branches the test images enter (the census below,
+// tests/test_detector_census.py).
 #include <algorithm>
 #include <cfloat>
 #include <climits>
@@ -44,6 +47,16 @@ constexpr float kInitSigma = 0.5f;        // SIFT_INIT_SIGMA
 constexpr float kDescSclFctr = 3.f;       // SIFT_DESCR_SCL_FCTR
 constexpr float kDescMagThr = 0.2f;       // SIFT_DESCR_MAG_THR
 constexpr float kIntDescFctr = 512.f;     // SIFT_INT_DESCR_FCTR
+
+// Census (ora_sift_census): how often the last ora_sift_detect_and_compute of this thread took each
+// branch.  Counting only: no counter is read by the detector.  The order is oracle.py's SIFT_CENSUS.
+enum Cen {
+    C_CANDIDATES, C_MOVE0, C_MOVE1, C_MOVE2, C_MOVE3, C_MOVE4, C_MOVE_LAYER, C_REJ_BOUNDS, C_REJ_ITERS, C_REJ_CONTRAST,
+    C_REJ_DET, C_REJ_EDGE, C_REJ_INTMAX, C_D_ZERO, C_ACCEPTED, C_MULTI_ORI, C_PEAK_WRAP, C_SNAP_ZERO, C_ORI_CUT,
+    C_DUPLICATES, C_DESC_RADIUS_CLAMP, C_DESC_BORDER_SKIP, C_O0_NEG, C_O0_GE_N, C_CLIP, C_SATURATE, C_OCTAVES,
+    C_OCTAVES_TOO_SMALL, C_COUNT
+};
+thread_local int64_t g_cen[C_COUNT];
 
 struct FImg {
     int w = 0, h = 0;
@@ -170,6 +183,7 @@ bool adjust(const std::vector<FImg>& dog, Kp& kpt, int octv, int& layer, int& r,
         const float a00 = dxx, a01 = dxy, a02 = dxs, a10 = dxy, a11 = dyy, a12 = dys, a20 = dxs, a21 = dys, a22 = dss;
         float X0 = 0, X1 = 0, X2 = 0;
         float d = (float)(double)(a00 * (a11 * a22 - a21 * a12) - a01 * (a10 * a22 - a20 * a12) + a02 * (a10 * a21 - a20 * a11));
+        if (d == 0) g_cen[C_D_ZERO]++;
         if (d != 0) {
             d = 1 / d;
             X0 = d * (dD0 * (a11 * a22 - a12 * a21) - a01 * (dD1 * a22 - a12 * dD2) + a02 * (dD1 * a21 - a11 * dD2));
@@ -180,15 +194,24 @@ bool adjust(const std::vector<FImg>& dog, Kp& kpt, int octv, int& layer, int& r,
         xr = -X1;
         xc = -X0;
         if (std::abs(xi) < 0.5f && std::abs(xr) < 0.5f && std::abs(xc) < 0.5f) break;
-        if (std::abs(xi) > (float)(INT_MAX / 3) || std::abs(xr) > (float)(INT_MAX / 3) || std::abs(xc) > (float)(INT_MAX / 3))
+        if (std::abs(xi) > (float)(INT_MAX / 3) || std::abs(xr) > (float)(INT_MAX / 3) || std::abs(xc) > (float)(INT_MAX / 3)) {
+            g_cen[C_REJ_INTMAX]++;
             return false;
+        }
+        g_cen[C_MOVE0 + i]++;
+        if (cv_round(xi) != 0) g_cen[C_MOVE_LAYER]++;
         c += cv_round(xc);
         r += cv_round(xr);
         layer += cv_round(xi);
-        if (layer < 1 || layer > kLayers || c < kBorder || c >= img.w - kBorder || r < kBorder || r >= img.h - kBorder)
+        if (layer < 1 || layer > kLayers || c < kBorder || c >= img.w - kBorder || r < kBorder || r >= img.h - kBorder) {
+            g_cen[C_REJ_BOUNDS]++;
             return false;
+        }
     }
-    if (i >= kMaxInterp) return false;
+    if (i >= kMaxInterp) {
+        g_cen[C_REJ_ITERS]++;
+        return false;
+    }
     {
         const int idx = octv * (kLayers + 2) + layer;
         const FImg &img = dog[idx], &prev = dog[idx - 1], &next = dog[idx + 1];
@@ -197,14 +220,21 @@ bool adjust(const std::vector<FImg>& dog, Kp& kpt, int octv, int& layer, int& r,
         const float dD2 = (next.at(r, c) - prev.at(r, c)) * deriv_scale;
         const float t = dD0 * xc + dD1 * xr + dD2 * xi;
         contr = img.at(r, c) * img_scale + t * 0.5f;
-        if (std::abs(contr) * kLayers < kContrast) return false;
+        if (std::abs(contr) * kLayers < kContrast) {
+            g_cen[C_REJ_CONTRAST]++;
+            return false;
+        }
         const float v2 = img.at(r, c) * 2.f;
         const float dxx = (img.at(r, c + 1) + img.at(r, c - 1) - v2) * second;
         const float dyy = (img.at(r + 1, c) + img.at(r - 1, c) - v2) * second;
         const float dxy = (img.at(r + 1, c + 1) - img.at(r + 1, c - 1) - img.at(r - 1, c + 1) + img.at(r - 1, c - 1)) * cross;
         const float tr = dxx + dyy, det = dxx * dyy - dxy * dxy;
-        if (det <= 0 || tr * tr * kEdge >= (kEdge + 1) * (kEdge + 1) * det) return false;
+        if (det <= 0 || tr * tr * kEdge >= (kEdge + 1) * (kEdge + 1) * det) {
+            g_cen[det <= 0 ? C_REJ_DET : C_REJ_EDGE]++;
+            return false;
+        }
     }
+    g_cen[C_ACCEPTED]++;
     kpt.x = (c + xc) * (float)(1 << octv);
     kpt.y = (r + xr) * (float)(1 << octv);
     kpt.octave = octv + (layer << 8) + (cv_round_d((xi + 0.5) * 255) << 16);
@@ -219,6 +249,7 @@ float orientation_hist(const FImg& img, int px, int py, int radius, float sigma,
     const float expf_scale = -1.f / (2.f * sigma * sigma);
     float temp[kOriBins + 4] = {0};
     float* th = temp + 2;
+    if (py - radius <= 0 || py + radius >= img.h - 1 || px - radius <= 0 || px + radius >= img.w - 1) g_cen[C_ORI_CUT]++;
     for (int i = -radius; i <= radius; i++) {
         const int y = py + i;
         if (y <= 0 || y >= img.h - 1) continue;
@@ -257,6 +288,7 @@ void descriptor(const FImg& img, float ptx, float pty, float ori, float scl, flo
     const float exp_scale = -1.f / (d * d * 0.5f);
     const float hist_width = kDescSclFctr * scl;
     int radius = cv_round(hist_width * 1.4142135623730951f * (d + 1) * 0.5f);
+    if (radius > (int)std::sqrt(((double)img.w) * img.w + ((double)img.h) * img.h)) g_cen[C_DESC_RADIUS_CLAMP]++;
     radius = std::min(radius, (int)std::sqrt(((double)img.w) * img.w + ((double)img.h) * img.h));
     cos_t /= hist_width;
     sin_t /= hist_width;
@@ -268,8 +300,10 @@ void descriptor(const FImg& img, float ptx, float pty, float ori, float scl, flo
             float rbin = r_rot + d / 2 - 0.5f;
             float cbin = c_rot + d / 2 - 0.5f;
             const int r = py + i, c = px + j;
-            if (!(rbin > -1 && rbin < d && cbin > -1 && cbin < d && r > 0 && r < img.h - 1 && c > 0 && c < img.w - 1))
+            if (!(rbin > -1 && rbin < d && cbin > -1 && cbin < d && r > 0 && r < img.h - 1 && c > 0 && c < img.w - 1)) {
+                if (rbin > -1 && rbin < d && cbin > -1 && cbin < d) g_cen[C_DESC_BORDER_SKIP]++;
                 continue;
+            }
             const float dx = img.at(r, c + 1) - img.at(r, c - 1);
             const float dy = img.at(r - 1, c) - img.at(r + 1, c);
             const float w = sift_exp((c_rot * c_rot + r_rot * r_rot) * exp_scale);
@@ -281,7 +315,9 @@ void descriptor(const FImg& img, float ptx, float pty, float ori, float scl, flo
             rbin -= r0;
             cbin -= c0;
             obin -= o0;
+            if (o0 < 0) g_cen[C_O0_NEG]++;
             if (o0 < 0) o0 += n;
+            if (o0 >= n) g_cen[C_O0_GE_N]++;
             if (o0 >= n) o0 -= n;
             const float v_r1 = mag * rbin, v_r0 = mag - v_r1;
             const float v_rc11 = v_r1 * cbin, v_rc10 = v_r1 - v_rc11;
@@ -314,6 +350,7 @@ void descriptor(const FImg& img, float ptx, float pty, float ori, float scl, flo
     const float thr = std::sqrt(nrm2) * kDescMagThr;
     nrm2 = 0;
     for (int k = 0; k < len; k++) {
+        if (raw[k] > thr) g_cen[C_CLIP]++;
         const float v = std::min(raw[k], thr);
         raw[k] = v;
         nrm2 += v * v;
@@ -321,6 +358,7 @@ void descriptor(const FImg& img, float ptx, float pty, float ori, float scl, flo
     nrm2 = kIntDescFctr / std::max(std::sqrt(nrm2), FLT_EPSILON);
     for (int k = 0; k < len; k++) {
         const int v = cv_round(raw[k] * nrm2);
+        if (v > 255) g_cen[C_SATURATE]++;
         dst[k] = (float)std::min(std::max(v, 0), 255);
     }
 }
@@ -339,6 +377,7 @@ bool kp_less(const Kp& a, const Kp& b) {  // KeyPoint12_LessThan (class_id is -1
 int ora_sift_detect_and_compute(const uint8_t* img, int w, int h, int stride, ora_keypoint* kps, float* desc, int cap,
                                 int* n_out) {
     *n_out = 0;
+    std::fill(g_cen, g_cen + C_COUNT, 0);
     if (w < 1 || h < 1) return -1;
     // createInitialImage: float, resize 2x INTER_LINEAR (weights 0 / 0.25 / 0.75: exact), GaussianBlur
     FImg up(2 * w, 2 * h);
@@ -412,6 +451,10 @@ int ora_sift_detect_and_compute(const uint8_t* img, int w, int h, int stride, or
     const int threshold = (int)std::floor(0.5 * kContrast / kLayers * 255);
     std::vector<Kp> found;
     float hist[kOriBins];
+    g_cen[C_OCTAVES] = nOct;
+    for (int o = 0; o < nOct; o++)
+        if (dog[(size_t)o * (kLayers + 2)].w <= 2 * kBorder || dog[(size_t)o * (kLayers + 2)].h <= 2 * kBorder)
+            g_cen[C_OCTAVES_TOO_SMALL]++;
     for (int o = 0; o < nOct; o++)
         for (int i = 1; i <= kLayers; i++) {
             const int idx = o * (kLayers + 2) + i;
@@ -442,22 +485,28 @@ int ora_sift_detect_and_compute(const uint8_t* img, int w, int h, int stride, or
                     }
                     if (!ext) continue;
                     int r1 = r, c1 = c, layer = i;
+                    g_cen[C_CANDIDATES]++;
                     Kp kpt{};
                     if (!adjust(dog, kpt, o, layer, r1, c1)) continue;
                     const float scl_octv = kpt.size * 0.5f / (float)(1 << o);
                     const float omax = orientation_hist(gp[(size_t)o * (kLayers + 3) + layer], c1, r1,
                                                         cv_round(kOriRadius * scl_octv), kOriSigFctr * scl_octv, hist);
                     const float mag_thr = omax * kOriPeak;
+                    int n_ori = 0;
                     for (int j = 0; j < kOriBins; j++) {
                         const int l = j > 0 ? j - 1 : kOriBins - 1, r2 = j < kOriBins - 1 ? j + 1 : 0;
                         if (hist[j] > hist[l] && hist[j] > hist[r2] && hist[j] >= mag_thr) {
                             float bin = (float)j + 0.5f * (hist[l] - hist[r2]) / (hist[l] - 2 * hist[j] + hist[r2]);
+                            if (bin < 0 || bin >= kOriBins) g_cen[C_PEAK_WRAP]++;
                             bin = bin < 0 ? kOriBins + bin : bin >= kOriBins ? bin - kOriBins : bin;
                             kpt.angle = 360.f - (360.f / kOriBins) * bin;
+                            if (std::abs(kpt.angle - 360.f) < FLT_EPSILON) g_cen[C_SNAP_ZERO]++;
                             if (std::abs(kpt.angle - 360.f) < FLT_EPSILON) kpt.angle = 0.f;
                             found.push_back(kpt);
+                            n_ori++;
                         }
                     }
+                    if (n_ori >= 2) g_cen[C_MULTI_ORI]++;
                 }
         }
     // removeDuplicatedSorted
@@ -467,6 +516,7 @@ int ora_sift_detect_and_compute(const uint8_t* img, int w, int h, int stride, or
         if (kp.empty() || q.x != kp.back().x || q.y != kp.back().y || q.size != kp.back().size || q.angle != kp.back().angle)
             kp.push_back(q);
     const int n = (int)kp.size();
+    g_cen[C_DUPLICATES] = (int64_t)found.size() - n;
     *n_out = n;
     if (n > cap) return -5;
     for (int i = 0; i < n; ++i) {
@@ -487,10 +537,16 @@ int ora_sift_detect_and_compute(const uint8_t* img, int w, int h, int stride, or
         const float size = out.size * scale;
         const float ptx = out.x * scale, pty = out.y * scale;
         float angle = 360.f - out.angle;
+        if (std::abs(angle - 360.f) < FLT_EPSILON) g_cen[C_SNAP_ZERO]++;
         if (std::abs(angle - 360.f) < FLT_EPSILON) angle = 0.f;
         descriptor(gp[(size_t)(octv - kFirstOctave) * (kLayers + 3) + layer], ptx, pty, angle, size * 0.5f,
                    desc + (size_t)i * 128);
         (void)oct;
     }
     return 0;
+}
+
+int ora_sift_census(int64_t* out, int cap) {
+    for (int i = 0; i < C_COUNT && i < cap; ++i) out[i] = g_cen[i];
+    return C_COUNT;
 }

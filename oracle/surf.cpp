@@ -18,6 +18,9 @@
 //   - INTER_AREA at an integer scale of 2 = (a + b + c + d + 2) >> 2 (the
 //     ResizeAreaFastVec path), other integer scales cvRound(sum * (1.f/area)).
 // Parity against OpenCV itself is unpinned (OpenCV is absent).
+// What is pinned: first-principles anchors on Gaussian blobs (blob position, sign, size order and orientation:
+// tests/test_detector_anchors.py), and which branches the test images enter (the census below,
+// tests/test_detector_census.py).
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -35,6 +38,15 @@ constexpr int kOriRadius = 6, kOriWin = 60;     // SURFInvoker::ORI_RADIUS, ORI_
 constexpr int kOriInc = 5;                      // SURF_ORI_SEARCH_INC
 constexpr float kOriSigma = 2.5f, kDescSigma = 3.3f;
 constexpr int kPatch = 20;                      // PATCH_SZ
+
+// Census (ora_surf_census): how often the last ora_surf_detect_and_compute of this thread took each
+// branch.  Counting only: no counter is read by the detector.  The order is oracle.py's SURF_CENSUS.
+enum Cen {
+    C_LAYERS_SKIPPED, C_MAXIMA, C_D_ZERO, C_REJ_ALL_ZERO, C_REJ_ABS_GT1, C_ACCEPTED, C_SIZE_CHANGED, C_DROP_GWS,
+    C_DROP_NANG, C_ORI_OUTSIDE, C_WIN_CLAMPED, C_AREA_SCALE2, C_AREA_INT, C_AREA_FRACTIONAL, C_EQUAL_RESPONSE,
+    C_CLASS_ID_ZERO, C_COUNT
+};
+thread_local int64_t g_cen[C_COUNT];
 
 int cv_round(float v) { return (int)std::nearbyint(v); }
 int cv_round_d(double v) { return (int)std::nearbyint(v); }
@@ -114,7 +126,10 @@ struct Layer {
 // them unwritten and never reads them)
 void calc_layer(const std::vector<int32_t>& sum, int sw, int sh, Layer& L) {
     const int size = L.size, step = L.step;
-    if (size > sh - 1 || size > sw - 1) return;
+    if (size > sh - 1 || size > sw - 1) {
+        g_cen[C_LAYERS_SKIPPED]++;
+        return;
+    }
     HF Dx[3], Dy[3], Dxy[4];
     resize_haar(kDxS, Dx, 3, 9, size, sw);
     resize_haar(kDyS, Dy, 3, 9, size, sw);
@@ -145,6 +160,7 @@ bool interpolate(const float (&N9)[3][9], int dx, int dy, int ds, ora_keypoint& 
     const float a22 = N9[0][4] - 2 * N9[1][4] + N9[2][4];
     float x0 = 0, x1 = 0, x2 = 0;
     float d = (float)(double)(a00 * (a11 * a22 - a21 * a12) - a01 * (a10 * a22 - a20 * a12) + a02 * (a10 * a21 - a20 * a11));
+    if (d == 0) g_cen[C_D_ZERO]++;
     if (d != 0) {
         d = 1 / d;
         x0 = d * (b0 * (a11 * a22 - a12 * a21) - a01 * (b1 * a22 - a12 * b2) + a02 * (b1 * a21 - a11 * b2));
@@ -152,7 +168,11 @@ bool interpolate(const float (&N9)[3][9], int dx, int dy, int ds, ora_keypoint& 
         x2 = d * (a00 * (a11 * b2 - b1 * a21) - a01 * (a10 * b2 - b1 * a20) + b0 * (a10 * a21 - a11 * a20));
     }
     const bool ok = (x0 != 0 || x1 != 0 || x2 != 0) && std::abs(x0) <= 1 && std::abs(x1) <= 1 && std::abs(x2) <= 1;
+    if (!(x0 != 0 || x1 != 0 || x2 != 0)) g_cen[C_REJ_ALL_ZERO]++;
+    else if (!ok) g_cen[C_REJ_ABS_GT1]++;
     if (ok) {
+        g_cen[C_ACCEPTED]++;
+        if ((float)cv_round(kp.size + x2 * ds) != kp.size) g_cen[C_SIZE_CHANGED]++;
         kp.x += x0 * dx;
         kp.y += x1 * dy;
         kp.size = (float)cv_round(kp.size + x2 * ds);
@@ -202,6 +222,7 @@ void resize_area21(const std::vector<uint8_t>& W, int n, uint8_t (*P)[kPatch + 1
     const double inv_scale = (double)D / n, scale = 1. / inv_scale;
     const int iscale = cv_round_d(scale);
     if (std::abs(scale - iscale) < DBL_EPSILON) {  // resizeAreaFast_
+        g_cen[iscale == 2 ? C_AREA_SCALE2 : C_AREA_INT]++;
         const int area = iscale * iscale;
         const float fs = 1.f / area;
         for (int dy = 0; dy < D; ++dy)
@@ -214,6 +235,7 @@ void resize_area21(const std::vector<uint8_t>& W, int n, uint8_t (*P)[kPatch + 1
             }
         return;
     }
+    g_cen[C_AREA_FRACTIONAL]++;
     AreaCell c[D];
     area_cells(n, D, scale, c);
     // the ResizeArea_Invoker loop over ytab entries (dy, sy, beta) in order
@@ -248,6 +270,7 @@ extern "C" int ora_surf_detect_and_compute(const uint8_t* img, int w, int h, int
                                            ora_keypoint* kps, float* desc, int cap, int* n_out) {
     if (!img || !n_out || w < 1 || h < 1 || stride < w || cap < 0 || (cap > 0 && (!kps || !desc))) return -1;
     *n_out = 0;
+    std::fill(g_cen, g_cen + C_COUNT, 0);
     // integral(img, sum, CV_32S)
     const int sw = w + 1, sh = h + 1;
     std::vector<int32_t> sum((size_t)sw * sh, 0);
@@ -297,13 +320,17 @@ extern "C" int ora_surf_detect_and_compute(const uint8_t* img, int w, int h, int
                     for (int k = 0; k < 9; ++k)
                         if (!(t == 1 && k == 4)) mx = mx && v > N9[t][k];
                 if (!mx) continue;
+                g_cen[C_MAXIMA]++;
                 const float center_i = sum_i + (size - 1) * 0.5f, center_j = sum_j + (size - 1) * 0.5f;
                 const float tr = B.trace[(size_t)i * B.cols + j];
                 ora_keypoint kp{center_j, center_i, (float)size, -1.f, v, octave, (tr > 0) - (tr < 0)};
+                if (kp.class_id == 0) g_cen[C_CLASS_ID_ZERO]++;
                 if (interpolate(N9, step, step, size - A.size, kp)) K.push_back(kp);
             }
     }
     std::sort(K.begin(), K.end(), kp_greater);
+    for (size_t k = 1; k < K.size(); ++k)
+        if (K[k].response == K[k - 1].response) g_cen[C_EQUAL_RESPONSE]++;
     // SURFInvoker: orientation and 64-d descriptor per keypoint
     const std::vector<float> Go = gauss_kernel(2 * kOriRadius + 1, kOriSigma), Gd = gauss_kernel(kPatch, kDescSigma);
     int apx[(2 * kOriRadius + 1) * (2 * kOriRadius + 1)], apy[(2 * kOriRadius + 1) * (2 * kOriRadius + 1)];
@@ -323,6 +350,7 @@ extern "C" int ora_surf_detect_and_compute(const uint8_t* img, int w, int h, int
         const float s = kp.size * 1.2f / 9.0f;
         const int gws = 2 * cv_round(2 * s);
         if (sh < gws || sw < gws) {
+            g_cen[C_DROP_GWS]++;
             kp.size = -1;
             continue;
         }
@@ -334,7 +362,10 @@ extern "C" int ora_surf_detect_and_compute(const uint8_t* img, int w, int h, int
         for (int t = 0; t < nori; ++t) {
             const int x = cv_round(kp.x + apx[t] * s - (float)(gws - 1) / 2);
             const int y = cv_round(kp.y + apy[t] * s - (float)(gws - 1) / 2);
-            if (y < 0 || y >= sh - gws || x < 0 || x >= sw - gws) continue;
+            if (y < 0 || y >= sh - gws || x < 0 || x >= sw - gws) {
+                g_cen[C_ORI_OUTSIDE]++;
+                continue;
+            }
             const int32_t* p = sum.data() + (size_t)y * sw + x;
             const float vx = haar(p, gx, 2), vy = haar(p, gy, 2);
             X[nang] = vx * apw[t];
@@ -342,6 +373,7 @@ extern "C" int ora_surf_detect_and_compute(const uint8_t* img, int w, int h, int
             nang++;
         }
         if (nang == 0) {
+            g_cen[C_DROP_NANG]++;
             kp.size = -1;
             continue;
         }
@@ -386,6 +418,7 @@ extern "C" int ora_surf_detect_and_compute(const uint8_t* img, int w, int h, int
                     v = (uint8_t)cv_round(q[0] * (1.f - a) * (1.f - b) + q[1] * a * (1.f - b) + q[stride] * (1.f - a) * b +
                                           q[stride + 1] * a * b);
                 } else {
+                    g_cen[C_WIN_CLAMPED]++;
                     const int x = std::min(std::max(cv_round_d(px), 0), nc1), y = std::min(std::max(cv_round_d(py), 0), nr1);
                     v = img[(size_t)y * stride + x];
                 }
@@ -432,4 +465,9 @@ extern "C" int ora_surf_detect_and_compute(const uint8_t* img, int w, int h, int
     }
     *n_out = m;
     return m > cap ? -5 : 0;  // -5: cap too small, *n_out = the count needed (as the SIFT entry)
+}
+
+extern "C" int ora_surf_census(int64_t* out, int cap) {
+    for (int i = 0; i < C_COUNT && i < cap; ++i) out[i] = g_cen[i];
+    return C_COUNT;
 }
