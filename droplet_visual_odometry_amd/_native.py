@@ -165,6 +165,8 @@ _SIGNATURES = {
     "dvo_knn_stream_create": ([_vp, ctypes.POINTER(KnnStreamConfig), ctypes.POINTER(_vp)], _c),
     "dvo_knn_stream_destroy": ([_vp], None),
     "dvo_knn_stream_process": ([_vp, _vp, _c, _i64, _c, _vp], _c),
+    "dvo_knn_stream_detect": ([_vp, _vp, _c, _i64, _c, _vp], _c),
+    "dvo_knn_stream_finish": ([_vp, _vp, _vp, _c, _c], _c),
     "dvo_knn_stream_sync": ([_vp], _c),
     "dvo_knn_stream_hip_stream": ([_vp], _vp),
     "dvo_knn_stream_set_detect_group": ([_vp, _c], _c),
@@ -174,6 +176,8 @@ _SIGNATURES = {
     "dvo_knn_stream_get_rng_state": ([_vp, ctypes.POINTER(ctypes.c_uint64)], _c),
     "dvo_knn_stream_flann_bytes": ([_c, _c, _c], ctypes.c_size_t),
     "dvo_flann_rng_plan_host": ([ctypes.c_uint64, _vp, _c, _c, _c, _vp, ctypes.POINTER(ctypes.c_uint64)], _c),
+    "dvo_flann_rng_shard_host": ([ctypes.c_uint64, _vp, _c, _c, _c, _vp, _c, _c, _vp, ctypes.POINTER(ctypes.c_uint64),
+                                  ctypes.POINTER(ctypes.c_uint64)], _c),
     "dvo_knn_stream_get_features": ([_vp, _c, _vp, _vp, _c, _ip], _c),
     "dvo_knn_stream_get_matches": ([_vp, _c, _vp, _c, _ip], _c),
     "dvo_knn_stream_set_profiling": ([_vp, _c], _c),

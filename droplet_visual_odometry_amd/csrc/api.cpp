@@ -2463,14 +2463,16 @@ struct KnnBatch {
     // Steps 2 to 4 of a call over `frames` slots: frame state, pack + k-NN (+ merge), ratio test and gather.
     // fl (the FLANN mode's scratch): the kd-forests and their search take the k-NN's place, and
     // the lists hold squared L2.
+    // state_done: step 2 ran already (dvo_knn_stream_detect).  shard: a sharded FLANN call's hand-off.
     hipError_t match(int frames, double ratio, float* pts, int32_t* nmatch, PairHeader* hdr, hipStream_t s,
-                     const FlannBatchArgs* fl = nullptr, int levels = 0) const {
-        hipError_t e = launch_knn_frame_state(n, frames, cap, fstate, s);
+                     const FlannBatchArgs* fl = nullptr, int levels = 0, bool state_done = false,
+                     const FlannShard* shard = nullptr) const {
+        hipError_t e = state_done ? hipSuccess : launch_knn_frame_state(n, frames, cap, fstate, s);
         if (e != hipSuccess || frames < 2) return e;
         if (fl) {
             FlannBatchArgs fa = *fl;
             fa.desc = desc, fa.fstate = fstate, fa.cap = cap, fa.dim = dim, fa.idx = idx, fa.dist = dist;
-            e = launch_flann_batch(fa, frames, levels, s);
+            e = launch_flann_batch(fa, frames, levels, s, shard);
         } else {
             const KnnBatchArgs ka{desc, fstate, bytes, norms, rejected, cap, dim, dist, idx, pdist, pidx};
             e = launch_knn_batch(ka, frames, ranges_of(frames - 1), s);
@@ -2495,7 +2497,10 @@ struct dvo_knn_stream {
     SurfGroupDev sgrp;  // dvo_knn_stream_set_surf_group: sgrp.group > 0 detects through launch_surf_group
     FlannBatchArgs fl{};  // dvo_knn_stream_set_flann: fl.trees > 0 matches through launch_flann_batch
     DeviceAllocs fl_mem;  // its scratch and the theRNG state word
-    int last_frames = 0;
+    int last_frames = 0;     // frames whose features the slots hold (dvo_knn_stream_get_features)
+    int pending = 0;         // frames detected by dvo_knn_stream_detect and not yet finished
+    int matched_frames = 0;  // frames of the last finished call (dvo_knn_stream_get_matches)
+    bool pending_timed = false;  // the pending detection recorded ev[0], ev[1]
     bool profiling = false, timed = false;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 
@@ -2575,11 +2580,20 @@ void dvo_knn_stream_destroy(dvo_knn_stream* s) {
 int dvo_knn_stream_process(dvo_knn_stream* st, const uint8_t* d_frames, int n_frames, int64_t frame_stride, int stride,
                            dvo_pair_record* d_records) {
     if (!st) return DVO_EINVAL;
+    if (n_frames > 1 && n_frames <= st->cfg.max_frames && !d_records)
+        return fail(st->ctx, DVO_EINVAL, "bad frame or record buffer");
+    const int rc = dvo_knn_stream_detect(st, d_frames, n_frames, frame_stride, stride, nullptr);
+    return rc ? rc : dvo_knn_stream_finish(st, d_records, nullptr, 1, 0);
+}
+
+int dvo_knn_stream_detect(dvo_knn_stream* st, const uint8_t* d_frames, int n_frames, int64_t frame_stride, int stride,
+                          uint64_t* d_draws) {
+    if (!st) return DVO_EINVAL;
     dvo_ctx* ctx = st->ctx;
     const dvo_knn_stream_config& c = st->cfg;
     const int w = c.width, h = c.height;
     if (n_frames < 1 || n_frames > c.max_frames) return fail(ctx, DVO_EINVAL, "n_frames out of range (1..max_frames)");
-    if (!d_frames || stride < w || (n_frames > 1 && !d_records)) return fail(ctx, DVO_EINVAL, "bad frame or record buffer");
+    if (!d_frames || stride < w) return fail(ctx, DVO_EINVAL, "bad frame or record buffer");
     HIP_TRY(hipSetDevice(ctx->device));
     // a group detector has its own scratch: the context's plan is not used
     const bool grouped = st->grp.group > 0 || st->sgrp.group > 0;
@@ -2589,8 +2603,8 @@ int dvo_knn_stream_process(dvo_knn_stream* st, const uint8_t* d_frames, int n_fr
     const KnnBatch& b = st->b;
     const bool sift = c.detector == DVO_DETECT_SIFT;
     hipEvent_t* ev = st->profiling ? st->ev : nullptr;
-    st->last_frames = 0;
-    st->timed = false;
+    st->last_frames = st->pending = st->matched_frames = 0;  // a pending detection is replaced
+    st->timed = st->pending_timed = false;
     if (ev) HIP_TRY(hipEventRecord(ev[0], s));
     // detection in place on the caller's frames: a group of frames per launch straight into the
     // frame slots, or frame by frame on the plan's single scratch
@@ -2625,9 +2639,34 @@ int dvo_knn_stream_process(dvo_knn_stream* st, const uint8_t* d_frames, int n_fr
         }
     }
     if (ev) HIP_TRY(hipEventRecord(ev[1], s));
+    HIP_TRY(launch_knn_frame_state(b.n, n_frames, b.cap, b.fstate, s));
+    if (d_draws) HIP_TRY(launch_flann_shard_draws(b.fstate, n_frames, st->fl.trees, d_draws, s));
+    st->last_frames = st->pending = n_frames;
+    st->pending_timed = ev != nullptr;
+    return DVO_OK;
+}
+
+int dvo_knn_stream_finish(dvo_knn_stream* st, dvo_pair_record* d_records, const uint64_t* d_shard_draws, int world,
+                          int rank) {
+    if (!st) return DVO_EINVAL;
+    dvo_ctx* ctx = st->ctx;
+    const dvo_knn_stream_config& c = st->cfg;
+    const int n_frames = st->pending;
+    if (n_frames < 1) return fail(ctx, DVO_EINVAL, "no pending dvo_knn_stream_detect");
+    if (world < 1 || world > kFlannShardMax || rank < 0 || rank >= world)
+        return fail(ctx, DVO_EINVAL, "world out of range (1..1024) or rank outside it");
+    if (n_frames > 1 && !d_records) return fail(ctx, DVO_EINVAL, "bad frame or record buffer");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const KnnBatch& b = st->b;
+    hipEvent_t* ev = st->profiling && st->pending_timed ? st->ev : nullptr;
+    st->pending = 0;
     const int pairs = n_frames - 1;
     const PairArrays& v = st->pairs.all;
-    HIP_TRY(b.match(n_frames, c.ratio, v.pts, v.nmatch, v.hdr, s, st->fl.trees > 0 ? &st->fl : nullptr));
+    const bool flann = st->fl.trees > 0;
+    const FlannShard shard{d_shard_draws, world, rank};
+    HIP_TRY(b.match(n_frames, c.ratio, v.pts, v.nmatch, v.hdr, s, flann ? &st->fl : nullptr, 0, true,
+                    flann && d_shard_draws ? &shard : nullptr));
     if (ev) HIP_TRY(hipEventRecord(ev[2], s));
     if (pairs >= 1) {
         // the stream's round schedule (not kStageOneRound): a record does not depend on the split into calls
@@ -2639,7 +2678,7 @@ int dvo_knn_stream_process(dvo_knn_stream* st, const uint8_t* d_frames, int n_fr
         HIP_TRY(hipEventRecord(ev[3], s));
         st->timed = true;
     }
-    st->last_frames = n_frames;
+    st->matched_frames = n_frames;
     return DVO_OK;
 }
 
@@ -2659,6 +2698,7 @@ int dvo_knn_stream_set_detect_group(dvo_knn_stream* s, int group) {
     dvo_ctx* ctx = s->ctx;
     if (s->cfg.detector != DVO_DETECT_SIFT) return fail(ctx, DVO_EINVAL, "the group detector is SIFT only");
     if (group < 0 || group > kSiftGroupMax) return fail(ctx, DVO_EINVAL, "group out of range (0..64)");
+    s->pending = 0;  // a detection waiting for dvo_knn_stream_finish is dropped
     if (group == s->grp.group) return DVO_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // the old scratch may be in use
@@ -2671,6 +2711,7 @@ int dvo_knn_stream_set_surf_group(dvo_knn_stream* s, int group) {
     dvo_ctx* ctx = s->ctx;
     if (s->cfg.detector != DVO_DETECT_SURF) return fail(ctx, DVO_EINVAL, "the group SURF detector needs a SURF stream");
     if (group < 0 || group > kSurfGroupMax) return fail(ctx, DVO_EINVAL, "group out of range (0..64)");
+    s->pending = 0;  // a detection waiting for dvo_knn_stream_finish is dropped
     if (group == s->sgrp.group) return DVO_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // the old scratch may be in use
@@ -2683,6 +2724,7 @@ int dvo_knn_stream_set_flann(dvo_knn_stream* s, int trees, int checks) {
     dvo_ctx* ctx = s->ctx;
     if (trees < 0 || trees > 64) return fail(ctx, DVO_EINVAL, "trees out of range (0..64)");
     if (trees > 0 && checks < 1) return fail(ctx, DVO_EINVAL, "checks must be >= 1");
+    s->pending = 0;  // a detection waiting for dvo_knn_stream_finish is dropped
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // the old scratch may be in use
     if (trees != s->fl.trees) {
@@ -2740,6 +2782,16 @@ int dvo_flann_rng_plan_host(uint64_t state, const int32_t* counts, int frames, i
     return DVO_OK;
 }
 
+int dvo_flann_rng_shard_host(uint64_t state, const int32_t* counts, int frames, int cap, int trees,
+                             const uint64_t* shard_draws, int world, int rank, uint64_t* starts, uint64_t* final_state,
+                             uint64_t* own_draws) {
+    if (frames < 0 || (frames > 0 && !counts) || cap < 1 || trees < 1 || trees > 64 || (frames > 1 && !starts) ||
+        world < 1 || world > kFlannShardMax || rank < 0 || rank >= world)
+        return DVO_EINVAL;
+    flann_rng_shard_host(state, counts, frames, cap, trees, shard_draws, world, rank, starts, final_state, own_draws);
+    return DVO_OK;
+}
+
 int dvo_knn_stream_set_profiling(dvo_knn_stream* s, int enable) {
     if (!s) return DVO_EINVAL;
     dvo_ctx* ctx = s->ctx;
@@ -2794,7 +2846,7 @@ int dvo_knn_stream_get_matches(dvo_knn_stream* s, int pair, dvo_dmatch* out, int
     if (!s || !m) return DVO_EINVAL;
     dvo_ctx* ctx = s->ctx;
     *m = 0;
-    if (pair < 0 || pair >= s->last_frames - 1) return fail(ctx, DVO_EINVAL, "pair outside the last call");
+    if (pair < 0 || pair >= s->matched_frames - 1) return fail(ctx, DVO_EINVAL, "pair outside the last call");
     HIP_TRY(hipSetDevice(ctx->device));
     int32_t nm = 0;
     HIP_TRY(hipMemcpyAsync(&nm, s->pairs.all.nmatch + pair, 4, hipMemcpyDeviceToHost, ctx->stream));

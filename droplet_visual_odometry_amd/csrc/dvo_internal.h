@@ -537,12 +537,29 @@ bool flann_batch_layout(FlannBatchArgs& a, int P_, int cap, int trees, Take&& ta
 size_t flann_batch_bytes(int pairs, int cap, int trees);
 // RNG plan, then per tree draws / shuffle / root / `levels` level launches / tail, then the search
 // and the global-heap pass of frames - 1 pairs: 3 + trees (levels + 8) launches.
-hipError_t launch_flann_batch(const FlannBatchArgs& a, int frames, int levels, hipStream_t s);
+// shard (a sharded stream's call, dvo_knn_stream_finish): draws[world] device words, the draws of
+// every rank's pairs of the window; the plan starts after those of the ranks below `rank` and
+// leaves the state past all of them.  draws[rank] is not read (the plan counts its own pairs).
+struct FlannShard {
+    const uint64_t* draws;
+    int world, rank;  // world 1..kFlannShardMax
+};
+constexpr int kFlannShardMax = 1024;  // one entry per lane of the plan's workgroup
+hipError_t launch_flann_batch(const FlannBatchArgs& a, int frames, int levels, hipStream_t s,
+                              const FlannShard* shard = nullptr);
 hipError_t launch_flann_set_state(uint64_t* d_state, uint64_t value, hipStream_t s);
+// *d_draws = the draws the frames - 1 pairs of fstate will consume (0 with trees == 0), one workgroup.
+hipError_t launch_flann_shard_draws(const int32_t* d_fstate, int frames, int trees, uint64_t* d_draws, hipStream_t s);
 // The RNG plan's arithmetic on the host (the kernel's __host__ __device__ text): counts are
 // detector counts (one above cap marks the frame), starts[frames - 1], *state_out after the call.
 void flann_rng_plan_host(uint64_t state, const int32_t* counts, int frames, int cap, int trees, uint64_t* starts,
                          uint64_t* state_out);
+// The sharded plan on the host: one rank's frames (frames >= 0; fewer than 2 is a rank without
+// pairs) with the ranks' draw counts shard_draws[world] (NULL: none before or after).  starts,
+// state_out and own_draws may be NULL.
+void flann_rng_shard_host(uint64_t state, const int32_t* counts, int frames, int cap, int trees,
+                          const uint64_t* shard_draws, int world, int rank, uint64_t* starts, uint64_t* state_out,
+                          uint64_t* own_draws);
 // The k-NN modes' ratio test, ordered compaction and keypoint gather (ratio.hip): query q of the
 // matcher's k = 2 output is kept when (double)d0 < ratio * (double)d1, d the float32 values
 // DMatch.distance holds (squared: sqrtf of FLANN's squared L2).  Kept matches in ascending q.

@@ -571,8 +571,16 @@ __device__ __forceinline__ FlannSearch flann_pair_search(const FlannBatchArgs& a
 // RNG plan, one workgroup: pair p's forest starts after the draws of the built pairs before it
 // (an exclusive scan of their draw counts, then a jump by that count), every (pair, tree, chunk)
 // start follows from the pair's, and the stream's state moves past the whole call.
-__global__ __launch_bounds__(1024) void flann_rng_plan_kernel(FlannBatchArgs a, int pairs) {
-    __shared__ uint64_t part[1024];
+//
+// A sharded stream (FlannShard) runs the same plan on every rank over that rank's pairs of a
+// window: `pre` are the draws of the ranks below it and `post` those of the ranks above it, so the
+// plan starts from the state jumped by pre and leaves it jumped by pre + own + post, the state
+// after the whole window on every rank.  mwc_jump_by composes (a jump by a, then one by b, is a
+// jump by a + b), so each start equals the one a single plan over the whole window computes.
+// Headroom of the 64-bit sums: a call's draws are at most 65,535 pairs x 64 trees x 131,071 draws
+// (2 cap - 1 at cap = 65,536), about 5.5e11 < 2^40; 1024 ranks of them stay below 2^50.
+__device__ __forceinline__ void flann_rng_plan_body(const FlannBatchArgs& a, int pairs, uint64_t pre, uint64_t post,
+                                                    uint64_t* part /* LDS [1024] */) {
     const int tid = threadIdx.x;
     const int per = (pairs + 1023) / 1024, b = min(pairs, tid * per), e = min(pairs, b + per);
     uint64_t sum = 0;
@@ -585,7 +593,7 @@ __global__ __launch_bounds__(1024) void flann_rng_plan_kernel(FlannBatchArgs a, 
         part[tid] += v;
         __syncthreads();
     }
-    const uint64_t st0 = *a.state;
+    const uint64_t st0 = mwc_jump_by(*a.state, pre);
     uint64_t run = part[tid] - sum;
     for (int p = b; p < e; ++p) {
         a.starts[p] = mwc_jump_by(st0, run);
@@ -593,7 +601,7 @@ __global__ __launch_bounds__(1024) void flann_rng_plan_kernel(FlannBatchArgs a, 
     }
     __syncthreads();  // every thread has read the state, and the starts are written
     if (tid == 0) {
-        *a.state = mwc_jump_by(st0, part[1023]);
+        *a.state = mwc_jump_by(st0, part[1023] + post);
         a.ctl[0] = 0;
         a.ctl[1] = 0;
     }
@@ -605,6 +613,47 @@ __global__ __launch_bounds__(1024) void flann_rng_plan_kernel(FlannBatchArgs a, 
         const int draws = 2 * nt - 1;
         a.cs[i] = mwc_jump_by(a.starts[p], (uint64_t)t * draws + (uint64_t)((int64_t)draws * c / kFlannChunks));
     }
+}
+
+__global__ __launch_bounds__(1024) void flann_rng_plan_kernel(FlannBatchArgs a, int pairs) {
+    __shared__ uint64_t part[1024];
+    flann_rng_plan_body(a, pairs, 0, 0, part);
+}
+
+// the workgroup's sum of v, to every thread; part is free again on return
+__device__ __forceinline__ uint64_t flann_block_sum(uint64_t* part /* LDS [1024] */, uint64_t v) {
+    const int tid = threadIdx.x;
+    part[tid] = v;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+        if (tid < o) part[tid] += part[tid + o];
+        __syncthreads();
+    }
+    const uint64_t s = part[0];
+    __syncthreads();
+    return s;
+}
+
+// The sharded twin: one entry of the ranks' draw counts per lane (world <= 1024), summed below and
+// above this rank; entry [rank] is not read.
+__global__ __launch_bounds__(1024) void flann_rng_plan_shard_kernel(FlannBatchArgs a, int pairs, FlannShard sh) {
+    __shared__ uint64_t part[1024];
+    const int tid = threadIdx.x;
+    const uint64_t v = tid < sh.world && tid != sh.rank ? sh.draws[tid] : 0;
+    const uint64_t pre = flann_block_sum(part, tid < sh.rank ? v : 0);
+    const uint64_t post = flann_block_sum(part, tid > sh.rank ? v : 0);
+    flann_rng_plan_body(a, pairs, pre, post, part);
+}
+
+// The draws the call's pairs will consume (what the plan's scan ends at), for the ranks above
+// this one: one workgroup, one plain 64-bit store.
+__global__ __launch_bounds__(1024) void flann_shard_draws_kernel(const int32_t* fstate, int pairs, int trees,
+                                                                 uint64_t* out) {
+    __shared__ uint64_t part[1024];
+    uint64_t sum = 0;
+    for (int p = threadIdx.x; p < pairs; p += 1024) sum += flann_pair_draws(fstate[2 * p], fstate[2 * p + 2], trees);
+    sum = flann_block_sum(part, sum);
+    if (threadIdx.x == 0) *out = sum;
 }
 
 __global__ void flann_set_state_kernel(uint64_t* state, uint64_t value) { *state = value; }
@@ -829,12 +878,38 @@ void flann_rng_plan_host(uint64_t state, const int32_t* counts, int frames, int 
     *state_out = mwc_jump_by(state, run);
 }
 
-hipError_t launch_flann_batch(const FlannBatchArgs& a, int frames, int levels, hipStream_t s) {
+void flann_rng_shard_host(uint64_t state, const int32_t* counts, int frames, int cap, int trees,
+                          const uint64_t* shard_draws, int world, int rank, uint64_t* starts, uint64_t* state_out,
+                          uint64_t* own_draws) {
+    auto brings = [&](int f) { return counts[f] > cap ? 0 : std::max(counts[f], 0); };  // knn_frame_state_kernel
+    uint64_t pre = 0, post = 0;
+    for (int i = 0; shard_draws && i < world; ++i)
+        if (i != rank) (i < rank ? pre : post) += shard_draws[i];
+    const uint64_t st0 = mwc_jump_by(state, pre);
+    uint64_t run = 0;
+    for (int p = 0; p + 1 < frames; ++p) {
+        if (starts) starts[p] = mwc_jump_by(st0, run);
+        run += flann_pair_draws(brings(p), brings(p + 1), trees);
+    }
+    if (state_out) *state_out = mwc_jump_by(st0, run + post);
+    if (own_draws) *own_draws = run;
+}
+
+hipError_t launch_flann_shard_draws(const int32_t* d_fstate, int frames, int trees, uint64_t* d_draws, hipStream_t s) {
+    hipLaunchKernelGGL(flann_shard_draws_kernel, dim3(1), dim3(1024), 0, s, d_fstate, std::max(frames - 1, 0), trees,
+                       d_draws);
+    return hipGetLastError();
+}
+
+hipError_t launch_flann_batch(const FlannBatchArgs& a, int frames, int levels, hipStream_t s, const FlannShard* shard) {
     const int P = frames - 1;
     if (P < 1) return hipSuccess;
+    if (shard)
+        hipLaunchKernelGGL(flann_rng_plan_shard_kernel, dim3(1), dim3(1024), 0, s, a, P, *shard);
+    else
+        hipLaunchKernelGGL(flann_rng_plan_kernel, dim3(1), dim3(1024), 0, s, a, P);
     const int L = levels > 0 ? levels : kFlannLevels, C = a.cap;
     const dim3 rows((C + 255) / 256, P);
-    hipLaunchKernelGGL(flann_rng_plan_kernel, dim3(1), dim3(1024), 0, s, a, P);
     for (int t = 0; t < a.trees; ++t) {  // serial: tree t shuffles the order tree t - 1 left
         hipLaunchKernelGGL(flann_prep_batch_kernel, dim3((C + 2 + 255) / 256, P), dim3(256), 0, s, a, t);
         hipLaunchKernelGGL(flann_draws_batch_kernel, dim3(1, P), dim3(kFlannChunks), 0, s, a, t);

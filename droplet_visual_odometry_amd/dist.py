@@ -20,6 +20,14 @@ first pair is then the last successful pair's wherever it was computed —
 including when the pairs at a shard boundary fail — so records, T_rel and
 T_abs are bit-identical to one rank processing the whole stream.
 
+The k-NN modes shard the same way (`ShardedKnnRunner` around
+stream.KnnFrameStream).  Their `flann` matcher couples pairs once more,
+upstream of the records: pair p's kd-forest starts from the cv::theRNG() state
+left by every built pair before it (v3:207-212).  Each rank therefore detects
+first, the ranks all-gather one device word each (the draws their pairs will
+take), and each rank's RNG plan starts after the draws of the ranks below it
+(dvo_knn_stream_detect / dvo_knn_stream_finish).
+
 The host helpers `local_chain` / `compose_chain` fold per-rank partial
 products instead (equal up to reassociation, tests/test_dist.py).
 """
@@ -283,6 +291,163 @@ class ShardedStreamRunner:
     def close(self):
         for f in self.fss:
             f.close()
+        if self.chain is not None:
+            self.chain.close()
+
+
+def init_process_group(backend: str, rank: int, world: int, device=None, timeout_s: float = 120.0):
+    """torch.distributed.init_process_group with a finite timeout, which the group's collectives
+    inherit: a rank whose partner died fails after timeout_s instead of waiting for ever.
+    backend "nccl" (RCCL; device = the rank's GPU) or "gloo".  MASTER_ADDR / MASTER_PORT come from
+    the environment."""
+    import datetime
+    import torch.distributed as dist
+    kw = dict(rank=rank, world_size=world, timeout=datetime.timedelta(seconds=float(timeout_s)))
+    if backend == "nccl" and device is not None:
+        kw["device_id"] = device
+    dist.init_process_group(backend, **kw)
+
+
+class ShardedKnnRunner:
+    """One rank's loop over a pose stream of the k-NN modes sharded across ranks: the twin of
+    ShardedStreamRunner for stream.KnnFrameStream (detector "sift" or "surf", matcher "bf" or
+    "flann"), with the same calling convention and the same window and shard arithmetic
+    (shard_window).  The records, T_rel, T_abs and the final rng_state equal one KnnFrameStream
+    processing the whole stream, bit for bit.
+
+    Per window each rank runs, in order: (1) KnnFrameStream.detect on its n_local + 1 frames, which
+    in FLANN mode also writes the theRNG draws its pairs will consume into a device word; (2) in
+    FLANN mode an all-gather of that one word per rank, on torch's stream after an event from the
+    library stream (with host_gather through host memory, gloo); (3) KnnFrameStream.finish straight
+    into a ShardedPoseStream send slot, ordered after the gather: the RNG plan starts after the
+    draws of the ranks below and leaves the state past the whole window, so pair p's forest starts
+    where one stream's would and every rank ends the window with the same state; (4)
+    ShardedPoseStream.exchange; (5) PoseTail.rel_range on every rank over its own pairs; (6)
+    exchange_T; (7) rank 0's HostPoseChain.  BFMatcher mode skips (2).
+
+    `step(frames, c_prev, c_cur)` runs one window and returns [(records, T_rel, T_abs)] as
+    ShardedStreamRunner.step does (one window per step: nothing stays in flight, `drain()` returns
+    []); T_abs is a Future of the host array on rank 0, None elsewhere.  Every rank calls step in
+    the same order.
+
+    Ordering without host synchronisation on the RCCL path: `slots` (>= 2) send slots take turns;
+    the library stream waits for a slot's `done` event (its previous collective) before the finish
+    that rewrites it; torch's stream waits for the detection before the draws gather and for the
+    records before the exchange; finish waits for the gather.  The draws words live in per-slot
+    buffers under the same events.  Every rank needs at least one pair per window
+    (window_pairs >= world)."""
+
+    def __init__(self, width: int, height: int, K, window_pairs: int, world: int, rank: int, marker_length: float,
+                 detector: str = "sift", matcher: str = "bf", feat_cap: int | None = None, detect_group: int = 0,
+                 surf_group: int = 0, trees: int = 5, checks: int = 50, rng_state: int | None = None,
+                 hessian_threshold: float = 400.0, max_iters: int = 1000, k: int = 4, host_gather: bool = False,
+                 group=None, ctx=None, slots: int = 2):
+        if detector not in ("sift", "surf"):
+            raise ValueError("detector must be 'sift' or 'surf'")
+        if matcher not in ("bf", "flann"):
+            raise ValueError("matcher must be 'bf' or 'flann'")
+        if int(world) < 1 or not 0 <= int(rank) < int(world):
+            raise ValueError("rank must be in 0..world - 1")
+        if int(window_pairs) < 1:
+            raise ValueError("window_pairs must be >= 1")
+        if int(window_pairs) < int(world):
+            raise ValueError("every rank needs a pair per window: window_pairs >= world")
+        if matcher == "bf" and rng_state is not None:
+            raise ValueError("rng_state needs matcher='flann'")
+        if matcher == "flann" and int(world) > 1024:
+            raise ValueError("the FLANN hand-off takes at most 1024 ranks")
+        if int(slots) < 2:
+            raise ValueError("at least two send slots")
+        import torch
+        from droplet_visual_odometry_amd._native import Context
+        from droplet_visual_odometry_amd.stream import HostPoseChain, KnnFrameStream, PoseTail
+        self.ctx = ctx if ctx is not None else Context(0)
+        dev = self.device = torch.device("cuda", self.ctx.device)
+        self.world, self.rank, self.host_gather, self.group = int(world), int(rank), host_gather, group
+        self.flann = matcher == "flann"
+        self.shs = [ShardedPoseStream(world, rank, window_pairs, dev, k=k, group=group, host_gather=host_gather)
+                    for _ in range(int(slots))]
+        self.n_local = self.shs[0].n_local
+        self.ks = KnnFrameStream(width, height, K, self.n_local + 1, detector=detector, feat_cap=feat_cap,
+                                 hessian_threshold=hessian_threshold, max_iters=max_iters, ctx=self.ctx,
+                                 detect_group=detect_group, surf_group=surf_group, matcher=matcher, trees=trees,
+                                 checks=checks, rng_state=rng_state)
+        # per slot: this rank's draws word (detect writes it) and the gathered words (finish reads them)
+        self.own = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in self.shs] if self.flann else None
+        self.all = [torch.zeros(self.world, dtype=torch.int64, device=dev) for _ in self.shs] if self.flann else None
+        self.tail = PoseTail(K, marker_length, ctx=self.ctx)
+        self.chain = HostPoseChain(window_pairs, len(self.shs) + 1, dev) if rank == 0 else None
+        self.i = 0
+
+    @property
+    def rng_state(self) -> int:
+        """The stream's theRNG state after the windows so far (waits for them): equal on all ranks."""
+        return self.ks.rng_state
+
+    def reset_pose(self, P0=None, T0=None):
+        """Carry-in of the whole pose stream, as ShardedStreamRunner.reset_pose."""
+        self.tail.reset(P0, None)
+        if self.chain is not None:
+            self.chain.reset(T0)
+
+    def _gather_draws(self, own, all_):
+        import torch
+        import torch.distributed as dist
+        # at world 1 too: one path, whatever the world size
+        if self.host_gather:
+            self.ks.sync()
+            got = torch.empty(self.world, dtype=torch.int64)
+            dist.all_gather_into_tensor(got, own.cpu(), group=self.group)
+            all_.copy_(got)
+        else:
+            torch.cuda.current_stream(self.device).wait_event(self.ks.record_event())
+            dist.all_gather_into_tensor(all_, own, group=self.group)
+
+    def step(self, frames, c_prev, c_cur, wait_torch: bool = True):
+        """wait_torch as ShardedStreamRunner.step: pass False only for frames already resident (a
+        slot's first use is still ordered after its zero-fill)."""
+        import torch
+        s = self.i % len(self.shs)
+        sh = self.shs[s]
+        first_use = self.i < len(self.shs)
+        self.i += 1
+        if frames.shape[0] != self.n_local + 1:
+            raise ValueError(f"rank {self.rank} needs {self.n_local + 1} frames per window")
+        ks = self.ks
+        ks.wait_event(sh.done)  # the slot's previous collective has read its send buffer
+        sh.set_corners(c_prev, c_cur)  # torch's stream, after that collective
+        if self.flann:
+            own, all_ = self.own[s], self.all[s]
+            ks.detect(frames, draws=own, wait_torch=wait_torch or first_use)
+            self._gather_draws(own, all_)
+            ks.finish(sh.records, shard_draws=all_, rank=self.rank, wait_torch=True)  # after the gather
+        else:
+            ks.detect(frames, wait_torch=wait_torch or first_use)
+            ks.finish(sh.records, wait_torch=False)
+        if self.host_gather:
+            ks.sync()
+        else:
+            torch.cuda.current_stream(self.device).wait_event(ks.record_event())
+        recs, cp, cc = sh.exchange()
+        self.tail.rel_range(recs, cp, cc, sh.p0_local, sh.n_local, sh.T_send)
+        T_rel = sh.exchange_T()
+        if self.rank != 0:
+            return [(recs, None, None)]
+        return [(recs, T_rel, self.chain.submit(T_rel))]
+
+    def drain(self):
+        """Nothing stays in flight after step; kept for ShardedStreamRunner's calling convention."""
+        return []
+
+    def sync(self):
+        import torch
+        self.ks.sync()
+        torch.cuda.synchronize()
+        if self.chain is not None:
+            self.chain.wait()
+
+    def close(self):
+        self.ks.close()
         if self.chain is not None:
             self.chain.close()
 

@@ -17,7 +17,8 @@ mirrors its argument meaning, output layout and failure points:
                        knn_sift / surf / flann modes      visual_odometry_v3.py:373, :204-238, :297, :303
   stream.KnnFrameStream  the same for a batch of device-resident frames (matcher="bf" | "flann"; the
                        FLANN forests are built on the device: test_flann_batch, flann_rng_plan_host,
-                       knn_stream_flann_bytes below)
+                       knn_stream_flann_bytes below; sharded across ranks by dist.ShardedKnnRunner, whose
+                       theRNG hand-off flann_rng_shard_host repeats on the host)
   find_essential_mat   cv::findEssentialMat(RANSAC)       visual_odometry_v3.py:297-300
   recover_pose         cv::recoverPose                    visual_odometry_v3.py:303-306
   triangulate_points   cv::triangulatePoints              visual_odometry_v3.py:265
@@ -1079,6 +1080,29 @@ def flann_rng_plan_host(counts, cap, trees=5, rng_state=THE_RNG_SEED):
     if rc:
         raise DVOError(rc, "dvo_flann_rng_plan_host: bad arguments")
     return starts[:len(counts) - 1].copy(), int(st.value)
+
+
+def flann_rng_shard_host(counts, cap, trees=5, rng_state=THE_RNG_SEED, shard_draws=None, world=1, rank=0):
+    """One rank's RNG plan of a sharded FLANN stream on the host (dvo_flann_rng_shard_host, the
+    text of dvo_knn_stream_finish's plan; no GPU needed).  counts: the detector counts of the rank's
+    frames (empty or one frame: a rank without pairs); shard_draws: every rank's draws word for
+    the window (entry [rank] is not read; None: nothing before or after).  Returns (starts
+    uint64[len(counts) - 1], the state after the whole window, the rank's own draws word)."""
+    from ._native import load_library
+    counts = np.ascontiguousarray(counts, np.int32).reshape(-1)
+    starts = np.zeros(max(len(counts) - 1, 1), np.uint64)
+    sd = None
+    if shard_draws is not None:
+        sd = np.ascontiguousarray(shard_draws, np.uint64).reshape(-1)
+        if len(sd) != int(world):
+            raise ValueError("shard_draws must hold one word per rank")
+    st, own = ctypes.c_uint64(), ctypes.c_uint64()
+    rc = load_library().dvo_flann_rng_shard_host(ctypes.c_uint64(int(rng_state)), ptr(counts) if len(counts) else None,
+                                                 len(counts), int(cap), int(trees), None if sd is None else ptr(sd),
+                                                 int(world), int(rank), ptr(starts), ctypes.byref(st), ctypes.byref(own))
+    if rc:
+        raise DVOError(rc, "dvo_flann_rng_shard_host: bad arguments")
+    return starts[:max(len(counts) - 1, 0)].copy(), int(st.value), int(own.value)
 
 
 def knn_stream_flann_bytes(max_frames, feat_cap, trees=5) -> int:

@@ -480,7 +480,10 @@ class KnnFrameStream:
     more device memory.  The records are ops.KnnPairStream(matcher="flann").pair's chained through
     its returned state: the stream keeps cv::theRNG()'s state on the device (rng_state; enabling
     sets ops.THE_RNG_SEED, rng_state=... another start), advances it by trees (2 nt - 1) draws per
-    built pair, and carries it from call to call, so the records do not depend on the split."""
+    built pair, and carries it from call to call, so the records do not depend on the split.
+
+    process() is detect() followed by finish(); a stream sharded across ranks (dist.ShardedKnnRunner)
+    calls the two phases itself, with the all-gather of the ranks' draws words between them."""
 
     def __init__(self, width: int, height: int, K, max_frames: int, detector="sift", feat_cap: int | None = None,
                  hessian_threshold: float = 400.0, ratio: float = 0.75, prob: float = 0.999, threshold: float = 1.0,
@@ -524,6 +527,7 @@ class KnnFrameStream:
                 self.rng_state = rng_state
         self._ext = torch.cuda.ExternalStream(self.hip_stream, device=self.device)
         self._held = collections.deque()  # (event, tensors) in flight on the library's stream
+        self._pending = 0  # frames of the last detect() (sizes finish()'s records)
         self.width, self.height, self.max_frames = int(width), int(height), int(max_frames)
         self.dim = 64 if cfg.detector == 1 else 128
         self.K = K.reshape(3, 3)
@@ -539,13 +543,13 @@ class KnnFrameStream:
         """SIFT frames per detection launch from the next process() on (0: frame by frame).  Waits
         for the stream and allocates or frees the group's scratch; DVOError(DVO_EINVAL) on a SURF stream."""
         self.ctx.check(self.ctx.lib.dvo_knn_stream_set_detect_group(self.h, int(group)))
-        self.detect_group = int(group)
+        self.detect_group, self._pending = int(group), 0  # a pending detect() is dropped
 
     def set_surf_group(self, group: int):
         """SURF frames per detection launch from the next process() on (0: frame by frame).  Waits
         for the stream and allocates or frees the group's scratch; DVOError(DVO_EINVAL) on a SIFT stream."""
         self.ctx.check(self.ctx.lib.dvo_knn_stream_set_surf_group(self.h, int(group)))
-        self.surf_group = int(group)
+        self.surf_group, self._pending = int(group), 0  # a pending detect() is dropped
 
     def set_flann(self, trees: int, checks: int = 50):
         """The FLANN kd-forest matcher from the next process() on: trees 1..64 and checks >= 1; trees
@@ -553,6 +557,7 @@ class KnnFrameStream:
         rng_state to ops.THE_RNG_SEED; DVOError(DVO_EINVAL) on bad arguments."""
         self.ctx.check(self.ctx.lib.dvo_knn_stream_set_flann(self.h, int(trees), int(checks)))
         self.trees, self.checks = int(trees), int(checks) if trees else 0
+        self._pending = 0  # a pending detect() is dropped
 
     @property
     def matcher(self) -> str:
@@ -574,6 +579,21 @@ class KnnFrameStream:
         """Enqueue the batch (asynchronous).  frames: a uint8 [n, H, W] device tensor (rows contiguous,
         any row pitch) or a numpy array, which is uploaded first.  With wait_torch the batch is
         ordered after work queued on torch's current stream; pass False for frames already resident."""
+        frames, wait_torch = self._check_frames(frames, wait_torch)
+        n = frames.shape[0]
+        if records is None:
+            records = self.new_records(n - 1)
+            wait_torch = True  # the zero-fill runs on torch's stream: order the library's writes after it
+        if wait_torch:
+            self._after_torch()
+        self._pending = 0  # process replaces a pending detect()
+        self.ctx.check(self.ctx.lib.dvo_knn_stream_process(self.h, frames.data_ptr() if n else None, n,
+                                                           frames.stride(0), frames.stride(1),
+                                                           records.data_ptr() if n > 1 else None))
+        self._hold(frames, records)
+        return records
+
+    def _check_frames(self, frames, wait_torch):
         if isinstance(frames, np.ndarray):
             if frames.dtype != np.uint8 or frames.ndim != 3:
                 raise ValueError("frames must be uint8 [n, H, W]")
@@ -586,21 +606,92 @@ class KnnFrameStream:
             raise ValueError(f"frame size {w}x{h} != stream {self.width}x{self.height}")
         if n and (frames.stride(2) != 1 or frames.stride(1) < w):
             raise ValueError("frames rows must be contiguous")
-        if records is None:
-            records = self.new_records(n - 1)
-            wait_torch = True  # the zero-fill runs on torch's stream: order the library's writes after it
-        if wait_torch:
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(self.device))
-            self._ext.wait_event(ev)
-        self.ctx.check(self.ctx.lib.dvo_knn_stream_process(self.h, frames.data_ptr() if n else None, n,
-                                                           frames.stride(0), frames.stride(1),
-                                                           records.data_ptr() if n > 1 else None))
-        ev = torch.cuda.Event()  # keep the tensors alive until the library's stream is past them
+        return frames, wait_torch
+
+    def _after_torch(self):
+        """Order the library's stream after the work queued on torch's current stream."""
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        self._ext.wait_event(ev)
+
+    def _hold(self, *tensors):
+        """Keep the tensors alive until the library's stream is past them."""
+        ev = torch.cuda.Event()
         ev.record(self._ext)
-        self._held.append((ev, (frames, records)))
+        self._held.append((ev, tensors))
         while self._held and self._held[0][0].query():
             self._held.popleft()
+
+    def record_event(self) -> torch.cuda.Event:
+        """An event on the library's stream after everything enqueued so far."""
+        ev = torch.cuda.Event()
+        ev.record(self._ext)
+        return ev
+
+    def wait_event(self, ev):
+        """Order the library's stream after a torch.cuda.Event (None: nothing to wait for)."""
+        if ev is not None:
+            self._ext.wait_event(ev)
+
+    @staticmethod
+    def _word_tensor(t, n, what):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.uint64, torch.int64) \
+                or t.dim() != 1 or t.numel() != n or (n > 1 and t.stride(0) != 1):
+            raise ValueError(f"{what} must be a contiguous uint64 or int64 device tensor of {n} element(s)")
+        return t
+
+    def detect(self, frames, draws: torch.Tensor | None = None, wait_torch: bool = True):
+        """The first phase of process() (dvo_knn_stream_detect, asynchronous): the frames are detected
+        and features() works; finish() does the rest.  draws: a 1-element uint64 or int64 device
+        tensor (or such a view into a larger one, a rank's slot of a gather buffer) that receives
+        the theRNG draws the call's pairs will consume, 0 on a BFMatcher stream.  A detect while
+        another is pending replaces it.  Returns the device frames."""
+        frames, wait_torch = self._check_frames(frames, wait_torch)
+        n = frames.shape[0]
+        if draws is not None:
+            self._word_tensor(draws, 1, "draws")
+            if draws.device != self.device:
+                raise ValueError("draws must live on the stream's device")
+        if wait_torch:
+            self._after_torch()
+        self._pending = 0  # a refused call leaves nothing pending
+        self.ctx.check(self.ctx.lib.dvo_knn_stream_detect(self.h, frames.data_ptr() if n else None, n,
+                                                          frames.stride(0), frames.stride(1),
+                                                          None if draws is None else draws.data_ptr()))
+        self._pending = n
+        self._hold(frames, draws)
+        return frames
+
+    def finish(self, records: torch.Tensor | None = None, shard_draws: torch.Tensor | None = None, rank: int = 0,
+               wait_torch: bool = True) -> torch.Tensor:
+        """The second phase (dvo_knn_stream_finish, asynchronous): matching or forests, ratio test,
+        geometry and the records of the frames detect() left pending.  shard_draws: a device tensor
+        of one draws word per rank of a sharded stream (its length is the world size; entry
+        [rank] is not read): a FLANN stream plans its pairs after the draws of the ranks below
+        `rank` and leaves rng_state past the whole window; a BFMatcher stream ignores it.  With
+        wait_torch the phase is ordered after work queued on torch's current stream (the zero-fill
+        of new records, the collective that wrote shard_draws).  DVOError(DVO_EINVAL) when nothing
+        is pending."""
+        n = self._pending
+        world = 1
+        if shard_draws is not None:
+            world = shard_draws.numel() if isinstance(shard_draws, torch.Tensor) else 0
+            self._word_tensor(shard_draws, world, "shard_draws")
+            if shard_draws.device != self.device:
+                raise ValueError("shard_draws must live on the stream's device")
+        if records is None:
+            records = self.new_records(n - 1)
+            wait_torch = True
+        elif records.dtype != torch.uint8 or not records.is_cuda or not records.is_contiguous() \
+                or records.numel() < max(n - 1, 0) * PAIR_RECORD_DTYPE.itemsize:
+            raise ValueError(f"records must be a contiguous uint8 device tensor of {max(n - 1, 0)} records or more")
+        if wait_torch:
+            self._after_torch()
+        self.ctx.check(self.ctx.lib.dvo_knn_stream_finish(self.h, records.data_ptr(),
+                                                          None if shard_draws is None else shard_draws.data_ptr(),
+                                                          int(world), int(rank)))
+        self._pending = 0  # (a refused call leaves the detection pending)
+        self._hold(records, shard_draws)
         return records
 
     def sync(self):

@@ -508,6 +508,36 @@ int dvo_knn_stream_create(dvo_ctx* ctx, const dvo_knn_stream_config* cfg, dvo_kn
 void dvo_knn_stream_destroy(dvo_knn_stream* s);
 int dvo_knn_stream_process(dvo_knn_stream* s, const uint8_t* d_frames, int n_frames, int64_t frame_stride, int stride,
                            dvo_pair_record* d_records);
+/* dvo_knn_stream_process in two phases, for a stream sharded across ranks (a collective runs
+ * between them); process is detect(..., NULL) followed by finish(records, NULL, 1, 0) and launches
+ * the same kernels.  Neither phase synchronises, reads back or allocates.
+ *
+ * detect: detection of the n_frames frames (frame by frame or through a group detector) and the
+ * frame state.  With d_draws non-NULL (DEVICE memory, e.g. this rank's slot of an all-gather
+ * buffer) one more kernel writes a 64-bit word there: the theRNG draws the call's pairs will
+ * consume, the sum over its pairs of trees (2 nt - 1) for a pair that builds (nq >= 1, nt >= 2),
+ * 0 on a BFMatcher stream.  The stream is then "detected, pending": dvo_knn_stream_get_features
+ * works, dvo_knn_stream_get_matches does not until finish.  A detect while another is pending
+ * replaces it.  DVO_EINVAL as process (d_records aside).
+ *
+ * finish: matching or forests, ratio test, geometry, records and the status rewrite of the pending
+ * frames.  d_shard_draws NULL: exactly process's second half.  Non-NULL: `world` DEVICE words, the
+ * draws word of every rank for this window (entry [rank] is never read); a FLANN stream's RNG plan
+ * then starts from the stream's state jumped by pre = the sum of the entries below `rank` and
+ * leaves the state jumped by pre + own + post, post = the sum of the entries above `rank` and own
+ * counted from the frames, so every rank's state word is the state after the whole window, and
+ * the window's records equal one stream's over all its frames.  A call with a single pending
+ * frame has no pair and plans nothing, as in process: its state does not move, so a sharded
+ * stream gives every rank at least one pair per window.  A BFMatcher stream ignores the array.  dvo_knn_stream_set_rng_state between the phases is allowed and ordered before the plan;
+ * dvo_knn_stream_set_detect_group, _set_surf_group and _set_flann drop the pending detection.
+ * dvo_knn_stream_stage_times keeps its three figures across the two calls (a collective the
+ * caller orders between them counts into the matching figure).
+ * DVO_EINVAL: nothing pending, world outside 1..1024, rank outside 0..world - 1, d_records NULL
+ * with more than one pending frame. */
+int dvo_knn_stream_detect(dvo_knn_stream* s, const uint8_t* d_frames, int n_frames, int64_t frame_stride, int stride,
+                          uint64_t* d_draws);
+int dvo_knn_stream_finish(dvo_knn_stream* s, dvo_pair_record* d_records, const uint64_t* d_shard_draws, int world,
+                          int rank);
 int dvo_knn_stream_sync(dvo_knn_stream* s);
 /* The HIP stream the calls run on (the context's). */
 void* dvo_knn_stream_hip_stream(dvo_knn_stream* s);
@@ -568,6 +598,15 @@ size_t dvo_knn_stream_flann_bytes(int max_frames, int feat_cap, int trees);
  * kernel runs the same text. */
 int dvo_flann_rng_plan_host(uint64_t state, const int32_t* counts, int frames, int cap, int trees, uint64_t* starts,
                             uint64_t* state_out);
+/* Host only: the sharded plan of dvo_knn_stream_finish for one rank: counts[frames] are the
+ * detector counts of the rank's frames (frames >= 0; fewer than 2 is a rank without pairs),
+ * shard_draws[world] the ranks' draws words (NULL: nothing before or after; entry [rank] is not
+ * read).  starts[frames - 1], *final_state = the state after the whole window, *own_draws = the
+ * rank's draws word (any of the three may be NULL, starts only with frames < 2).  DVO_EINVAL:
+ * world outside 1..1024, rank outside 0..world - 1, cap < 1, trees outside 1..64. */
+int dvo_flann_rng_shard_host(uint64_t state, const int32_t* counts, int frames, int cap, int trees,
+                             const uint64_t* shard_draws, int world, int rank, uint64_t* starts, uint64_t* final_state,
+                             uint64_t* own_draws);
 /* After the last process call (these synchronise): frame `frame`'s features, desc n x 128 (SIFT)
  * or n x 64 (SURF) floats, *n = the detector's count (DVO_ECAP if > cap or the frame is marked);
  * pair `pair`'s kept matches in ascending queryIdx, *m = count (DVO_ECAP if > cap). */
