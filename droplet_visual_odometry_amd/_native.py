@@ -182,6 +182,12 @@ _SIGNATURES = {
     "dvo_knn_stream_get_matches": ([_vp, _c, _vp, _c, _ip], _c),
     "dvo_knn_stream_set_profiling": ([_vp, _c], _c),
     "dvo_knn_stream_stage_times": ([_vp, _vp], _c),
+    "dvo_knn_stream_set_raw_input": ([_vp, _c], _c),
+    "dvo_knn_stream_raw_input_bytes": ([_c, _c, _c], ctypes.c_size_t),
+    "dvo_knn_stream_detect_raw": ([_vp, _vp, _vp, _c, _i64, _c, _c, _vp], _c),
+    "dvo_knn_stream_process_raw": ([_vp, _vp, _vp, _c, _i64, _c, _c, _vp], _c),
+    "dvo_knn_stream_detect_jpeg": ([_vp, _vp, _vp, _vp, _vp, _c, _vp], _c),
+    "dvo_knn_stream_process_jpeg": ([_vp, _vp, _vp, _vp, _vp, _c, _vp], _c),
     "dvo_stream_hip_stream": ([_vp], _vp),
     "dvo_stream_set_profiling": ([_vp, _c], _c),
     "dvo_stream_reset_pose": ([_vp, _vp, _vp], _c),

@@ -2503,9 +2503,18 @@ struct dvo_knn_stream {
     bool pending_timed = false;  // the pending detection recorded ev[0], ev[1]
     bool profiling = false, timed = false;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    // dvo_knn_stream_set_raw_input: max_frames gray frames of raw_pitch-byte rows, what a colour,
+    // distorted or JPEG call detects on
+    DeviceAllocs raw_mem;
+    uint8_t* raw = nullptr;
+    int raw_pitch = 0;
+    // A raw-input call records ev_in[k] before its input launch, k the one the last accepted call
+    // does not use (first_ev; -1: that call began at ev[0]), so a refused call disturbs no figure.
+    hipEvent_t ev_in[2] = {nullptr, nullptr};
+    int first_ev = -1;
 
     ~dvo_knn_stream() {
-        for (auto e : ev)
+        for (auto e : {ev[0], ev[1], ev[2], ev[3], ev_in[0], ev_in[1]})
             if (e) hipEventDestroy(e);
     }
 };
@@ -2586,14 +2595,15 @@ int dvo_knn_stream_process(dvo_knn_stream* st, const uint8_t* d_frames, int n_fr
     return rc ? rc : dvo_knn_stream_finish(st, d_records, nullptr, 1, 0);
 }
 
-int dvo_knn_stream_detect(dvo_knn_stream* st, const uint8_t* d_frames, int n_frames, int64_t frame_stride, int stride,
-                          uint64_t* d_draws) {
-    if (!st) return DVO_EINVAL;
+namespace {
+// Detection of n_frames gray frames (d_frames, frame_stride, stride: the caller's, or the raw-input
+// slab) and the frame state: dvo_knn_stream_detect after its argument checks.  ev_in: the event a
+// raw-input call recorded before its input launch; it takes ev[0]'s place in the stage times.
+int knn_stream_detect_gray(dvo_knn_stream* st, const uint8_t* d_frames, int n_frames, int64_t frame_stride, int stride,
+                           uint64_t* d_draws, int ev_in = -1) {
     dvo_ctx* ctx = st->ctx;
     const dvo_knn_stream_config& c = st->cfg;
     const int w = c.width, h = c.height;
-    if (n_frames < 1 || n_frames > c.max_frames) return fail(ctx, DVO_EINVAL, "n_frames out of range (1..max_frames)");
-    if (!d_frames || stride < w) return fail(ctx, DVO_EINVAL, "bad frame or record buffer");
     HIP_TRY(hipSetDevice(ctx->device));
     // a group detector has its own scratch: the context's plan is not used
     const bool grouped = st->grp.group > 0 || st->sgrp.group > 0;
@@ -2605,7 +2615,8 @@ int dvo_knn_stream_detect(dvo_knn_stream* st, const uint8_t* d_frames, int n_fra
     hipEvent_t* ev = st->profiling ? st->ev : nullptr;
     st->last_frames = st->pending = st->matched_frames = 0;  // a pending detection is replaced
     st->timed = st->pending_timed = false;
-    if (ev) HIP_TRY(hipEventRecord(ev[0], s));
+    if (ev && ev_in < 0) HIP_TRY(hipEventRecord(ev[0], s));
+    st->first_ev = ev_in;
     // detection in place on the caller's frames: a group of frames per launch straight into the
     // frame slots, or frame by frame on the plan's single scratch
     if (st->grp.group > 0)
@@ -2644,6 +2655,17 @@ int dvo_knn_stream_detect(dvo_knn_stream* st, const uint8_t* d_frames, int n_fra
     st->last_frames = st->pending = n_frames;
     st->pending_timed = ev != nullptr;
     return DVO_OK;
+}
+}  // namespace
+
+int dvo_knn_stream_detect(dvo_knn_stream* st, const uint8_t* d_frames, int n_frames, int64_t frame_stride, int stride,
+                          uint64_t* d_draws) {
+    if (!st) return DVO_EINVAL;
+    dvo_ctx* ctx = st->ctx;
+    const dvo_knn_stream_config& c = st->cfg;
+    if (n_frames < 1 || n_frames > c.max_frames) return fail(ctx, DVO_EINVAL, "n_frames out of range (1..max_frames)");
+    if (!d_frames || stride < c.width) return fail(ctx, DVO_EINVAL, "bad frame or record buffer");
+    return knn_stream_detect_gray(st, d_frames, n_frames, frame_stride, stride, d_draws);
 }
 
 int dvo_knn_stream_finish(dvo_knn_stream* st, dvo_pair_record* d_records, const uint64_t* d_shard_draws, int world,
@@ -2797,8 +2819,8 @@ int dvo_knn_stream_set_profiling(dvo_knn_stream* s, int enable) {
     dvo_ctx* ctx = s->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
     if (enable)
-        for (auto& e : s->ev)
-            if (!e) HIP_TRY(hipEventCreate(&e));
+        for (hipEvent_t* e : {&s->ev[0], &s->ev[1], &s->ev[2], &s->ev[3], &s->ev_in[0], &s->ev_in[1]})
+            if (!*e) HIP_TRY(hipEventCreate(e));
     s->profiling = enable != 0;
     s->timed = false;
     return DVO_OK;
@@ -2812,7 +2834,7 @@ int dvo_knn_stream_stage_times(dvo_knn_stream* s, double* ms) {
     HIP_TRY(hipEventSynchronize(s->ev[3]));
     for (int k = 0; k < 3; ++k) {
         float t = 0.f;
-        HIP_TRY(hipEventElapsedTime(&t, s->ev[k], s->ev[k + 1]));
+        HIP_TRY(hipEventElapsedTime(&t, k == 0 && s->first_ev >= 0 ? s->ev_in[s->first_ev] : s->ev[k], s->ev[k + 1]));
         ms[k] = t;
     }
     return DVO_OK;
@@ -4049,6 +4071,151 @@ int dvo_stream_submit_jpeg(dvo_stream* s, dvo_jpeg* j, dvo_undistort* u, const u
     const int rc = check_stream_jpeg(s, j, u, bufs, lens, n, 2, d_records);
     if (rc) return rc;
     return run_stream_jpeg(s, j, u, bufs, lens, n, d_records, false);
+}
+
+// ---------------------------------------------------------------------------
+// Raw input for the k-NN stream: colour (v3:132), distorted (v3:133) and JPEG (v3:127) frames are
+// brought to gray in the stream's own slab on its HIP stream, and detection runs on the slab.
+// ---------------------------------------------------------------------------
+namespace {
+
+size_t knn_raw_pitch(int width) { return ((size_t)width + 15) & ~(size_t)15; }
+
+// what check_stream_bgr and check_stream_jpeg refuse, for a dvo_knn_stream
+int check_knn_raw_common(dvo_knn_stream* s, const dvo_undistort* u, int n, const dvo_pair_record* d_records,
+                         bool records_needed, bool slab_needed) {
+    dvo_ctx* ctx = s->ctx;
+    if (u && (u->U.w != s->cfg.width || u->U.h != s->cfg.height))
+        return fail(ctx, DVO_EINVAL, "undistort size != stream size");
+    if (u && u->ctx->device != ctx->device)
+        return fail(ctx, DVO_EINVAL, "undistorter and stream are on different devices");
+    if (n < 1 || n > s->cfg.max_frames) return fail(ctx, DVO_EINVAL, "n_frames out of range (1..max_frames)");
+    if (records_needed && n > 1 && !d_records) return fail(ctx, DVO_EINVAL, "null records");
+    if (slab_needed && !s->raw)
+        return fail(ctx, DVO_EINVAL, "raw input is not enabled: call dvo_knn_stream_set_raw_input(stream, 1) first");
+    return DVO_OK;
+}
+
+int check_knn_raw(dvo_knn_stream* s, const dvo_undistort* u, const uint8_t* d_frames, int n, int stride, int channels,
+                  const dvo_pair_record* d_records, bool records_needed) {
+    dvo_ctx* ctx = s->ctx;
+    if (channels != 1 && !channels_ok(channels)) return fail(ctx, DVO_EINVAL, "channels must be 1, 3 or 4");
+    if (!d_frames || (int64_t)stride < (int64_t)s->cfg.width * channels)
+        return fail(ctx, DVO_EINVAL, "bad frame buffer (null, or rows shorter than width * channels)");
+    return check_knn_raw_common(s, u, n, d_records, records_needed, channels != 1 || u);
+}
+
+int check_knn_jpeg(dvo_knn_stream* s, dvo_jpeg* j, const dvo_undistort* u, const uint8_t* const* bufs, const int64_t* lens,
+                   int n, const dvo_pair_record* d_records, bool records_needed) {
+    dvo_ctx* ctx = s->ctx;
+    if (!j) return fail(ctx, DVO_EINVAL, "null decoder");
+    if (j->ctx->device != ctx->device) return fail(ctx, DVO_EINVAL, "decoder and stream are on different devices");
+    if (!bufs || !lens) return fail(ctx, DVO_EINVAL, "null buffer");
+    return check_knn_raw_common(s, u, n, d_records, records_needed, true);
+}
+
+// the event a profiled raw-input call begins at: recorded before the input launch (-1: not profiled)
+int knn_raw_begin(dvo_knn_stream* s, int* ev_in) {
+    dvo_ctx* ctx = s->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    *ev_in = -1;
+    if (!s->profiling) return DVO_OK;
+    *ev_in = s->first_ev == 0 ? 1 : 0;
+    HIP_TRY(hipEventRecord(s->ev_in[*ev_in], ctx->stream));
+    return DVO_OK;
+}
+
+// checked arguments: one launch into the slab, then detection there
+int knn_detect_raw(dvo_knn_stream* s, dvo_undistort* u, const uint8_t* d_frames, int n, int64_t frame_stride, int stride,
+                   int channels, uint64_t* d_draws) {
+    dvo_ctx* ctx = s->ctx;
+    if (channels == 1 && !u) return knn_stream_detect_gray(s, d_frames, n, frame_stride, stride, d_draws);
+    int ev_in = -1;
+    const int rc = knn_raw_begin(s, &ev_in);
+    if (rc) return rc;
+    const int w = s->cfg.width, h = s->cfg.height, pw = s->raw_pitch;
+    const int64_t fs = (int64_t)pw * h;
+    hipStream_t st = ctx->stream;
+    if (channels == 1)
+        HIP_TRY(launch_undistort_remap(u->U, u->d_xy, u->d_frac, d_frames, n, frame_stride, stride, s->raw, fs, pw, st));
+    else if (u)
+        HIP_TRY(launch_undistort_remap_bgr(u->U, u->d_xy, u->d_frac, kGray14, d_frames, n, frame_stride, stride, channels,
+                                           s->raw, fs, pw, st));
+    else
+        HIP_TRY(launch_bgr2gray(kGray14, d_frames, n, frame_stride, stride, channels, w, h, s->raw, fs, pw, st));
+    return knn_stream_detect_gray(s, s->raw, n, fs, pw, d_draws, ev_in);
+}
+
+// checked arguments: the decoder writes (and with u remaps) into the slab, then detection there.
+// A header the parser refuses returns before anything is launched or the stream's state changes.
+int knn_detect_jpeg(dvo_knn_stream* s, dvo_jpeg* j, dvo_undistort* u, const uint8_t* const* bufs, const int64_t* lens,
+                    int n, uint64_t* d_draws) {
+    dvo_ctx* ctx = s->ctx;
+    int ev_in = -1;
+    int rc = knn_raw_begin(s, &ev_in);
+    if (rc) return rc;
+    const int pw = s->raw_pitch;
+    const int64_t fs = (int64_t)pw * s->cfg.height;
+    rc = jpeg_decode_impl(j, bufs, lens, n, 1, s->raw, fs, pw, j->stream_entropy, ctx->stream, u, s->cfg.width,
+                          s->cfg.height);
+    if (rc) return j->ctx == ctx ? rc : fail(ctx, rc, j->ctx->err);
+    return knn_stream_detect_gray(s, s->raw, n, fs, pw, d_draws, ev_in);
+}
+
+}  // namespace
+
+size_t dvo_knn_stream_raw_input_bytes(int width, int height, int max_frames) {
+    if (width < 1 || height < 1 || max_frames < 1) return 0;
+    return (size_t)max_frames * knn_raw_pitch(width) * (size_t)height;
+}
+
+int dvo_knn_stream_set_raw_input(dvo_knn_stream* s, int enable) {
+    if (!s) return DVO_EINVAL;
+    dvo_ctx* ctx = s->ctx;
+    if ((enable != 0) == (s->raw != nullptr)) return DVO_OK;
+    s->pending = 0;  // a detection waiting for dvo_knn_stream_finish is dropped
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // the old slab may be in use
+    s->raw_mem.release();
+    s->raw = nullptr;
+    s->raw_pitch = 0;
+    if (!enable) return DVO_OK;
+    const hipError_t he =
+        s->raw_mem.alloc(&s->raw, dvo_knn_stream_raw_input_bytes(s->cfg.width, s->cfg.height, s->cfg.max_frames));
+    if (he != hipSuccess) s->raw = nullptr;
+    HIP_TRY(he);
+    s->raw_pitch = (int)knn_raw_pitch(s->cfg.width);
+    return DVO_OK;
+}
+
+int dvo_knn_stream_detect_raw(dvo_knn_stream* s, dvo_undistort* u, const uint8_t* d_frames, int n_frames,
+                              int64_t frame_stride, int stride, int channels, uint64_t* d_draws) {
+    if (!s) return DVO_EINVAL;
+    const int rc = check_knn_raw(s, u, d_frames, n_frames, stride, channels, nullptr, false);
+    return rc ? rc : knn_detect_raw(s, u, d_frames, n_frames, frame_stride, stride, channels, d_draws);
+}
+
+int dvo_knn_stream_process_raw(dvo_knn_stream* s, dvo_undistort* u, const uint8_t* d_frames, int n_frames,
+                               int64_t frame_stride, int stride, int channels, dvo_pair_record* d_records) {
+    if (!s) return DVO_EINVAL;
+    int rc = check_knn_raw(s, u, d_frames, n_frames, stride, channels, d_records, true);
+    if (!rc) rc = knn_detect_raw(s, u, d_frames, n_frames, frame_stride, stride, channels, nullptr);
+    return rc ? rc : dvo_knn_stream_finish(s, d_records, nullptr, 1, 0);
+}
+
+int dvo_knn_stream_detect_jpeg(dvo_knn_stream* s, dvo_jpeg* j, dvo_undistort* u, const uint8_t* const* bufs,
+                               const int64_t* lens, int n, uint64_t* d_draws) {
+    if (!s) return DVO_EINVAL;
+    const int rc = check_knn_jpeg(s, j, u, bufs, lens, n, nullptr, false);
+    return rc ? rc : knn_detect_jpeg(s, j, u, bufs, lens, n, d_draws);
+}
+
+int dvo_knn_stream_process_jpeg(dvo_knn_stream* s, dvo_jpeg* j, dvo_undistort* u, const uint8_t* const* bufs,
+                                const int64_t* lens, int n, dvo_pair_record* d_records) {
+    if (!s) return DVO_EINVAL;
+    int rc = check_knn_jpeg(s, j, u, bufs, lens, n, d_records, true);
+    if (!rc) rc = knn_detect_jpeg(s, j, u, bufs, lens, n, nullptr);
+    return rc ? rc : dvo_knn_stream_finish(s, d_records, nullptr, 1, 0);
 }
 
 int dvo_jpeg_get_coefficients(dvo_jpeg* j, int frame, int16_t* out, int64_t cap, int64_t* n_out) {

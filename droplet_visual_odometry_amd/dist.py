@@ -335,13 +335,19 @@ class ShardedKnnRunner:
     that rewrites it; torch's stream waits for the detection before the draws gather and for the
     records before the exchange; finish waits for the gather.  The draws words live in per-slot
     buffers under the same events.  Every rank needs at least one pair per window
-    (window_pairs >= world)."""
+    (window_pairs >= world).
+
+    raw_input: the stream takes what KnnFrameStream(raw_input=True) takes, and step's frames may be
+    a mono batch, a colour batch [n_local + 1, H, W, 3 or 4] or a list of n_local + 1 JPEG files;
+    undistort (an ops.Undistorter on this rank's device; it implies raw_input) remaps every window's
+    frames on the way, whatever their form: K is then the new camera matrix.  The input stage is
+    part of step (1), on the library's stream; the rest of the schedule is the same."""
 
     def __init__(self, width: int, height: int, K, window_pairs: int, world: int, rank: int, marker_length: float,
                  detector: str = "sift", matcher: str = "bf", feat_cap: int | None = None, detect_group: int = 0,
                  surf_group: int = 0, trees: int = 5, checks: int = 50, rng_state: int | None = None,
                  hessian_threshold: float = 400.0, max_iters: int = 1000, k: int = 4, host_gather: bool = False,
-                 group=None, ctx=None, slots: int = 2):
+                 group=None, ctx=None, slots: int = 2, undistort=None, raw_input: bool = False):
         if detector not in ("sift", "surf"):
             raise ValueError("detector must be 'sift' or 'surf'")
         if matcher not in ("bf", "flann"):
@@ -371,7 +377,8 @@ class ShardedKnnRunner:
         self.ks = KnnFrameStream(width, height, K, self.n_local + 1, detector=detector, feat_cap=feat_cap,
                                  hessian_threshold=hessian_threshold, max_iters=max_iters, ctx=self.ctx,
                                  detect_group=detect_group, surf_group=surf_group, matcher=matcher, trees=trees,
-                                 checks=checks, rng_state=rng_state)
+                                 checks=checks, rng_state=rng_state, raw_input=raw_input or undistort is not None)
+        self.undistort = undistort
         # per slot: this rank's draws word (detect writes it) and the gathered words (finish reads them)
         self.own = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in self.shs] if self.flann else None
         self.all = [torch.zeros(self.world, dtype=torch.int64, device=dev) for _ in self.shs] if self.flann else None
@@ -403,26 +410,35 @@ class ShardedKnnRunner:
             torch.cuda.current_stream(self.device).wait_event(self.ks.record_event())
             dist.all_gather_into_tensor(all_, own, group=self.group)
 
+    def _detect(self, frames, jpeg, draws, wait_torch):
+        """Step (1): the window's frames in whichever form they come (a JPEG call always waits for torch)."""
+        if jpeg:
+            self.ks.detect_jpeg(frames, draws=draws, undistort=self.undistort)
+        else:
+            self.ks.detect(frames, draws=draws, wait_torch=wait_torch, undistort=self.undistort)
+
     def step(self, frames, c_prev, c_cur, wait_torch: bool = True):
-        """wait_torch as ShardedStreamRunner.step: pass False only for frames already resident (a
-        slot's first use is still ordered after its zero-fill)."""
+        """frames: the rank's n_local + 1 frames, a mono batch or, on a raw_input runner, a colour
+        batch or a list of JPEG files.  wait_torch as ShardedStreamRunner.step: pass False only for
+        frames already resident (a slot's first use is still ordered after its zero-fill)."""
         import torch
         s = self.i % len(self.shs)
         sh = self.shs[s]
         first_use = self.i < len(self.shs)
         self.i += 1
-        if frames.shape[0] != self.n_local + 1:
+        jpeg = isinstance(frames, (list, tuple))
+        if (len(frames) if jpeg else frames.shape[0]) != self.n_local + 1:
             raise ValueError(f"rank {self.rank} needs {self.n_local + 1} frames per window")
         ks = self.ks
         ks.wait_event(sh.done)  # the slot's previous collective has read its send buffer
         sh.set_corners(c_prev, c_cur)  # torch's stream, after that collective
         if self.flann:
             own, all_ = self.own[s], self.all[s]
-            ks.detect(frames, draws=own, wait_torch=wait_torch or first_use)
+            self._detect(frames, jpeg, own, wait_torch or first_use)
             self._gather_draws(own, all_)
             ks.finish(sh.records, shard_draws=all_, rank=self.rank, wait_torch=True)  # after the gather
         else:
-            ks.detect(frames, wait_torch=wait_torch or first_use)
+            self._detect(frames, jpeg, None, wait_torch or first_use)
             ks.finish(sh.records, wait_torch=False)
         if self.host_gather:
             ks.sync()

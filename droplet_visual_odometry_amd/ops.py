@@ -1113,6 +1113,14 @@ def knn_stream_flann_bytes(max_frames, feat_cap, trees=5) -> int:
     return int(load_library().dvo_knn_stream_flann_bytes(int(max_frames), int(feat_cap), int(trees)))
 
 
+def knn_stream_raw_input_bytes(width, height, max_frames) -> int:
+    """Device bytes stream.KnnFrameStream(raw_input=True) allocates beside the mono stream's
+    (dvo_knn_stream_raw_input_bytes): the gray slab, max_frames * ((width + 15) & ~15) * height;
+    0 for an argument below 1."""
+    from ._native import load_library
+    return int(load_library().dvo_knn_stream_raw_input_bytes(int(width), int(height), int(max_frames)))
+
+
 KNN_DETECTORS = {"sift": 0, "surf": 1}
 KNN_MATCHERS = {"bf": 0, "flann": 1}
 

@@ -483,13 +483,22 @@ class KnnFrameStream:
     built pair, and carries it from call to call, so the records do not depend on the split.
 
     process() is detect() followed by finish(); a stream sharded across ranks (dist.ShardedKnnRunner)
-    calls the two phases itself, with the all-gather of the ranks' draws words between them."""
+    calls the two phases itself, with the all-gather of the ranks' draws words between them.
+
+    raw_input (dvo_knn_stream_set_raw_input): the stream also takes what a camera delivers, as
+    FrameStream does: colour frames ([n, H, W, 3 or 4], cv.cvtColor), distorted frames (undistort=
+    an ops.Undistorter, cv.undistort) and JPEG files (process_jpeg / detect_jpeg, cv.imdecode).  One
+    launch on the stream's own HIP stream brings them to gray in a slab of
+    ops.knn_stream_raw_input_bytes(width, height, max_frames) more device memory, and detection
+    runs there; the records are those of process() on the gray frames ops.bgr2gray_device,
+    Undistorter.apply or JpegDecoder.decode make.  Construct the stream with the new camera matrix
+    as K when its frames are undistorted.  Plain mono frames stay in place, slab or not."""
 
     def __init__(self, width: int, height: int, K, max_frames: int, detector="sift", feat_cap: int | None = None,
                  hessian_threshold: float = 400.0, ratio: float = 0.75, prob: float = 0.999, threshold: float = 1.0,
                  max_iters: int = 1000, dist_thresh: float = 50.0, ctx: Context | None = None, *,
                  detect_group: int = 0, surf_group: int = 0, matcher: str = "bf", trees: int = 5, checks: int = 50,
-                 rng_state: int | None = None):
+                 rng_state: int | None = None, raw_input: bool = False):
         from ._native import KnnStreamConfig
         from .ops import KNN_DETECTORS, KNN_MATCHERS
         self.h = None
@@ -525,6 +534,10 @@ class KnnFrameStream:
             self.set_flann(trees, checks)
             if rng_state is not None:
                 self.rng_state = rng_state
+        self.raw_input = False
+        self._jpeg = None
+        if raw_input:
+            self.set_raw_input(True)
         self._ext = torch.cuda.ExternalStream(self.hip_stream, device=self.device)
         self._held = collections.deque()  # (event, tensors) in flight on the library's stream
         self._pending = 0  # frames of the last detect() (sizes finish()'s records)
@@ -559,6 +572,14 @@ class KnnFrameStream:
         self.trees, self.checks = int(trees), int(checks) if trees else 0
         self._pending = 0  # a pending detect() is dropped
 
+    def set_raw_input(self, enable: bool = True):
+        """Colour, distorted and JPEG input from the next call on (False: mono frames only).  A change
+        waits for the stream, allocates or frees the gray slab and drops a pending detect()."""
+        enable = bool(enable)
+        self.ctx.check(self.ctx.lib.dvo_knn_stream_set_raw_input(self.h, int(enable)))
+        if enable != self.raw_input:
+            self.raw_input, self._pending = enable, 0
+
     @property
     def matcher(self) -> str:
         return "flann" if self.trees else "bf"
@@ -575,23 +596,67 @@ class KnnFrameStream:
     def rng_state(self, state: int):
         self.ctx.check(self.ctx.lib.dvo_knn_stream_set_rng_state(self.h, ctypes.c_uint64(int(state))))
 
-    def process(self, frames, records: torch.Tensor | None = None, wait_torch: bool = True) -> torch.Tensor:
+    def process(self, frames, records: torch.Tensor | None = None, wait_torch: bool = True,
+                undistort=None) -> torch.Tensor:
         """Enqueue the batch (asynchronous).  frames: a uint8 [n, H, W] device tensor (rows contiguous,
         any row pitch) or a numpy array, which is uploaded first.  With wait_torch the batch is
-        ordered after work queued on torch's current stream; pass False for frames already resident."""
-        frames, wait_torch = self._check_frames(frames, wait_torch)
+        ordered after work queued on torch's current stream; pass False for frames already resident.
+        On a raw_input stream: colour frames (uint8 [n, H, W, C], C = 3 or 4: B, G, R first) are
+        converted to gray, and with undistort (an ops.Undistorter) colour or mono frames are
+        remapped, into the stream's slab on the way (dvo_knn_stream_process_raw)."""
+        if self._is_raw(frames, undistort):
+            frames, wait_torch, c = self._check_raw(frames, wait_torch, undistort)
+        else:
+            (frames, wait_torch), c = self._check_frames(frames, wait_torch), 0
         n = frames.shape[0]
         if records is None:
             records = self.new_records(n - 1)
             wait_torch = True  # the zero-fill runs on torch's stream: order the library's writes after it
         if wait_torch:
             self._after_torch()
-        self._pending = 0  # process replaces a pending detect()
-        self.ctx.check(self.ctx.lib.dvo_knn_stream_process(self.h, frames.data_ptr() if n else None, n,
-                                                           frames.stride(0), frames.stride(1),
-                                                           records.data_ptr() if n > 1 else None))
+        if c:
+            self.ctx.check(self.ctx.lib.dvo_knn_stream_process_raw(
+                self.h, undistort.h_ if undistort is not None else None, frames.data_ptr(), n, frames.stride(0),
+                frames.stride(1), c, records.data_ptr() if n > 1 else None))  # a refused call changes nothing
+            self._pending = 0
+        else:
+            self._pending = 0  # process replaces a pending detect()
+            self.ctx.check(self.ctx.lib.dvo_knn_stream_process(self.h, frames.data_ptr() if n else None, n,
+                                                               frames.stride(0), frames.stride(1),
+                                                               records.data_ptr() if n > 1 else None))
         self._hold(frames, records)
         return records
+
+    @staticmethod
+    def _is_raw(frames, undistort) -> bool:
+        """Whether the batch takes the raw-input path: colour frames, or any frames to be undistorted."""
+        return undistort is not None or (isinstance(frames, np.ndarray) and frames.ndim == 4) \
+            or (isinstance(frames, torch.Tensor) and frames.dim() == 4)
+
+    def _check_undistort(self, undistort):
+        if not self.raw_input:
+            raise ValueError("the stream takes mono frames only: construct it with raw_input=True or call "
+                             "set_raw_input(True)")
+        if undistort is not None and (undistort.w, undistort.h) != (self.width, self.height):
+            raise ValueError(f"undistorter size {undistort.w}x{undistort.h} != stream {self.width}x{self.height}")
+
+    def _check_raw(self, frames, wait_torch, undistort):
+        """(device frames, wait_torch, channels) of a raw-input batch; ValueError before any library call."""
+        from .ops import check_colour_frames
+        if isinstance(frames, np.ndarray) and frames.ndim == 4:
+            if frames.dtype != np.uint8 or frames.shape[3] not in (3, 4):
+                raise ValueError("frames must be uint8 [n, H, W, 3 or 4]")
+            frames = torch.from_numpy(np.ascontiguousarray(frames)).to(self.device)
+            wait_torch = True
+        if isinstance(frames, torch.Tensor) and frames.dim() == 4:
+            n, _, _, c = check_colour_frames(frames, "frames", (self.width, self.height), "stream")
+        else:
+            (frames, wait_torch), c = self._check_frames(frames, wait_torch), 1
+            n = frames.shape[0]
+        if n < 1:
+            raise ValueError("frames is empty")
+        self._check_undistort(undistort)
+        return frames, wait_torch, c
 
     def _check_frames(self, frames, wait_torch):
         if isinstance(frames, np.ndarray):
@@ -640,27 +705,96 @@ class KnnFrameStream:
             raise ValueError(f"{what} must be a contiguous uint64 or int64 device tensor of {n} element(s)")
         return t
 
-    def detect(self, frames, draws: torch.Tensor | None = None, wait_torch: bool = True):
+    def detect(self, frames, draws: torch.Tensor | None = None, wait_torch: bool = True, undistort=None):
         """The first phase of process() (dvo_knn_stream_detect, asynchronous): the frames are detected
         and features() works; finish() does the rest.  draws: a 1-element uint64 or int64 device
         tensor (or such a view into a larger one, a rank's slot of a gather buffer) that receives
         the theRNG draws the call's pairs will consume, 0 on a BFMatcher stream.  A detect while
-        another is pending replaces it.  Returns the device frames."""
-        frames, wait_torch = self._check_frames(frames, wait_torch)
+        another is pending replaces it.  Returns the device frames.  Colour frames and undistort=
+        as in process() (dvo_knn_stream_detect_raw); such a call, when refused, leaves a pending
+        detection as it was."""
+        if self._is_raw(frames, undistort):
+            frames, wait_torch, c = self._check_raw(frames, wait_torch, undistort)
+        else:
+            (frames, wait_torch), c = self._check_frames(frames, wait_torch), 0
         n = frames.shape[0]
+        self._check_draws(draws)
+        if wait_torch:
+            self._after_torch()
+        if c:
+            self.ctx.check(self.ctx.lib.dvo_knn_stream_detect_raw(
+                self.h, undistort.h_ if undistort is not None else None, frames.data_ptr(), n, frames.stride(0),
+                frames.stride(1), c, None if draws is None else draws.data_ptr()))
+        else:
+            self._pending = 0  # a refused call leaves nothing pending
+            self.ctx.check(self.ctx.lib.dvo_knn_stream_detect(self.h, frames.data_ptr() if n else None, n,
+                                                              frames.stride(0), frames.stride(1),
+                                                              None if draws is None else draws.data_ptr()))
+        self._pending = n
+        self._hold(frames, draws)
+        return frames
+
+    def _check_draws(self, draws):
         if draws is not None:
             self._word_tensor(draws, 1, "draws")
             if draws.device != self.device:
                 raise ValueError("draws must live on the stream's device")
-        if wait_torch:
-            self._after_torch()
-        self._pending = 0  # a refused call leaves nothing pending
-        self.ctx.check(self.ctx.lib.dvo_knn_stream_detect(self.h, frames.data_ptr() if n else None, n,
-                                                          frames.stride(0), frames.stride(1),
-                                                          None if draws is None else draws.data_ptr()))
+
+    # ---- JPEG frames (dvo_knn_stream_process_jpeg / _detect_jpeg): see include/dvo.h -----------
+    @property
+    def jpeg_decoder(self):
+        """The stream's ops.JpegDecoder (made at the first JPEG call); its status() tells which
+        frames of the last JPEG call were corrupt, after a sync()."""
+        if self._jpeg is None:
+            from .ops import JpegDecoder
+            group = min(int(self.max_frames), JpegDecoder.default_group_frames(self.width, self.height))
+            self._jpeg = JpegDecoder(self.width, self.height, group_frames=group, ctx=self.ctx)
+        return self._jpeg
+
+    def _check_jpeg(self, blobs, undistort, entropy):
+        from .ops import JPEG_ENTROPY, jpeg_blobs
+        arrs, ptrs, lens = jpeg_blobs(blobs, self.max_frames)
+        self._check_undistort(undistort)
+        if entropy is not None and entropy not in JPEG_ENTROPY:
+            raise ValueError(f"entropy must be one of {sorted(JPEG_ENTROPY)}")
+        dec = self.jpeg_decoder
+        if entropy is not None:
+            dec.set_stream_entropy(entropy)
+        return arrs, ptrs, lens, dec
+
+    def process_jpeg(self, blobs, records: torch.Tensor | None = None, undistort=None, entropy=None) -> torch.Tensor:
+        """process() of a list of JPEG files (bytes-like) of the stream's size, on a raw_input stream:
+        decoded to gray on the device, and remapped by `undistort` (ops.Undistorter) if given, into
+        the stream's slab.  entropy: "device" or "device_split" (ops.JpegDecoder.decode), kept for
+        the calls that follow; None: as it is ("device" at first).  A frame with corrupt
+        entropy-coded data does not fail the call: jpeg_decoder.status() names it."""
+        arrs, ptrs, lens, dec = self._check_jpeg(blobs, undistort, entropy)
+        n = len(arrs)
+        if records is None:
+            records = self.new_records(n - 1)
+        self._after_torch()
+        self.ctx.check(self.ctx.lib.dvo_knn_stream_process_jpeg(
+            self.h, dec.h_, undistort.h_ if undistort is not None else None, ptrs, lens, n,
+            records.data_ptr() if n > 1 else None))
+        dec._n = n
+        self._pending = 0
+        self._hold(records)
+        return records
+
+    def detect_jpeg(self, blobs, draws: torch.Tensor | None = None, undistort=None, entropy=None):
+        """detect() of a list of JPEG files (see process_jpeg); finish() does the rest.  Returns the
+        number of frames."""
+        arrs, ptrs, lens, dec = self._check_jpeg(blobs, undistort, entropy)
+        n = len(arrs)
+        self._check_draws(draws)
+        self._after_torch()
+        self.ctx.check(self.ctx.lib.dvo_knn_stream_detect_jpeg(
+            self.h, dec.h_, undistort.h_ if undistort is not None else None, ptrs, lens, n,
+            None if draws is None else draws.data_ptr()))
+        dec._n = n
         self._pending = n
-        self._hold(frames, draws)
-        return frames
+        self._hold(draws)
+        return n
 
     def finish(self, records: torch.Tensor | None = None, shard_draws: torch.Tensor | None = None, rank: int = 0,
                wait_torch: bool = True) -> torch.Tensor:
@@ -737,6 +871,9 @@ class KnnFrameStream:
         if getattr(self, "h", None):
             self.ctx.lib.dvo_knn_stream_destroy(self.h)  # synchronises the stream first
             self.h = None
+            if getattr(self, "_jpeg", None) is not None:  # its work ran on the stream just synchronised
+                self._jpeg.close()
+                self._jpeg = None
             if getattr(self, "_held", None):
                 self._held.clear()
 

@@ -617,6 +617,49 @@ int dvo_knn_stream_get_matches(dvo_knn_stream* s, int pair, dvo_dmatch* out, int
  * (synchronises; DVO_EINVAL before a profiled call). */
 int dvo_knn_stream_set_profiling(dvo_knn_stream* s, int enable);
 int dvo_knn_stream_stage_times(dvo_knn_stream* s, double* ms);
+/* Raw input for the k-NN stream: colour (cv.cvtColor, v3:132), distorted (cv.undistort, v3:133)
+ * and JPEG (cv.imdecode, v3:127) frames, as dvo_stream_process_bgr / _undistorted / _jpeg take
+ * them for the ORB stream.  The input is brought to gray in a slab of the stream's own, on the
+ * stream's HIP stream, by one launch per call (the decoder: its launches per group), and
+ * detection runs on the slab; everything after is dvo_knn_stream_detect / _finish unchanged, so
+ * records, features and matches equal those of dvo_knn_stream_process on the gray frames that
+ * dvo_bgr2gray, dvo_undistort_apply(_bgr) or dvo_jpeg_decode make.
+ *
+ * set_raw_input: enable != 0 allocates the slab, max_frames frames of ((width + 15) & ~15)-byte
+ * rows = dvo_knn_stream_raw_input_bytes(width, height, max_frames) bytes; 0 frees it.  A change
+ * synchronises the stream and drops a pending detection; a call that changes nothing does
+ * nothing.  A stream that never enables it allocates nothing more.  The detect and process calls
+ * allocate nothing and make no synchronisation and no device-to-host copy (the decoder waits for
+ * its own staging half, as in dvo_jpeg_decode, and queues its status copy).
+ *
+ * detect_raw / process_raw: d_frames holds n_frames frames of `channels` bytes per pixel (1 mono,
+ * 3 BGR, 4 BGRA), rows `stride` bytes apart, frames frame_stride bytes apart; u may be NULL.
+ * channels == 1 without u is dvo_knn_stream_detect / _process (in place, no slab).  Otherwise:
+ * colour -> bgr2gray, colour with u -> the fused gray + remap, mono with u -> the remap.
+ * detect_jpeg / process_jpeg: n baseline JPEGs of the stream's size, decoded with j's stream
+ * entropy mode (dvo_jpeg_set_stream_entropy) and remapped by u if given.  Corrupt entropy-coded
+ * data does not fail the call: dvo_jpeg_status names the frame and its records come from what
+ * the decoder left.  The process forms are the detect form and dvo_knn_stream_finish(records,
+ * NULL, 1, 0).  d_draws as in dvo_knn_stream_detect.
+ * dvo_knn_stream_stage_times: the first figure of these calls is input + detection.
+ *
+ * Refused before anything is launched, with a pending detection, the frame slots and the FLANN
+ * state left as they were: DVO_EINVAL for channels outside {1, 3, 4}, stride < width * channels,
+ * a null buffer, n outside 1..max_frames, null records with n > 1 (process forms), an
+ * undistorter of another size, an undistorter or decoder of another device, a slab that is
+ * needed and not enabled, a JPEG of another size; the parser's DVO_EUNSUPPORTED or DVO_ECORRUPT
+ * for a JPEG whose header cannot be taken. */
+int dvo_knn_stream_set_raw_input(dvo_knn_stream* s, int enable);
+/* Host only: the slab's bytes, max_frames * ((width + 15) & ~15) * height; 0 for an argument < 1. */
+size_t dvo_knn_stream_raw_input_bytes(int width, int height, int max_frames);
+int dvo_knn_stream_detect_raw(dvo_knn_stream* s, dvo_undistort* u, const uint8_t* d_frames, int n_frames,
+                              int64_t frame_stride, int stride, int channels, uint64_t* d_draws);
+int dvo_knn_stream_process_raw(dvo_knn_stream* s, dvo_undistort* u, const uint8_t* d_frames, int n_frames,
+                               int64_t frame_stride, int stride, int channels, dvo_pair_record* d_records);
+int dvo_knn_stream_detect_jpeg(dvo_knn_stream* s, dvo_jpeg* j, dvo_undistort* u, const uint8_t* const* bufs,
+                               const int64_t* lens, int n, uint64_t* d_draws);
+int dvo_knn_stream_process_jpeg(dvo_knn_stream* s, dvo_jpeg* j, dvo_undistort* u, const uint8_t* const* bufs,
+                                const int64_t* lens, int n, dvo_pair_record* d_records);
 /* dvo_stream_process on undistorted frames: the n raw frames are remapped by u
  * into the stream's own frame slab first (same HIP stream), as the reference
  * undistorts every frame before detection (v3:120, v3:135). */
