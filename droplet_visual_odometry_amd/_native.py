@@ -131,6 +131,11 @@ _SIGNATURES = {
     "dvo_bf_knn_float": ([_vp, _vp, _c, _vp, _c, _c, _c, _c, _vp, _vp], _c),
     "dvo_flann_knn": ([_vp, _vp, _c, _vp, _c, _c, _c, _c, _c, ctypes.POINTER(ctypes.c_uint64), _vp, _vp], _c),
     "dvo_sift_detect_and_compute": ([_vp, _vp, _c, _c, _c, _vp, _vp, _c, _ip], _c),
+    "dvo_sift_detect_and_compute_n": ([_vp, _vp, _c, _c, _c, _c, _vp, _vp, _c, _ip], _c),
+    "dvo_sift_retain_bytes": ([_c], _i64),
+    "dvo_sift_batch_set_nfeatures": ([_vp, _c], _c),
+    "dvo_knn_pair_set_nfeatures": ([_vp, _c], _c),
+    "dvo_knn_stream_set_nfeatures": ([_vp, _c], _c),
     "dvo_sift_batch_bytes": ([_c, _c, _c], _i64),
     "dvo_sift_batch_create": ([_vp, _c, _c, _c, ctypes.POINTER(_vp)], _c),
     "dvo_sift_batch_destroy": ([_vp], None),

@@ -41,6 +41,15 @@ struct SiftGroupDev {
     DeviceAllocs mem;
 };
 
+// Scratch of SIFT's retain stage (SIFT_create(nfeatures > 0)) for `frames` frames of a launch: what
+// SiftRetainArgs describes.  Empty until an nfeatures setter or dvo_sift_detect_and_compute_n asks
+// for it (sift_retain_ensure).  a.nfeatures stays 0 here: a call fills in its handle's value.
+struct SiftRetainDev {
+    int frames = 0;
+    SiftRetainArgs a{};
+    DeviceAllocs mem;
+};
+
 struct SurfPlanDev {  // per-size device buffers of dvo_surf_detect_and_compute
     int w = 0, h = 0;
     SurfArgs a{};
@@ -63,6 +72,7 @@ struct dvo_ctx {
     hipStream_t stream = nullptr;
     std::string err;
     SiftPlanDev sift;
+    SiftRetainDev sift_retain;  // one frame's retain scratch, for launch_sift on the plan above (any size)
     SurfPlanDev surf;
     CallSlots call;  // grow-only device and pinned buffers of the per-call entry points (CallMem)
     dvo_stream* call_stream = nullptr;  // cached plan for detectAndCompute
@@ -1541,10 +1551,49 @@ int sift_group_alloc(dvo_ctx* ctx, int w, int h, int group, SiftGroupDev& D) {
     return DVO_OK;
 }
 
+// One frame's share of the retain stage's scratch (SiftRetainArgs): the list, the responses, their
+// positions and the two position arrays of kp_cap + 1.
+int64_t sift_retain_frame_bytes() {
+    return (int64_t)kSiftKpCap * ((int64_t)sizeof(dvo_keypoint) + 8) + 2 * (int64_t)(kSiftKpCap + 1) * 4;
+}
+
+// The retain scratch for at least `frames` frames, allocated whole after waiting for the context's
+// stream (a setter's or a synchronous call's job: nothing is allocated inside a detect call).
+// D is empty on failure.
+int sift_retain_ensure(dvo_ctx* ctx, SiftRetainDev& D, int frames) {
+    if (D.frames >= frames) return DVO_OK;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // the old scratch may be in use
+    D = SiftRetainDev{};
+    const int64_t G = frames, C = kSiftKpCap;
+    hipError_t e = hipSuccess;
+    auto A_ = [&](auto*& p, int64_t n) {
+        if (e == hipSuccess) e = D.mem.alloc(&p, (size_t)n * sizeof(*p));
+    };
+    A_(D.a.list, G * C);
+    A_(D.a.resp, G * C);
+    A_(D.a.idx, G * C);
+    A_(D.a.lpos, G * (C + 1));
+    A_(D.a.rasc, G * (C + 1));
+    if (e != hipSuccess) {
+        D = SiftRetainDev{};
+        return fail(ctx, DVO_EHIP, std::string("SIFT retain buffers: ") + hipGetErrorString(e));
+    }
+    D.frames = frames;
+    return DVO_OK;
+}
+
 // n frames through the group detector, in chunks of D.group on stream s: frame f's keypoints and
 // descriptors go to kps + f * feat_cap and desc + f * feat_cap * 128, its (count, flags) to counts + 2 f.
+// nfeatures > 0: retainBest before the descriptors, on R's scratch (D.group frames of it).
 int sift_group_detect(dvo_ctx* ctx, const SiftGroupDev& D, const uint8_t* d_frames, int n, int64_t frame_stride, int stride,
-                      int feat_cap, dvo_keypoint* kps, float* desc, int32_t* counts, hipStream_t s) {
+                      int feat_cap, dvo_keypoint* kps, float* desc, int32_t* counts, hipStream_t s, int nfeatures = 0,
+                      const SiftRetainDev* R = nullptr) {
+    SiftRetainArgs ra{};
+    if (nfeatures > 0) {
+        if (!R || R->frames < D.group) return fail(ctx, DVO_EINVAL, "SIFT retain scratch is missing");
+        ra = R->a;
+        ra.nfeatures = nfeatures;
+    }
     for (int f0 = 0; f0 < n; f0 += D.group) {
         const int frames = std::min(D.group, n - f0);
         SiftGroupArgs g = D.g;
@@ -1554,7 +1603,7 @@ int sift_group_detect(dvo_ctx* ctx, const SiftGroupDev& D, const uint8_t* d_fram
         g.feat_cap = feat_cap;
         HIP_TRY(hipMemsetAsync(g.b.ncand, 0, (size_t)frames * 16, s));  // the chunk's counters, all four per frame
         HIP_TRY(launch_sift_group(g, frames, d_frames + (int64_t)f0 * frame_stride, frame_stride, D.w, D.h, stride, D.taps,
-                                  D.tap_off, D.tap_n, s));
+                                  D.tap_off, D.tap_n, s, nfeatures > 0 ? &ra : nullptr));
     }
     return DVO_OK;
 }
@@ -1563,6 +1612,8 @@ int sift_group_detect(dvo_ctx* ctx, const SiftGroupDev& D, const uint8_t* d_fram
 struct dvo_sift_batch {
     dvo_ctx* ctx = nullptr;
     SiftGroupDev d;
+    int nfeatures = 0;     // dvo_sift_batch_set_nfeatures
+    SiftRetainDev retain;  // its scratch, d.group frames once nfeatures was set
 };
 
 int64_t dvo_sift_batch_bytes(int w, int h, int group) {
@@ -1570,6 +1621,24 @@ int64_t dvo_sift_batch_bytes(int w, int h, int group) {
     SiftLayout L{};
     int off[6], n[6];
     return group * sift_group_bytes(w, h, L).frame() + (int64_t)sift_taps(off, n).size() * 4;
+}
+
+int64_t dvo_sift_retain_bytes(int group) {
+    return group < 1 || group > kSiftGroupMax ? 0 : group * sift_retain_frame_bytes();
+}
+
+int dvo_sift_batch_set_nfeatures(dvo_sift_batch* b, int nfeatures) {
+    if (!b) return DVO_EINVAL;
+    dvo_ctx* ctx = b->ctx;
+    if (nfeatures < 0) return fail(ctx, DVO_EINVAL, "nfeatures must be >= 0");
+    if (nfeatures == b->nfeatures) return DVO_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (nfeatures > 0) {
+        const int rc = sift_retain_ensure(ctx, b->retain, b->d.group);
+        if (rc) return rc;
+    }
+    b->nfeatures = nfeatures;
+    return DVO_OK;
 }
 
 int dvo_sift_batch_create(dvo_ctx* ctx, int w, int h, int group, dvo_sift_batch** out) {
@@ -1605,7 +1674,7 @@ int dvo_sift_batch_detect(dvo_sift_batch* b, const uint8_t* d_frames, int n_fram
     if (feat_cap < 1 || feat_cap > kSiftKpCap) return fail(ctx, DVO_EINVAL, "feat_cap out of range (1..65536)");
     HIP_TRY(hipSetDevice(ctx->device));
     return sift_group_detect(ctx, b->d, d_frames, n_frames, frame_stride, stride, feat_cap, d_kps, d_desc, d_counts,
-                             ctx->stream);
+                             ctx->stream, b->nfeatures, &b->retain);
 }
 
 namespace {
@@ -1922,17 +1991,29 @@ int dvo_surf_detect_and_compute(dvo_ctx* ctx, const uint8_t* img, int w, int h, 
 
 int dvo_sift_detect_and_compute(dvo_ctx* ctx, const uint8_t* img, int w, int h, int stride, dvo_keypoint* kps,
                                 float* desc, int cap, int* n_out) {
+    return dvo_sift_detect_and_compute_n(ctx, img, w, h, stride, 0, kps, desc, cap, n_out);
+}
+
+int dvo_sift_detect_and_compute_n(dvo_ctx* ctx, const uint8_t* img, int w, int h, int stride, int nfeatures,
+                                  dvo_keypoint* kps, float* desc, int cap, int* n_out) {
     if (!ctx || !n_out) return DVO_EINVAL;
     *n_out = 0;
+    if (nfeatures < 0) return fail(ctx, DVO_EINVAL, "nfeatures must be >= 0");
     if (!img || stride < w) return fail(ctx, DVO_EINVAL, "bad image buffer");
     if (w < 1 || h < 1 || w >= kMaxW || h >= kMaxW) return fail(ctx, DVO_EINVAL, "image size out of range (1..4095)");
     HIP_TRY(hipSetDevice(ctx->device));
     int rc = sift_plan(ctx, w, h);
     if (rc) return rc;
     SiftPlanDev& P = ctx->sift;
+    SiftRetainArgs ra{};
+    if (nfeatures > 0) {  // a synchronous call: the scratch is made here, once, before anything is launched
+        if ((rc = sift_retain_ensure(ctx, ctx->sift_retain, 1))) return rc;
+        ra = ctx->sift_retain.a;
+        ra.nfeatures = nfeatures;
+    }
     HIP_TRY(hipMemsetAsync(P.a.ncand, 0, 16, ctx->stream));
     HIP_TRY(hipMemcpy2DAsync(P.img, P.pitch, img, stride, w, h, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(launch_sift(P.a, P.img, w, h, P.pitch, P.taps, P.tap_off, P.tap_n, ctx->stream));
+    HIP_TRY(launch_sift(P.a, P.img, w, h, P.pitch, P.taps, P.tap_off, P.tap_n, ctx->stream, nfeatures > 0 ? &ra : nullptr));
     int cnt[4];
     HIP_TRY(hipMemcpyAsync(cnt, P.a.ncand, 16, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -2100,6 +2181,7 @@ struct dvo_knn_pair {
     dvo_ctx* ctx = nullptr;
     dvo_knn_pair_config cfg{};
     int dim = 0, kp_cap = 0, cus = 0;
+    int nfeatures = 0;  // dvo_knn_pair_set_nfeatures (SIFT): retainBest on the context's retain scratch
     struct Slot {  // one frame's features on the device
         dvo_keypoint* kps = nullptr;
         float* desc = nullptr;
@@ -2175,6 +2257,23 @@ int dvo_knn_pair_create(dvo_ctx* ctx, const dvo_knn_pair_config* cfg, dvo_knn_pa
     return DVO_OK;
 }
 
+int dvo_knn_pair_set_nfeatures(dvo_knn_pair* p, int nfeatures) {
+    if (!p) return DVO_EINVAL;
+    dvo_ctx* ctx = p->ctx;
+    if (p->cfg.detector != DVO_DETECT_SIFT)
+        return fail(ctx, DVO_EINVAL, "nfeatures is SIFT's: OpenCV's SURF_create has no such parameter");
+    if (nfeatures < 0) return fail(ctx, DVO_EINVAL, "nfeatures must be >= 0");
+    if (nfeatures == p->nfeatures) return DVO_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (nfeatures > 0) {
+        const int rc = sift_retain_ensure(ctx, ctx->sift_retain, 1);
+        if (rc) return rc;
+    }
+    p->nfeatures = nfeatures;
+    p->cache_valid = false;  // the cached previous-frame features were retained under the old value
+    return DVO_OK;
+}
+
 void dvo_knn_pair_destroy(dvo_knn_pair* p) {
     if (!p) return;
     hipSetDevice(p->ctx->device);
@@ -2212,7 +2311,10 @@ int dvo_knn_pair_run(dvo_knn_pair* p, const uint8_t* prev_img, const uint8_t* cu
             SiftPlanDev& D = ctx->sift;
             HIP_TRY(hipMemsetAsync(D.a.ncand, 0, 16, s));
             HIP_TRY(hipMemcpy2DAsync(D.img, D.pitch, hp, w, w, h, hipMemcpyHostToDevice, s));
-            HIP_TRY(launch_sift(D.a, D.img, w, h, D.pitch, D.taps, D.tap_off, D.tap_n, s));
+            if (p->nfeatures > 0 && ctx->sift_retain.frames < 1) return fail(ctx, DVO_EINVAL, "SIFT retain scratch is missing");
+            SiftRetainArgs ra = ctx->sift_retain.a;
+            ra.nfeatures = p->nfeatures;
+            HIP_TRY(launch_sift(D.a, D.img, w, h, D.pitch, D.taps, D.tap_off, D.tap_n, s, p->nfeatures > 0 ? &ra : nullptr));
             HIP_TRY(launch_feature_copy(D.a.kps, D.a.desc, D.a.nkp, D.a.flags, p->kp_cap, 128, sl.kps, sl.desc, sl.n, s));
         } else {
             SurfPlanDev& D = ctx->surf;
@@ -2494,6 +2596,8 @@ struct dvo_knn_stream {
     PairSets pairs;    // one set of max_frames - 1 pairs: pairs.all.g is the stream's GeomArgs
     DeviceAllocs mem;  // the frame slots, the match arrays and the round-local geometry arrays
     SiftGroupDev grp;  // dvo_knn_stream_set_detect_group: grp.group > 0 detects through launch_sift_group
+    int nfeatures = 0;     // dvo_knn_stream_set_nfeatures (SIFT): retainBest in either detection route
+    SiftRetainDev retain;  // the group route's retain scratch (the frame-by-frame route uses the context's)
     SurfGroupDev sgrp;  // dvo_knn_stream_set_surf_group: sgrp.group > 0 detects through launch_surf_group
     FlannBatchArgs fl{};  // dvo_knn_stream_set_flann: fl.trees > 0 matches through launch_flann_batch
     DeviceAllocs fl_mem;  // its scratch and the theRNG state word
@@ -2620,7 +2724,8 @@ int knn_stream_detect_gray(dvo_knn_stream* st, const uint8_t* d_frames, int n_fr
     // detection in place on the caller's frames: a group of frames per launch straight into the
     // frame slots, or frame by frame on the plan's single scratch
     if (st->grp.group > 0)
-        rc = sift_group_detect(ctx, st->grp, d_frames, n_frames, frame_stride, stride, b.cap, b.kps, b.desc, b.n, s);
+        rc = sift_group_detect(ctx, st->grp, d_frames, n_frames, frame_stride, stride, b.cap, b.kps, b.desc, b.n, s,
+                               st->nfeatures, &st->retain);
     else if (st->sgrp.group > 0)
         rc = surf_group_detect(ctx, st->sgrp, d_frames, n_frames, frame_stride, stride, c.hessian_threshold, b.cap, b.kps,
                                b.desc, b.n, s);
@@ -2633,7 +2738,10 @@ int knn_stream_detect_gray(dvo_knn_stream* st, const uint8_t* d_frames, int n_fr
         if (sift) {
             SiftPlanDev& D = ctx->sift;
             HIP_TRY(hipMemsetAsync(D.a.ncand, 0, 16, s));
-            HIP_TRY(launch_sift(D.a, img, w, h, stride, D.taps, D.tap_off, D.tap_n, s));
+            if (st->nfeatures > 0 && ctx->sift_retain.frames < 1) return fail(ctx, DVO_EINVAL, "SIFT retain scratch is missing");
+            SiftRetainArgs ra = ctx->sift_retain.a;
+            ra.nfeatures = st->nfeatures;
+            HIP_TRY(launch_sift(D.a, img, w, h, stride, D.taps, D.tap_off, D.tap_n, s, st->nfeatures > 0 ? &ra : nullptr));
             HIP_TRY(launch_feature_copy(D.a.kps, D.a.desc, D.a.nkp, D.a.flags, b.cap, 128, kps, desc, dn, s));
         } else {
             SurfPlanDev& D = ctx->surf;
@@ -2725,7 +2833,29 @@ int dvo_knn_stream_set_detect_group(dvo_knn_stream* s, int group) {
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // the old scratch may be in use
     s->grp = SiftGroupDev{};
-    return group ? sift_group_alloc(ctx, s->cfg.width, s->cfg.height, group, s->grp) : DVO_OK;
+    if (!group) return DVO_OK;
+    int rc = sift_group_alloc(ctx, s->cfg.width, s->cfg.height, group, s->grp);
+    if (rc || s->nfeatures == 0) return rc;
+    if ((rc = sift_retain_ensure(ctx, s->retain, group))) s->grp = SiftGroupDev{};  // no group detector without it
+    return rc;
+}
+
+int dvo_knn_stream_set_nfeatures(dvo_knn_stream* s, int nfeatures) {
+    if (!s) return DVO_EINVAL;
+    dvo_ctx* ctx = s->ctx;
+    if (s->cfg.detector != DVO_DETECT_SIFT)
+        return fail(ctx, DVO_EINVAL, "nfeatures is SIFT's: OpenCV's SURF_create has no such parameter");
+    if (nfeatures < 0) return fail(ctx, DVO_EINVAL, "nfeatures must be >= 0");
+    if (nfeatures == s->nfeatures) return DVO_OK;
+    s->pending = 0;  // a detection waiting for dvo_knn_stream_finish is dropped
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (nfeatures > 0) {  // both routes' scratch now: dvo_knn_stream_set_detect_group may be switched off later
+        int rc = sift_retain_ensure(ctx, ctx->sift_retain, 1);
+        if (!rc && s->grp.group > 0) rc = sift_retain_ensure(ctx, s->retain, s->grp.group);
+        if (rc) return rc;
+    }
+    s->nfeatures = nfeatures;
+    return DVO_OK;
 }
 
 int dvo_knn_stream_set_surf_group(dvo_knn_stream* s, int group) {

@@ -275,6 +275,20 @@ struct SiftGroupArgs {
     int fused_blur;  // the blurs of layers 1..5 in one launch each (blur_fused_group_kernel), not a row and a column pass
 };
 
+// SIFT_create(nfeatures).detectAndCompute's retainBest (retain_kernel / retain_group_kernel), between
+// the sort and the descriptors.  With nfeatures > 0 the sort writes the whole deduplicated list (up
+// to kp_cap) to `list`, and retain gathers the kept keypoints from there, in libstdc++'s order, into
+// the detector's output list.  Frame f of a group has its arrays f strides further: list, resp and
+// idx by kp_cap, lpos and rasc by kp_cap + 1.
+struct SiftRetainArgs {
+    int nfeatures;       // > 0
+    dvo_keypoint* list;  // the sorted, deduplicated list retain reads
+    float* resp;         // the responses retain_best_block permutes
+    int32_t* idx;        // their positions in list, permuted with them
+    int32_t* lpos;       // retain_best_block's position arrays, kp_cap + 1 each
+    int32_t* rasc;
+};
+
 // SURF_create(hessianThreshold).detectAndCompute (surf.hip): nOctaves 4,
 // nOctaveLayers 3, 64-d descriptors, orientation on.
 constexpr int kSurfOct = 4, kSurfLayers = 5, kSurfTot = kSurfOct * kSurfLayers;
@@ -441,14 +455,15 @@ hipError_t launch_knn_float(const float* d_q, int nq, const float* d_t, int nt, 
 // d_work: match_pair_work_size(nq, nt) bytes.  Output in queryIdx order.
 size_t match_pair_work_size(int nq, int nt);
 // d_taps: the 6 Gaussian kernels (initial blur, layers 1..5) back to back.
+// R (nfeatures > 0): retainBest between the sort and the descriptors; null: everything is kept.
 hipError_t launch_sift(const SiftArgs& A, const uint8_t* d_img, int w, int h, int stride, const float* d_taps,
-                       const int* tap_off, const int* tap_n, hipStream_t s);
+                       const int* tap_off, const int* tap_n, hipStream_t s, const SiftRetainArgs* R = nullptr);
 // The same stages for `frames` frames (<= the frames G's scratch holds), one launch per stage with
 // the frame as a grid dimension; frame f's image is d_frames + f * frame_stride.  The caller has
 // cleared the frames' counters.
 hipError_t launch_sift_group(const SiftGroupArgs& G, int frames, const uint8_t* d_frames, int64_t frame_stride, int w,
                              int h, int stride, const float* d_taps, const int* tap_off, const int* tap_n,
-                             hipStream_t s);
+                             hipStream_t s, const SiftRetainArgs* R = nullptr);
 hipError_t launch_surf(const SurfArgs& a, hipStream_t s);
 // The same stages for `frames` frames (<= the frames G's scratch holds), one launch per stage with
 // the frame as a grid dimension.  The caller has cleared the frames' counters, det and trace.

@@ -17,6 +17,8 @@
 //                      parallel, accumulated in sample order per bin), peaks
 //   sort_kernel        KeyPoint12_LessThan order + removeDuplicatedSorted +
 //                      firstOctave = -1 rescale (one workgroup, bitonic network)
+//   retain_kernel      SIFT_create(nfeatures > 0) only: KeyPointsFilter::retainBest, the
+//                      libstdc++ nth_element + partition permutation (one workgroup)
 //   descriptor_kernel  one wave per keypoint: calcSIFTDescriptor, the 360-bin
 //                      trilinear histogram filled in sample order, normalised
 //
@@ -30,6 +32,7 @@
 #include <climits>
 
 #include "dvo_internal.h"
+#include "retain_best.h"
 
 namespace dvo {
 namespace {
@@ -544,6 +547,70 @@ __global__ __launch_bounds__(kSortNT) void sort_group_kernel(SiftGroupArgs G) {
     sort_body(G.l, frame_bufs(G, blockIdx.x), G.feat_cap, G.out_n + 2 * (int64_t)blockIdx.x);
 }
 
+// retain_best_block's accessor: the responses and, moved with them, their positions in the list.
+struct SiftVals {
+    float* v;
+    int32_t* idx;
+    struct Elem {
+        float v;
+        int32_t k;
+    };
+    __device__ float val(int i) const { return v[i]; }
+    __device__ void swap(int i, int j) const {
+        float t = v[i];
+        v[i] = v[j];
+        v[j] = t;
+        int32_t u = idx[i];
+        idx[i] = idx[j];
+        idx[j] = u;
+    }
+    __device__ Elem get(int i) const { return Elem{v[i], idx[i]}; }
+    __device__ void put(int i, Elem e) const {
+        v[i] = e.v;
+        idx[i] = e.k;
+    }
+    __device__ static float ev(Elem e) { return e.v; }
+};
+
+// KeyPointsFilter::retainBest(keypoints, nfeatures) of frame f, one workgroup: the sort left the
+// frame's whole list (*nkp <= kp_cap entries) in R.list; the kept keypoints go to dst in the order
+// libstdc++'s nth_element + partition leave them (entries below dst_cap only), the kept count to
+// *nkp and, if given, dn[0].  A list of at most nfeatures entries is copied as it is.
+__device__ __forceinline__ void retain_body(const SiftRetainArgs& R, int f, int kp_cap, dvo_keypoint* dst, int dst_cap,
+                                            int* nkp, int32_t* dn) {
+    __shared__ int lds[64];
+    const int64_t F = f;
+    const dvo_keypoint* src = R.list + F * kp_cap;
+    const int n = min(*nkp, kp_cap);
+    if (n <= R.nfeatures) {
+        for (int i = threadIdx.x; i < min(n, dst_cap); i += kSortNT) dst[i] = src[i];
+        return;
+    }
+    float* resp = R.resp + F * kp_cap;
+    int32_t* idx = R.idx + F * kp_cap;
+    for (int i = threadIdx.x; i < n; i += kSortNT) {
+        resp[i] = src[i].response;
+        idx[i] = i;
+    }
+    __syncthreads();
+    const int k = retain_best_block(SiftVals{resp, idx}, n, R.nfeatures, -1, R.lpos + F * (kp_cap + 1),
+                                    R.rasc + F * (kp_cap + 1), lds);
+    for (int i = threadIdx.x; i < min(k, dst_cap); i += kSortNT) dst[i] = src[idx[i]];
+    if (threadIdx.x == 0) {
+        *nkp = k;
+        if (dn) dn[0] = k;
+    }
+}
+
+__global__ __launch_bounds__(kSortNT) void retain_kernel(SiftArgs A, SiftRetainArgs R) {
+    retain_body(R, 0, A.kp_cap, A.kps, A.kp_cap, A.nkp, nullptr);
+}
+
+__global__ __launch_bounds__(kSortNT) void retain_group_kernel(SiftGroupArgs G, SiftRetainArgs R) {
+    const SiftBufs B = frame_bufs(G, blockIdx.x);
+    retain_body(R, blockIdx.x, G.l.kp_cap, B.kps, G.feat_cap, B.nkp, G.out_n + 2 * (int64_t)blockIdx.x);
+}
+
 // calcSIFTDescriptor, one wave per keypoint: keypoints first, first + step, ... below nk of B.kps.
 __device__ __forceinline__ void descriptor_body(const SiftLayout& A, const SiftBufs& B, int nk, int first, int step) {
     __shared__ float hist[kHistN];
@@ -680,7 +747,7 @@ __global__ __launch_bounds__(64) void descriptor_group_kernel(SiftGroupArgs G) {
 }  // namespace
 
 hipError_t launch_sift(const SiftArgs& A, const uint8_t* d_img, int w, int h, int stride, const float* d_taps,
-                       const int* tap_off, const int* tap_n, hipStream_t s) {
+                       const int* tap_off, const int* tap_n, hipStream_t s, const SiftRetainArgs* R) {
     auto grid = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
     float* base = A.gp + A.gp_off[0];
     hipLaunchKernelGGL(up2_kernel, grid((int64_t)A.ow[0] * A.oh[0]), dim3(256), 0, s, d_img, w, h, stride, base);
@@ -710,14 +777,21 @@ hipError_t launch_sift(const SiftArgs& A, const uint8_t* d_img, int w, int h, in
         hipLaunchKernelGGL(extrema_kernel, eg, dim3(256), 0, s, A, o, threshold);
     }
     hipLaunchKernelGGL(refine_kernel, dim3(4096), dim3(64), 0, s, A);
-    hipLaunchKernelGGL(sort_kernel, dim3(1), dim3(kSortNT), 0, s, A);
+    if (R && R->nfeatures > 0) {  // the sort's list goes to R->list, the kept keypoints from there to A.kps
+        SiftArgs S = A;
+        S.kps = R->list;
+        hipLaunchKernelGGL(sort_kernel, dim3(1), dim3(kSortNT), 0, s, S);
+        hipLaunchKernelGGL(retain_kernel, dim3(1), dim3(kSortNT), 0, s, A, *R);
+    } else {
+        hipLaunchKernelGGL(sort_kernel, dim3(1), dim3(kSortNT), 0, s, A);
+    }
     hipLaunchKernelGGL(descriptor_kernel, dim3(4096), dim3(64), 0, s, A);
     return hipGetLastError();
 }
 
 hipError_t launch_sift_group(const SiftGroupArgs& G, int frames, const uint8_t* d_frames, int64_t frame_stride, int w,
                              int h, int stride, const float* d_taps, const int* tap_off, const int* tap_n,
-                             hipStream_t s) {
+                             hipStream_t s, const SiftRetainArgs* R) {
     const SiftLayout& L = G.l;
     const unsigned F = (unsigned)frames;
     // memory-bound stages: about kBlocks workgroups per launch, the frame's items grid-strided
@@ -762,7 +836,17 @@ hipError_t launch_sift_group(const SiftGroupArgs& G, int frames, const uint8_t* 
     // one wave per item: 4096 waves a frame as launch_sift, fewer as the group fills the card
     const unsigned waves = (unsigned)std::min(4096, std::max(128, 8192 / frames));
     hipLaunchKernelGGL(refine_group_kernel, dim3(waves, F), dim3(64), 0, s, G);
-    hipLaunchKernelGGL(sort_group_kernel, dim3(F), dim3(kSortNT), 0, s, G);
+    if (R && R->nfeatures > 0) {
+        // retain sees the whole list, also where it is longer than feat_cap: the sort writes frame f's
+        // to R->list + f * kp_cap, and only the kept keypoints are cut at the slot's feat_cap
+        SiftGroupArgs S = G;
+        S.out_kps = R->list;
+        S.feat_cap = L.kp_cap;
+        hipLaunchKernelGGL(sort_group_kernel, dim3(F), dim3(kSortNT), 0, s, S);
+        hipLaunchKernelGGL(retain_group_kernel, dim3(F), dim3(kSortNT), 0, s, G, *R);
+    } else {
+        hipLaunchKernelGGL(sort_group_kernel, dim3(F), dim3(kSortNT), 0, s, G);
+    }
     hipLaunchKernelGGL(descriptor_group_kernel, dim3(waves, F), dim3(64), 0, s, G);
     return hipGetLastError();
 }

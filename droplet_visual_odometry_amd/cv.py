@@ -584,14 +584,21 @@ def drawKeypoints(image, keypoints, outImage=None, color=(0, 255, 0), flags=0):
 
 
 class SIFT:
-    """cv2.SIFT with SIFT_create()'s defaults (v3:100), on the GPU
-    (dvo_sift_detect_and_compute): keypoints and float32[N, 128] descriptors
-    for the float k-NN matchers of the sift / knn_sift / flann modes."""
+    """cv2.SIFT (v3:100: SIFT_create()), on the GPU (dvo_sift_detect_and_compute_n):
+    keypoints and float32[N, 128] descriptors for the float k-NN matchers of the
+    sift / knn_sift / flann modes.  nfeatures > 0 keeps the best by response as
+    OpenCV 4.x's retainBest does: in libstdc++'s nth_element + partition order,
+    with every keypoint that ties at the boundary, so the count can exceed
+    nfeatures.  The other parameters are implemented at their defaults only."""
 
     def __init__(self, nfeatures=0, nOctaveLayers=3, contrastThreshold=0.04, edgeThreshold=10, sigma=1.6):
-        if (nfeatures != 0 or nOctaveLayers != 3 or not np.isclose(contrastThreshold, 0.04)
+        if (nOctaveLayers != 3 or not np.isclose(contrastThreshold, 0.04)
                 or not np.isclose(edgeThreshold, 10) or not np.isclose(sigma, 1.6)):
-            raise error("only the SIFT_create() defaults are implemented (the reference uses them, v3:100)")
+            raise error("only nfeatures is implemented; the other parameters must be SIFT_create()'s defaults "
+                        "(the reference uses them, v3:100)")
+        if isinstance(nfeatures, bool) or int(nfeatures) != nfeatures or nfeatures < 0:
+            raise error("nfeatures must be an integer >= 0")
+        self.nfeatures = int(nfeatures)
 
     def detectAndCompute(self, image, mask, descriptors=None, useProvidedKeypoints=False):
         if mask is not None:
@@ -600,7 +607,7 @@ class SIFT:
             raise error("useProvidedKeypoints is not supported")
         img = _gray(image)
         try:
-            kps, desc = ops.sift_detect_and_compute(img)
+            kps, desc = ops.sift_detect_and_compute(img, nfeatures=self.nfeatures)
         except DVOError as e:
             raise error(str(e)) from e
         return KeyPoints(kps), (desc if len(kps) else None)
@@ -610,6 +617,9 @@ class SIFT:
 
     def descriptorSize(self):
         return 128
+
+    def getNFeatures(self):
+        return self.nfeatures
 
 
 def SIFT_create(nfeatures=0, nOctaveLayers=3, contrastThreshold=0.04, edgeThreshold=10, sigma=1.6):

@@ -341,13 +341,16 @@ class ShardedKnnRunner:
     a mono batch, a colour batch [n_local + 1, H, W, 3 or 4] or a list of n_local + 1 JPEG files;
     undistort (an ops.Undistorter on this rank's device; it implies raw_input) remaps every window's
     frames on the way, whatever their form: K is then the new camera matrix.  The input stage is
-    part of step (1), on the library's stream; the rest of the schedule is the same."""
+    part of step (1), on the library's stream; the rest of the schedule is the same.
+
+    nfeatures (SIFT only): SIFT_create(nfeatures) on every rank's stream (KnnFrameStream's
+    nfeatures); retain is part of step (1), and FLANN's draws words count the kept features."""
 
     def __init__(self, width: int, height: int, K, window_pairs: int, world: int, rank: int, marker_length: float,
                  detector: str = "sift", matcher: str = "bf", feat_cap: int | None = None, detect_group: int = 0,
                  surf_group: int = 0, trees: int = 5, checks: int = 50, rng_state: int | None = None,
                  hessian_threshold: float = 400.0, max_iters: int = 1000, k: int = 4, host_gather: bool = False,
-                 group=None, ctx=None, slots: int = 2, undistort=None, raw_input: bool = False):
+                 group=None, ctx=None, slots: int = 2, undistort=None, raw_input: bool = False, nfeatures: int = 0):
         if detector not in ("sift", "surf"):
             raise ValueError("detector must be 'sift' or 'surf'")
         if matcher not in ("bf", "flann"):
@@ -377,7 +380,8 @@ class ShardedKnnRunner:
         self.ks = KnnFrameStream(width, height, K, self.n_local + 1, detector=detector, feat_cap=feat_cap,
                                  hessian_threshold=hessian_threshold, max_iters=max_iters, ctx=self.ctx,
                                  detect_group=detect_group, surf_group=surf_group, matcher=matcher, trees=trees,
-                                 checks=checks, rng_state=rng_state, raw_input=raw_input or undistort is not None)
+                                 checks=checks, rng_state=rng_state, raw_input=raw_input or undistort is not None,
+                                 nfeatures=nfeatures)
         self.undistort = undistort
         # per slot: this rank's draws word (detect writes it) and the gathered words (finish reads them)
         self.own = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in self.shs] if self.flann else None

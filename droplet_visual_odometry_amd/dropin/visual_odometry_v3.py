@@ -390,7 +390,8 @@ class VisualOdometry:
             cfg = (w, h, det.nfeatures, det.fastThreshold, det.opencv, K.tobytes(), cc)
         else:
             hessian = det.hessianThreshold if self.mode == "surf" else None
-            cfg = (w, h, self.mode, hessian, K.tobytes())
+            nfeatures = 0 if self.mode == "surf" else det.nfeatures  # SIFT_create(nfeatures=N)
+            cfg = (w, h, self.mode, hessian, nfeatures, K.tobytes())
         if self._pair_engine is None or self._pair_engine[0] != cfg:
             self._pair_engine = None
             self._pair_last = None
@@ -400,7 +401,8 @@ class VisualOdometry:
             else:
                 detector, matcher = self._KNN_MODES[self.mode]
                 engine = ops.KnnPairStream(w, h, K, detector=detector, matcher=matcher,
-                                           hessian_threshold=400.0 if hessian is None else hessian)
+                                           hessian_threshold=400.0 if hessian is None else hessian,
+                                           nfeatures=nfeatures)
             self._pair_engine = (cfg, engine)
         fs = self._pair_engine[1]
         kprev, kcur = _FeatureCache.key(prev), _FeatureCache.key(cur)

@@ -35,7 +35,7 @@ import ctypes
 
 import numpy as np
 
-from ._native import (DMATCH_DTYPE, DVO_ECAP, DVO_ECORRUPT, DVO_EUNSUPPORTED, DVO_OK, KEYPOINT_DTYPE, PAIR_RECORD_DTYPE, Context, DVOError, StreamConfig,
+from ._native import (DMATCH_DTYPE, DVO_ECAP, DVO_ECORRUPT, DVO_EINVAL, DVO_EUNSUPPORTED, DVO_OK, KEYPOINT_DTYPE, PAIR_RECORD_DTYPE, Context, DVOError, StreamConfig,
                       load_library, orb_params, ptr)
 
 
@@ -66,10 +66,21 @@ def detect_and_compute(img: np.ndarray, nfeatures: int = 500, fast_threshold: in
         return kps[:n.value].copy(), desc[:n.value].copy()
 
 
-def sift_detect_and_compute(img: np.ndarray, ctx=None):
-    """SIFT_create().detectAndCompute(img, None): keypoints (KEYPOINT_DTYPE, in
-    OpenCV's removeDuplicatedSorted order) and float32[N, 128] descriptors."""
+def _check_nfeatures(nfeatures) -> int:
+    """SIFT_create's nfeatures as the library takes it: an integer >= 0 (0 keeps everything)."""
+    if isinstance(nfeatures, bool) or int(nfeatures) != nfeatures or int(nfeatures) < 0:
+        raise DVOError(DVO_EINVAL, "nfeatures must be an integer >= 0")
+    return int(nfeatures)
+
+
+def sift_detect_and_compute(img: np.ndarray, ctx=None, nfeatures: int = 0):
+    """SIFT_create(nfeatures).detectAndCompute(img, None): keypoints (KEYPOINT_DTYPE, in
+    OpenCV's removeDuplicatedSorted order) and float32[N, 128] descriptors.  nfeatures > 0
+    (dvo_sift_detect_and_compute_n): the keypoints OpenCV 4.x's retainBest keeps, in the order
+    libstdc++'s nth_element + partition leave them; ties at the boundary response are all kept,
+    so N can exceed nfeatures."""
     c = _ctx(ctx)
+    nfeatures = _check_nfeatures(nfeatures)
     img = np.ascontiguousarray(img)
     if img.dtype != np.uint8 or img.ndim != 2:
         raise DVOError(-1, "sift_detect_and_compute expects a mono8 image (uint8[H, W])")
@@ -79,8 +90,8 @@ def sift_detect_and_compute(img: np.ndarray, ctx=None):
         kps = np.zeros(cap, KEYPOINT_DTYPE)
         desc = np.zeros((cap, 128), np.float32)
         n = ctypes.c_int()
-        rc = c.lib.dvo_sift_detect_and_compute(c.h, ptr(img), w, h, img.strides[0], ptr(kps), ptr(desc), cap,
-                                               ctypes.byref(n))
+        rc = c.lib.dvo_sift_detect_and_compute_n(c.h, ptr(img), w, h, img.strides[0], nfeatures, ptr(kps), ptr(desc),
+                                                 cap, ctypes.byref(n))
         if rc == DVO_ECAP and n.value > cap:
             cap = n.value
             continue
@@ -93,11 +104,13 @@ class SiftBatch:
     size, `group` frames per launch (dvo_sift_batch_detect): every stage of the detector runs once
     over the group.  Every frame's features are bit-identical to sift_detect_and_compute's,
     whatever the group.  The scratch (scratch_bytes: about 83 MB per frame of the group at
-    640x480) is allocated here, none in detect."""
+    640x480) is allocated here, none in detect.  nfeatures > 0 (SIFT_create(nfeatures), also
+    set_nfeatures): retainBest runs over the group before the descriptors, on each frame's whole
+    list; the counts are then the kept counts, and retain_bytes(group) more bytes are allocated."""
 
     SIFT_LIST_CAP = 65536
 
-    def __init__(self, width: int, height: int, group: int, ctx=None):
+    def __init__(self, width: int, height: int, group: int, ctx=None, nfeatures: int = 0):
         self.h = None
         self.ctx = _ctx(ctx)
         h = ctypes.c_void_p()
@@ -106,6 +119,21 @@ class SiftBatch:
         self.h = h
         self.width, self.height, self.group = int(width), int(height), int(group)
         self._ext = None
+        self.nfeatures = 0
+        if nfeatures:
+            self.set_nfeatures(nfeatures)
+
+    def set_nfeatures(self, nfeatures: int):
+        """dvo_sift_batch_set_nfeatures: SIFT_create(nfeatures) for the detect calls that follow
+        (0: everything is kept, and no retain launch)."""
+        self.ctx.check(self.ctx.lib.dvo_sift_batch_set_nfeatures(self.h, _check_nfeatures(nfeatures)))
+        self.nfeatures = int(nfeatures)
+
+    @staticmethod
+    def retain_bytes(group: int) -> int:
+        """dvo_sift_retain_bytes: the extra device bytes of the retain stage for `group` frames
+        (host arithmetic only; 0 for a group outside 1..64)."""
+        return int(load_library().dvo_sift_retain_bytes(int(group)))
 
     @staticmethod
     def scratch_bytes(width: int, height: int, group: int) -> int:
@@ -235,6 +263,10 @@ class SurfBatch:
         self.width, self.height, self.group = int(width), int(height), int(group)
         self.list_cap = max(4096, self.width * self.height // 64)  # the detector's keypoint list
         self._ext = None
+
+    def set_nfeatures(self, nfeatures: int):
+        """Refused: nfeatures is SIFT's (SiftBatch.set_nfeatures)."""
+        raise DVOError(DVO_EINVAL, "nfeatures is SIFT's: OpenCV's SURF_create has no such parameter")
 
     @staticmethod
     def scratch_bytes(width: int, height: int, group: int) -> int:
@@ -1133,10 +1165,12 @@ class KnnPairStream:
     (visual_odometry_v3.py:384-408 up to v3:303) in one synchronous library
     call: one frame up, the 256-B pair record back.  With reuse_prev=True the
     previous frame is the last call's current frame (allowed after a pair whose
-    record status is 0).  The drop-in's fused path (D8) uses it; no torch involved."""
+    record status is 0).  The drop-in's fused path (D8) uses it; no torch involved.
+    nfeatures > 0 (SIFT only): SIFT_create(nfeatures), both frames' features are
+    sift_detect_and_compute(img, nfeatures=N)'s."""
 
     def __init__(self, width, height, K, detector="sift", matcher="bf", hessian_threshold=400.0, trees=5, checks=50,
-                 ratio=0.75, prob=0.999, threshold=1.0, max_iters=1000, dist_thresh=50.0, ctx=None):
+                 ratio=0.75, prob=0.999, threshold=1.0, max_iters=1000, dist_thresh=50.0, ctx=None, nfeatures=0):
         from ._native import KnnPairConfig
         self.ctx = _ctx(ctx)
         cfg = KnnPairConfig()
@@ -1157,6 +1191,20 @@ class KnnPairStream:
         self.width, self.height = int(width), int(height)
         self.dim = 64 if cfg.detector == 1 else 128
         self.flann = cfg.matcher == 1
+        self.nfeatures = 0
+        self._redetect = False
+        if nfeatures:
+            self.set_nfeatures(nfeatures)
+
+    def set_nfeatures(self, nfeatures):
+        """dvo_knn_pair_set_nfeatures: SIFT_create(nfeatures) for the pairs that follow.  A change
+        drops the cached previous-frame features: the next pair(reuse_prev=True) must be given the
+        previous frame too and detects it again.  DVOError(DVO_EINVAL) on a SURF handle."""
+        n = _check_nfeatures(nfeatures)
+        self.ctx.check(self.ctx.lib.dvo_knn_pair_set_nfeatures(self.h, n))
+        if n != self.nfeatures:
+            self._redetect = True
+        self.nfeatures = n
 
     def pair(self, prev_img, cur_img, reuse_prev=False, rng_state=None):
         """(record, theRNG state after the call); rng_state: cv::theRNG()'s state before it
@@ -1164,6 +1212,11 @@ class KnnPairStream:
         cur = np.ascontiguousarray(cur_img, np.uint8)
         if cur.shape != (self.height, self.width):
             raise ValueError(f"frame shape {cur.shape} != {(self.height, self.width)}")
+        if reuse_prev and self._redetect:  # the cache holds features retained under another nfeatures
+            if prev_img is None:
+                raise DVOError(DVO_EINVAL, "nfeatures changed: pair(reuse_prev=True) needs the previous frame again")
+            reuse_prev = False
+        self._redetect = False
         prev = None
         if not reuse_prev:
             prev = np.ascontiguousarray(prev_img, np.uint8)

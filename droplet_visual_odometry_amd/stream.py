@@ -474,6 +474,14 @@ class KnnFrameStream:
     of ops.SurfBatch with the stream's hessian_threshold), for ops.SurfBatch.scratch_bytes(width,
     height, G) more device memory.  Same records either way.
 
+    nfeatures (SIFT only; dvo_knn_stream_set_nfeatures): SIFT_create(nfeatures).  0 keeps everything
+    a frame's detector finds, so one textured frame can pass feat_cap.  N > 0 keeps each frame's best
+    N by response as OpenCV 4.x's retainBest does (ops.sift_detect_and_compute(img, nfeatures=N)'s
+    features, in that order, boundary ties included), frame by frame and with a detect_group, for
+    both matchers; only a frame whose kept count passes feat_cap is DVO_ECAP.  Give feat_cap = N
+    plus room for boundary ties.  ops.SiftBatch.retain_bytes(1), and retain_bytes(G) with a
+    detect_group, more device memory.
+
     matcher: "bf" (the default) or "flann", the reference's 'flann' mode (dvo_knn_stream_set_flann):
     every pair's randomized kd-forest (trees) is built and searched (checks) on the device in place
     of BFMatcher, with no read-back, for ops.knn_stream_flann_bytes(max_frames, feat_cap, trees)
@@ -498,7 +506,7 @@ class KnnFrameStream:
                  hessian_threshold: float = 400.0, ratio: float = 0.75, prob: float = 0.999, threshold: float = 1.0,
                  max_iters: int = 1000, dist_thresh: float = 50.0, ctx: Context | None = None, *,
                  detect_group: int = 0, surf_group: int = 0, matcher: str = "bf", trees: int = 5, checks: int = 50,
-                 rng_state: int | None = None, raw_input: bool = False):
+                 rng_state: int | None = None, raw_input: bool = False, nfeatures: int = 0):
         from ._native import KnnStreamConfig
         from .ops import KNN_DETECTORS, KNN_MATCHERS
         self.h = None
@@ -529,6 +537,10 @@ class KnnFrameStream:
         self.surf_group = 0
         if surf_group:
             self.set_surf_group(surf_group)
+        self.nfeatures = 0
+        self._pending = 0
+        if nfeatures:
+            self.set_nfeatures(nfeatures)
         self.trees = self.checks = 0
         if matcher == "flann":
             self.set_flann(trees, checks)
@@ -563,6 +575,16 @@ class KnnFrameStream:
         for the stream and allocates or frees the group's scratch; DVOError(DVO_EINVAL) on a SIFT stream."""
         self.ctx.check(self.ctx.lib.dvo_knn_stream_set_surf_group(self.h, int(group)))
         self.surf_group, self._pending = int(group), 0  # a pending detect() is dropped
+
+    def set_nfeatures(self, nfeatures: int):
+        """SIFT_create(nfeatures) from the next detection on (0: everything is kept).  A change waits
+        for the stream, allocates the retain stage's scratch once and drops a pending detect();
+        DVOError(DVO_EINVAL) on a SURF stream or a negative value."""
+        from .ops import _check_nfeatures
+        n = _check_nfeatures(nfeatures)
+        self.ctx.check(self.ctx.lib.dvo_knn_stream_set_nfeatures(self.h, n))
+        if n != self.nfeatures:
+            self.nfeatures, self._pending = n, 0
 
     def set_flann(self, trees: int, checks: int = 50):
         """The FLANN kd-forest matcher from the next process() on: trees 1..64 and checks >= 1; trees

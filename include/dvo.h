@@ -133,6 +133,27 @@ int dvo_flann_knn(dvo_ctx* ctx, const float* dq, int nq, const float* dt, int nt
 int dvo_sift_detect_and_compute(dvo_ctx* ctx, const uint8_t* img, int w, int h, int stride, dvo_keypoint* kps,
                                 float* desc, int cap, int* n_out);
 
+/* cv::xfeatures2d::SIFT_create(nfeatures).detectAndCompute(img, None) (visual_odometry_v3.py:100
+ * construction, :373 call) with the detector's first constructor argument; the other parameters
+ * at their defaults.  nfeatures == 0 is dvo_sift_detect_and_compute.  nfeatures > 0: OpenCV 4.x's
+ * KeyPointsFilter::retainBest(keypoints, nfeatures) runs on the device between
+ * removeDuplicatedSorted and the descriptors: nothing where the list has at most nfeatures
+ * entries; else libstdc++'s nth_element(begin, begin + nfeatures - 1, end, response >), the
+ * boundary response read at nfeatures - 1, std::partition(begin + nfeatures, end, response >=
+ * boundary), and the list cut there.  Keypoints and descriptors come out in the order those two
+ * leave, not sorted by response, and every keypoint that ties with the boundary is kept, so the
+ * count can exceed nfeatures (the extra orientations of an extremum share its response).  The
+ * descriptors are computed for the kept keypoints only.  *n_out = the kept count (DVO_ECAP if >
+ * cap).  The first call with nfeatures > 0 on a context allocates the retain stage's scratch,
+ * dvo_sift_retain_bytes(1) bytes.  DVO_EINVAL: nfeatures < 0, and as dvo_sift_detect_and_compute. */
+int dvo_sift_detect_and_compute_n(dvo_ctx* ctx, const uint8_t* img, int w, int h, int stride, int nfeatures,
+                                  dvo_keypoint* kps, float* desc, int cap, int* n_out);
+/* The extra device bytes of the retain stage for `group` frames per launch (host only: no context,
+ * no device; 0 for a group outside 1..64): per frame one keypoint list, the responses, their
+ * positions and two position arrays of 65537, group * (65536 * (28 + 4 + 4) + 2 * 65537 * 4),
+ * 2.9 MB a frame.  A handle whose nfeatures was never set allocates none of it.  (v3:100, :373) */
+int64_t dvo_sift_retain_bytes(int group);
+
 /* The same SIFT_create().detectAndCompute (visual_odometry_v3.py:373) for DEVICE-resident
  * frames of one size, a group of frames per launch: every stage of the detector (upscale, the
  * blurs, downsample, DoG, extrema, refine, sort, descriptor) is one launch over `group` frames,
@@ -173,6 +194,16 @@ int dvo_sift_batch_detect(dvo_sift_batch* b, const uint8_t* d_frames, int n_fram
                           int feat_cap, dvo_keypoint* d_kps, float* d_desc, int32_t* d_counts);
 /* The HIP stream the detect calls run on (the context's). */
 void* dvo_sift_batch_hip_stream(dvo_sift_batch* b);
+/* SIFT_create(nfeatures) (v3:100, :373) for the detect calls that follow: retainBest as in
+ * dvo_sift_detect_and_compute_n, one more launch over the group between the sort and the
+ * descriptors; 0 (the default) launches and allocates what the handle always did.  Retain sees a
+ * frame's whole list, also where that is longer than feat_cap: d_counts[2 f] is the KEPT count,
+ * and a frame is complete when that is <= feat_cap (give feat_cap = nfeatures plus room for
+ * boundary ties).  Every frame's features equal dvo_sift_detect_and_compute_n's.  A setter that
+ * changes the value to one > 0 synchronises the context's stream and allocates
+ * dvo_sift_retain_bytes(group) bytes once; detect allocates nothing; dvo_sift_batch_bytes keeps
+ * its value.  DVO_EINVAL: nfeatures < 0. */
+int dvo_sift_batch_set_nfeatures(dvo_sift_batch* b, int nfeatures);
 
 /* Replaces cv::xfeatures2d::SURF_create(hessianThreshold).detectAndCompute(img,
  * None) — the detector of the 'surf' mode, visual_odometry_v3.py:104
@@ -451,6 +482,14 @@ typedef struct {
 } dvo_knn_pair_config;
 int dvo_knn_pair_create(dvo_ctx* ctx, const dvo_knn_pair_config* cfg, dvo_knn_pair** out);
 void dvo_knn_pair_destroy(dvo_knn_pair* p);
+/* SIFT_create(nfeatures) (v3:100, :373) for the runs that follow: both frames' features are
+ * dvo_sift_detect_and_compute_n's (retainBest before the descriptors; FLANN's draws follow the
+ * kept train count).  0 is the default.  A call that changes the value invalidates the cached
+ * previous-frame features: the next dvo_knn_pair_run must detect both frames (reuse_prev is
+ * DVO_EINVAL until a run succeeded), and allocates the context's retain scratch,
+ * dvo_sift_retain_bytes(1) bytes, once.  A call that changes nothing does nothing.
+ * DVO_EINVAL: a SURF handle (OpenCV's SURF_create has no such parameter), nfeatures < 0. */
+int dvo_knn_pair_set_nfeatures(dvo_knn_pair* p, int nfeatures);
 int dvo_knn_pair_run(dvo_knn_pair* p, const uint8_t* prev_img, const uint8_t* cur_img, int stride, int reuse_prev,
                      uint64_t* rng_state /* FLANN: in/out as dvo_flann_knn; else may be NULL */, dvo_pair_record* rec_out);
 /* The last pair's kept matches (queryIdx, trainIdx, 0, distance), ascending queryIdx; *m = count (DVO_ECAP if > cap). */
@@ -529,7 +568,8 @@ int dvo_knn_stream_process(dvo_knn_stream* s, const uint8_t* d_frames, int n_fra
  * the window's records equal one stream's over all its frames.  A call with a single pending
  * frame has no pair and plans nothing, as in process: its state does not move, so a sharded
  * stream gives every rank at least one pair per window.  A BFMatcher stream ignores the array.  dvo_knn_stream_set_rng_state between the phases is allowed and ordered before the plan;
- * dvo_knn_stream_set_detect_group, _set_surf_group and _set_flann drop the pending detection.
+ * dvo_knn_stream_set_detect_group, _set_surf_group, _set_flann and (where it changes the value)
+ * _set_nfeatures drop the pending detection.
  * dvo_knn_stream_stage_times keeps its three figures across the two calls (a collective the
  * caller orders between them counts into the matching figure).
  * DVO_EINVAL: nothing pending, world outside 1..1024, rank outside 0..world - 1, d_records NULL
@@ -554,6 +594,20 @@ int dvo_knn_stream_set_detect_group(dvo_knn_stream* s, int group);
  * matches either way.  The setter synchronises the context's stream and allocates (or frees)
  * dvo_surf_batch_bytes(width, height, group) bytes.  DVO_EINVAL: a SIFT stream, group outside 0..64. */
 int dvo_knn_stream_set_surf_group(dvo_knn_stream* s, int group);
+/* SIFT_create(nfeatures) (v3:100, :373) for the detections that follow, in both routes: frame by
+ * frame retainBest runs inside the context's detector, with a detect group inside the group
+ * detector, where it sees a frame's whole list before anything is cut at feat_cap.  Every frame
+ * slot then holds dvo_sift_detect_and_compute_n's features, a record's counts are the kept
+ * counts, both matchers take the kept features (FLANN's draws follow the kept train counts, in one
+ * call, in two phases and sharded), and a frame is DVO_ECAP only where its KEPT count exceeds
+ * feat_cap: give feat_cap = nfeatures plus room for boundary ties.  0 (the default) launches and
+ * allocates what the stream always did.  A call that changes the value drops a pending detection,
+ * synchronises the context's stream and, for a value > 0, allocates the retain scratch once:
+ * dvo_sift_retain_bytes(1) on the context and dvo_sift_retain_bytes(group) with a detect group
+ * (dvo_knn_stream_set_detect_group allocates the latter when it follows).  A call that changes
+ * nothing does nothing.  DVO_EINVAL: a SURF stream (OpenCV's SURF_create has no such parameter),
+ * nfeatures < 0. */
+int dvo_knn_stream_set_nfeatures(dvo_knn_stream* s, int nfeatures);
 /* The 'flann' mode in the batch (v3:207-212: FlannBasedMatcher(KDTREE, trees = 5), checks = 50):
  * trees 1..64 with checks >= 1 makes the process calls that follow build the randomized
  * kd-forest of every pair's train frame and search k = 2 for every query on the device, in
