@@ -128,6 +128,10 @@ _SIGNATURES = {
     "dvo_last_error": ([_vp], ctypes.c_char_p),
     "dvo_orb_detect_and_compute": ([_vp, ctypes.POINTER(OrbParams), _vp, _c, _c, _c, _vp, _vp, _c, _ip], _c),
     "dvo_bf_match_hamming": ([_vp, _vp, _c, _vp, _c, _c, _vp, _c, _ip], _c),
+    "dvo_bf_knn_hamming": ([_vp, _vp, _c, _vp, _c, _c, _vp, _vp], _c),
+    "dvo_test_bf_knn_hamming": ([_vp, _vp, _c, _vp, _c, _c, _c, _vp, _vp], _c),
+    "dvo_test_hamming_ratio_batch": ([_vp, _vp, _vp, _vp, _c, _c, _d, _vp, _vp, _vp, _vp, _vp], _c),
+    "dvo_stream_set_ratio_test": ([_vp, _d], _c),
     "dvo_bf_knn_float": ([_vp, _vp, _c, _vp, _c, _c, _c, _c, _vp, _vp], _c),
     "dvo_flann_knn": ([_vp, _vp, _c, _vp, _c, _c, _c, _c, _c, ctypes.POINTER(ctypes.c_uint64), _vp, _vp], _c),
     "dvo_sift_detect_and_compute": ([_vp, _vp, _c, _c, _c, _vp, _vp, _c, _ip], _c),

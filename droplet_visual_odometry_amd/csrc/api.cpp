@@ -91,6 +91,7 @@ struct dvo_stream {
     bool carry_ev_valid = false;
     dvo_stream* carry_owner = nullptr;  // stream whose carry this one uses (itself by default)
     bool own_hs = false;
+    double ratio = 0;  // > 0: match with Hamming 2-NN + this ratio test, not cfg.cross_check (dvo_stream_set_ratio_test)
     int last_nframes = 0;
     int last_pairs = 0;           // pairs of that call (n - 1 for a stream, n / 2 for independent pairs)
     bool last_has_pairs = false;  // the last call ran match + geometry
@@ -526,6 +527,7 @@ int retire_sets(dvo_stream* s) {
         if (!st.used || st.round < kRansacRounds) continue;
         const PairArrays v = s->pairs.view(k);
         HIP_TRY(launch_retire(v.g, st.pairs, v.hdr, st.rec, s->hs));
+        if (s->ratio > 0) HIP_TRY(launch_hamming_ratio_status(v.hdr, st.pairs, st.rec, nullptr, s->hs));
         s->retired_rec[s->retired] = st.rec;
         s->retired_pairs[s->retired] = st.pairs;
         ++s->retired;
@@ -587,7 +589,10 @@ int run_stream(dvo_stream* s, const uint8_t* d_frames, int n, int64_t fstride, i
     if (detect_only) return DVO_OK;
     if (pairs >= 1) {
         // match into set k (its KeyPoint_convert points and counts), the frame-side record values
-        HIP_TRY(launch_match(P, s->cfg.cross_check, s->hs, ev));
+        if (s->ratio > 0)
+            HIP_TRY(launch_match_ratio(P, s->ratio, s->hs, ev));
+        else
+            HIP_TRY(launch_match(P, s->cfg.cross_check, s->hs, ev));
         HIP_TRY(launch_pair_header(P, P.buf.hdr, s->hs));
         HIP_TRY(launch_geometry_args(s->pairs.view(k).g, pairs, kStageNormalize, s->hs));
         s->sets[k] = dvo_stream::PairSet{true, 0, pairs, d_rec};
@@ -995,8 +1000,12 @@ int dvo_stream_pair(dvo_stream* s, const uint8_t* prev_img, const uint8_t* cur_i
     const int nqb = ((int)kc + 255) / 256, nst = ((int)kc + 63) / 64;
     int tsplit = 1;
     while (tsplit < 16 && nqb * tsplit * 2 <= 256 && nst >= tsplit * 8) tsplit *= 2;
-    HIP_TRY(launch_match(P, s->cfg.cross_check, s->hs, nullptr, tsplit));
+    if (s->ratio > 0)
+        HIP_TRY(launch_match_ratio(P, s->ratio, s->hs));
+    else
+        HIP_TRY(launch_match(P, s->cfg.cross_check, s->hs, nullptr, tsplit));
     HIP_TRY(launch_geometry(P, s->pairs.all.g, s->pair_rec, s->hs, nullptr, true));
+    if (s->ratio > 0) HIP_TRY(launch_hamming_ratio_status(P.buf.hdr, 1, s->pair_rec, nullptr, s->hs));
     uint8_t* hr = nullptr;
     HIP_TRY(mem.get(s->pair_rec, sizeof(dvo_pair_record), &hr));
     HIP_TRY(hipStreamSynchronize(s->hs));
@@ -1018,6 +1027,16 @@ int dvo_stream_pair(dvo_stream* s, const uint8_t* prev_img, const uint8_t* cur_i
     s->last_frames = s->d_frames;
     s->last_fstride = fst;
     s->last_pitch = pw;
+    return DVO_OK;
+}
+
+int dvo_stream_set_ratio_test(dvo_stream* s, double ratio) {
+    if (!s) return DVO_EINVAL;
+    dvo_ctx* ctx = s->ctx;
+    if (!std::isfinite(ratio) || ratio < 0) return fail(ctx, DVO_EINVAL, "ratio must be finite and >= 0 (0: off)");
+    if (sets_pending(s))
+        return fail(ctx, DVO_EINVAL, "dvo_stream_set_ratio_test: submitted batches are pending (dvo_stream_drain)");
+    s->ratio = ratio;
     return DVO_OK;
 }
 
@@ -1192,6 +1211,58 @@ int dvo_bf_match_hamming(dvo_ctx* ctx, const uint8_t* dq, int nq, const uint8_t*
     if (m > cap) return fail(ctx, DVO_ECAP, "caller capacity too small");
     if (m) std::memcpy(out, hout, (size_t)m * sizeof(dvo_dmatch));
     return DVO_OK;
+}
+
+int dvo_test_bf_knn_hamming(dvo_ctx* ctx, const uint8_t* dq, int nq, const uint8_t* dt, int nt, int k, int tsplit,
+                            int32_t* train_idx, float* dist) {
+    if (!ctx) return DVO_EINVAL;
+    if (k < 1 || k > 2) return fail(ctx, DVO_EINVAL, "k must be 1 or 2");
+    if (tsplit < 0 || tsplit > 16) return fail(ctx, DVO_EINVAL, "tsplit must be 0 (chosen by size) .. 16");
+    if (nq < 0 || nt < 0 || nq > 8192 || nt > 8192)
+        return fail(ctx, DVO_EINVAL, "descriptor count out of range (0..8192)");
+    if (nq == 0) return DVO_OK;
+    if (!dq || !train_idx || !dist || (nt > 0 && !dt)) return fail(ctx, DVO_EINVAL, "null buffer");
+    if (nt == 0) {  // batchDistance leaves every slot at (-1, FLT_MAX)
+        for (size_t i = 0; i < (size_t)nq * k; ++i) {
+            train_idx[i] = -1;
+            dist[i] = FLT_MAX;
+        }
+        return DVO_OK;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (tsplit == 0) tsplit = hamming_knn_split(nq, nt);
+    const size_t out_n = (size_t)nq * k;
+    CallMem mem(ctx->call, ctx->stream);
+    uint8_t* bq = mem.dev<uint8_t>((size_t)nq * 32);
+    uint8_t* bt = mem.dev<uint8_t>((size_t)nt * 32);
+    uint8_t* bw = mem.dev<uint8_t>(hamming_knn_work_size(nq, tsplit));
+    int32_t* bi = mem.dev<int32_t>(out_n);
+    float* bd = mem.dev<float>(out_n);
+    HIP_TRY(mem.error());
+    uint8_t *hi = nullptr, *hd = nullptr;
+    // after the first upload an error drains the stream before returning (the copies use the
+    // context's pinned buffers, which the next per-call entry point rewrites)
+    auto body = [&]() -> int {
+        HIP_TRY(mem.put(bq, dq, (size_t)nq * 32));
+        HIP_TRY(mem.put(bt, dt, (size_t)nt * 32));
+        HIP_TRY(launch_knn_hamming_pair(bq, nq, bt, nt, k, tsplit, bw, bi, bd, ctx->stream));
+        HIP_TRY(mem.get(bi, out_n * 4, &hi));
+        HIP_TRY(mem.get(bd, out_n * 4, &hd));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return DVO_OK;
+    };
+    if (int rc = body()) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    std::memcpy(train_idx, hi, out_n * 4);
+    std::memcpy(dist, hd, out_n * 4);
+    return DVO_OK;
+}
+
+int dvo_bf_knn_hamming(dvo_ctx* ctx, const uint8_t* dq, int nq, const uint8_t* dt, int nt, int k, int32_t* train_idx,
+                       float* dist) {
+    return dvo_test_bf_knn_hamming(ctx, dq, nq, dt, nt, k, 0, train_idx, dist);
 }
 
 int dvo_bf_knn_float(dvo_ctx* ctx, const float* dq, int nq, const float* dt, int nt, int dim, int k, int norm,
@@ -2606,6 +2677,8 @@ struct dvo_knn_stream {
     int matched_frames = 0;  // frames of the last finished call (dvo_knn_stream_get_matches)
     bool pending_timed = false;  // the pending detection recorded ev[0], ev[1]
     bool profiling = false, timed = false;
+    bool times_read = false;  // times_ms holds the figures of the last timed call (read once: a later
+    double times_ms[3] = {};  // hipEventElapsedTime of the same events may differ in the last digit)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     // dvo_knn_stream_set_raw_input: max_frames gray frames of raw_pitch-byte rows, what a colour,
     // distorted or JPEG call detects on
@@ -2718,7 +2791,7 @@ int knn_stream_detect_gray(dvo_knn_stream* st, const uint8_t* d_frames, int n_fr
     const bool sift = c.detector == DVO_DETECT_SIFT;
     hipEvent_t* ev = st->profiling ? st->ev : nullptr;
     st->last_frames = st->pending = st->matched_frames = 0;  // a pending detection is replaced
-    st->timed = st->pending_timed = false;
+    st->timed = st->pending_timed = st->times_read = false;
     if (ev && ev_in < 0) HIP_TRY(hipEventRecord(ev[0], s));
     st->first_ev = ev_in;
     // detection in place on the caller's frames: a group of frames per launch straight into the
@@ -2807,6 +2880,7 @@ int dvo_knn_stream_finish(dvo_knn_stream* st, dvo_pair_record* d_records, const 
     if (ev) {
         HIP_TRY(hipEventRecord(ev[3], s));
         st->timed = true;
+        st->times_read = false;
     }
     st->matched_frames = n_frames;
     return DVO_OK;
@@ -2952,7 +3026,7 @@ int dvo_knn_stream_set_profiling(dvo_knn_stream* s, int enable) {
         for (hipEvent_t* e : {&s->ev[0], &s->ev[1], &s->ev[2], &s->ev[3], &s->ev_in[0], &s->ev_in[1]})
             if (!*e) HIP_TRY(hipEventCreate(e));
     s->profiling = enable != 0;
-    s->timed = false;
+    s->timed = s->times_read = false;
     return DVO_OK;
 }
 
@@ -2960,13 +3034,17 @@ int dvo_knn_stream_stage_times(dvo_knn_stream* s, double* ms) {
     if (!s || !ms) return DVO_EINVAL;
     dvo_ctx* ctx = s->ctx;
     if (!s->timed) return fail(ctx, DVO_EINVAL, "no profiled dvo_knn_stream_process call");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipEventSynchronize(s->ev[3]));
-    for (int k = 0; k < 3; ++k) {
-        float t = 0.f;
-        HIP_TRY(hipEventElapsedTime(&t, k == 0 && s->first_ev >= 0 ? s->ev_in[s->first_ev] : s->ev[k], s->ev[k + 1]));
-        ms[k] = t;
+    if (!s->times_read) {
+        HIP_TRY(hipSetDevice(ctx->device));
+        HIP_TRY(hipEventSynchronize(s->ev[3]));
+        for (int k = 0; k < 3; ++k) {
+            float t = 0.f;
+            HIP_TRY(hipEventElapsedTime(&t, k == 0 && s->first_ev >= 0 ? s->ev_in[s->first_ev] : s->ev[k], s->ev[k + 1]));
+            s->times_ms[k] = t;
+        }
+        s->times_read = true;
     }
+    for (int k = 0; k < 3; ++k) ms[k] = s->times_ms[k];
     return DVO_OK;
 }
 
@@ -3073,6 +3151,79 @@ int dvo_test_knn_batch(dvo_ctx* ctx, const float* desc, const dvo_keypoint* kps,
     std::memcpy(pts, hp, P * C * 16);
     std::memcpy(hdr, hh, P * sizeof(PairHeader));
     std::memcpy(missing, hs, P * 4);
+    return DVO_OK;
+}
+
+// Test hook: the ORB stream's ratio-mode match stage (launch_match_ratio) and pair statuses on host arrays.
+int dvo_test_hamming_ratio_batch(dvo_ctx* ctx, const uint8_t* desc, const dvo_keypoint* kps, const int32_t* counts,
+                                 int frames, int cap, double ratio, int32_t* top2, int32_t* nmatch, dvo_dmatch* matches,
+                                 float* pts, int32_t* status) {
+    if (!ctx || !desc || !kps || !counts || !top2 || !nmatch || !matches || !pts || !status) return DVO_EINVAL;
+    if (frames < 2 || frames > 4096 || cap < 1 || cap > 8192)
+        return fail(ctx, DVO_EINVAL, "frames 2..4096, cap 1..8192");
+    if (!std::isfinite(ratio) || !(ratio > 0)) return fail(ctx, DVO_EINVAL, "ratio must be finite and > 0");
+    for (int f = 0; f < frames; ++f)
+        if (counts[f] < 0 || counts[f] > cap) return fail(ctx, DVO_EINVAL, "count out of range (0..cap)");
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    CallMem mem(ctx->call, s);
+    const size_t F = (size_t)frames, P = F - 1, C = (size_t)cap;
+    StreamParams sp{};
+    sp.plan.kp_cap = cap;
+    sp.nframes = frames;
+    sp.pair_step = 1;
+    Buffers& b = sp.buf;
+    b.desc = mem.dev<uint8_t>(F * C * 32);
+    b.kps = mem.dev<dvo_keypoint>(F * C);
+    b.nkp = mem.dev<int32_t>(F);
+    b.status = mem.dev<int32_t>(F);
+    b.nn = mem.dev<int32_t>(2 * F * C);
+    b.mq = mem.dev<int32_t>(F * C);
+    b.mt = mem.dev<int32_t>(F * C);
+    b.md = mem.dev<float>(F * C);
+    b.pts = mem.dev<float>(F * C * 4);
+    b.nmatch = mem.dev<int32_t>(F);
+    b.hdr = mem.dev<PairHeader>(F);
+    int32_t* d_status = mem.dev<int32_t>(F);
+    HIP_TRY(mem.error());
+    uint8_t *hw, *hn, *hq, *ht, *hd, *hp, *hs;
+    auto body = [&]() -> int {
+        HIP_TRY(mem.put(b.desc, desc, F * C * 32));
+        HIP_TRY(mem.put(b.kps, kps, F * C * sizeof(dvo_keypoint)));
+        HIP_TRY(mem.put(b.nkp, counts, F * 4));
+        HIP_TRY(hipMemsetAsync(b.status, 0, F * 4, s));
+        HIP_TRY(hipMemsetAsync(b.nn, 0xFF, 2 * F * C * 4, s));  // slots the kernels leave read as "none"
+        HIP_TRY(launch_match_ratio(sp, ratio, s));
+        HIP_TRY(launch_pair_header(sp, b.hdr, s));
+        HIP_TRY(launch_hamming_ratio_status(b.hdr, (int)P, nullptr, d_status, s));
+        HIP_TRY(mem.get(b.nn, 2 * F * C * 4, &hw));
+        HIP_TRY(mem.get(b.nmatch, P * 4, &hn));
+        HIP_TRY(mem.get(b.mq, P * C * 4, &hq));
+        HIP_TRY(mem.get(b.mt, P * C * 4, &ht));
+        HIP_TRY(mem.get(b.md, P * C * 4, &hd));
+        HIP_TRY(mem.get(b.pts, P * C * 16, &hp));
+        HIP_TRY(mem.get(d_status, P * 4, &hs));
+        HIP_TRY(hipStreamSynchronize(s));
+        return DVO_OK;
+    };
+    if (int rc = body()) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    std::memcpy(nmatch, hn, P * 4);
+    std::memcpy(status, hs, P * 4);
+    std::memcpy(pts, hp, P * C * 16);
+    const int32_t *w = (const int32_t*)hw, *mq = (const int32_t*)hq, *mt = (const int32_t*)ht;
+    const float* md = (const float*)hd;
+    for (size_t p = 0; p < P; ++p) {
+        for (size_t q = 0; q < C; ++q) {  // [P][cap][2]: nearest, second
+            top2[(p * C + q) * 2] = w[p * C + q];
+            top2[(p * C + q) * 2 + 1] = w[(F + p) * C + q];
+        }
+        const size_t m = (size_t)std::min(std::max(nmatch[p], 0), cap);
+        for (size_t i = 0; i < C; ++i)
+            matches[p * C + i] = i < m ? dvo_dmatch{mq[p * C + i], mt[p * C + i], 0, md[p * C + i]} : dvo_dmatch{-1, -1, 0, 0.f};
+    }
     return DVO_OK;
 }
 

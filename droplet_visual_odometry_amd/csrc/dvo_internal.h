@@ -470,6 +470,25 @@ hipError_t launch_surf(const SurfArgs& a, hipStream_t s);
 hipError_t launch_surf_group(const SurfGroupArgs& G, int frames, hipStream_t s);
 hipError_t launch_match_pair(const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int cross_check, void* d_work,
                              dvo_dmatch* d_out, int* d_m, hipStream_t s);
+// Hamming 2-NN + ratio test, the ORB stream's opt-in matcher (dvo_stream_set_ratio_test): what
+// launch_match leaves for the geometry stage (mq / mt / md / pts / nmatch), kept matches in ascending
+// queryIdx; P.buf.nn holds the packed nearest (forward half) and second (the other half) words.
+hipError_t launch_match_ratio(const StreamParams& P, double ratio, hipStream_t s, hipEvent_t* ev = nullptr);
+// its second step (ratio.hip): the ratio test and gather of every pair from the packed words
+hipError_t launch_hamming_ratio(const StreamParams& P, double ratio, hipStream_t s);
+// The reference raises in `for m, n in matches` on a pair whose train frame has fewer than 2
+// descriptors: records[p] (null: none) becomes DVO_ENOFEAT with the counts, zeros elsewhere, unless
+// the pair is DVO_ECAP or has no query (those keep their record); status[p] (null: none) the
+// pair's status before RANSAC: DVO_ECAP, DVO_ENOFEAT or DVO_OK.
+hipError_t launch_hamming_ratio_status(const PairHeader* hdr, int pairs, dvo_pair_record* records, int32_t* status,
+                                       hipStream_t s);
+// One pair's BFMatcher(NORM_HAMMING).knnMatch (k 1 or 2) on nn2_mfma_kernel: tsplit train splits
+// (hamming_knn_split picks), d_work of hamming_knn_work_size(nq, tsplit) bytes, rows of k
+// (index, distance), (-1, FLT_MAX) where fewer than k trains exist.
+int hamming_knn_split(int nq, int nt);
+size_t hamming_knn_work_size(int nq, int tsplit);
+hipError_t launch_knn_hamming_pair(const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int k, int tsplit,
+                                   void* d_work, int32_t* d_idx, float* d_dist, hipStream_t s);
 // FLANN randomized kd-tree k-NN (flann.hip; the 'flann' mode's FlannBasedMatcher).
 struct FlannBuildArgs {
     const float* data;  // train set [n][dim]

@@ -10,6 +10,8 @@
 // and, through a one-pair parameter block, for the per-call C-ABI.
 // crosscheck_*_kernel: mutual-NN filter, then a bitonic sort of the unique
 // keys (distance << 16 | queryIdx) in LDS, then the point gather.
+// nn2_mfma_kernel: the two nearest trains of every query, for
+// BFMatcher(NORM_HAMMING).knnMatch(k = 2) and the stream's ratio test (opt-in).
 #include <algorithm>
 #include <cfloat>
 #include <climits>
@@ -240,6 +242,160 @@ void nn_mfma_kernel(StreamParams P, NnOperands O, int pairs, int nqb, int tsplit
         }
 }
 
+// ---- Hamming 2-NN: BFMatcher(NORM_HAMMING).knnMatch(k = 2) ---------------------
+// The forward half of nn_mfma_kernel with two running values per accumulator
+// register: same operand expansion, LDS staging and swizzle, XCD grouping and
+// key (Hamming * 8192 + trainIdx, exact in f32, compared as bit patterns).  No
+// backward keys, so the accumulators start at 2^20 + the lane's train index (the
+// MFMA's C input) and end as the keys themselves.  The keys of a query are
+// unique (the train index is in them), so its two smallest are batchDistance's
+// K = 2 result: ascending distance, the lower train index first on ties.
+// Columns past nt carry 2^20 + 2^30: above every real key, and decoded as "none".
+constexpr float kKeyEnd = (float)(257 << 13);  // keys of real trains lie below (Hamming <= 256)
+__device__ __forceinline__ int nn2_word(int kbits) {
+    const float f = __int_as_float(kbits);
+    return f < kKeyEnd ? key_old((int)f) : -1;
+}
+
+__device__ __forceinline__ void nn2_stage(const v4i* btc, const v4i (&A)[2][kMKs], int (&best)[2][16],
+                                          int (&second)[2][16], int t0, int nt, int r, int h) {
+#pragma unroll 1
+    for (int tt = 0; tt < kMStage / 32; ++tt) {
+        const int j = t0 + 32 * tt + r;
+        const float c = (float)kKeyBase + (float)(j < nt ? j : (1 << 30));
+        acc_t acc0, acc1;
+#pragma unroll
+        for (int g = 0; g < 16; ++g) acc0[g] = acc1[g] = c;
+#pragma unroll
+        for (int ks = 0; ks < kMKs; ++ks) {
+            const v4i B = btc[(32 * tt + r) * kMChunks + ((2 * ks + h) ^ (r & kChunkMask))];
+            acc0 = mfma_chunk(A[0][ks], B, acc0);
+            acc1 = mfma_chunk(A[1][ks], B, acc1);
+        }
+#pragma unroll
+        for (int g = 0; g < 16; ++g) {
+            const int k0 = __float_as_int(acc0[g]), k1 = __float_as_int(acc1[g]);
+            second[0][g] = min(second[0][g], max(best[0][g], k0));
+            best[0][g] = min(best[0][g], k0);
+            second[1][g] = min(second[1][g], max(best[1][g], k1));
+            best[1][g] = min(best[1][g], k1);
+        }
+    }
+}
+
+// Where a launch leaves its packed (Hamming << 16 | index) words, -1 for "none": query q of pair p,
+// train split ts at first / second[p * pair_stride + ts * split_stride + q].  Every (pair, split,
+// q < nq) slot is written, so the arrays need no fill.
+struct Nn2Out {
+    int32_t* first;
+    int32_t* second;
+    int64_t pair_stride, split_stride;
+};
+
+// tsplit > 1: each workgroup takes a contiguous 1 / tsplit of the train stages and leaves a
+// partial (nearest, second) pair of its own; hamming_knn_merge_kernel folds them.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DVO_MATCH_WAVES)))
+void nn2_mfma_kernel(StreamParams P, NnOperands O, Nn2Out W, int pairs, int nqb, int tsplit) {
+    __shared__ v4i bt[2][kMStage * kMChunks];
+    const int nwg = gridDim.x;  // a multiple of 8
+    const int L0 = (blockIdx.x & 7) * (nwg >> 3) + (blockIdx.x >> 3);
+    const int L = L0 / tsplit, ts = L0 - L * tsplit;
+    const int p = L / nqb, qb = L - p * nqb;
+    if (p >= pairs) return;
+    const int cap = P.plan.kp_cap;
+    const int fp = pair_frame(P, p);
+    const int nq = O.nq_fix >= 0 ? O.nq_fix : min(P.buf.nkp[fp], cap);
+    const int nt = O.nt_fix >= 0 ? O.nt_fix : min(P.buf.nkp[fp + 1], cap);
+    const int qbase = qb * kMQB;
+    if (qbase >= nq) return;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    const uint4* XQ = reinterpret_cast<const uint4*>(O.q0 + fp * O.stride);
+    const uint2* XT = reinterpret_cast<const uint2*>(O.t0 + fp * O.stride);
+    const int64_t oo = (int64_t)p * W.pair_stride + (int64_t)ts * W.split_stride;
+    const int qs = qbase + wid * 64;  // this wave's first query
+    v4i A[2][kMKs];
+    int best[2][16], second[2][16];
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+        const int q = qs + 32 * s2 + r;
+        const uint4 w0 = q < nq ? XQ[2 * (int64_t)q] : make_uint4(0, 0, 0, 0);
+        const uint4 w1 = q < nq ? XQ[2 * (int64_t)q + 1] : make_uint4(0, 0, 0, 0);
+        const uint32_t wd[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+#pragma unroll
+        for (int ks = 0; ks < kMKs; ++ks)  // chunk 2 ks + h; a zero fragment past nq
+            A[s2][ks] = q < nq ? expand_chunk(wd[2 * ks + h], kExpQ) : (v4i){0, 0, 0, 0};
+#pragma unroll
+        for (int g = 0; g < 16; ++g) best[s2][g] = second[s2][g] = kKeyNone;
+    }
+    const int nst_all = (nt + kMStage - 1) / kMStage;
+    const int st0 = (int)((int64_t)nst_all * ts / tsplit), nst = (int)((int64_t)nst_all * (ts + 1) / tsplit);
+    // a stage: 64 trains x 32 bytes, 8 bytes (chunks 2 qd, 2 qd + 1) per thread
+    const int tr = threadIdx.x >> 2, qd = threadIdx.x & 3;
+    uint2 v;
+    auto load_stage = [&](int st) { v = XT[(int64_t)min(st * kMStage + tr, nt - 1) * 4 + qd]; };  // clamped
+    auto store_stage = [&](int st, int b) {
+        const bool in = st * kMStage + tr < nt;  // zero operands past nt
+        constexpr int kPer = kMChunks / 4;
+#pragma unroll
+        for (int c = 0; c < kPer; ++c) {
+            const int ch = kPer * qd + c;
+            const uint32_t bits = c == 0 ? v.x : v.y;
+            bt[b][tr * kMChunks + (ch ^ (tr & kChunkMask))] = in ? expand_chunk(bits, kExpT) : (v4i){0, 0, 0, 0};
+        }
+    };
+    if (st0 < nst) {
+        load_stage(st0);
+        store_stage(st0, 0);
+    }
+    __syncthreads();
+    for (int st = st0; st < nst; ++st) {
+        const int cur = (st - st0) & 1;
+        if (st + 1 < nst) load_stage(st + 1);
+        nn2_stage(bt[cur], A, best, second, st * kMStage, nt, r, h);
+        if (st + 1 < nst) store_stage(st + 1, cur ^ 1);
+        __syncthreads();
+    }
+    // the 32 lanes of a half hold 32 disjoint column sets of a row: merge their pairs
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+        for (int g = 0; g < 16; ++g) {
+            int b = best[s2][g], s = second[s2][g];
+#pragma unroll
+            for (int o = 1; o < 32; o <<= 1) {
+                const int ob = __shfl_xor(b, o), os = __shfl_xor(s, o);
+                s = min(max(b, ob), min(s, os));
+                b = min(b, ob);
+            }
+            const int qr = qs + 32 * s2 + (g & 3) + 8 * (g >> 2) + 4 * h;
+            if (r == g && qr < nq) {
+                W.first[oo + qr] = nn2_word(b);
+                W.second[oo + qr] = nn2_word(s);
+            }
+        }
+}
+
+// The per-call path's closing pass: the tsplit partial pairs of a query (unsigned order: -1 is
+// "none", above every word) into knnMatch's rows, (-1, FLT_MAX) where fewer than k trains exist.
+__global__ __launch_bounds__(256) void hamming_knn_merge_kernel(Nn2Out W, int tsplit, int nq, int k, int32_t* idx,
+                                                                float* dist) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= nq) return;
+    uint32_t b = 0xFFFFFFFFu, s = 0xFFFFFFFFu;
+    for (int ts = 0; ts < tsplit; ++ts) {
+        const uint32_t ob = (uint32_t)W.first[ts * W.split_stride + q], os = (uint32_t)W.second[ts * W.split_stride + q];
+        s = min(max(b, ob), min(s, os));
+        b = min(b, ob);
+    }
+    for (int i = 0; i < k; ++i) {
+        const uint32_t w = i == 0 ? b : s;
+        const bool none = w == 0xFFFFFFFFu;
+        idx[(int64_t)q * k + i] = none ? -1 : (int)(w & 0xFFFF);
+        dist[(int64_t)q * k + i] = none ? FLT_MAX : (float)(w >> 16);
+    }
+}
+
 constexpr int kXNT = 1024;
 constexpr int kMaxSort = 8192;
 
@@ -455,6 +611,55 @@ hipError_t launch_match_pair(const uint8_t* d_q, int nq, const uint8_t* d_t, int
     const NnOperands O{d_q, d_t, 0, nq, nt};
     hipLaunchKernelGGL(nn_mfma_kernel, dim3(nwg), dim3(256), 0, s, P, O, 1, nqb, tsplit);
     hipLaunchKernelGGL(crosscheck_pair_kernel, dim3(1), dim3(kXNT), 0, s, fwd, bwd, nq, nt, cross_check, d_out, d_m);
+    return hipGetLastError();
+}
+
+// The stream's opt-in matcher (dvo_stream_set_ratio_test): every pair's Hamming 2-NN, the nearest
+// into the forward half of P.buf.nn and the second into the half the cross check keeps backward
+// keys in, then the ratio test and gather into mq / mt / md / pts / nmatch (ratio.hip).  Unsplit:
+// a batch has pairs enough, and the one pair of dvo_stream_pair has no room for partial lists.
+hipError_t launch_match_ratio(const StreamParams& P, double ratio, hipStream_t s, hipEvent_t* ev) {
+    const int pairs = stream_pairs(P);
+    if (pairs < 1) return hipSuccess;
+    mark(ev, 5, 0, s);
+    const int cap = P.plan.kp_cap;
+    const int nqb = (cap + kMQB - 1) / kMQB;
+    const int nwg = ((pairs * nqb + 7) / 8) * 8;  // XCD grouping needs a multiple of 8 blocks
+    const NnOperands O{P.buf.desc, P.buf.desc + (int64_t)cap * 32, (int64_t)cap * 32, -1, -1};
+    const Nn2Out W{P.buf.nn, P.buf.nn + (int64_t)P.nframes * cap, cap, 0};
+    hipLaunchKernelGGL(nn2_mfma_kernel, dim3(nwg), dim3(256), 0, s, P, O, W, pairs, nqb, 1);
+    const hipError_t e = launch_hamming_ratio(P, ratio, s);
+    mark(ev, 5, 1, s);
+    return e != hipSuccess ? e : hipGetLastError();
+}
+
+int hamming_knn_split(int nq, int nt) {
+    const int nqb = (nq + kMQB - 1) / kMQB, nst = (nt + kMStage - 1) / kMStage;
+    int tsplit = 1;
+    while (tsplit < 16 && nqb * tsplit * 2 <= 256 && nst >= tsplit * 4) tsplit *= 2;  // <= 256 workgroups, >= 2 stages each
+    return tsplit;
+}
+
+size_t hamming_knn_work_size(int nq, int tsplit) {
+    return (size_t)tsplit * 2 * ((size_t)(nq + kMQB - 1) / kMQB * kMQB) * sizeof(int32_t);
+}
+
+// One pair's knnMatch (dvo_bf_knn_hamming): the train stages over tsplit workgroups per query
+// block, a partial (nearest, second) list each in d_work, then the merge.
+hipError_t launch_knn_hamming_pair(const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int k, int tsplit,
+                                   void* d_work, int32_t* d_idx, float* d_dist, hipStream_t s) {
+    const int nqb = (nq + kMQB - 1) / kMQB;
+    const int64_t capq = (int64_t)nqb * kMQB;
+    StreamParams P{};
+    P.plan.kp_cap = (int)capq;
+    P.nframes = 2;
+    P.pair_step = 1;
+    int32_t* w = static_cast<int32_t*>(d_work);
+    const Nn2Out W{w, w + capq, 0, 2 * capq};
+    const NnOperands O{d_q, d_t, 0, nq, nt};
+    const int nwg = ((nqb * tsplit + 7) / 8) * 8;
+    hipLaunchKernelGGL(nn2_mfma_kernel, dim3(nwg), dim3(256), 0, s, P, O, W, 1, nqb, tsplit);
+    hipLaunchKernelGGL(hamming_knn_merge_kernel, dim3(nqb), dim3(256), 0, s, W, tsplit, nq, k, d_idx, d_dist);
     return hipGetLastError();
 }
 

@@ -12,6 +12,9 @@
 // launch (a workgroup per pair, the counts read from the frame slots); knn_frame_state_kernel and
 // knn_status_kernel are that path's bookkeeping: which frames overflow their slot, and the records
 // of the pairs the reference raises on before findEssentialMat.
+//
+// hamming_ratio_stream_kernel runs the body on the ORB stream's packed Hamming 2-NN words
+// (dvo_stream_set_ratio_test), and hamming_ratio_status_kernel marks the pairs the reference raises on.
 #include "dvo_internal.h"
 
 namespace dvo {
@@ -23,12 +26,14 @@ constexpr int kRatioNT = 1024;  // one workgroup: 16 waves walk the queries 1024
 // Python's test on the float32 values DMatch.distance holds: the product and the compare are
 // double (a float32 product 0.75f * d1 rounds and keeps a different set).  One workgroup of
 // kRatioNT lanes runs one pair; h is the header it leaves.
-__device__ __forceinline__ void ratio_gather_pair(const RatioArgs& a, const PairHeader h) {
+// load(q, id, dd): the two train indices and distances of query q; store(slot, q, t, d0): the
+// kept match of a slot.  The float matchers read a.idx / a.dist and write a.matches
+// (ratio_gather_pair); the Hamming stream reads packed words and writes mq / mt / md.
+template <class Load, class Store>
+__device__ __forceinline__ void ratio_gather_body(const RatioArgs& a, const PairHeader h, Load load, Store store) {
     __shared__ int wtot[kRatioNT / 64];
     __shared__ int wmiss[kRatioNT / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int2* idx2 = reinterpret_cast<const int2*>(a.idx);
-    const float2* dist2 = reinterpret_cast<const float2*>(a.dist);
     int base = 0;  // matches kept by the chunks before this one
     bool missing = false;
     for (int q0 = 0; q0 < a.nq; q0 += kRatioNT) {
@@ -37,8 +42,9 @@ __device__ __forceinline__ void ratio_gather_pair(const RatioArgs& a, const Pair
         int t = -1;
         float d0 = 0.f;
         if (q < a.nq) {
-            const int2 id = idx2[q];
-            const float2 dd = dist2[q];
+            int2 id;
+            float2 dd;
+            load(q, id, dd);
             float d1 = dd.y;
             d0 = dd.x;
             if (a.squared) {  // FlannBasedMatcher::convertToDMatches: std::sqrt(float)
@@ -65,7 +71,7 @@ __device__ __forceinline__ void ratio_gather_pair(const RatioArgs& a, const Pair
             const dvo_keypoint& kq = a.kq[q];
             const dvo_keypoint& kt = a.kt[t];
             reinterpret_cast<float4*>(a.pts)[slot] = make_float4(kq.x, kq.y, kt.x, kt.y);
-            reinterpret_cast<int4*>(a.matches)[slot] = make_int4(q, t, 0, __float_as_int(d0));
+            store(slot, q, t, d0);
         }
         base += total;
         __syncthreads();  // wtot is rewritten by the next chunk
@@ -77,9 +83,66 @@ __device__ __forceinline__ void ratio_gather_pair(const RatioArgs& a, const Pair
         int any = 0;
         for (int w = 0; w < kRatioNT / 64; ++w) any |= wmiss[w];
         *a.nmatch = base;
-        *a.hdr = h;
-        *a.missing = any;
+        if (a.hdr) *a.hdr = h;
+        if (a.missing) *a.missing = any;
     }
+}
+
+__device__ __forceinline__ void ratio_gather_pair(const RatioArgs& a, const PairHeader h) {
+    const int2* idx2 = reinterpret_cast<const int2*>(a.idx);
+    const float2* dist2 = reinterpret_cast<const float2*>(a.dist);
+    ratio_gather_body(
+        a, h,
+        [&](int q, int2& id, float2& dd) {
+            id = idx2[q];
+            dd = dist2[q];
+        },
+        [&](int slot, int q, int t, float d0) {
+            reinterpret_cast<int4*>(a.matches)[slot] = make_int4(q, t, 0, __float_as_int(d0));
+        });
+}
+
+// The ORB stream's ratio mode (launch_match_ratio): pair blockIdx.x's packed Hamming words
+// (distance << 16 | trainIdx, -1 none; nearest in the forward half of P.buf.nn, second in the other)
+// through the same body, the kept matches where crosscheck_stream_kernel leaves its own.
+__global__ __launch_bounds__(kRatioNT) void hamming_ratio_stream_kernel(StreamParams P, double ratio) {
+    const int p = blockIdx.x;
+    const int cap = P.plan.kp_cap;
+    const int fp = pair_frame(P, p);
+    const int nq = min(P.buf.nkp[fp], cap), nt = min(P.buf.nkp[fp + 1], cap);
+    const int32_t* w1 = P.buf.nn + (int64_t)p * cap;
+    const int32_t* w2 = P.buf.nn + ((int64_t)P.nframes + p) * cap;
+    int32_t* mq = P.buf.mq + (int64_t)p * cap;
+    int32_t* mt = P.buf.mt + (int64_t)p * cap;
+    float* md = P.buf.md + (int64_t)p * cap;
+    const RatioArgs a{nullptr, nullptr, P.buf.kps + (int64_t)fp * cap, P.buf.kps + (int64_t)(fp + 1) * cap, nq, nq, nt,
+                      ratio, 0, P.buf.pts + (int64_t)p * cap * 4, nullptr, P.buf.nmatch + p, nullptr, nullptr};
+    ratio_gather_body(
+        a, PairHeader{},
+        [&](int q, int2& id, float2& dd) {
+            const int a1 = w1[q], a2 = w2[q];
+            id = make_int2(a1 < 0 ? -1 : a1 & 0xFFFF, a2 < 0 ? -1 : a2 & 0xFFFF);
+            dd = make_float2((float)(a1 >> 16), (float)(a2 >> 16));
+        },
+        [&](int slot, int q, int t, float d0) {
+            mq[slot] = q;
+            mt[slot] = t;
+            md[slot] = d0;
+        });
+}
+
+__global__ __launch_bounds__(64) void hamming_ratio_status_kernel(const PairHeader* hdr, int pairs, dvo_pair_record* rec,
+                                                                  int32_t* status) {
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= pairs) return;
+    const PairHeader h = hdr[p];
+    if (status) status[p] = h.flags ? DVO_ECAP : (h.nkp_prev == 0 || h.nkp_cur < 2) ? DVO_ENOFEAT : DVO_OK;
+    if (!rec || h.flags || h.nkp_prev == 0 || h.nkp_cur >= 2) return;
+    dvo_pair_record r{};
+    r.n_kp_prev = h.nkp_prev;
+    r.n_kp_cur = h.nkp_cur;
+    r.status = DVO_ENOFEAT;
+    rec[p] = r;
 }
 
 __global__ __launch_bounds__(kRatioNT) void ratio_gather_kernel(RatioArgs a) {
@@ -142,6 +205,20 @@ __global__ __launch_bounds__(64) void knn_status_kernel(const int32_t* n, const 
 
 hipError_t launch_ratio_gather(const RatioArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(ratio_gather_kernel, dim3(1), dim3(kRatioNT), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_hamming_ratio(const StreamParams& P, double ratio, hipStream_t s) {
+    const int pairs = stream_pairs(P);
+    if (pairs < 1) return hipSuccess;
+    hipLaunchKernelGGL(hamming_ratio_stream_kernel, dim3(pairs), dim3(kRatioNT), 0, s, P, ratio);
+    return hipGetLastError();
+}
+
+hipError_t launch_hamming_ratio_status(const PairHeader* hdr, int pairs, dvo_pair_record* records, int32_t* status,
+                                       hipStream_t s) {
+    if (pairs < 1) return hipSuccess;
+    hipLaunchKernelGGL(hamming_ratio_status_kernel, dim3((pairs + 63) / 64), dim3(64), 0, s, hdr, pairs, records, status);
     return hipGetLastError();
 }
 

@@ -262,7 +262,8 @@ class BFMatcher:
     crossCheck follows OpenCV 4.x (mutual nearest neighbour) unless
     legacy_crosscheck=True (default: OPENCV_SEMANTICS == "3.2") selects OpenCV
     3.x's reverse-pass semantics; it is implemented for NORM_HAMMING (the
-    reference sets it only there)."""
+    reference sets it only there).  knnMatch on NORM_HAMMING serves k = 1 and
+    k = 2 (ops.bf_knn_hamming), the ratio-test filter for ORB descriptors."""
 
     def __init__(self, normType=NORM_L2, crossCheck=False, legacy_crosscheck=None):
         self.normType = normType
@@ -302,9 +303,37 @@ class BFMatcher:
             raise error("match masks are not supported")
         if queryDescriptors is None or trainDescriptors is None:
             raise error("(-215:Assertion failed) descriptors must not be empty")
-        self._check_l1()
-        out = _knn_lists(_float_desc(queryDescriptors), _float_desc(trainDescriptors), int(k), ops.NORM_L1)
+        if self.normType == NORM_HAMMING:
+            out = self._knn_hamming(queryDescriptors, trainDescriptors, int(k))
+        else:
+            self._check_l1()
+            out = _knn_lists(_float_desc(queryDescriptors), _float_desc(trainDescriptors), int(k), ops.NORM_L1)
         return [r for r in out if r] if compactResult else out
+
+    def _knn_hamming(self, queryDescriptors, trainDescriptors, k):
+        """knnMatch of 32-byte descriptors (ops.bf_knn_hamming): rows of up to k DMatch."""
+        q = np.asarray(queryDescriptors)
+        t = np.asarray(trainDescriptors)
+        if q.dtype != np.uint8 or t.dtype != np.uint8 or q.shape[-1] != 32 or t.shape[-1] != 32:
+            raise error("(-215:Assertion failed) NORM_HAMMING needs uint8 descriptors of 32 bytes")
+        if self.crossCheck and k > 1:
+            raise error("(-215:Assertion failed) knn == 1 || !crossCheck")
+        if k < 1 or k > 2:
+            raise error("NORM_HAMMING knnMatch is implemented for k = 1 and k = 2")
+        q, t = q.reshape(-1, 32), t.reshape(-1, 32)
+        if len(q) == 0 or len(t) == 0:
+            return [[] for _ in range(len(q))] if len(t) == 0 else []
+        if self.crossCheck:  # k = 1: the cross-checked match list, a row per query
+            out = [[] for _ in range(len(q))]
+            for m in self.match(q, t):
+                out[m.queryIdx].append(m)
+            return out
+        try:
+            idx, dist = ops.bf_knn_hamming(q, t, k)
+        except DVOError as e:
+            raise error(str(e)) from e
+        return [[DMatch(qi, int(idx[qi, s]), 0, float(dist[qi, s])) for s in range(k) if idx[qi, s] >= 0]
+                for qi in range(len(q))]
 
 
 # cv::theRNG(): per-thread process state in OpenCV.  FLANN's kd-tree builds draw

@@ -388,6 +388,24 @@ def bf_knn_float(dq: np.ndarray, dt: np.ndarray, k: int = 2, norm: int = NORM_L1
     return idx[:nq].copy(), dist[:nq].copy()
 
 
+def bf_knn_hamming(dq: np.ndarray, dt: np.ndarray, k: int = 2, tsplit: int = 0, ctx=None):
+    """BFMatcher(NORM_HAMMING).knnMatch(dq, dt, k) on 32-byte descriptors, k 1 or 2: (train_idx
+    int32[nq, k], dist float32[nq, k]) in OpenCV's order (ascending distance, lower train index
+    first on ties); -1 / FLT_MAX where fewer than k trains exist.  tsplit (tests, timing): the
+    train splits per query block, 0 = the library's choice; the result does not depend on it."""
+    c = _ctx(ctx)
+    dq = np.ascontiguousarray(dq, np.uint8).reshape(-1, 32)
+    dt = np.ascontiguousarray(dt, np.uint8).reshape(-1, 32)
+    nq, nt = len(dq), len(dt)
+    idx = np.zeros((max(nq, 1), k), np.int32)
+    dist = np.zeros((max(nq, 1), k), np.float32)
+    if tsplit:
+        c.check(c.lib.dvo_test_bf_knn_hamming(c.h, ptr(dq), nq, ptr(dt), nt, int(k), int(tsplit), ptr(idx), ptr(dist)))
+    else:
+        c.check(c.lib.dvo_bf_knn_hamming(c.h, ptr(dq), nq, ptr(dt), nt, int(k), ptr(idx), ptr(dist)))
+    return idx[:nq].copy(), dist[:nq].copy()
+
+
 THE_RNG_SEED = 0xFFFFFFFF  # cv::theRNG() of a fresh thread (cv::RNG() state)
 
 
@@ -989,7 +1007,9 @@ class PairStream:
     no torch involved."""
 
     def __init__(self, width, height, K, nfeatures=500, fast_threshold=20, cross_check=1, opencv="4.x", prob=0.999,
-                 threshold=1.0, max_iters=1000, dist_thresh=50.0, ctx=None):
+                 threshold=1.0, max_iters=1000, dist_thresh=50.0, ctx=None, ratio=None):
+        """ratio: None / 0 matches with cross_check; a ratio > 0 with knnMatch(k = 2) and the ratio
+        test instead (set_ratio_test)."""
         self.ctx = _ctx(ctx)
         cfg = StreamConfig()
         cfg.width, cfg.height, cfg.max_frames = int(width), int(height), 2
@@ -1003,6 +1023,13 @@ class PairStream:
         self.ctx.check(self.ctx.lib.dvo_stream_create(self.ctx.h, ctypes.byref(cfg), ctypes.byref(h)))
         self.h = h
         self.width, self.height = int(width), int(height)
+        if ratio:
+            self.set_ratio_test(ratio)
+
+    def set_ratio_test(self, ratio):
+        """Match later pairs with the Hamming 2-NN and `m.distance < ratio * n.distance`
+        (dvo_stream_set_ratio_test); None / 0: back to cross_check."""
+        self.ctx.check(self.ctx.lib.dvo_stream_set_ratio_test(self.h, float(ratio or 0.0)))
 
     def pair(self, prev_img, cur_img, reuse_prev=False) -> np.ndarray:
         cur = np.ascontiguousarray(cur_img, np.uint8)
@@ -1071,6 +1098,30 @@ def test_knn_batch(desc, kps, counts, ranges=0, ratio=0.75, ctx=None):
                                      ptr(out["idx"]), ptr(out["dist"]), ptr(out["nmatch"]), ptr(out["matches"]),
                                      ptr(out["pts"]), ptr(out["hdr"]), ptr(out["missing"]), ctypes.byref(used)))
     out["ranges_used"] = used.value
+    return out
+
+
+def test_hamming_ratio_batch(desc, kps, counts, ratio=0.75, ctx=None):
+    """The ratio-mode match stage of FrameStream(ratio=) (Hamming 2-NN, ratio test, gather) and the
+    pair statuses on host arrays: desc uint8[F, cap, 32] frame slots, kps KEYPOINT_DTYPE[F, cap],
+    counts int[F] (0..cap); pair p is frames p (queries), p + 1 (trains).  Returns a dict of per-pair
+    arrays: top2 int32[P, cap, 2] (packed distance << 16 | trainIdx of the nearest and the second, -1
+    none), nmatch int32[P], matches DMATCH_DTYPE[P, cap] and pts float32[P, cap, 4] (entries <
+    nmatch), status int32[P] (0 or DVO_ENOFEAT)."""
+    c = _ctx(ctx)
+    desc = np.ascontiguousarray(desc, np.uint8)
+    kps = np.ascontiguousarray(kps, KEYPOINT_DTYPE)
+    counts = np.ascontiguousarray(counts, np.int32)
+    if desc.ndim != 3 or desc.shape[2] != 32 or kps.shape != desc.shape[:2] or counts.shape != desc.shape[:1]:
+        raise DVOError(-1, "desc uint8[F, cap, 32], kps [F, cap] and counts [F] must agree")
+    F, cap, _ = desc.shape
+    P = max(F - 1, 1)
+    out = dict(top2=np.zeros((P, cap, 2), np.int32), nmatch=np.zeros(P, np.int32),
+               matches=np.zeros((P, cap), DMATCH_DTYPE), pts=np.zeros((P, cap, 4), np.float32),
+               status=np.zeros(P, np.int32))
+    c.check(c.lib.dvo_test_hamming_ratio_batch(c.h, ptr(desc), ptr(kps), ptr(counts), F, cap, float(ratio),
+                                               ptr(out["top2"]), ptr(out["nmatch"]), ptr(out["matches"]),
+                                               ptr(out["pts"]), ptr(out["status"])))
     return out
 
 

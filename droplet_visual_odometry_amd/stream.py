@@ -25,10 +25,13 @@ from ._native import (DMATCH_DTYPE, KEYPOINT_DTYPE, PAIR_RECORD_DTYPE, Context, 
 class FrameStream:
     def __init__(self, width: int, height: int, K, nfeatures: int = 500, max_frames: int = 64, prob: float = 0.999,
                  threshold: float = 1.0, max_iters: int = 1000, cross_check: int | None = None,
-                 dist_thresh: float = 50.0, device: int | None = None, ctx: Context | None = None, opencv="4.x"):
+                 dist_thresh: float = 50.0, device: int | None = None, ctx: Context | None = None, opencv="4.x",
+                 ratio: float | None = None):
         """opencv: the OpenCV version whose semantics the path reproduces, "4.x"
         (default) or "3.2" (ORB pyramid / retainBest, and cross_check defaults
-        to the 3.x reverse pass); see include/dvo.h DVO_OPENCV_*."""
+        to the 3.x reverse pass); see include/dvo.h DVO_OPENCV_*.
+        ratio: None / 0 (default) matches with cross_check; a ratio > 0 matches with
+        knnMatch(k = 2) and Lowe's ratio test instead (set_ratio_test)."""
         from ._native import opencv_semantics
         sem = opencv_semantics(opencv)
         if cross_check is None:
@@ -58,10 +61,20 @@ class FrameStream:
         self._pending = {}  # records of submitted, not yet retired batches (by device address)
         self.width, self.height, self.max_frames, self.nfeatures = width, height, max_frames, nfeatures
         self.K = K.reshape(3, 3)
+        if ratio:
+            self.set_ratio_test(ratio)
 
     @property
     def hip_stream(self) -> int:
         return self.ctx.lib.dvo_stream_hip_stream(self.h) or 0
+
+    def set_ratio_test(self, ratio: float | None):
+        """Match every later batch with the Hamming 2-NN and the reference's k-NN filter
+        `m.distance < ratio * n.distance` (v3:223-228) instead of the cross check: kept matches in
+        ascending queryIdx, n_matches their count, DVO_ENOFEAT for a pair whose current frame has
+        fewer than 2 descriptors.  None / 0: back to cross_check.  Refused (DVOError) while
+        submitted batches are pending, and for a negative or non-finite ratio."""
+        self.ctx.check(self.ctx.lib.dvo_stream_set_ratio_test(self.h, float(0.0 if ratio is None else ratio)))
 
     def new_records(self, n_pairs: int) -> torch.Tensor:
         return torch.zeros(max(n_pairs, 1) * PAIR_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=self.device)

@@ -92,6 +92,13 @@ int dvo_orb_detect_and_compute(dvo_ctx* ctx, const dvo_orb_params* params, const
 int dvo_bf_match_hamming(dvo_ctx* ctx, const uint8_t* dq, int nq, const uint8_t* dt, int nt, int cross_check,
                          dvo_dmatch* out, int cap, int* m_out);
 
+/* cv::BFMatcher(NORM_HAMMING).knnMatch(query, train, k) on 32-byte descriptors,
+ * k 1 or 2, nq and nt 0..8192 as dvo_bf_match_hamming.  Per query, train_idx /
+ * dist get k entries in OpenCV's order (ascending distance, lower train index
+ * first on ties); -1 / FLT_MAX where fewer than k trains exist. */
+int dvo_bf_knn_hamming(dvo_ctx* ctx, const uint8_t* dq, int nq, const uint8_t* dt, int nt, int k, int32_t* train_idx,
+                       float* dist);
+
 /* Replaces cv::BFMatcher(NORM_L1).knnMatch(query, train, k) (k = 1: .match) on
  * float descriptors — the SIFT/SURF modes, visual_odometry_v3.py:99-106
  * (construction) and :200-204, :214-215 (calls) — and, with DVO_NORM_L2SQR,
@@ -933,6 +940,21 @@ int dvo_jpeg_get_split_info(dvo_jpeg* j, int* max_passes, int* segments, int* fa
 int dvo_stream_set_profiling(dvo_stream* s, int enable);
 int dvo_stream_stage_times(dvo_stream* s, double* ms /* DVO_NSTAGES */, int* calls);
 
+/* Opt-in match filter of the ORB stream: knnMatch(k = 2) and Lowe's ratio test
+ * (visual_odometry_v3.py:223-228, `m.distance < ratio * n.distance` in Python
+ * floats) instead of the cross check.  ratio 0 (the default): off, the stream
+ * matches with cfg.cross_check.  A finite ratio > 0: every later process /
+ * process_pairs / submit / submit_pairs / pair call and the undistorted, BGR and
+ * JPEG input calls match with the Hamming 2-NN and keep query q when the test
+ * passes; cfg.cross_check is ignored.  Kept matches are in ascending queryIdx
+ * (the k-NN modes' order, not the cross check's (distance, queryIdx)), and
+ * n_matches counts them.  A pair whose current frame has fewer than 2
+ * descriptors (the reference's `for m, n in matches` raises) gets DVO_ENOFEAT,
+ * the counts filled, zeros elsewhere; a pair without a query descriptor keeps
+ * the record it gets with the ratio test off.  DVO_EINVAL for a NaN, infinite or
+ * negative ratio, and while submitted batches are pending. */
+int dvo_stream_set_ratio_test(dvo_stream* s, double ratio);
+
 /* Host copies of intermediate results of the last dvo_stream_process (tests).
  * get_pyramid(blurred = 1): the detection path blurs only the 39 x 44 descriptor
  * windows inside the describe kernel, so the whole GaussianBlur of the level is
@@ -1011,6 +1033,21 @@ int dvo_test_ratio_gather(dvo_ctx* ctx, const int32_t* idx, const float* dist, i
 int dvo_test_knn_batch(dvo_ctx* ctx, const float* desc, const dvo_keypoint* kps, const int32_t* counts, int frames,
                        int cap, int dim, int ranges, double ratio, int32_t* idx, float* dist, int32_t* nmatch,
                        dvo_dmatch* matches, float* pts, int32_t* hdr, int32_t* missing, int* ranges_used);
+/* dvo_bf_knn_hamming with the train stages split over tsplit workgroups per query block
+ * (1..16; 0: the library's choice by size, what dvo_bf_knn_hamming runs).  The result does
+ * not depend on tsplit. */
+int dvo_test_bf_knn_hamming(dvo_ctx* ctx, const uint8_t* dq, int nq, const uint8_t* dt, int nt, int k, int tsplit,
+                            int32_t* train_idx, float* dist);
+/* The ratio-mode match stage of dvo_stream (dvo_stream_set_ratio_test) through the production
+ * launches, on host arrays: `frames` frame slots of cap rows (cap <= 8192), desc
+ * [frames][cap][32], kps [frames][cap], counts [frames] (0..cap).  Per pair p = frames p, p + 1:
+ * top2 [P][cap][2] the packed (Hamming << 16 | trainIdx) nearest and second words of the first
+ * nq queries, -1 where there is none (and in the rows past nq), nmatch [P], matches [P][cap]
+ * (entries past nmatch are (-1, -1, 0, 0)), pts [P][cap][4] (rows below nmatch are written),
+ * status [P]: the status the pair's record gets before RANSAC (DVO_OK, DVO_ENOFEAT). */
+int dvo_test_hamming_ratio_batch(dvo_ctx* ctx, const uint8_t* desc, const dvo_keypoint* kps, const int32_t* counts,
+                                 int frames, int cap, double ratio, int32_t* top2, int32_t* nmatch, dvo_dmatch* matches,
+                                 float* pts, int32_t* status);
 /* The batched kd-forest build and search of dvo_knn_stream_process's FLANN mode through the
  * production launches, on host arrays: desc [frames][cap][dim], counts [frames] (a count above
  * cap marks the frame), state = the incoming theRNG state, levels = level launches per tree
