@@ -45,6 +45,10 @@ PAIR_RECORD_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("E", "<f8
                               ("status", "<i4"), ("n_models", "<i4"), ("n_hypotheses", "<i4"), ("pad0", "<i4"),
                               ("reserved", "<f8", (6,))])
 assert PAIR_RECORD_DTYPE.itemsize == 256
+# dvo_landmark: a pair's triangulated inlier point (dvo_stream_set_landmarks)
+LANDMARK_DTYPE = np.dtype([("match", "<i4"), ("reserved", "<i4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"),
+                           ("y2", "<f4"), ("X", "<f8"), ("Y", "<f8"), ("Z", "<f8")])
+assert LANDMARK_DTYPE.itemsize == 48
 
 
 class DVOError(RuntimeError):
@@ -166,6 +170,9 @@ _SIGNATURES = {
     "dvo_stream_pose_tail_batch": ([_vp, _vp, _c, _vp, _vp, _c, _d, _vp, _vp], _c),
     "dvo_stream_pair": ([_vp, _vp, _vp, _c, _c, _vp], _c),
     "dvo_stream_sync": ([_vp], _c),
+    "dvo_stream_set_landmarks": ([_vp, _vp, _vp, _c], _c),
+    "dvo_knn_stream_set_landmarks": ([_vp, _vp, _vp, _c], _c),
+    "dvo_test_landmarks": ([_vp, _vp, _vp, _c, _c, _vp, _d, _d, _c, _d, _c, _vp, _vp, _vp], _c),
     "dvo_knn_pair_create": ([_vp, ctypes.POINTER(KnnPairConfig), ctypes.POINTER(_vp)], _c),
     "dvo_knn_pair_destroy": ([_vp], None),
     "dvo_knn_pair_run": ([_vp, _vp, _vp, _c, _c, ctypes.POINTER(ctypes.c_uint64), _vp], _c),
@@ -268,7 +275,11 @@ def load_library(path: str = LIB_PATH):
                               "(hipcc, gfx950). droplet_visual_odometry_amd has no CPU fallback.")
         L = ctypes.CDLL(path)
         for name, (args, res) in _SIGNATURES.items():
-            fn = getattr(L, name)
+            fn = getattr(L, name, None)
+            if fn is None and path != _DEFAULT_LIB:
+                continue  # an experiment build of older sources (tools/ab_libs.sh): calling the entry raises
+            if fn is None:
+                raise ImportError(f"{path} does not export {name}")
             fn.argtypes = args
             fn.restype = res
         if path == _DEFAULT_LIB and os.path.isdir(os.path.join(HERE, "csrc")):

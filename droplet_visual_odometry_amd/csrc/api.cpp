@@ -11,6 +11,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "device_mem.h"
@@ -79,6 +80,13 @@ struct dvo_ctx {
     int call_w = 0, call_h = 0, call_nf = 0;
 };
 
+// The caller's buffers of a landmark binding (dvo_stream_set_landmarks): [pairs][cap] entries, [pairs] counts.
+struct LandmarkBinding {
+    dvo_landmark* out = nullptr;  // null: no binding
+    int32_t* count = nullptr;
+    int cap = 0;
+};
+
 struct dvo_stream {
     dvo_ctx* ctx = nullptr;
     dvo_stream_config cfg{};
@@ -116,7 +124,9 @@ struct dvo_stream {
         int round = 0;  // the round this set runs next
         int pairs = 0;
         dvo_pair_record* rec = nullptr;  // the caller's records of the batch
+        LandmarkBinding lm;              // the batch's landmark binding, written when the set retires
     };
+    LandmarkBinding lm_next;  // dvo_stream_set_landmarks: taken by the next batch
     PairSet sets[kMaxSets];
     // their arrays: 1 set until the first submit, then kRansacRounds; pairs.all.g is the stream's GeomArgs
     PairSets pairs;
@@ -528,6 +538,8 @@ int retire_sets(dvo_stream* s) {
         const PairArrays v = s->pairs.view(k);
         HIP_TRY(launch_retire(v.g, st.pairs, v.hdr, st.rec, s->hs));
         if (s->ratio > 0) HIP_TRY(launch_hamming_ratio_status(v.hdr, st.pairs, st.rec, nullptr, s->hs));
+        if (st.lm.out)  // after the records are final: a landmark pair is one whose record got through
+            HIP_TRY(launch_landmarks(v.g, st.pairs, st.rec, s->pairs.lm, st.lm.out, st.lm.count, st.lm.cap, s->hs));
         s->retired_rec[s->retired] = st.rec;
         s->retired_pairs[s->retired] = st.pairs;
         ++s->retired;
@@ -551,6 +563,8 @@ bool sets_pending(const dvo_stream* s) {
 int run_stream(dvo_stream* s, const uint8_t* d_frames, int n, int64_t fstride, int pitch, dvo_pair_record* d_rec,
                bool detect_only, int pair_step = 1, bool drain = true) {
     dvo_ctx* ctx = s->ctx;
+    // a landmark binding is for this batch alone, whether or not the call gets as far as its pairs
+    const LandmarkBinding lm = detect_only ? LandmarkBinding{} : std::exchange(s->lm_next, LandmarkBinding{});
     const int want = drain ? 1 : kRansacRounds;
     if (!detect_only && s->pairs.nsets < want) {
         // the first pipelined submit grows the sets; a drained call after a failed grow allocates one
@@ -595,7 +609,7 @@ int run_stream(dvo_stream* s, const uint8_t* d_frames, int n, int64_t fstride, i
             HIP_TRY(launch_match(P, s->cfg.cross_check, s->hs, ev));
         HIP_TRY(launch_pair_header(P, P.buf.hdr, s->hs));
         HIP_TRY(launch_geometry_args(s->pairs.view(k).g, pairs, kStageNormalize, s->hs));
-        s->sets[k] = dvo_stream::PairSet{true, 0, pairs, d_rec};
+        s->sets[k] = dvo_stream::PairSet{true, 0, pairs, d_rec, lm};
         s->last_set = k;
         // nsets >= 1 here: every path that matches has passed ensure_sets above
         s->next_set = (k + 1) % s->pairs.nsets;
@@ -1037,6 +1051,20 @@ int dvo_stream_set_ratio_test(dvo_stream* s, double ratio) {
     if (sets_pending(s))
         return fail(ctx, DVO_EINVAL, "dvo_stream_set_ratio_test: submitted batches are pending (dvo_stream_drain)");
     s->ratio = ratio;
+    return DVO_OK;
+}
+
+int dvo_stream_set_landmarks(dvo_stream* s, dvo_landmark* d_out, int32_t* d_count, int cap) {
+    if (!s) return DVO_EINVAL;
+    dvo_ctx* ctx = s->ctx;
+    if (!d_out) {
+        s->lm_next = LandmarkBinding{};
+        return DVO_OK;
+    }
+    if (cap < 1 || !d_count) return fail(ctx, DVO_EINVAL, "landmarks need cap >= 1 and a count buffer");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(s->pairs.ensure_landmarks(s->cfg.max_frames, s->plan.kp_cap));  // the first binding sizes the scratch
+    s->lm_next = LandmarkBinding{d_out, d_count, cap};
     return DVO_OK;
 }
 
@@ -2685,6 +2713,7 @@ struct dvo_knn_stream {
     DeviceAllocs raw_mem;
     uint8_t* raw = nullptr;
     int raw_pitch = 0;
+    LandmarkBinding lm_next;  // dvo_knn_stream_set_landmarks: taken by the next finish
     // A raw-input call records ev_in[k] before its input launch, k the one the last accepted call
     // does not use (first_ev; -1: that call began at ev[0]), so a refused call disturbs no figure.
     hipEvent_t ev_in[2] = {nullptr, nullptr};
@@ -2864,6 +2893,7 @@ int dvo_knn_stream_finish(dvo_knn_stream* st, dvo_pair_record* d_records, const 
     const KnnBatch& b = st->b;
     hipEvent_t* ev = st->profiling && st->pending_timed ? st->ev : nullptr;
     st->pending = 0;
+    const LandmarkBinding lm = std::exchange(st->lm_next, LandmarkBinding{});  // for this batch alone
     const int pairs = n_frames - 1;
     const PairArrays& v = st->pairs.all;
     const bool flann = st->fl.trees > 0;
@@ -2876,6 +2906,8 @@ int dvo_knn_stream_finish(dvo_knn_stream* st, dvo_pair_record* d_records, const 
         HIP_TRY(launch_geometry_args(v.g, pairs, kStageNormalize | kStageRansac, s));
         HIP_TRY(launch_retire(v.g, pairs, v.hdr, d_records, s));
         HIP_TRY(launch_knn_status(b.n, b.fstate, b.missing, pairs, d_records, s));
+        if (lm.out)  // after the records are final: a landmark pair is one whose record got through
+            HIP_TRY(launch_landmarks(v.g, pairs, d_records, st->pairs.lm, lm.out, lm.count, lm.cap, s));
     }
     if (ev) {
         HIP_TRY(hipEventRecord(ev[3], s));
@@ -2883,6 +2915,20 @@ int dvo_knn_stream_finish(dvo_knn_stream* st, dvo_pair_record* d_records, const 
         st->times_read = false;
     }
     st->matched_frames = n_frames;
+    return DVO_OK;
+}
+
+int dvo_knn_stream_set_landmarks(dvo_knn_stream* s, dvo_landmark* d_out, int32_t* d_count, int cap) {
+    if (!s) return DVO_EINVAL;
+    dvo_ctx* ctx = s->ctx;
+    if (!d_out) {
+        s->lm_next = LandmarkBinding{};
+        return DVO_OK;
+    }
+    if (cap < 1 || !d_count) return fail(ctx, DVO_EINVAL, "landmarks need cap >= 1 and a count buffer");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(s->pairs.ensure_landmarks(s->b.F - 1, s->b.cap));  // the first binding sizes the scratch
+    s->lm_next = LandmarkBinding{d_out, d_count, cap};
     return DVO_OK;
 }
 
@@ -3495,6 +3541,92 @@ int dvo_test_ransac_hypotheses(dvo_ctx* ctx, const double* pts, const int32_t* m
         for (size_t o = 0; o < PH; ++o) path[o] = -1;
         for (int k = 0; k < kDkMaxPasses; ++k) parked[k] = -1;
     }
+    return DVO_OK;
+}
+
+int dvo_test_landmarks(dvo_ctx* ctx, const float* pts, const int32_t* m, int pairs, int stride, const double* K,
+                       double prob, double threshold, int max_iters, double dist_thresh, int cap, dvo_landmark* out,
+                       int32_t* count, dvo_pair_record* rec) {
+    if (!ctx || !pts || !m || !K || !out || !count || !rec) return DVO_EINVAL;
+    if (pairs < 1 || pairs > 65535 || stride < 1 || cap < 1) return fail(ctx, DVO_EINVAL, "bad pair count, stride or cap");
+    if (!(prob > 0 && prob < 1) || !(threshold > 0) || !std::isfinite(threshold) || max_iters < 1 ||
+        max_iters > (1 << 20) || !std::isfinite(dist_thresh))
+        return fail(ctx, DVO_EINVAL, "bad prob, threshold, max_iters or dist_thresh");
+    for (int p = 0; p < pairs; ++p)
+        if (m[p] < 5 || m[p] > stride) return fail(ctx, DVO_EINVAL, "m[p] must be in [5, stride]");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t P = (size_t)pairs, hc = (size_t)max_iters, PH = P * hc, npt = P * stride * 4;
+    const size_t tiles = (size_t)landmark_tiles(stride);
+    CallMem mem(ctx->call, ctx->stream);
+    GeomArgs g{};
+    float* dpts = mem.dev<float>(npt);
+    int32_t* dm = mem.dev<int32_t>(P);
+    g.pts_f = dpts;
+    g.m_arr = dm;
+    g.pts_stride = stride;
+    set_camera(g, K);
+    g.prob = prob;
+    g.threshold = threshold;
+    g.max_iters = max_iters;
+    g.dist_thresh = dist_thresh;
+    g.hyp_cap = max_iters;
+    g.npts = mem.dev<double>(npt);
+    g.models = mem.dev<double>(PH * 90);
+    g.nmod = mem.dev<int32_t>(PH);
+    g.cnt = mem.dev<int32_t>(PH * 10);
+    g.subsets = mem.dev<int32_t>(PH * 5);
+    g.rs = mem.dev<RansacState>(P);
+    g.fprec = mem.dev<double>(((PH + 63) / 64 + P) * 128 * 64);
+    g.dk_off = mem.dev<int32_t>(P + 1);
+    g.a_off = mem.dev<int32_t>(P + 1);
+    g.s_off = mem.dev<int32_t>(P + 1);
+    g.dk_ctl = mem.dev<int32_t>(2 + kDkMaxPasses);
+    g.dk_list = mem.dev<int32_t>((size_t)(kDkMaxPasses - 1) * PH);
+    g.dk_list_cap = (int64_t)PH;
+    g.E = mem.dev<double>(P * 90);
+    g.info = mem.dev<int32_t>(P * 4);
+    g.Rt = mem.dev<double>(P * 12);
+    g.good = mem.dev<int32_t>(P);
+    g.pose_P = mem.dev<double>(P * 72);
+    g.pose_cnt = mem.dev<int32_t>(P * 5);
+    PairHeader* dhdr = mem.dev<PairHeader>(P);
+    dvo_pair_record* drec = mem.dev<dvo_pair_record>(P);
+    LandmarkScratch L;
+    L.tmp = mem.dev<LandmarkTmp>(P * tiles * kLandmarkTile);
+    L.tcnt = mem.dev<int32_t>(P * tiles);
+    dvo_landmark* dout = mem.dev<dvo_landmark>(P * (size_t)cap);
+    int32_t* dcount = mem.dev<int32_t>(P);
+    HIP_TRY(mem.error());
+    std::vector<PairHeader> hdr(P);
+    for (int p = 0; p < pairs; ++p) hdr[p] = PairHeader{m[p], m[p], 0, 0};
+    HIP_TRY(mem.put(dpts, pts, npt * sizeof(float)));
+    HIP_TRY(mem.put(dm, m, P * 4));
+    HIP_TRY(mem.put(dhdr, hdr.data(), P * sizeof(PairHeader)));
+    HIP_TRY(mem.put(dout, out, P * (size_t)cap * sizeof(dvo_landmark)));
+    for (int p = 0; p < pairs; ++p) {  // findEssentialMat pair by pair, as dvo_find_essential_mat launches it
+        GeomArgs gp = g;
+        gp.pts_f += (size_t)p * stride * 4;
+        gp.m_arr += p;
+        gp.npts += (size_t)p * stride * 4;
+        gp.models += (size_t)p * hc * 90;
+        gp.nmod += (size_t)p * hc;
+        gp.cnt += (size_t)p * hc * 10;
+        gp.subsets += (size_t)p * hc * 5;
+        gp.rs += p;
+        gp.E += (size_t)p * 90;
+        gp.info += (size_t)p * 4;
+        HIP_TRY(launch_geometry_args(gp, 1, kStageNormalize | kStageRansac | kStageOneRound, ctx->stream));
+    }
+    HIP_TRY(launch_retire(g, pairs, dhdr, drec, ctx->stream));  // every pair at once, as a stream's set retires
+    HIP_TRY(launch_landmarks(g, pairs, drec, L, dout, dcount, cap, ctx->stream));
+    uint8_t *hout, *hcount, *hrec;
+    HIP_TRY(mem.get(dout, P * (size_t)cap * sizeof(dvo_landmark), &hout));
+    HIP_TRY(mem.get(dcount, P * 4, &hcount));
+    HIP_TRY(mem.get(drec, P * sizeof(dvo_pair_record), &hrec));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    std::memcpy(out, hout, P * (size_t)cap * sizeof(dvo_landmark));
+    std::memcpy(count, hcount, P * 4);
+    std::memcpy(rec, hrec, P * sizeof(dvo_pair_record));
     return DVO_OK;
 }
 

@@ -155,6 +155,27 @@ struct PairSets {
         return hipSuccess;
     }
 
+    // The landmark kernels' scratch (launch_landmarks): empty until the stream's first binding
+    // (dvo_stream_set_landmarks), then one copy for F pairs of cap points whatever the number of
+    // sets, since it is live only between the two launches of one set's retire.  It does not
+    // depend on the sets' arrays: ensure() and release() leave it alone, and because F and cap
+    // are the stream's for life it is allocated once and never regrown (nothing is freed, no
+    // pointer a queued kernel holds goes stale).  A failure leaves it empty.
+    LandmarkScratch lm;
+    DeviceAllocs lm_mem;
+    hipError_t ensure_landmarks(int F_, int cap_) {
+        if (lm.tmp) return hipSuccess;
+        const size_t tiles = (size_t)landmark_tiles(cap_), n = (size_t)(F_ > 0 ? F_ : 1) * tiles;
+        DeviceAllocs fresh;
+        LandmarkScratch l;
+        hipError_t e = fresh.alloc(&l.tmp, n * kLandmarkTile * sizeof(LandmarkTmp) + 256);
+        if (e == hipSuccess) e = fresh.alloc(&l.tcnt, n * sizeof(int32_t) + 256);
+        if (e != hipSuccess) return e;
+        lm_mem = std::move(fresh);
+        lm = l;
+        return hipSuccess;
+    }
+
     // Set k's view: pairs [k F, (k + 1) F) of every per-set array.
     PairArrays view(int k) const {
         PairArrays v = all;

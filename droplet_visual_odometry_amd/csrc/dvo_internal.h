@@ -376,6 +376,23 @@ hipError_t launch_pair_header(const StreamParams& P, PairHeader* hdr, hipStream_
 hipError_t launch_ransac_round(const GeomArgs& g_all, const RoundSpec& spec, hipStream_t s);
 hipError_t launch_retire(const GeomArgs& g_set, int pairs, const PairHeader* hdr, dvo_pair_record* records,
                          hipStream_t s);
+// The landmarks of a retired set (dvo_stream_set_landmarks), after its records are final: per
+// (tile of kLandmarkTile matches, pair) the inlier test, the chosen decomposition's
+// triangulation and tests and an ordered compaction inside the tile into L.tmp / L.tcnt, then a
+// scan over the pair's tile counts and the copy into the caller's slots.  g_set.pts_f holds the
+// pixel coordinates.  The scratch is live only between the two launches.
+constexpr int kLandmarkTile = 256;
+struct LandmarkTmp {  // a landmark inside its tile
+    double X, Y, Z;
+    int32_t match, pad;
+};
+struct LandmarkScratch {
+    LandmarkTmp* tmp = nullptr;  // [pairs][tiles][kLandmarkTile]
+    int32_t* tcnt = nullptr;     // [pairs][tiles]
+};
+inline int landmark_tiles(int64_t pts_stride) { return (int)((pts_stride + kLandmarkTile - 1) / kLandmarkTile); }
+hipError_t launch_landmarks(const GeomArgs& g_set, int pairs, const dvo_pair_record* records, const LandmarkScratch& L,
+                            dvo_landmark* out, int32_t* count, int cap, hipStream_t s);
 // five-point record blocks a merged round can need (sizes the stream's GeomArgs::fprec, dk_list)
 int64_t round_blocks_bound(int F, int hyp_cap);
 int64_t round_items_bound(int F, int hyp_cap);

@@ -2193,6 +2193,14 @@ __global__ __launch_bounds__(kPNT) void pose_count_kernel(GeomArgs g) {
     }
 }
 
+// recoverPose's tie-ordered choice among the four cheirality counts
+__device__ __forceinline__ int pose_pick_of(const int* gd) {
+    if (gd[0] >= gd[1] && gd[0] >= gd[2] && gd[0] >= gd[3]) return 0;
+    if (gd[1] >= gd[0] && gd[1] >= gd[2] && gd[1] >= gd[3]) return 1;
+    if (gd[2] >= gd[0] && gd[2] >= gd[1] && gd[2] >= gd[3]) return 2;
+    return 3;
+}
+
 __global__ __launch_bounds__(64) void pose_pick_kernel(GeomArgs g, int pairs) {
     const int p = blockIdx.x * 64 + threadIdx.x;
     if (p >= pairs) return;
@@ -2203,11 +2211,7 @@ __global__ __launch_bounds__(64) void pose_pick_kernel(GeomArgs g, int pairs) {
         return;
     }
     const int* gd = cnt + 1;
-    int pick;
-    if (gd[0] >= gd[1] && gd[0] >= gd[2] && gd[0] >= gd[3]) pick = 0;
-    else if (gd[1] >= gd[0] && gd[1] >= gd[2] && gd[1] >= gd[3]) pick = 1;
-    else if (gd[2] >= gd[0] && gd[2] >= gd[1] && gd[2] >= gd[3]) pick = 2;
-    else pick = 3;
+    const int pick = pose_pick_of(gd);
     const double* P = g.pose_P + (int64_t)p * kPoseRec;
     double* Rt = g.Rt + (int64_t)p * 12;
     for (int k = 0; k < 9; ++k) Rt[k] = P[(pick & 1 ? 57 : 48) + k];
@@ -2480,6 +2484,85 @@ __global__ __launch_bounds__(64) void pose_chain_kernel(TailArgs a) {
     if (lane == 0 && last_ok >= 0 && a.carry) proj_of(a.K, rec_Rt(a.rec, last_ok), a.carry);
 }
 
+// ---- landmarks (dvo.h dvo_stream_set_landmarks): recoverPose's triangulatedPoints, v3:303 ----
+// Tile blockIdx.x of pair blockIdx.y's matches, one thread per match.  Correspondence i is kept
+// when it is an inlier of the record's E (ransac_finish_kernel's mask test; every point of a
+// five-point pair) and its own triangulation against the chosen decomposition passes
+// recoverPose's tests.  No mirror here: for decompositions 2 and 3 the mirror fixes the null
+// vector only up to sign, which the tests do not see and X / X3 would.  The SVD runs for inliers
+// only.  Kept points are compacted inside the tile in ascending i (wave ballots and mbcnt ranks,
+// as ratio_gather_body) into the tile's scratch slots; every tile of every pair leaves its count.
+__global__ __launch_bounds__(kLandmarkTile) void landmark_tile_kernel(GeomArgs g, const dvo_pair_record* rec,
+                                                                      LandmarkScratch L, int tiles) {
+    __shared__ int wtot[kLandmarkTile / 64];
+    const int p = blockIdx.y, tile = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t slot0 = (int64_t)p * tiles + tile;
+    const int m = rec_ok(rec, p) ? min(pair_m(g, p), (int)g.pts_stride) : 0;
+    if (tile * kLandmarkTile >= m) {  // a failed pair, or a tile past the pair's matches
+        if (tid == 0) L.tcnt[slot0] = 0;
+        return;
+    }
+    const int i = tile * kLandmarkTile + tid;
+    bool keep = false;
+    double X[4] = {0, 0, 0, 1};
+    if (i < m) {
+        const double* pt = g.npts + ((int64_t)p * g.pts_stride + i) * 4;
+        bool in = true;
+        if (m > 5) {
+            double Ed[9];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) Ed[k] = g.E[(int64_t)p * 90 + k];
+            const double thr = g.threshold / ((g.fx + g.fy) / 2);
+            const float t = (float)(thr * thr);
+            in = sampson_inlier(Ed, pt[0], pt[1], pt[2], pt[3], t, t >= FLT_MIN);
+        }
+        if (in) {
+            const double P0[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+            const int pick = pose_pick_of(g.pose_cnt + (int64_t)p * 5 + 1);
+            const double* Pc = g.pose_P + (int64_t)p * kPoseRec + pick * 12;
+            double Pl[12];
+#pragma unroll
+            for (int k = 0; k < 12; ++k) Pl[k] = Pc[k];
+            triangulate_one(P0, Pl, pt[0], pt[1], pt[2], pt[3], X);
+            keep = pose_tests(X, Pl, g.dist_thresh, false);
+        }
+    }
+    const unsigned long long bal = __ballot(keep);
+    const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+    if (lane == 0) wtot[wave] = __popcll(bal);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < kLandmarkTile / 64; ++w) {
+        const int c = wtot[w];
+        before += w < wave ? c : 0;
+        total += c;
+    }
+    if (keep) L.tmp[slot0 * kLandmarkTile + before + rank] = LandmarkTmp{X[0] / X[3], X[1] / X[3], X[2] / X[3], i, 0};
+    if (tid == 0) L.tcnt[slot0] = total;
+}
+
+// The pair's scan over its tile counts (a few dozen tiles at most: every thread adds them up),
+// then the tile's landmarks into the caller's slots below cap, and the pair's full count.
+__global__ __launch_bounds__(kLandmarkTile) void landmark_place_kernel(GeomArgs g, LandmarkScratch L, int tiles,
+                                                                       dvo_landmark* out, int32_t* count, int cap) {
+    const int p = blockIdx.y, tile = blockIdx.x;
+    const int32_t* tc = L.tcnt + (int64_t)p * tiles;
+    int before = 0, total = 0;
+    for (int t = 0; t < tiles; ++t) {
+        const int c = tc[t];
+        before += t < tile ? c : 0;
+        total += c;
+    }
+    if (tile == 0 && threadIdx.x == 0) count[p] = total;
+    const int j = threadIdx.x, slot = before + j;
+    if (j >= tc[tile] || slot >= cap) return;
+    const LandmarkTmp e = L.tmp[((int64_t)p * tiles + tile) * kLandmarkTile + j];
+    const float* px = g.pts_f + ((int64_t)p * g.pts_stride + e.match) * 4;
+    out[(int64_t)p * cap + slot] = dvo_landmark{e.match, 0, px[0], px[1], px[2], px[3], e.X, e.Y, e.Z};
+}
+
 __global__ void test_update_num_iters_kernel(double p, const double* ep, int n, int mp, int mi, int32_t* out) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) out[i] = ransac_update_num_iters(p, ep[i], mp, mi);
@@ -2543,6 +2626,17 @@ hipError_t launch_retire(const GeomArgs& g_set, int pairs, const PairHeader* hdr
     hipError_t e = launch_geometry_args(g_set, pairs, kStagePose, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(records_kernel, dim3((pairs + 63) / 64), dim3(64), 0, s, g_set, hdr, pairs, records);
+    return hipGetLastError();
+}
+
+hipError_t launch_landmarks(const GeomArgs& g_set, int pairs, const dvo_pair_record* records, const LandmarkScratch& L,
+                            dvo_landmark* out, int32_t* count, int cap, hipStream_t s) {
+    if (pairs <= 0) return hipSuccess;
+    if (!g_set.pts_f || !records || !L.tmp || !L.tcnt || !out || !count || cap < 1) return hipErrorInvalidValue;
+    const int tiles = landmark_tiles(g_set.pts_stride);
+    const dim3 grid((unsigned)tiles, (unsigned)pairs);
+    hipLaunchKernelGGL(landmark_tile_kernel, grid, dim3(kLandmarkTile), 0, s, g_set, records, L, tiles);
+    hipLaunchKernelGGL(landmark_place_kernel, grid, dim3(kLandmarkTile), 0, s, g_set, L, tiles, out, count, cap);
     return hipGetLastError();
 }
 

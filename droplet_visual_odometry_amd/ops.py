@@ -1125,6 +1125,30 @@ def test_hamming_ratio_batch(desc, kps, counts, ratio=0.75, ctx=None):
     return out
 
 
+def test_landmarks(pts, m, K, cap, out=None, prob=0.999, threshold=1.0, max_iters=1000, dist_thresh=50.0, ctx=None):
+    """The landmark kernels of the streams (stream.Landmarks) on host arrays: pts float32[P, stride, 4]
+    pixel coordinates (x1, y1, x2, y2), m int[P] counts (5..stride).  findEssentialMat, the
+    stream's retire and the landmarks of all pairs.  out: LANDMARK_DTYPE[P, cap] whose bytes the
+    kernels leave alone outside the written slots (default zeros).  Returns (out, count int32[P],
+    records PAIR_RECORD_DTYPE[P])."""
+    from ._native import LANDMARK_DTYPE
+    c = _ctx(ctx)
+    pts = np.ascontiguousarray(pts, np.float32)
+    m = np.ascontiguousarray(m, np.int32)
+    if pts.ndim != 3 or pts.shape[2] != 4 or m.shape != pts.shape[:1]:
+        raise DVOError(-1, "pts float32[P, stride, 4] and m [P] must agree")
+    P, stride, _ = pts.shape
+    out = np.zeros((P, cap), LANDMARK_DTYPE) if out is None else out
+    if out.dtype != LANDMARK_DTYPE or out.shape != (P, cap) or not out.flags.c_contiguous:
+        raise DVOError(-1, "out must be a contiguous LANDMARK_DTYPE[P, cap] array")
+    count = np.zeros(P, np.int32)
+    rec = np.zeros(P, PAIR_RECORD_DTYPE)
+    K = np.ascontiguousarray(K, np.float64).reshape(9)
+    c.check(c.lib.dvo_test_landmarks(c.h, ptr(pts), ptr(m), P, stride, ptr(K), float(prob), float(threshold),
+                                     int(max_iters), float(dist_thresh), int(cap), ptr(out), ptr(count), ptr(rec)))
+    return out, count, rec
+
+
 def test_flann_batch(desc, counts, trees=5, checks=50, rng_state=None, levels=0, ctx=None):
     """The batched kd-forest build and search of dvo_knn_stream_process's FLANN mode
     (stream.KnnFrameStream(matcher="flann")) on host arrays: desc float32[F, cap, dim] frame slots,

@@ -19,7 +19,45 @@ import ctypes
 import numpy as np
 import torch
 
-from ._native import (DMATCH_DTYPE, KEYPOINT_DTYPE, PAIR_RECORD_DTYPE, Context, StreamConfig, _vp, orb_params, ptr)
+from ._native import (DMATCH_DTYPE, KEYPOINT_DTYPE, LANDMARK_DTYPE, PAIR_RECORD_DTYPE, Context, StreamConfig, _vp,
+                      orb_params, ptr)
+
+
+class Landmarks:
+    """Device buffers for one batch's landmarks (dvo_stream_set_landmarks): each pair's matches
+    that are inliers of its E and pass recoverPose's tests, with their triangulated positions in
+    the previous frame's camera coordinates, in units of the baseline (see include/dvo.h).
+    entries: uint8 [n_pairs, cap, 48] (LANDMARK_DTYPE); counts: int32 [n_pairs], the full number
+    per pair (above cap: the pair overflowed and holds its first cap), 0 for a failed pair.  Bind
+    it with FrameStream.bind_landmarks / KnnFrameStream.bind_landmarks before the batch's call and
+    read it after the batch has retired and the stream is synchronised."""
+
+    def __init__(self, n_pairs: int, cap: int, device):
+        if n_pairs < 1 or cap < 1:
+            raise ValueError("Landmarks needs n_pairs >= 1 and cap >= 1")
+        self.n_pairs, self.cap = int(n_pairs), int(cap)
+        self.entries = torch.zeros((self.n_pairs, self.cap, LANDMARK_DTYPE.itemsize), dtype=torch.uint8, device=device)
+        self.counts = torch.zeros(self.n_pairs, dtype=torch.int32, device=device)
+
+    def count(self, pair: int) -> int:
+        return int(self.counts[pair].item())
+
+    def numpy(self, pair: int) -> np.ndarray:
+        """The pair's first min(count, cap) landmarks (LANDMARK_DTYPE), in ascending match index."""
+        n = min(self.count(pair), self.cap)
+        return self.entries[pair, :n].cpu().numpy().reshape(-1).view(LANDMARK_DTYPE).copy()
+
+
+def _bind_landmarks(stream, setter, lm):
+    """The one-shot binding of both stream classes; returns what to keep referenced."""
+    if lm is None:
+        stream.ctx.check(setter(stream.h, None, None, 0))
+        return None
+    if not isinstance(lm, Landmarks) or lm.entries.device != stream.device or lm.counts.device != stream.device:
+        raise ValueError("bind_landmarks takes a Landmarks on the stream's device (or None)")
+    stream._after_torch()  # the buffers' fill ran on torch's stream: order the library's writes after it
+    stream.ctx.check(setter(stream.h, lm.entries.data_ptr(), lm.counts.data_ptr(), lm.cap))
+    return lm
 
 
 class FrameStream:
@@ -59,6 +97,8 @@ class FrameStream:
         # caller keeps and whether or not sync() has drained _held.
         self._last = ()
         self._pending = {}  # records of submitted, not yet retired batches (by device address)
+        self._lm_next = None  # bind_landmarks: the Landmarks the next batch takes
+        self._lm_pending = {}  # Landmarks of batches not yet retired, by their records' device address
         self.width, self.height, self.max_frames, self.nfeatures = width, height, max_frames, nfeatures
         self.K = K.reshape(3, 3)
         if ratio:
@@ -78,6 +118,17 @@ class FrameStream:
 
     def new_records(self, n_pairs: int) -> torch.Tensor:
         return torch.zeros(max(n_pairs, 1) * PAIR_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+
+    def bind_landmarks(self, lm: Landmarks | None):
+        """Have the next batch (the next process / process_pairs / submit / submit_pairs call, colour,
+        undistorted and JPEG frames included) write its landmarks into `lm` when it retires
+        (dvo_stream_set_landmarks); lm needs a row per pair of that batch.  One-shot: the batch
+        after it writes nothing.  None clears a binding no batch has taken yet."""
+        self._lm_next = _bind_landmarks(self, self.ctx.lib.dvo_stream_set_landmarks, lm)
+
+    def _lm_fits(self, pairs: int):
+        if self._lm_next is not None and self._lm_next.n_pairs < pairs:
+            raise ValueError(f"the bound Landmarks holds {self._lm_next.n_pairs} pairs, the batch has {pairs}")
 
     def process(self, frames: torch.Tensor, records: torch.Tensor | None = None, wait_torch: bool = True,
                 undistort=None) -> torch.Tensor:
@@ -100,6 +151,7 @@ class FrameStream:
             wait_torch = True  # the zero-fill runs on torch's stream: order the library's writes after it
         if wait_torch:
             self._after_torch()
+        self._lm_fits(n - 1)
         if n > 1:
             self._pending[records.data_ptr()] = records
         if undistort is not None:  # ops.Undistorter: frames are remapped into the stream's slab first
@@ -134,6 +186,7 @@ class FrameStream:
             wait_torch = True
         if wait_torch:
             self._after_torch()
+        self._lm_fits(n2 // 2)
         self._pending[records.data_ptr()] = records
         self.ctx.check(self.ctx.lib.dvo_stream_process_pairs(self.h, frames.data_ptr(), n2 // 2, frames.stride(0),
                                                              frames.stride(1), records.data_ptr()))
@@ -175,6 +228,7 @@ class FrameStream:
             wait_torch = True  # the zero-fill runs on torch's stream: order the library's writes after it
         if wait_torch:
             self._after_torch()
+        self._lm_fits(n - 1)
         if n > 1:
             self._pending[records.data_ptr()] = records
         self.ctx.check(self.ctx.lib.dvo_stream_process_bgr(
@@ -194,6 +248,7 @@ class FrameStream:
             raise ValueError("records too small")
         if wait_torch:
             self._after_torch()
+        self._lm_fits(n - 1)
         self.ctx.check(self.ctx.lib.dvo_stream_submit_bgr(
             self.h, undistort.h_ if undistort is not None else None, frames.data_ptr(), n, frames.stride(0),
             frames.stride(1), c, records.data_ptr()))
@@ -235,6 +290,7 @@ class FrameStream:
         if records is None:
             records = self.new_records(n - 1)
         self._after_torch()
+        self._lm_fits(n - 1)
         if n > 1:
             self._pending[records.data_ptr()] = records
         self.ctx.check(self.ctx.lib.dvo_stream_process_jpeg(
@@ -256,6 +312,7 @@ class FrameStream:
         if entropy is not None:
             dec.set_stream_entropy(entropy)
         self._after_torch()
+        self._lm_fits(n - 1)
         self.ctx.check(self.ctx.lib.dvo_stream_submit_jpeg(
             self.h, dec.h_, undistort.h_ if undistort is not None else None, ptrs, lens, n, records.data_ptr()))
         dec._n = n
@@ -284,6 +341,7 @@ class FrameStream:
             raise ValueError("records too small")
         if wait_torch:
             self._after_torch()
+        self._lm_fits(n - 1)
         self.ctx.check(self.ctx.lib.dvo_stream_submit(self.h, frames.data_ptr(), n, frames.stride(0),
                                                       frames.stride(1), records.data_ptr()))
         self._pending[records.data_ptr()] = records
@@ -297,6 +355,7 @@ class FrameStream:
             raise ValueError("records too small")
         if wait_torch:
             self._after_torch()
+        self._lm_fits(n2 // 2)
         self.ctx.check(self.ctx.lib.dvo_stream_submit_pairs(self.h, frames.data_ptr(), n2 // 2, frames.stride(0),
                                                             frames.stride(1), records.data_ptr()))
         self._pending[records.data_ptr()] = records
@@ -314,17 +373,25 @@ class FrameStream:
         recs = (_vp * cap)()
         pairs = (ctypes.c_int * cap)()
         n = self.ctx.lib.dvo_stream_retired(self.h, recs, pairs, cap)
-        out = []
+        # the call just made took the bound Landmarks: it stays referenced with that batch's
+        # records (the newest pending ones) until the batch retires
+        lm, self._lm_next = self._lm_next, None
+        if lm is not None and self._pending:
+            self._lm_pending[next(reversed(self._pending))] = lm
+        out, lms = [], []
         for i in range(min(n, cap)):
             t = self._pending.pop(recs[i], None)
             if t is None:
                 raise RuntimeError("retired records that were not submitted through this FrameStream")
             out.append((t, int(pairs[i])))
+            lm = self._lm_pending.pop(recs[i], None)
+            if lm is not None:
+                lms += [lm.entries, lm.counts]
         if out:
-            # the retire kernels (records_kernel) writing these records are queued on the library's
-            # stream by the call that retired them: keep the tensors alive until they have run,
-            # whether or not the caller keeps the returned list (process() drops it)
-            self._hold(*[t for t, _ in out])
+            # the retire kernels (records_kernel, the landmark kernels) writing these buffers are
+            # queued on the library's stream by the call that retired them: keep the tensors alive
+            # until they have run, whether or not the caller keeps the returned list (process() drops it)
+            self._hold(*[t for t, _ in out], *lms)
         return out
 
     def pose_tail_batch(self, records: torch.Tensor, pairs: int, corners_prev: torch.Tensor,
@@ -459,6 +526,7 @@ class FrameStream:
                 self._held.clear()
             self._last = ()
             self._pending = {}
+            self._lm_next, self._lm_pending = None, {}
 
     def __del__(self):
         try:
@@ -566,6 +634,7 @@ class KnnFrameStream:
         self._ext = torch.cuda.ExternalStream(self.hip_stream, device=self.device)
         self._held = collections.deque()  # (event, tensors) in flight on the library's stream
         self._pending = 0  # frames of the last detect() (sizes finish()'s records)
+        self._lm_next = None  # bind_landmarks: the Landmarks the next process() / finish() takes
         self.width, self.height, self.max_frames = int(width), int(height), int(max_frames)
         self.dim = 64 if cfg.detector == 1 else 128
         self.K = K.reshape(3, 3)
@@ -576,6 +645,21 @@ class KnnFrameStream:
 
     def new_records(self, n_pairs: int) -> torch.Tensor:
         return torch.zeros(max(n_pairs, 1) * PAIR_RECORD_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
+
+    def bind_landmarks(self, lm: Landmarks | None):
+        """Have the next batch (the next process*() or finish(); detect*() alone does not take it)
+        write its landmarks into `lm` (dvo_knn_stream_set_landmarks); lm needs a row per pair of
+        that batch.  One-shot: the batch after it writes nothing.  None clears a pending binding."""
+        self._lm_next = _bind_landmarks(self, self.ctx.lib.dvo_knn_stream_set_landmarks, lm)
+
+    def _lm_fits(self, pairs: int):
+        if self._lm_next is not None and self._lm_next.n_pairs < pairs:
+            raise ValueError(f"the bound Landmarks holds {self._lm_next.n_pairs} pairs, the batch has {pairs}")
+
+    def _lm_taken(self):
+        """The tensors of the Landmarks the call just made took (to keep alive with its records)."""
+        lm, self._lm_next = self._lm_next, None
+        return () if lm is None else (lm.entries, lm.counts)
 
     def set_detect_group(self, group: int):
         """SIFT frames per detection launch from the next process() on (0: frame by frame).  Waits
@@ -649,6 +733,7 @@ class KnnFrameStream:
             wait_torch = True  # the zero-fill runs on torch's stream: order the library's writes after it
         if wait_torch:
             self._after_torch()
+        self._lm_fits(n - 1)
         if c:
             self.ctx.check(self.ctx.lib.dvo_knn_stream_process_raw(
                 self.h, undistort.h_ if undistort is not None else None, frames.data_ptr(), n, frames.stride(0),
@@ -659,7 +744,7 @@ class KnnFrameStream:
             self.ctx.check(self.ctx.lib.dvo_knn_stream_process(self.h, frames.data_ptr() if n else None, n,
                                                                frames.stride(0), frames.stride(1),
                                                                records.data_ptr() if n > 1 else None))
-        self._hold(frames, records)
+        self._hold(frames, records, *self._lm_taken())
         return records
 
     @staticmethod
@@ -808,12 +893,13 @@ class KnnFrameStream:
         if records is None:
             records = self.new_records(n - 1)
         self._after_torch()
+        self._lm_fits(n - 1)
         self.ctx.check(self.ctx.lib.dvo_knn_stream_process_jpeg(
             self.h, dec.h_, undistort.h_ if undistort is not None else None, ptrs, lens, n,
             records.data_ptr() if n > 1 else None))
         dec._n = n
         self._pending = 0
-        self._hold(records)
+        self._hold(records, *self._lm_taken())
         return records
 
     def detect_jpeg(self, blobs, draws: torch.Tensor | None = None, undistort=None, entropy=None):
@@ -856,11 +942,12 @@ class KnnFrameStream:
             raise ValueError(f"records must be a contiguous uint8 device tensor of {max(n - 1, 0)} records or more")
         if wait_torch:
             self._after_torch()
+        self._lm_fits(n - 1)
         self.ctx.check(self.ctx.lib.dvo_knn_stream_finish(self.h, records.data_ptr(),
                                                           None if shard_draws is None else shard_draws.data_ptr(),
                                                           int(world), int(rank)))
         self._pending = 0  # (a refused call leaves the detection pending)
-        self._hold(records, shard_draws)
+        self._hold(records, shard_draws, *self._lm_taken())
         return records
 
     def sync(self):

@@ -965,6 +965,43 @@ int dvo_stream_get_features(dvo_stream* s, int frame, dvo_keypoint* kps, uint8_t
 int dvo_stream_get_matches(dvo_stream* s, int pair, dvo_dmatch* out, int cap, int* m);
 int dvo_stream_get_pyramid(dvo_stream* s, int frame, int level, int blurred, uint8_t* out, int cap);
 
+/* ---------------------------------------------------------------------------
+ * Landmarks: the triangulated inlier points of each pair of a stream batch, what
+ * cv.recoverPose(E, p1, p2, K, distanceThresh, mask, triangulatedPoints) hands back
+ * at v3:303, restricted to the matches both masks keep.
+ * Correspondence i of a pair whose record has status DVO_OK and n_models 1 (in the
+ * order of get_matches, the order findEssentialMat saw) is a landmark iff
+ *   1. it is an inlier of the record's E: findEssentialMat's mask, the Sampson test
+ *      at threshold / ((fx + fy) / 2); all five when the pair has five matches; and
+ *   2. it passes recoverPose's four tests (X2 X3 > 0, both depths in (0, dist_thresh))
+ *      for the decomposition recoverPose chose, on its own DLT triangulation against
+ *      that decomposition's [R | t].
+ * Its position is (X0 / X3, X1 / X3, X2 / X3) in double: the previous frame's camera
+ * coordinates, in units of the baseline (recoverPose's |t| = 1).  Metric scale is the
+ * consumer's: multiply by the pair's scale from the pose tail.
+ * Per pair, landmarks go in ascending i to slots [0, min(count, cap)) of the pair's
+ * cap entries; count[pair] is the full number (above cap: an overflow), 0 for a pair
+ * that failed.  Bytes of the entry buffer outside the written slots are not touched. */
+typedef struct {              /* 48 bytes */
+    int32_t match, reserved;  /* index into the pair's match list; 0 */
+    float x1, y1, x2, y2;     /* the pixel coordinates the stream's point buffer holds */
+    double X, Y, Z;
+} dvo_landmark;
+/* Binds device buffers, d_out [pairs][cap] entries and d_count [pairs], for the NEXT batch
+ * only: the next dvo_stream_process / _process_pairs / _submit / _submit_pairs call or one of
+ * their undistorted, BGR or JPEG variants (v3:303, recoverPose(..., triangulatedPoints)).  The
+ * binding travels with that batch as its records pointer does and is written when the batch
+ * retires, on the stream's HIP stream, after the records; the buffers must stay allocated
+ * until then.  d_out == NULL clears a pending binding.  DVO_EINVAL for a non-null d_out with
+ * cap < 1 or d_count == NULL.  The first binding allocates the kernel's scratch (32 B per
+ * slot of a set's point buffer, rounded up to 256 slots per pair); a stream that never binds
+ * launches and holds what it did before.  dvo_stream_pair does not take a binding. */
+int dvo_stream_set_landmarks(dvo_stream* s, dvo_landmark* d_out, int32_t* d_count, int cap);
+/* The same for a k-NN stream (v3:303, recoverPose(..., triangulatedPoints)): the next batch is
+ * the next dvo_knn_stream_process* or dvo_knn_stream_finish; a detect call alone does not
+ * consume the binding. */
+int dvo_knn_stream_set_landmarks(dvo_knn_stream* s, dvo_landmark* d_out, int32_t* d_count, int cap);
+
 /* Test hooks: exercise one device algorithm in isolation. */
 /* KeyPointsFilter::retainBest permutation on `n` float responses (GPU emulation
  * of libstdc++ nth_element + partition); depth < 0 = libstdc++ default. */
@@ -1058,6 +1095,16 @@ int dvo_test_hamming_ratio_batch(dvo_ctx* ctx, const uint8_t* desc, const dvo_ke
 int dvo_test_flann_batch(dvo_ctx* ctx, const float* desc, const int32_t* counts, int frames, int cap, int dim, int trees,
                          int checks, uint64_t state, int levels, int32_t* idx, float* dist, uint64_t* starts,
                          uint64_t* state_out, int* n_global, int* depth);
+/* The landmark kernels (dvo_stream_set_landmarks; v3:303, recoverPose(..., triangulatedPoints))
+ * on host arrays, at sizes no detector produces on demand: pts [pairs][stride][4] pixel
+ * coordinates, m [pairs] counts (5 <= m[p] <= stride; stride need not be a multiple of 64).
+ * Normalise and findEssentialMat under the per-call RANSAC schedule pair by pair, then the
+ * stream's retire (E, recoverPose, the records) and the landmarks of all pairs at once.  out
+ * [pairs][cap] is copied up whole before the run and back whole after it, so untouched slots
+ * keep the caller's bytes; count [pairs]; rec [pairs] the records (n_kp_prev = n_kp_cur = m). */
+int dvo_test_landmarks(dvo_ctx* ctx, const float* pts, const int32_t* m, int pairs, int stride, const double* K,
+                       double prob, double threshold, int max_iters, double dist_thresh, int cap, dvo_landmark* out,
+                       int32_t* count, dvo_pair_record* rec);
 
 #ifdef __cplusplus
 }
