@@ -49,6 +49,9 @@ assert PAIR_RECORD_DTYPE.itemsize == 256
 LANDMARK_DTYPE = np.dtype([("match", "<i4"), ("reserved", "<i4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"),
                            ("y2", "<f4"), ("X", "<f8"), ("Y", "<f8"), ("Z", "<f8")])
 assert LANDMARK_DTYPE.itemsize == 48
+# dvo_track_scale: a pair's baseline ratio to its predecessor from their shared landmarks (dvo_stream_set_tracks)
+TRACK_SCALE_DTYPE = np.dtype([("ratio", "<f8"), ("q1", "<f8"), ("q3", "<f8"), ("n_common", "<i4"), ("n_prev", "<i4")])
+assert TRACK_SCALE_DTYPE.itemsize == 32
 
 
 class DVOError(RuntimeError):
@@ -173,6 +176,9 @@ _SIGNATURES = {
     "dvo_stream_set_landmarks": ([_vp, _vp, _vp, _c], _c),
     "dvo_knn_stream_set_landmarks": ([_vp, _vp, _vp, _c], _c),
     "dvo_test_landmarks": ([_vp, _vp, _vp, _c, _c, _vp, _d, _d, _c, _d, _c, _vp, _vp, _vp], _c),
+    "dvo_stream_set_tracks": ([_vp, _vp, _vp], _c),
+    "dvo_knn_stream_set_tracks": ([_vp, _vp, _vp], _c),
+    "dvo_test_tracks": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c, _c, _c, _c, _c, _vp, _vp], _c),
     "dvo_knn_pair_create": ([_vp, ctypes.POINTER(KnnPairConfig), ctypes.POINTER(_vp)], _c),
     "dvo_knn_pair_destroy": ([_vp], None),
     "dvo_knn_pair_run": ([_vp, _vp, _vp, _c, _c, ctypes.POINTER(ctypes.c_uint64), _vp], _c),

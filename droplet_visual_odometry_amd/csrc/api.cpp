@@ -87,6 +87,13 @@ struct LandmarkBinding {
     int cap = 0;
 };
 
+// The caller's buffers of a tracks binding (dvo_stream_set_tracks), beside a landmark binding.
+struct TracksBinding {
+    int32_t* link = nullptr;  // [pairs][the landmark binding's cap], or null
+    dvo_track_scale* scale = nullptr;  // [pairs], or null; both null: no binding
+    explicit operator bool() const { return link || scale; }
+};
+
 struct dvo_stream {
     dvo_ctx* ctx = nullptr;
     dvo_stream_config cfg{};
@@ -125,8 +132,10 @@ struct dvo_stream {
         int pairs = 0;
         dvo_pair_record* rec = nullptr;  // the caller's records of the batch
         LandmarkBinding lm;              // the batch's landmark binding, written when the set retires
+        TracksBinding tr;                // its tracks binding (the set's index copy was taken at the match)
     };
     LandmarkBinding lm_next;  // dvo_stream_set_landmarks: taken by the next batch
+    TracksBinding tr_next;    // dvo_stream_set_tracks: taken with it
     PairSet sets[kMaxSets];
     // their arrays: 1 set until the first submit, then kRansacRounds; pairs.all.g is the stream's GeomArgs
     PairSets pairs;
@@ -540,6 +549,19 @@ int retire_sets(dvo_stream* s) {
         if (s->ratio > 0) HIP_TRY(launch_hamming_ratio_status(v.hdr, st.pairs, st.rec, nullptr, s->hs));
         if (st.lm.out)  // after the records are final: a landmark pair is one whose record got through
             HIP_TRY(launch_landmarks(v.g, st.pairs, st.rec, s->pairs.lm, st.lm.out, st.lm.count, st.lm.cap, s->hs));
+        if (st.lm.out && st.tr) {  // on the lists the landmark kernels just left, with the set's own indices
+            TrackArgs a = s->pairs.track_args(k, s->cfg.max_frames, s->plan.kp_cap);
+            const size_t off = (size_t)k * s->cfg.max_frames * s->plan.kp_cap;
+            a.mq = s->pairs.tr.iq + off;
+            a.mt = s->pairs.tr.it + off;
+            a.idx_stride = s->plan.kp_cap;
+            a.idx_step = 1;
+            a.rec = st.rec;
+            a.link = st.tr.link;
+            a.cap = st.lm.cap;
+            a.scale = st.tr.scale;
+            HIP_TRY(launch_tracks(a, st.pairs, s->hs));
+        }
         s->retired_rec[s->retired] = st.rec;
         s->retired_pairs[s->retired] = st.pairs;
         ++s->retired;
@@ -565,6 +587,9 @@ int run_stream(dvo_stream* s, const uint8_t* d_frames, int n, int64_t fstride, i
     dvo_ctx* ctx = s->ctx;
     // a landmark binding is for this batch alone, whether or not the call gets as far as its pairs
     const LandmarkBinding lm = detect_only ? LandmarkBinding{} : std::exchange(s->lm_next, LandmarkBinding{});
+    const TracksBinding tr = detect_only ? TracksBinding{} : std::exchange(s->tr_next, TracksBinding{});
+    if (tr && pair_step != 1)  // both bindings are consumed
+        return fail(ctx, DVO_EINVAL, "tracks need consecutive pairs: the pairs of a *_pairs call share no frame");
     const int want = drain ? 1 : kRansacRounds;
     if (!detect_only && s->pairs.nsets < want) {
         // the first pipelined submit grows the sets; a drained call after a failed grow allocates one
@@ -608,8 +633,15 @@ int run_stream(dvo_stream* s, const uint8_t* d_frames, int n, int64_t fstride, i
         else
             HIP_TRY(launch_match(P, s->cfg.cross_check, s->hs, ev));
         HIP_TRY(launch_pair_header(P, P.buf.hdr, s->hs));
+        if (lm.out && tr) {
+            // the match indices are the stream's, not the set's: a later batch overwrites them
+            // before this one retires, so a batch with tracks keeps its own copy
+            const size_t off = (size_t)k * s->cfg.max_frames * s->plan.kp_cap, nb = (size_t)pairs * s->plan.kp_cap * 4;
+            HIP_TRY(hipMemcpyAsync(s->pairs.tr.iq + off, s->buf.mq, nb, hipMemcpyDeviceToDevice, s->hs));
+            HIP_TRY(hipMemcpyAsync(s->pairs.tr.it + off, s->buf.mt, nb, hipMemcpyDeviceToDevice, s->hs));
+        }
         HIP_TRY(launch_geometry_args(s->pairs.view(k).g, pairs, kStageNormalize, s->hs));
-        s->sets[k] = dvo_stream::PairSet{true, 0, pairs, d_rec, lm};
+        s->sets[k] = dvo_stream::PairSet{true, 0, pairs, d_rec, lm, tr};
         s->last_set = k;
         // nsets >= 1 here: every path that matches has passed ensure_sets above
         s->next_set = (k + 1) % s->pairs.nsets;
@@ -1059,12 +1091,28 @@ int dvo_stream_set_landmarks(dvo_stream* s, dvo_landmark* d_out, int32_t* d_coun
     dvo_ctx* ctx = s->ctx;
     if (!d_out) {
         s->lm_next = LandmarkBinding{};
+        s->tr_next = TracksBinding{};
         return DVO_OK;
     }
     if (cap < 1 || !d_count) return fail(ctx, DVO_EINVAL, "landmarks need cap >= 1 and a count buffer");
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(s->pairs.ensure_landmarks(s->cfg.max_frames, s->plan.kp_cap));  // the first binding sizes the scratch
     s->lm_next = LandmarkBinding{d_out, d_count, cap};
+    return DVO_OK;
+}
+
+int dvo_stream_set_tracks(dvo_stream* s, int32_t* d_link, dvo_track_scale* d_scale) {
+    if (!s) return DVO_EINVAL;
+    dvo_ctx* ctx = s->ctx;
+    if (!d_link && !d_scale) {
+        s->tr_next = TracksBinding{};
+        return DVO_OK;
+    }
+    if (!s->lm_next.out) return fail(ctx, DVO_EINVAL, "tracks go with a pending landmark binding");
+    HIP_TRY(hipSetDevice(ctx->device));
+    // the first binding sizes the scratch, for every set a pipelined stream will hold
+    HIP_TRY(s->pairs.ensure_tracks(kRansacRounds, s->cfg.max_frames, s->plan.kp_cap, true));
+    s->tr_next = TracksBinding{d_link, d_scale};
     return DVO_OK;
 }
 
@@ -2714,6 +2762,7 @@ struct dvo_knn_stream {
     uint8_t* raw = nullptr;
     int raw_pitch = 0;
     LandmarkBinding lm_next;  // dvo_knn_stream_set_landmarks: taken by the next finish
+    TracksBinding tr_next;    // dvo_knn_stream_set_tracks: taken with it
     // A raw-input call records ev_in[k] before its input launch, k the one the last accepted call
     // does not use (first_ev; -1: that call began at ev[0]), so a refused call disturbs no figure.
     hipEvent_t ev_in[2] = {nullptr, nullptr};
@@ -2894,6 +2943,7 @@ int dvo_knn_stream_finish(dvo_knn_stream* st, dvo_pair_record* d_records, const 
     hipEvent_t* ev = st->profiling && st->pending_timed ? st->ev : nullptr;
     st->pending = 0;
     const LandmarkBinding lm = std::exchange(st->lm_next, LandmarkBinding{});  // for this batch alone
+    const TracksBinding tr = std::exchange(st->tr_next, TracksBinding{});
     const int pairs = n_frames - 1;
     const PairArrays& v = st->pairs.all;
     const bool flann = st->fl.trees > 0;
@@ -2908,6 +2958,18 @@ int dvo_knn_stream_finish(dvo_knn_stream* st, dvo_pair_record* d_records, const 
         HIP_TRY(launch_knn_status(b.n, b.fstate, b.missing, pairs, d_records, s));
         if (lm.out)  // after the records are final: a landmark pair is one whose record got through
             HIP_TRY(launch_landmarks(v.g, pairs, d_records, st->pairs.lm, lm.out, lm.count, lm.cap, s));
+        if (lm.out && tr) {  // on the lists the landmark kernels just left; the batch's DMatch array is still its own
+            TrackArgs a = st->pairs.track_args(0, b.F - 1, b.cap);
+            a.mq = &b.matches->queryIdx;
+            a.mt = &b.matches->trainIdx;
+            a.idx_stride = b.cap;
+            a.idx_step = (int)(sizeof(dvo_dmatch) / sizeof(int32_t));
+            a.rec = d_records;
+            a.link = tr.link;
+            a.cap = lm.cap;
+            a.scale = tr.scale;
+            HIP_TRY(launch_tracks(a, pairs, s));
+        }
     }
     if (ev) {
         HIP_TRY(hipEventRecord(ev[3], s));
@@ -2923,12 +2985,27 @@ int dvo_knn_stream_set_landmarks(dvo_knn_stream* s, dvo_landmark* d_out, int32_t
     dvo_ctx* ctx = s->ctx;
     if (!d_out) {
         s->lm_next = LandmarkBinding{};
+        s->tr_next = TracksBinding{};
         return DVO_OK;
     }
     if (cap < 1 || !d_count) return fail(ctx, DVO_EINVAL, "landmarks need cap >= 1 and a count buffer");
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(s->pairs.ensure_landmarks(s->b.F - 1, s->b.cap));  // the first binding sizes the scratch
     s->lm_next = LandmarkBinding{d_out, d_count, cap};
+    return DVO_OK;
+}
+
+int dvo_knn_stream_set_tracks(dvo_knn_stream* s, int32_t* d_link, dvo_track_scale* d_scale) {
+    if (!s) return DVO_EINVAL;
+    dvo_ctx* ctx = s->ctx;
+    if (!d_link && !d_scale) {
+        s->tr_next = TracksBinding{};
+        return DVO_OK;
+    }
+    if (!s->lm_next.out) return fail(ctx, DVO_EINVAL, "tracks go with a pending landmark binding");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(s->pairs.ensure_tracks(1, s->b.F - 1, s->b.cap, false));  // the first binding sizes the scratch
+    s->tr_next = TracksBinding{d_link, d_scale};
     return DVO_OK;
 }
 
@@ -3627,6 +3704,72 @@ int dvo_test_landmarks(dvo_ctx* ctx, const float* pts, const int32_t* m, int pai
     std::memcpy(out, hout, P * (size_t)cap * sizeof(dvo_landmark));
     std::memcpy(count, hcount, P * 4);
     std::memcpy(rec, hrec, P * sizeof(dvo_pair_record));
+    return DVO_OK;
+}
+
+int dvo_test_tracks(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* count, const int32_t* mq, const int32_t* mt,
+                    const int32_t* m, const dvo_pair_record* rec, int pairs, int cap, int stride, int kp_cap,
+                    int cap_out, int32_t* link, dvo_track_scale* scale) {
+    if (!ctx || !lm || !count || !mq || !mt || !m || !rec || !link || !scale) return DVO_EINVAL;
+    if (pairs < 1 || pairs > 65535 || cap < 1 || stride < 1 || kp_cap < 1 || cap_out < 1)
+        return fail(ctx, DVO_EINVAL, "bad pair count, cap, stride, kp_cap or cap_out");
+    const size_t P = (size_t)pairs, tiles = (size_t)landmark_tiles(stride);
+    std::vector<LandmarkTmp> tmp(P * tiles * kLandmarkTile);
+    std::vector<int32_t> tcnt(P * tiles, 0);
+    for (int p = 0; p < pairs; ++p) {
+        if (m[p] < 0 || m[p] > stride || count[p] < 0 || count[p] > cap || count[p] > m[p])
+            return fail(ctx, DVO_EINVAL, "need 0 <= count[p] <= min(cap, m[p]) and m[p] <= stride");
+        for (int i = 0; i < m[p]; ++i) {
+            const size_t at = (size_t)p * stride + i;
+            if (mq[at] < 0 || mq[at] >= kp_cap || mt[at] < 0 || mt[at] >= kp_cap)
+                return fail(ctx, DVO_EINVAL, "match index outside [0, kp_cap)");
+        }
+        for (int o = 0; o < count[p]; ++o) {  // into the tile of its match, as landmark_tile_kernel compacts
+            const dvo_landmark& e = lm[(size_t)p * cap + o];
+            if (e.match < 0 || e.match >= m[p] || (o > 0 && e.match <= lm[(size_t)p * cap + o - 1].match))
+                return fail(ctx, DVO_EINVAL, "landmark matches must ascend inside [0, m[p])");
+            const size_t t = (size_t)p * tiles + e.match / kLandmarkTile;
+            tmp[t * kLandmarkTile + tcnt[t]++] = LandmarkTmp{e.X, e.Y, e.Z, e.match, 0};
+        }
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    CallMem mem(ctx->call, ctx->stream);
+    TrackArgs a{};
+    LandmarkTmp* dtmp = mem.dev<LandmarkTmp>(tmp.size());
+    int32_t* dtcnt = mem.dev<int32_t>(tcnt.size());
+    int32_t* dq = mem.dev<int32_t>(P * stride);
+    int32_t* dt = mem.dev<int32_t>(P * stride);
+    dvo_pair_record* drec = mem.dev<dvo_pair_record>(P);
+    a.table = mem.dev<int32_t>(P * kp_cap);
+    a.ratio = mem.dev<double>(P * stride);
+    a.lcnt = mem.dev<int32_t>(P * tiles);
+    a.link = mem.dev<int32_t>(P * cap_out);
+    a.scale = mem.dev<dvo_track_scale>(P);
+    HIP_TRY(mem.error());
+    a.L.tmp = dtmp;
+    a.L.tcnt = dtcnt;
+    a.tiles = (int)tiles;
+    a.mq = dq;
+    a.mt = dt;
+    a.idx_stride = stride;
+    a.idx_step = 1;
+    a.rec = drec;
+    a.kp_cap = kp_cap;
+    a.pts_stride = stride;
+    a.cap = cap_out;
+    HIP_TRY(mem.put(dtmp, tmp.data(), tmp.size() * sizeof(LandmarkTmp)));
+    HIP_TRY(mem.put(dtcnt, tcnt.data(), tcnt.size() * 4));
+    HIP_TRY(mem.put(dq, mq, P * stride * 4));
+    HIP_TRY(mem.put(dt, mt, P * stride * 4));
+    HIP_TRY(mem.put(drec, rec, P * sizeof(dvo_pair_record)));
+    HIP_TRY(mem.put(a.link, link, P * cap_out * 4));
+    HIP_TRY(launch_tracks(a, pairs, ctx->stream));
+    uint8_t *hlink, *hscale;
+    HIP_TRY(mem.get(a.link, P * cap_out * 4, &hlink));
+    HIP_TRY(mem.get(a.scale, P * sizeof(dvo_track_scale), &hscale));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    std::memcpy(link, hlink, P * cap_out * 4);
+    std::memcpy(scale, hscale, P * sizeof(dvo_track_scale));
     return DVO_OK;
 }
 

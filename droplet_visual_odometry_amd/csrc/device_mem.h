@@ -176,6 +176,43 @@ struct PairSets {
         return hipSuccess;
     }
 
+    // The track kernels' scratch (launch_tracks): empty until the stream's first tracks binding
+    // (dvo_stream_set_tracks), then `sets` copies for F pairs of cap points, sets being the most
+    // the stream will ever hold: like the landmark scratch it is allocated once, whatever ensure()
+    // does later, and never regrown.  own_idx: the ORB stream's per-set copy of its match indices.
+    TrackScratch tr;
+    int tr_sets = 0;
+    DeviceAllocs tr_mem;
+    hipError_t ensure_tracks(int sets, int F_, int cap_, bool own_idx) {
+        if (tr.table) return hipSuccess;
+        const size_t P = (size_t)sets * (F_ > 0 ? F_ : 1), n = P * cap_;
+        DeviceAllocs fresh;
+        TrackScratch t;
+        hipError_t e = fresh.alloc(&t.table, n * sizeof(int32_t) + 256);
+        if (e == hipSuccess) e = fresh.alloc(&t.ratio, n * sizeof(double) + 256);
+        if (e == hipSuccess) e = fresh.alloc(&t.lcnt, P * landmark_tiles(cap_) * sizeof(int32_t) + 256);
+        if (e == hipSuccess && own_idx) e = fresh.alloc(&t.iq, n * sizeof(int32_t) + 256);
+        if (e == hipSuccess && own_idx) e = fresh.alloc(&t.it, n * sizeof(int32_t) + 256);
+        if (e != hipSuccess) return e;
+        tr_mem = std::move(fresh);
+        tr = t;
+        tr_sets = sets;
+        return hipSuccess;
+    }
+    // Set k's part of it: the kernels' arguments but for the indices, the records and the caller's buffers.
+    TrackArgs track_args(int k, int F_, int cap_) const {
+        const size_t P = (size_t)k * (F_ > 0 ? F_ : 1), n = P * cap_;
+        TrackArgs a{};
+        a.L = lm;
+        a.tiles = landmark_tiles(cap_);
+        a.table = tr.table + n;
+        a.kp_cap = cap_;
+        a.ratio = tr.ratio + n;
+        a.pts_stride = cap_;
+        a.lcnt = tr.lcnt + P * a.tiles;
+        return a;
+    }
+
     // Set k's view: pairs [k F, (k + 1) F) of every per-set array.
     PairArrays view(int k) const {
         PairArrays v = all;

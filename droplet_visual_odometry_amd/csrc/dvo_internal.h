@@ -393,6 +393,39 @@ struct LandmarkScratch {
 inline int landmark_tiles(int64_t pts_stride) { return (int)((pts_stride + kLandmarkTile - 1) / kLandmarkTile); }
 hipError_t launch_landmarks(const GeomArgs& g_set, int pairs, const dvo_pair_record* records, const LandmarkScratch& L,
                             dvo_landmark* out, int32_t* count, int cap, hipStream_t s);
+// The tracks of a retired set (dvo_stream_set_tracks; tracks.hip), right after its landmarks while
+// L still holds the set's full lists: the table kernel (each landmark's ordinal, atomicMin, at its
+// trainIdx), the link kernel (pair p's queryIdx looked up in pair p - 1's table; the link into the
+// caller's slot, the ratio compacted in order into the pair's ratio array) and the select kernel
+// (a workgroup per pair: exact radix select of the three ranks).  Match i of pair p has its
+// indices at mq / mt [(p * idx_stride + i) * idx_step]: separate arrays (step 1), or the two
+// fields of a dvo_dmatch array (step 4).  Only table rows [0, pairs) are preset.
+constexpr int32_t kTrackEmpty = 0x7f7f7f7f;  // a table cell no landmark reached (the memset byte 0x7f)
+constexpr int kTrackLds = 2048;              // ratios of a pair the select kernel keeps in LDS
+struct TrackScratch {
+    int32_t* table = nullptr;  // [sets][pairs][kp_cap] smallest landmark ordinal per trainIdx
+    double* ratio = nullptr;   // [sets][pairs][pts_stride] a tile's linked ratios from its first ordinal on
+    int32_t* lcnt = nullptr;   // [sets][pairs][tiles] linked landmarks per tile
+    int32_t* iq = nullptr;     // [sets][pairs][pts_stride] the ORB stream's copy of queryIdx, trainIdx
+    int32_t* it = nullptr;
+};
+struct TrackArgs {
+    LandmarkScratch L;  // the set's full landmark lists
+    int tiles;
+    const int32_t *mq, *mt;
+    int64_t idx_stride;
+    int idx_step;
+    const dvo_pair_record* rec;
+    int32_t* table;
+    int kp_cap;
+    double* ratio;
+    int64_t pts_stride;
+    int32_t* lcnt;
+    int32_t* link;  // the caller's [pairs][cap], or null
+    int cap;
+    dvo_track_scale* scale;  // the caller's [pairs], or null
+};
+hipError_t launch_tracks(const TrackArgs& a, int pairs, hipStream_t s);
 // five-point record blocks a merged round can need (sizes the stream's GeomArgs::fprec, dk_list)
 int64_t round_blocks_bound(int F, int hyp_cap);
 int64_t round_items_bound(int F, int hyp_cap);

@@ -1149,6 +1149,33 @@ def test_landmarks(pts, m, K, cap, out=None, prob=0.999, threshold=1.0, max_iter
     return out, count, rec
 
 
+def test_tracks(lm, count, mq, mt, m, rec, kp_cap, cap_out=None, link=None, ctx=None):
+    """The track kernels of the streams (stream.Tracks) on host arrays: lm LANDMARK_DTYPE[P, cap] the
+    full landmark lists (count int[P] of them, match ascending), mq / mt int32[P, stride] the match
+    indices (m int[P] of them, each below kp_cap), rec PAIR_RECORD_DTYPE[P] (R and t are read).
+    link: int32[P, cap_out] whose bytes the kernels leave alone outside the written slots (default
+    -1; cap_out defaults to cap).  Returns (link, scale TRACK_SCALE_DTYPE[P])."""
+    from ._native import LANDMARK_DTYPE, TRACK_SCALE_DTYPE
+    c = _ctx(ctx)
+    mq = np.ascontiguousarray(mq, np.int32)
+    mt = np.ascontiguousarray(mt, np.int32)
+    count = np.ascontiguousarray(count, np.int32)
+    m = np.ascontiguousarray(m, np.int32)
+    if (lm.dtype != LANDMARK_DTYPE or lm.ndim != 2 or not lm.flags.c_contiguous or mq.ndim != 2 or mq.shape != mt.shape
+            or not (len(lm) == len(mq) == len(count) == len(m) == len(rec))):
+        raise DVOError(-1, "lm LANDMARK_DTYPE[P, cap], mq / mt int32[P, stride], count, m and rec [P] must agree")
+    rec = np.ascontiguousarray(rec, PAIR_RECORD_DTYPE)
+    P, cap = lm.shape
+    cap_out = cap if cap_out is None else int(cap_out)
+    link = np.full((P, cap_out), -1, np.int32) if link is None else link
+    if link.dtype != np.int32 or link.shape != (P, cap_out) or not link.flags.c_contiguous:
+        raise DVOError(-1, "link must be a contiguous int32[P, cap_out] array")
+    scale = np.zeros(P, TRACK_SCALE_DTYPE)
+    c.check(c.lib.dvo_test_tracks(c.h, ptr(lm), ptr(count), ptr(mq), ptr(mt), ptr(m), ptr(rec), P, cap, mq.shape[1],
+                                  int(kp_cap), cap_out, ptr(link), ptr(scale)))
+    return link, scale
+
+
 def test_flann_batch(desc, counts, trees=5, checks=50, rng_state=None, levels=0, ctx=None):
     """The batched kd-forest build and search of dvo_knn_stream_process's FLANN mode
     (stream.KnnFrameStream(matcher="flann")) on host arrays: desc float32[F, cap, dim] frame slots,

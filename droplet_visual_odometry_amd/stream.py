@@ -19,8 +19,8 @@ import ctypes
 import numpy as np
 import torch
 
-from ._native import (DMATCH_DTYPE, KEYPOINT_DTYPE, LANDMARK_DTYPE, PAIR_RECORD_DTYPE, Context, StreamConfig, _vp,
-                      orb_params, ptr)
+from ._native import (DMATCH_DTYPE, KEYPOINT_DTYPE, LANDMARK_DTYPE, PAIR_RECORD_DTYPE, TRACK_SCALE_DTYPE, Context,
+                      StreamConfig, _vp, orb_params, ptr)
 
 
 class Landmarks:
@@ -58,6 +58,67 @@ def _bind_landmarks(stream, setter, lm):
     stream._after_torch()  # the buffers' fill ran on torch's stream: order the library's writes after it
     stream.ctx.check(setter(stream.h, lm.entries.data_ptr(), lm.counts.data_ptr(), lm.cap))
     return lm
+
+
+class Tracks:
+    """Device buffers for one batch's tracks (dvo_stream_set_tracks), the companion of a Landmarks
+    with the same cap: per landmark slot the ordinal of the same scene point among the previous
+    pair's landmarks, and per pair the ratio of its baseline to the previous pair's from the
+    shared points (see include/dvo.h).  links: int32 [n_pairs, cap], written for the slots the
+    Landmarks holds, -1 where the point has no predecessor; a link can be >= cap when the previous
+    pair overflowed.  scales: uint8 [n_pairs, 32] (TRACK_SCALE_DTYPE).  Bind it with bind_tracks
+    after bind_landmarks; read it after the batch has retired and the stream is synchronised."""
+
+    def __init__(self, n_pairs: int, cap: int, device):
+        if n_pairs < 1 or cap < 1:
+            raise ValueError("Tracks needs n_pairs >= 1 and cap >= 1")
+        self.n_pairs, self.cap = int(n_pairs), int(cap)
+        self.links = torch.full((self.n_pairs, self.cap), -1, dtype=torch.int32, device=device)
+        self.scales = torch.zeros((self.n_pairs, TRACK_SCALE_DTYPE.itemsize), dtype=torch.uint8, device=device)
+
+    def numpy(self, pair: int, count: int) -> np.ndarray:
+        """The links of the pair's first min(count, cap) landmarks (count: Landmarks.count(pair))."""
+        return self.links[pair, :min(int(count), self.cap)].cpu().numpy().copy()
+
+    def scales_numpy(self) -> np.ndarray:
+        """TRACK_SCALE_DTYPE [n_pairs]: ratio, q1, q3, n_common, n_prev per pair."""
+        return self.scales.cpu().numpy().reshape(-1).view(TRACK_SCALE_DTYPE).copy()
+
+
+def _bind_tracks(stream, setter, tr):
+    """The one-shot tracks binding of both stream classes; returns what to keep referenced."""
+    if tr is None:
+        stream.ctx.check(setter(stream.h, None, None))
+        return None
+    lm = stream._lm_next
+    if lm is None:
+        raise ValueError("bind_tracks goes after bind_landmarks: tracks are a companion of a pending Landmarks")
+    if not isinstance(tr, Tracks) or tr.links.device != stream.device or tr.scales.device != stream.device:
+        raise ValueError("bind_tracks takes a Tracks on the stream's device (or None)")
+    if tr.cap != lm.cap or tr.n_pairs < lm.n_pairs:
+        raise ValueError(f"the Tracks ({tr.n_pairs} pairs, cap {tr.cap}) must have the bound Landmarks' cap and "
+                         f"pairs ({lm.n_pairs}, cap {lm.cap})")
+    stream._after_torch()  # the buffers' fill ran on torch's stream: order the library's writes after it
+    stream.ctx.check(setter(stream.h, tr.links.data_ptr(), tr.scales.data_ptr()))
+    return tr
+
+
+def carry_scale(anchor, scales) -> np.ndarray:
+    """Metric baseline length per pair of one batch: anchor float64 [pairs] holds the marker's scale
+    where a marker was seen (the pose tail) and NaN elsewhere; scales is the batch's
+    TRACK_SCALE_DTYPE [pairs] (Tracks.scales_numpy).  out[p] = anchor[p] where that is not NaN, else
+    out[p - 1] * ratio[p] when n_common[p] >= 1 and out[p - 1] is not NaN, else NaN.  No threshold
+    of its own: filter on n_common, q1 and q3 first (set n_common to 0 where the ratio is not trusted)."""
+    anchor = np.asarray(anchor, np.float64)
+    if anchor.ndim != 1 or len(scales) != len(anchor):
+        raise ValueError("anchor float64 [pairs] and scales [pairs] must agree")
+    out = np.full(len(anchor), np.nan)
+    for p in range(len(anchor)):
+        if not np.isnan(anchor[p]):
+            out[p] = anchor[p]
+        elif p >= 1 and scales["n_common"][p] >= 1 and not np.isnan(out[p - 1]):
+            out[p] = out[p - 1] * scales["ratio"][p]
+    return out
 
 
 class FrameStream:
@@ -99,6 +160,7 @@ class FrameStream:
         self._pending = {}  # records of submitted, not yet retired batches (by device address)
         self._lm_next = None  # bind_landmarks: the Landmarks the next batch takes
         self._lm_pending = {}  # Landmarks of batches not yet retired, by their records' device address
+        self._tr_next = None  # bind_tracks: the Tracks the next batch takes with its Landmarks
         self.width, self.height, self.max_frames, self.nfeatures = width, height, max_frames, nfeatures
         self.K = K.reshape(3, 3)
         if ratio:
@@ -125,10 +187,21 @@ class FrameStream:
         (dvo_stream_set_landmarks); lm needs a row per pair of that batch.  One-shot: the batch
         after it writes nothing.  None clears a binding no batch has taken yet."""
         self._lm_next = _bind_landmarks(self, self.ctx.lib.dvo_stream_set_landmarks, lm)
+        if lm is None:
+            self._tr_next = None  # the library clears a pending tracks binding with it
 
-    def _lm_fits(self, pairs: int):
+    def bind_tracks(self, tr: Tracks | None):
+        """Have the next batch also write its tracks into `tr` (dvo_stream_set_tracks), after its
+        landmarks.  Call it after bind_landmarks (ValueError otherwise), with a Tracks of the
+        same cap.  One-shot, like the landmark binding; None clears a pending binding.  Only for
+        batches of consecutive frames: process_pairs / submit_pairs raise ValueError."""
+        self._tr_next = _bind_tracks(self, self.ctx.lib.dvo_stream_set_tracks, tr)
+
+    def _lm_fits(self, pairs: int, shared: bool = True):
         if self._lm_next is not None and self._lm_next.n_pairs < pairs:
             raise ValueError(f"the bound Landmarks holds {self._lm_next.n_pairs} pairs, the batch has {pairs}")
+        if self._tr_next is not None and not shared:
+            raise ValueError("tracks link consecutive pairs: the pairs of process_pairs / submit_pairs share no frame")
 
     def process(self, frames: torch.Tensor, records: torch.Tensor | None = None, wait_torch: bool = True,
                 undistort=None) -> torch.Tensor:
@@ -186,7 +259,7 @@ class FrameStream:
             wait_torch = True
         if wait_torch:
             self._after_torch()
-        self._lm_fits(n2 // 2)
+        self._lm_fits(n2 // 2, shared=False)
         self._pending[records.data_ptr()] = records
         self.ctx.check(self.ctx.lib.dvo_stream_process_pairs(self.h, frames.data_ptr(), n2 // 2, frames.stride(0),
                                                              frames.stride(1), records.data_ptr()))
@@ -355,7 +428,7 @@ class FrameStream:
             raise ValueError("records too small")
         if wait_torch:
             self._after_torch()
-        self._lm_fits(n2 // 2)
+        self._lm_fits(n2 // 2, shared=False)
         self.ctx.check(self.ctx.lib.dvo_stream_submit_pairs(self.h, frames.data_ptr(), n2 // 2, frames.stride(0),
                                                             frames.stride(1), records.data_ptr()))
         self._pending[records.data_ptr()] = records
@@ -376,17 +449,20 @@ class FrameStream:
         # the call just made took the bound Landmarks: it stays referenced with that batch's
         # records (the newest pending ones) until the batch retires
         lm, self._lm_next = self._lm_next, None
+        tr, self._tr_next = self._tr_next, None
         if lm is not None and self._pending:
-            self._lm_pending[next(reversed(self._pending))] = lm
+            self._lm_pending[next(reversed(self._pending))] = (lm, tr)
         out, lms = [], []
         for i in range(min(n, cap)):
             t = self._pending.pop(recs[i], None)
             if t is None:
                 raise RuntimeError("retired records that were not submitted through this FrameStream")
             out.append((t, int(pairs[i])))
-            lm = self._lm_pending.pop(recs[i], None)
+            lm, tr = self._lm_pending.pop(recs[i], (None, None))
             if lm is not None:
                 lms += [lm.entries, lm.counts]
+            if tr is not None:
+                lms += [tr.links, tr.scales]
         if out:
             # the retire kernels (records_kernel, the landmark kernels) writing these buffers are
             # queued on the library's stream by the call that retired them: keep the tensors alive
@@ -526,7 +602,7 @@ class FrameStream:
                 self._held.clear()
             self._last = ()
             self._pending = {}
-            self._lm_next, self._lm_pending = None, {}
+            self._lm_next, self._lm_pending, self._tr_next = None, {}, None
 
     def __del__(self):
         try:
@@ -635,6 +711,7 @@ class KnnFrameStream:
         self._held = collections.deque()  # (event, tensors) in flight on the library's stream
         self._pending = 0  # frames of the last detect() (sizes finish()'s records)
         self._lm_next = None  # bind_landmarks: the Landmarks the next process() / finish() takes
+        self._tr_next = None  # bind_tracks: the Tracks it takes with them
         self.width, self.height, self.max_frames = int(width), int(height), int(max_frames)
         self.dim = 64 if cfg.detector == 1 else 128
         self.K = K.reshape(3, 3)
@@ -651,6 +728,14 @@ class KnnFrameStream:
         write its landmarks into `lm` (dvo_knn_stream_set_landmarks); lm needs a row per pair of
         that batch.  One-shot: the batch after it writes nothing.  None clears a pending binding."""
         self._lm_next = _bind_landmarks(self, self.ctx.lib.dvo_knn_stream_set_landmarks, lm)
+        if lm is None:
+            self._tr_next = None  # the library clears a pending tracks binding with it
+
+    def bind_tracks(self, tr: Tracks | None):
+        """Have the next batch also write its tracks into `tr` (dvo_knn_stream_set_tracks), after
+        its landmarks.  Call it after bind_landmarks (ValueError otherwise), with a Tracks of the
+        same cap.  One-shot; None clears a pending binding; detect*() alone does not take it."""
+        self._tr_next = _bind_tracks(self, self.ctx.lib.dvo_knn_stream_set_tracks, tr)
 
     def _lm_fits(self, pairs: int):
         if self._lm_next is not None and self._lm_next.n_pairs < pairs:
@@ -659,7 +744,8 @@ class KnnFrameStream:
     def _lm_taken(self):
         """The tensors of the Landmarks the call just made took (to keep alive with its records)."""
         lm, self._lm_next = self._lm_next, None
-        return () if lm is None else (lm.entries, lm.counts)
+        tr, self._tr_next = self._tr_next, None
+        return (() if lm is None else (lm.entries, lm.counts)) + (() if tr is None else (tr.links, tr.scales))
 
     def set_detect_group(self, group: int):
         """SIFT frames per detection launch from the next process() on (0: frame by frame).  Waits

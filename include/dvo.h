@@ -1002,6 +1002,67 @@ int dvo_stream_set_landmarks(dvo_stream* s, dvo_landmark* d_out, int32_t* d_coun
  * consume the binding. */
 int dvo_knn_stream_set_landmarks(dvo_knn_stream* s, dvo_landmark* d_out, int32_t* d_count, int cap);
 
+/* ---------------------------------------------------------------------------
+ * Tracks: the landmarks of consecutive pairs of one batch joined on the keypoint they
+ * share, and the ratio of the two baselines from the shared points.  An opt-in companion
+ * of a landmark binding.  The reference has metric scale only where a STag marker is
+ * seen (v3:263-291, 319-325); the ratios carry it through the pairs in between.
+ *
+ * Pair p has a full landmark list in ascending match order: the list count[p] counts,
+ * not the cap-limited slots.  A landmark's ORDINAL is its position in that list; below
+ * cap it is also its slot.  Frame j is detected once, so pair p - 1's trainIdx and pair
+ * p's queryIdx index the same keypoint array.
+ *
+ * Link.  Landmark o of pair p >= 1 with match (q, t) links to the ordinal of the landmark
+ * of pair p - 1 whose match has trainIdx == q; the smallest such ordinal if several
+ * qualify (the ratio-test modes can keep a train index for several queries).  -1 if
+ * none does, if p == 0, or if either pair has no landmarks.  A link may be >= cap when
+ * pair p - 1 overflowed the caller's landmark buffer: that is valid and says so.
+ *
+ * Ratio.  A linked landmark at Xb = (Xb, Yb, Zb) in pair p and Xa = (X, Y, Z) in pair
+ * p - 1, with R, t of pair p - 1's record, has ratio |R Xa + t| / |Xb|: baseline p over
+ * baseline p - 1, so a metric baseline length s obeys s[p] = ratio * s[p - 1].  In double,
+ * every operation rounded once, in this order:
+ *   y_i   = ((R[i][0] * X + R[i][1] * Y) + R[i][2] * Z) + t[i]
+ *   num   = sqrt((y0 * y0 + y1 * y1) + y2 * y2)
+ *   den   = sqrt((Xb * Xb + Yb * Yb) + Zb * Zb)
+ *   ratio = num / den
+ * Both depths lie in (0, dist_thresh) by recoverPose's tests, so it is finite and positive.
+ *
+ * Per pair.  n_common is the number of linked landmarks and r[0..n) their ratios in
+ * ascending order: ratio = r[(n - 1) / 2] (the lower median), q1 = r[(n - 1) / 4],
+ * q3 = r[3 (n - 1) / 4], integer divisions; all three 0.0 when n_common < 1.  n_common
+ * is -1 for pair 0 of a batch, which has no predecessor.  n_prev is the predecessor's
+ * full landmark count: 0 for pair 0 and where the predecessor failed.
+ * Links and statistics do not depend on cap.  The chain does not cross a batch boundary:
+ * a caller who needs it unbroken overlaps consecutive batches by one pair (two frames). */
+typedef struct {            /* 32 bytes */
+    double ratio, q1, q3;
+    int32_t n_common, n_prev;
+} dvo_track_scale;
+/* Binds device buffers for the NEXT batch only, beside the landmark binding pending for that
+ * batch: d_link [pairs][cap] with that binding's cap, written for slots [0, min(count, cap))
+ * (bytes outside them are not touched), and d_scale [pairs].  Either may be NULL (links only,
+ * scales only); both NULL clears a pending tracks binding, as clearing the landmark binding
+ * does.  DVO_EINVAL when no landmark binding is pending.  The binding travels with the batch
+ * as the landmark binding does and is written when the batch retires, after the landmarks,
+ * on the stream's HIP stream with no read-back.  dvo_stream_process_pairs and
+ * dvo_stream_submit_pairs build pairs that share no frame: such a call with a tracks binding
+ * pending returns DVO_EINVAL and consumes both bindings.
+ * The first tracks binding allocates the scratch, once, for every pair set the stream can
+ * hold (dvo_pipeline_depth()): per set and per slot of its point buffer 4 B of keypoint table
+ * ([pairs][kp_cap] int32), 8 B of ratios ([pairs][pts_stride] double) and 8 B for the set's
+ * own copy of (queryIdx, trainIdx), 20 B in all, and 4 B per 256 slots.  The copy is taken
+ * right after matching, only for batches that carry a tracks binding: the stream's match
+ * indices belong to the stream, and under pipelined submits a later batch has overwritten
+ * them when an earlier one retires.  A stream that never binds tracks launches and holds
+ * what it did before, and a landmarks-only batch writes what it wrote. */
+int dvo_stream_set_tracks(dvo_stream* s, int32_t* d_link, dvo_track_scale* d_scale);
+/* The same for a k-NN stream, whose one pair set retires inside the call and reads its
+ * dvo_dmatch array directly: 12 B of scratch per slot and 4 B per 256 slots.  A detect call
+ * alone consumes nothing. */
+int dvo_knn_stream_set_tracks(dvo_knn_stream* s, int32_t* d_link, dvo_track_scale* d_scale);
+
 /* Test hooks: exercise one device algorithm in isolation. */
 /* KeyPointsFilter::retainBest permutation on `n` float responses (GPU emulation
  * of libstdc++ nth_element + partition); depth < 0 = libstdc++ default. */
@@ -1105,6 +1166,16 @@ int dvo_test_flann_batch(dvo_ctx* ctx, const float* desc, const int32_t* counts,
 int dvo_test_landmarks(dvo_ctx* ctx, const float* pts, const int32_t* m, int pairs, int stride, const double* K,
                        double prob, double threshold, int max_iters, double dist_thresh, int cap, dvo_landmark* out,
                        int32_t* count, dvo_pair_record* rec);
+/* The three track kernels the streams launch (dvo_stream_set_tracks), on host arrays so that the
+ * sizes can be set exactly: lm [pairs][cap] the FULL landmark lists (count[p] <= cap; only match,
+ * X, Y, Z are read; match ascending and below m[p]), mq / mt [pairs][stride] the match indices
+ * (m[p] <= stride of them, each in [0, kp_cap)), rec [pairs] the records (R and t are read).  The
+ * lists are laid out tile by tile as the landmark kernels leave them (landmark i / 256 of the
+ * match index).  link [pairs][cap_out] is copied up whole before the run and back whole after
+ * it; cap_out may be below the counts.  scale [pairs]. */
+int dvo_test_tracks(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* count, const int32_t* mq, const int32_t* mt,
+                    const int32_t* m, const dvo_pair_record* rec, int pairs, int cap, int stride, int kp_cap,
+                    int cap_out, int32_t* link, dvo_track_scale* scale);
 
 #ifdef __cplusplus
 }
