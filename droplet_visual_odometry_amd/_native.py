@@ -52,6 +52,11 @@ assert LANDMARK_DTYPE.itemsize == 48
 # dvo_track_scale: a pair's baseline ratio to its predecessor from their shared landmarks (dvo_stream_set_tracks)
 TRACK_SCALE_DTYPE = np.dtype([("ratio", "<f8"), ("q1", "<f8"), ("q3", "<f8"), ("n_common", "<i4"), ("n_prev", "<i4")])
 assert TRACK_SCALE_DTYPE.itemsize == 32
+# dvo_track_pose: a pair's pose refined on the previous pair's landmarks (dvo_stream_set_track_poses)
+TRACK_POSE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("scale", "<f8"), ("rms", "<f8"),
+                             ("n_used", "<i4"), ("n_inliers", "<i4"), ("iters", "<i4"), ("status", "<i4")])
+assert TRACK_POSE_DTYPE.itemsize == 128
+TRACK_POSE_OK, TRACK_POSE_NONE, TRACK_POSE_DEGENERATE = 0, 1, 2
 
 
 class DVOError(RuntimeError):
@@ -179,6 +184,10 @@ _SIGNATURES = {
     "dvo_stream_set_tracks": ([_vp, _vp, _vp], _c),
     "dvo_knn_stream_set_tracks": ([_vp, _vp, _vp], _c),
     "dvo_test_tracks": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c, _c, _c, _c, _c, _vp, _vp], _c),
+    "dvo_stream_set_track_poses": ([_vp, _vp, _c, _d, _d, _c], _c),
+    "dvo_knn_stream_set_track_poses": ([_vp, _vp, _c, _d, _d, _c], _c),
+    "dvo_test_track_poses": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c, _c, _c, _c, _c, _vp, _c, _d, _d, _c, _vp, _vp,
+                              _vp], _c),
     "dvo_knn_pair_create": ([_vp, ctypes.POINTER(KnnPairConfig), ctypes.POINTER(_vp)], _c),
     "dvo_knn_pair_destroy": ([_vp], None),
     "dvo_knn_pair_run": ([_vp, _vp, _vp, _c, _c, ctypes.POINTER(ctypes.c_uint64), _vp], _c),

@@ -94,6 +94,34 @@ struct TracksBinding {
     explicit operator bool() const { return link || scale; }
 };
 
+// The caller's buffer and parameters of a pose binding (dvo_stream_set_track_poses), beside a tracks binding.
+struct TrackPoseBinding {
+    dvo_track_pose* out = nullptr;  // [pairs]; null: no binding
+    int iters = 0, min_points = 0;
+    double huber_px = 0, inlier_px = 0;
+    // the pose fields of a retiring set's TrackArgs, from the set's GeomArgs and its part of the scratch
+    void fill(TrackArgs& a, const GeomArgs& g, TrackCorr* corr) const {
+        a.pose = out;
+        a.pts_f = g.pts_f;
+        a.fx = g.fx, a.fy = g.fy, a.cx = g.cx, a.cy = g.cy;
+        a.corr = corr;
+        a.pose_iters = iters;
+        a.pose_min_points = min_points;
+        a.huber_px = huber_px;
+        a.inlier_px = inlier_px;
+    }
+};
+
+// The parameters of a pose binding with the defaults filled in; false: out of range.
+inline bool track_pose_params(TrackPoseBinding& b, int iters, double huber_px, double inlier_px, int min_points) {
+    if (std::isnan(huber_px) || std::isnan(inlier_px)) return false;
+    b.iters = iters > 0 ? iters : 10;
+    b.huber_px = huber_px > 0 ? huber_px : 1.0;
+    b.inlier_px = inlier_px > 0 ? inlier_px : 2.0;
+    b.min_points = min_points > 0 ? min_points : 6;
+    return b.iters <= kTrackPoseMaxIters && b.min_points >= 3;
+}
+
 struct dvo_stream {
     dvo_ctx* ctx = nullptr;
     dvo_stream_config cfg{};
@@ -133,9 +161,11 @@ struct dvo_stream {
         dvo_pair_record* rec = nullptr;  // the caller's records of the batch
         LandmarkBinding lm;              // the batch's landmark binding, written when the set retires
         TracksBinding tr;                // its tracks binding (the set's index copy was taken at the match)
+        TrackPoseBinding tp;             // its pose binding
     };
     LandmarkBinding lm_next;  // dvo_stream_set_landmarks: taken by the next batch
     TracksBinding tr_next;    // dvo_stream_set_tracks: taken with it
+    TrackPoseBinding tp_next;  // dvo_stream_set_track_poses: taken with them
     PairSet sets[kMaxSets];
     // their arrays: 1 set until the first submit, then kRansacRounds; pairs.all.g is the stream's GeomArgs
     PairSets pairs;
@@ -560,6 +590,7 @@ int retire_sets(dvo_stream* s) {
             a.link = st.tr.link;
             a.cap = st.lm.cap;
             a.scale = st.tr.scale;
+            if (st.tp.out) st.tp.fill(a, v.g, s->pairs.tr.corr + off);
             HIP_TRY(launch_tracks(a, st.pairs, s->hs));
         }
         s->retired_rec[s->retired] = st.rec;
@@ -588,7 +619,8 @@ int run_stream(dvo_stream* s, const uint8_t* d_frames, int n, int64_t fstride, i
     // a landmark binding is for this batch alone, whether or not the call gets as far as its pairs
     const LandmarkBinding lm = detect_only ? LandmarkBinding{} : std::exchange(s->lm_next, LandmarkBinding{});
     const TracksBinding tr = detect_only ? TracksBinding{} : std::exchange(s->tr_next, TracksBinding{});
-    if (tr && pair_step != 1)  // both bindings are consumed
+    const TrackPoseBinding tp = detect_only ? TrackPoseBinding{} : std::exchange(s->tp_next, TrackPoseBinding{});
+    if (tr && pair_step != 1)  // every binding is consumed
         return fail(ctx, DVO_EINVAL, "tracks need consecutive pairs: the pairs of a *_pairs call share no frame");
     const int want = drain ? 1 : kRansacRounds;
     if (!detect_only && s->pairs.nsets < want) {
@@ -641,7 +673,7 @@ int run_stream(dvo_stream* s, const uint8_t* d_frames, int n, int64_t fstride, i
             HIP_TRY(hipMemcpyAsync(s->pairs.tr.it + off, s->buf.mt, nb, hipMemcpyDeviceToDevice, s->hs));
         }
         HIP_TRY(launch_geometry_args(s->pairs.view(k).g, pairs, kStageNormalize, s->hs));
-        s->sets[k] = dvo_stream::PairSet{true, 0, pairs, d_rec, lm, tr};
+        s->sets[k] = dvo_stream::PairSet{true, 0, pairs, d_rec, lm, tr, tp};
         s->last_set = k;
         // nsets >= 1 here: every path that matches has passed ensure_sets above
         s->next_set = (k + 1) % s->pairs.nsets;
@@ -1092,6 +1124,7 @@ int dvo_stream_set_landmarks(dvo_stream* s, dvo_landmark* d_out, int32_t* d_coun
     if (!d_out) {
         s->lm_next = LandmarkBinding{};
         s->tr_next = TracksBinding{};
+        s->tp_next = TrackPoseBinding{};
         return DVO_OK;
     }
     if (cap < 1 || !d_count) return fail(ctx, DVO_EINVAL, "landmarks need cap >= 1 and a count buffer");
@@ -1104,6 +1137,7 @@ int dvo_stream_set_landmarks(dvo_stream* s, dvo_landmark* d_out, int32_t* d_coun
 int dvo_stream_set_tracks(dvo_stream* s, int32_t* d_link, dvo_track_scale* d_scale) {
     if (!s) return DVO_EINVAL;
     dvo_ctx* ctx = s->ctx;
+    s->tp_next = TrackPoseBinding{};  // a pose binding goes after the tracks binding it reads
     if (!d_link && !d_scale) {
         s->tr_next = TracksBinding{};
         return DVO_OK;
@@ -1113,6 +1147,26 @@ int dvo_stream_set_tracks(dvo_stream* s, int32_t* d_link, dvo_track_scale* d_sca
     // the first binding sizes the scratch, for every set a pipelined stream will hold
     HIP_TRY(s->pairs.ensure_tracks(kRansacRounds, s->cfg.max_frames, s->plan.kp_cap, true));
     s->tr_next = TracksBinding{d_link, d_scale};
+    return DVO_OK;
+}
+
+int dvo_stream_set_track_poses(dvo_stream* s, dvo_track_pose* d_pose, int iters, double huber_px, double inlier_px,
+                               int min_points) {
+    if (!s) return DVO_EINVAL;
+    dvo_ctx* ctx = s->ctx;
+    if (!d_pose) {
+        s->tp_next = TrackPoseBinding{};
+        return DVO_OK;
+    }
+    if (!s->lm_next.out || !s->tr_next.scale)
+        return fail(ctx, DVO_EINVAL, "track poses go with a pending tracks binding that has a scale buffer");
+    TrackPoseBinding b;
+    if (!track_pose_params(b, iters, huber_px, inlier_px, min_points))
+        return fail(ctx, DVO_EINVAL, "track poses: iters <= 32, min_points >= 3, no NaN");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(s->pairs.ensure_track_poses(s->cfg.max_frames, s->plan.kp_cap));  // the first binding sizes the scratch
+    b.out = d_pose;
+    s->tp_next = b;
     return DVO_OK;
 }
 
@@ -2763,6 +2817,7 @@ struct dvo_knn_stream {
     int raw_pitch = 0;
     LandmarkBinding lm_next;  // dvo_knn_stream_set_landmarks: taken by the next finish
     TracksBinding tr_next;    // dvo_knn_stream_set_tracks: taken with it
+    TrackPoseBinding tp_next;  // dvo_knn_stream_set_track_poses: taken with them
     // A raw-input call records ev_in[k] before its input launch, k the one the last accepted call
     // does not use (first_ev; -1: that call began at ev[0]), so a refused call disturbs no figure.
     hipEvent_t ev_in[2] = {nullptr, nullptr};
@@ -2944,6 +2999,7 @@ int dvo_knn_stream_finish(dvo_knn_stream* st, dvo_pair_record* d_records, const 
     st->pending = 0;
     const LandmarkBinding lm = std::exchange(st->lm_next, LandmarkBinding{});  // for this batch alone
     const TracksBinding tr = std::exchange(st->tr_next, TracksBinding{});
+    const TrackPoseBinding tp = std::exchange(st->tp_next, TrackPoseBinding{});
     const int pairs = n_frames - 1;
     const PairArrays& v = st->pairs.all;
     const bool flann = st->fl.trees > 0;
@@ -2968,6 +3024,7 @@ int dvo_knn_stream_finish(dvo_knn_stream* st, dvo_pair_record* d_records, const 
             a.link = tr.link;
             a.cap = lm.cap;
             a.scale = tr.scale;
+            if (tp.out) tp.fill(a, v.g, st->pairs.tr.corr);
             HIP_TRY(launch_tracks(a, pairs, s));
         }
     }
@@ -2986,6 +3043,7 @@ int dvo_knn_stream_set_landmarks(dvo_knn_stream* s, dvo_landmark* d_out, int32_t
     if (!d_out) {
         s->lm_next = LandmarkBinding{};
         s->tr_next = TracksBinding{};
+        s->tp_next = TrackPoseBinding{};
         return DVO_OK;
     }
     if (cap < 1 || !d_count) return fail(ctx, DVO_EINVAL, "landmarks need cap >= 1 and a count buffer");
@@ -2998,6 +3056,7 @@ int dvo_knn_stream_set_landmarks(dvo_knn_stream* s, dvo_landmark* d_out, int32_t
 int dvo_knn_stream_set_tracks(dvo_knn_stream* s, int32_t* d_link, dvo_track_scale* d_scale) {
     if (!s) return DVO_EINVAL;
     dvo_ctx* ctx = s->ctx;
+    s->tp_next = TrackPoseBinding{};  // a pose binding goes after the tracks binding it reads
     if (!d_link && !d_scale) {
         s->tr_next = TracksBinding{};
         return DVO_OK;
@@ -3006,6 +3065,26 @@ int dvo_knn_stream_set_tracks(dvo_knn_stream* s, int32_t* d_link, dvo_track_scal
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(s->pairs.ensure_tracks(1, s->b.F - 1, s->b.cap, false));  // the first binding sizes the scratch
     s->tr_next = TracksBinding{d_link, d_scale};
+    return DVO_OK;
+}
+
+int dvo_knn_stream_set_track_poses(dvo_knn_stream* s, dvo_track_pose* d_pose, int iters, double huber_px,
+                                   double inlier_px, int min_points) {
+    if (!s) return DVO_EINVAL;
+    dvo_ctx* ctx = s->ctx;
+    if (!d_pose) {
+        s->tp_next = TrackPoseBinding{};
+        return DVO_OK;
+    }
+    if (!s->lm_next.out || !s->tr_next.scale)
+        return fail(ctx, DVO_EINVAL, "track poses go with a pending tracks binding that has a scale buffer");
+    TrackPoseBinding b;
+    if (!track_pose_params(b, iters, huber_px, inlier_px, min_points))
+        return fail(ctx, DVO_EINVAL, "track poses: iters <= 32, min_points >= 3, no NaN");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(s->pairs.ensure_track_poses(s->b.F - 1, s->b.cap));  // the first binding sizes the scratch
+    b.out = d_pose;
+    s->tp_next = b;
     return DVO_OK;
 }
 
@@ -3707,9 +3786,11 @@ int dvo_test_landmarks(dvo_ctx* ctx, const float* pts, const int32_t* m, int pai
     return DVO_OK;
 }
 
-int dvo_test_tracks(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* count, const int32_t* mq, const int32_t* mt,
-                    const int32_t* m, const dvo_pair_record* rec, int pairs, int cap, int stride, int kp_cap,
-                    int cap_out, int32_t* link, dvo_track_scale* scale) {
+// dvo_test_tracks, and with tp (a binding without its buffer), K and pose dvo_test_track_poses
+static int test_tracks_run(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* count, const int32_t* mq,
+                           const int32_t* mt, const int32_t* m, const dvo_pair_record* rec, int pairs, int cap, int stride,
+                           int kp_cap, int cap_out, int32_t* link, dvo_track_scale* scale, const double* K,
+                           const TrackPoseBinding* tp, dvo_track_pose* pose) {
     if (!ctx || !lm || !count || !mq || !mt || !m || !rec || !link || !scale) return DVO_EINVAL;
     if (pairs < 1 || pairs > 65535 || cap < 1 || stride < 1 || kp_cap < 1 || cap_out < 1)
         return fail(ctx, DVO_EINVAL, "bad pair count, cap, stride, kp_cap or cap_out");
@@ -3732,6 +3813,16 @@ int dvo_test_tracks(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* count, 
             tmp[t * kLandmarkTile + tcnt[t]++] = LandmarkTmp{e.X, e.Y, e.Z, e.match, 0};
         }
     }
+    std::vector<float> pts;  // the point buffer the pose binding reads: each landmark's x2, y2 at its match
+    if (tp) {
+        pts.assign(P * stride * 4, 0.f);
+        for (int p = 0; p < pairs; ++p)
+            for (int o = 0; o < count[p]; ++o) {
+                const dvo_landmark& e = lm[(size_t)p * cap + o];
+                float* q = &pts[((size_t)p * stride + e.match) * 4];
+                q[0] = e.x1, q[1] = e.y1, q[2] = e.x2, q[3] = e.y2;
+            }
+    }
     HIP_TRY(hipSetDevice(ctx->device));
     CallMem mem(ctx->call, ctx->stream);
     TrackArgs a{};
@@ -3745,6 +3836,9 @@ int dvo_test_tracks(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* count, 
     a.lcnt = mem.dev<int32_t>(P * tiles);
     a.link = mem.dev<int32_t>(P * cap_out);
     a.scale = mem.dev<dvo_track_scale>(P);
+    float* dpts = tp ? mem.dev<float>(pts.size()) : nullptr;
+    TrackCorr* dcorr = tp ? mem.dev<TrackCorr>(P * stride) : nullptr;
+    dvo_track_pose* dpose = tp ? mem.dev<dvo_track_pose>(P) : nullptr;
     HIP_TRY(mem.error());
     a.L.tmp = dtmp;
     a.L.tcnt = dtcnt;
@@ -3763,14 +3857,43 @@ int dvo_test_tracks(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* count, 
     HIP_TRY(mem.put(dt, mt, P * stride * 4));
     HIP_TRY(mem.put(drec, rec, P * sizeof(dvo_pair_record)));
     HIP_TRY(mem.put(a.link, link, P * cap_out * 4));
+    if (tp) {
+        GeomArgs g{};
+        g.pts_f = dpts;
+        set_camera(g, K);
+        TrackPoseBinding b = *tp;
+        b.out = dpose;
+        b.fill(a, g, dcorr);
+        HIP_TRY(mem.put(dpts, pts.data(), pts.size() * sizeof(float)));
+    }
     HIP_TRY(launch_tracks(a, pairs, ctx->stream));
-    uint8_t *hlink, *hscale;
+    uint8_t *hlink, *hscale, *hpose = nullptr;
     HIP_TRY(mem.get(a.link, P * cap_out * 4, &hlink));
     HIP_TRY(mem.get(a.scale, P * sizeof(dvo_track_scale), &hscale));
+    if (tp) HIP_TRY(mem.get(dpose, P * sizeof(dvo_track_pose), &hpose));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     std::memcpy(link, hlink, P * cap_out * 4);
     std::memcpy(scale, hscale, P * sizeof(dvo_track_scale));
+    if (tp) std::memcpy(pose, hpose, P * sizeof(dvo_track_pose));
     return DVO_OK;
+}
+
+int dvo_test_tracks(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* count, const int32_t* mq, const int32_t* mt,
+                    const int32_t* m, const dvo_pair_record* rec, int pairs, int cap, int stride, int kp_cap,
+                    int cap_out, int32_t* link, dvo_track_scale* scale) {
+    return test_tracks_run(ctx, lm, count, mq, mt, m, rec, pairs, cap, stride, kp_cap, cap_out, link, scale, nullptr,
+                           nullptr, nullptr);
+}
+
+int dvo_test_track_poses(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* count, const int32_t* mq,
+                         const int32_t* mt, const int32_t* m, const dvo_pair_record* rec, int pairs, int cap, int stride,
+                         int kp_cap, int cap_out, const double* K, int iters, double huber_px, double inlier_px,
+                         int min_points, int32_t* link, dvo_track_scale* scale, dvo_track_pose* pose) {
+    if (!ctx || !K || !pose) return DVO_EINVAL;
+    TrackPoseBinding b;
+    if (!track_pose_params(b, iters, huber_px, inlier_px, min_points))
+        return fail(ctx, DVO_EINVAL, "track poses: iters <= 32, min_points >= 3, no NaN");
+    return test_tracks_run(ctx, lm, count, mq, mt, m, rec, pairs, cap, stride, kp_cap, cap_out, link, scale, K, &b, pose);
 }
 
 int dvo_test_five_point(dvo_ctx* ctx, const double* q1, const double* q2, double* models, int* n) {

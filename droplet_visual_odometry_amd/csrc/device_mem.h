@@ -199,7 +199,24 @@ struct PairSets {
         tr_sets = sets;
         return hipSuccess;
     }
-    // Set k's part of it: the kernels' arguments but for the indices, the records and the caller's buffers.
+    // The pose kernel's correspondences (dvo_stream_set_track_poses): 40 B per slot beside the
+    // ratios, for the sets the track scratch was sized for.  Allocated by the first pose binding
+    // (after the track scratch: a pose binding needs a pending tracks binding) and never regrown.
+    DeviceAllocs tp_mem;
+    hipError_t ensure_track_poses(int F_, int cap_) {
+        if (tr.corr) return hipSuccess;
+        if (!tr.table) return hipErrorInvalidValue;
+        const size_t n = (size_t)tr_sets * (F_ > 0 ? F_ : 1) * cap_;
+        DeviceAllocs fresh;
+        TrackCorr* c = nullptr;
+        const hipError_t e = fresh.alloc(&c, n * sizeof(TrackCorr) + 256);
+        if (e != hipSuccess) return e;
+        tp_mem = std::move(fresh);
+        tr.corr = c;
+        return hipSuccess;
+    }
+    // Set k's part of it: the kernels' arguments but for the indices, the records and the caller's buffers
+    // (and a pose binding's fields: TrackPoseBinding::fill in api.cpp).
     TrackArgs track_args(int k, int F_, int cap_) const {
         const size_t P = (size_t)k * (F_ > 0 ? F_ : 1), n = P * cap_;
         TrackArgs a{};

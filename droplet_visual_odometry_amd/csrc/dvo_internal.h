@@ -402,12 +402,23 @@ hipError_t launch_landmarks(const GeomArgs& g_set, int pairs, const dvo_pair_rec
 // fields of a dvo_dmatch array (step 4).  Only table rows [0, pairs) are preset.
 constexpr int32_t kTrackEmpty = 0x7f7f7f7f;  // a table cell no landmark reached (the memset byte 0x7f)
 constexpr int kTrackLds = 2048;              // ratios of a pair the select kernel keeps in LDS
+// Track poses (dvo_stream_set_track_poses): with TrackArgs::pose set, the link kernel also writes a
+// linked landmark's 3-D to 2-D correspondence (the header's Y, nu, nv) at the slot its ratio goes
+// to, and after the select kernel the pose kernel (a workgroup per pair) moves the tiles'
+// correspondences together, runs the header's Gauss-Newton steps on them from the record's R and
+// ratio * t, and writes the caller's dvo_track_pose.
+constexpr int kTrackPoseLds = 1024;  // correspondences of a pair the pose kernel keeps in LDS (40 KB)
+constexpr int kTrackPoseMaxIters = 32;
+struct TrackCorr {  // 40 B
+    double y[3], nu, nv;
+};
 struct TrackScratch {
     int32_t* table = nullptr;  // [sets][pairs][kp_cap] smallest landmark ordinal per trainIdx
     double* ratio = nullptr;   // [sets][pairs][pts_stride] a tile's linked ratios from its first ordinal on
     int32_t* lcnt = nullptr;   // [sets][pairs][tiles] linked landmarks per tile
     int32_t* iq = nullptr;     // [sets][pairs][pts_stride] the ORB stream's copy of queryIdx, trainIdx
     int32_t* it = nullptr;
+    TrackCorr* corr = nullptr;  // [sets][pairs][pts_stride] a tile's correspondences, as ratio (first pose binding)
 };
 struct TrackArgs {
     LandmarkScratch L;  // the set's full landmark lists
@@ -424,6 +435,13 @@ struct TrackArgs {
     int32_t* link;  // the caller's [pairs][cap], or null
     int cap;
     dvo_track_scale* scale;  // the caller's [pairs], or null
+    // track poses; all unused while pose is null
+    dvo_track_pose* pose;  // the caller's [pairs], or null (needs scale)
+    const float* pts_f;    // [pairs][pts_stride][4] the set's pixel coordinates (x2, y2 are read)
+    double fx, fy, cx, cy;
+    TrackCorr* corr;  // [pairs][pts_stride]
+    int pose_iters, pose_min_points;  // 1..kTrackPoseMaxIters, >= 3
+    double huber_px, inlier_px;       // > 0
 };
 hipError_t launch_tracks(const TrackArgs& a, int pairs, hipStream_t s);
 // five-point record blocks a merged round can need (sizes the stream's GeomArgs::fprec, dk_list)

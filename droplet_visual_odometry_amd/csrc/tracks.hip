@@ -14,7 +14,14 @@
 //   track_select_kernel  a workgroup per pair: the tiles' ratios moved together, then an exact
 //                        radix select on their 64-bit patterns (positive doubles order as
 //                        unsigned integers), most significant byte first, for the three ranks.
-// The ratio's arithmetic is the header's, one rounding per operation (-ffp-contract=off).
+// With a pose binding (dvo.h dvo_stream_set_track_poses) the link kernel also writes each linked
+// landmark's 3-D to 2-D correspondence beside its ratio, and a fourth kernel follows:
+//   track_pose_kernel    a workgroup per pair: the tiles' correspondences moved together, then
+//                        the header's Gauss-Newton steps from the record's R and ratio * t: 27
+//                        sums per step (lane sums, shuffles inside a wave, the four wave totals
+//                        through LDS), the 6 x 6 LDL^T solve and the Cayley update on lane 0, the
+//                        new pose and a stop flag broadcast through LDS; then the final pass.
+// The arithmetic is the header's, one rounding per operation (-ffp-contract=off).
 #include "dvo_internal.h"
 
 namespace dvo {
@@ -45,6 +52,7 @@ __global__ __launch_bounds__(kLandmarkTile) void track_link_kernel(TrackArgs a) 
     for (int t = 0; t < tile; ++t) first += tc[t];
     bool linked = false;
     double ratio = 0;
+    TrackCorr corr;
     if (tid < tc[tile]) {
         const LandmarkTmp b = track_entry(a, p, tile, tid);
         int lk = -1;
@@ -70,6 +78,15 @@ __global__ __launch_bounds__(kLandmarkTile) void track_link_kernel(TrackArgs a) 
             const double den = sqrt((b.X * b.X + b.Y * b.Y) + b.Z * b.Z);
             ratio = num / den;
             linked = true;
+            if (a.corr) {  // the pose kernel's correspondence: y and the landmark's x2, y2 as normalize_kernel has them
+                const double ax = 1. / a.fx, ay = 1. / a.fy, bx = -a.cx * ax, by = -a.cy * ay;
+                const float* px = a.pts_f + ((int64_t)p * a.pts_stride + b.match) * 4;
+                const double x2 = px[2], y2 = px[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) corr.y[k] = y[k];
+                corr.nu = x2 * ax + bx;
+                corr.nv = y2 * ay + by;
+            }
         }
         const int o = first + tid;
         if (a.link && o < a.cap) a.link[(int64_t)p * a.cap + o] = lk;
@@ -87,6 +104,7 @@ __global__ __launch_bounds__(kLandmarkTile) void track_link_kernel(TrackArgs a) 
     }
     // first + before + rank < first + tc[tile] <= the pair's landmarks <= pts_stride
     if (linked) a.ratio[(int64_t)p * a.pts_stride + first + before + rank] = ratio;
+    if (linked && a.corr) a.corr[(int64_t)p * a.pts_stride + first + before + rank] = corr;
     if (tid == 0) a.lcnt[(int64_t)p * a.tiles + tile] = total;
 }
 
@@ -175,6 +193,256 @@ __global__ __launch_bounds__(kSelNT) void track_select_kernel(TrackArgs a) {
     }
 }
 
+// ---- track poses (dvo.h dvo_stream_set_track_poses) ----------------------------------------------
+constexpr int kPoseNT = 256;    // the header's 256 lanes
+constexpr int kPoseTerms = 27;  // 21 of H's upper triangle, 6 of g
+
+// step 2 of the header's sum order: lane 0 ends with the wave's total (the lanes at and above s
+// add what the tree never reads)
+__device__ __forceinline__ double pose_wave_sum(double v) {
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) v = v + __shfl_down(v, s);
+    return v;
+}
+
+// H d = -g by the header's LDL^T, S the 27 sums; false: a pivot not > 0 or a non-finite d
+__device__ bool pose_solve(const double* S, double* d) {
+    double H[6][6], L[6][6], D[6], z[6];
+    {
+        int q = 0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = i; j < 6; ++j) H[i][j] = S[q++];
+    }
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        double dj = H[j][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) dj = dj - (L[j][k] * L[j][k]) * D[k];
+        if (!(dj > 0)) return false;
+        D[j] = dj;
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double x = H[j][i];
+#pragma unroll
+            for (int k = 0; k < j; ++k) x = x - (L[i][k] * L[j][k]) * D[k];
+            L[i][j] = x / dj;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double x = -S[21 + i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) x = x - L[i][k] * z[k];
+        z[i] = x;
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) z[i] = z[i] / D[i];
+    bool finite = true;
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        double x = z[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; ++k) x = x - L[k][i] * d[k];
+        d[i] = x;
+        finite = finite && isfinite(x);
+    }
+    return finite;
+}
+
+// R <- C R, t <- C t + d[3..6) with C the Cayley map of d[0..3) / 2, into o[12] (R row by row, then t)
+__device__ void pose_update(const double* R, const double* t, const double* d, double* o) {
+    const double vx = d[0] * 0.5, vy = d[1] * 0.5, vz = d[2] * 0.5;
+    const double vv = (vx * vx + vy * vy) + vz * vz, den = 1 + vv;
+    const double C[3][3] = {
+        {((1 - vv) + 2 * (vx * vx)) / den, (2 * (vx * vy) - 2 * vz) / den, (2 * (vx * vz) + 2 * vy) / den},
+        {(2 * (vx * vy) + 2 * vz) / den, ((1 - vv) + 2 * (vy * vy)) / den, (2 * (vy * vz) - 2 * vx) / den},
+        {(2 * (vx * vz) - 2 * vy) / den, (2 * (vy * vz) + 2 * vx) / den, ((1 - vv) + 2 * (vz * vz)) / den}};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) o[3 * i + j] = (C[i][0] * R[j] + C[i][1] * R[3 + j]) + C[i][2] * R[6 + j];
+        o[9 + i] = ((C[i][0] * t[0] + C[i][1] * t[1]) + C[i][2] * t[2]) + d[3 + i];
+    }
+}
+
+// A workgroup per pair.  Every barrier is reached by all 256 threads: a NONE pair leaves before
+// the first as a whole, and the trip counts (the tiles' lcnt, iters, the stop flag read after a
+// barrier) are the same for every thread.
+__global__ __launch_bounds__(kPoseNT) void track_pose_kernel(TrackArgs a) {
+    __shared__ double cs[5][kTrackPoseLds];  // y0, y1, y2, nu, nv of the correspondences that fit
+    __shared__ double wsum[kPoseNT / 64][kPoseTerms];
+    __shared__ int wcnt[kPoseNT / 64][2];
+    __shared__ double next[12];
+    __shared__ int stop;
+    const int p = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int32_t* tc = a.L.tcnt + (int64_t)p * a.tiles;
+    const int32_t* lc = a.lcnt + (int64_t)p * a.tiles;
+    int n = 0;
+    for (int t = 0; t < a.tiles; ++t) n += lc[t];
+    double R[9], tv[3];
+    {
+        const bool has = p >= 1 && n >= 1;  // a ratio to start from (pair 0 links nothing: n is 0 there)
+        const double ratio = has ? a.scale[p].ratio : 0.0;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) R[i] = has ? a.rec[p].R[i] : 0.0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) tv[i] = has ? ratio * a.rec[p].t[i] : 0.0;
+    }
+    dvo_track_pose o;
+    o.rms = 0;
+    o.n_used = o.n_inliers = o.iters = 0;
+    if (p == 0 || n < a.pose_min_points) {
+        if (tid == 0) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) o.R[i] = R[i];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) o.t[i] = tv[i];
+            o.scale = sqrt((tv[0] * tv[0] + tv[1] * tv[1]) + tv[2] * tv[2]);
+            o.status = DVO_TRACK_POSE_NONE;
+            a.pose[p] = o;
+        }
+        return;
+    }
+    // the tiles' correspondences together, in ordinal order, as the select kernel moves the ratios:
+    // into LDS when they fit, else down in place
+    TrackCorr* g = a.corr + (int64_t)p * a.pts_stride;
+    const bool in_lds = n <= kTrackPoseLds;
+    for (int t = 0, off = 0, first = 0; t < a.tiles; first += tc[t], ++t) {
+        const int c = lc[t];
+        if (c == 0) continue;  // the same for every thread
+        TrackCorr v;
+        if (tid < c) v = g[first + tid];
+        __syncthreads();
+        if (tid < c) {
+            if (in_lds) {
+#pragma unroll
+                for (int i = 0; i < 3; ++i) cs[i][off + tid] = v.y[i];
+                cs[3][off + tid] = v.nu;
+                cs[4][off + tid] = v.nv;
+            } else {
+                g[off + tid] = v;
+            }
+        }
+        __syncthreads();
+        off += c;
+    }
+    const double kh = a.huber_px / ((a.fx + a.fy) / 2), kh2 = kh * kh;
+    int status = DVO_TRACK_POSE_OK, it = 0;
+    for (; it < a.pose_iters; ++it) {
+        double acc[kPoseTerms];
+#pragma unroll
+        for (int q = 0; q < kPoseTerms; ++q) acc[q] = 0.0;
+        for (int k = tid; k < n; k += kPoseNT) {
+            double y0, y1, y2, nu, nv;
+            if (in_lds) {
+                y0 = cs[0][k], y1 = cs[1][k], y2 = cs[2][k], nu = cs[3][k], nv = cs[4][k];
+            } else {
+                const TrackCorr v = g[k];
+                y0 = v.y[0], y1 = v.y[1], y2 = v.y[2], nu = v.nu, nv = v.nv;
+            }
+            const double P0 = ((R[0] * y0 + R[1] * y1) + R[2] * y2) + tv[0];
+            const double P1 = ((R[3] * y0 + R[4] * y1) + R[5] * y2) + tv[1];
+            const double P2 = ((R[6] * y0 + R[7] * y1) + R[8] * y2) + tv[2];
+            const bool ok = P2 > 0;
+            const double ia = 1 / P2, u = P0 * ia, v = P1 * ia;
+            const double ru = u - nu, rv = v - nv, e2 = ru * ru + rv * rv;
+            const double w = e2 <= kh2 ? 1.0 : kh / sqrt(e2);
+            const double b = -(u * ia), c = -(v * ia);
+            const double Ju[6] = {b * P1, ia * P2 - b * P0, -(ia * P1), ia, 0.0, b};
+            const double Jv[6] = {c * P1 - ia * P2, -(c * P0), ia * P0, 0.0, ia, c};
+            int q = 0;
+#pragma unroll
+            for (int i = 0; i < 6; ++i)
+#pragma unroll
+                for (int j = i; j < 6; ++j, ++q) {
+                    const double term = w * (Ju[i] * Ju[j] + Jv[i] * Jv[j]);
+                    acc[q] = acc[q] + (ok ? term : 0.0);
+                }
+#pragma unroll
+            for (int i = 0; i < 6; ++i, ++q) {
+                const double term = w * (Ju[i] * ru + Jv[i] * rv);
+                acc[q] = acc[q] + (ok ? term : 0.0);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < kPoseTerms; ++q) {
+            const double v = pose_wave_sum(acc[q]);
+            if (lane == 0) wsum[wave][q] = v;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double S[kPoseTerms], d[6];
+#pragma unroll
+            for (int q = 0; q < kPoseTerms; ++q) S[q] = ((wsum[0][q] + wsum[1][q]) + wsum[2][q]) + wsum[3][q];
+            const bool solved = pose_solve(S, d);
+            if (solved) pose_update(R, tv, d, next);
+            stop = solved ? 0 : 1;
+        }
+        __syncthreads();
+        if (stop) {  // the same for every thread; the next write to it lies behind the next barrier
+            status = DVO_TRACK_POSE_DEGENERATE;
+            break;
+        }
+#pragma unroll
+        for (int i = 0; i < 9; ++i) R[i] = next[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) tv[i] = next[9 + i];
+    }
+    // the final pass on the last pose
+    double se = 0.0;
+    int used = 0, inl = 0;
+    const double in2 = a.inlier_px * a.inlier_px;
+    for (int k = tid; k < n; k += kPoseNT) {
+        double y0, y1, y2, nu, nv;
+        if (in_lds) {
+            y0 = cs[0][k], y1 = cs[1][k], y2 = cs[2][k], nu = cs[3][k], nv = cs[4][k];
+        } else {
+            const TrackCorr v = g[k];
+            y0 = v.y[0], y1 = v.y[1], y2 = v.y[2], nu = v.nu, nv = v.nv;
+        }
+        const double P0 = ((R[0] * y0 + R[1] * y1) + R[2] * y2) + tv[0];
+        const double P1 = ((R[3] * y0 + R[4] * y1) + R[5] * y2) + tv[1];
+        const double P2 = ((R[6] * y0 + R[7] * y1) + R[8] * y2) + tv[2];
+        const bool ok = P2 > 0;
+        const double ia = 1 / P2, u = P0 * ia, v = P1 * ia;
+        const double ex = a.fx * (u - nu), ey = a.fy * (v - nv);
+        const double e = ex * ex + ey * ey;
+        const bool in = ok && e <= in2;
+        used += ok;
+        inl += in;
+        se = se + (in ? e : 0.0);
+    }
+    se = pose_wave_sum(se);
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+        used += __shfl_down(used, s);
+        inl += __shfl_down(inl, s);
+    }
+    if (lane == 0) {  // wsum was last read before the loop's final barrier
+        wsum[wave][0] = se;
+        wcnt[wave][0] = used;
+        wcnt[wave][1] = inl;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const double sum = ((wsum[0][0] + wsum[1][0]) + wsum[2][0]) + wsum[3][0];
+        o.n_used = ((wcnt[0][0] + wcnt[1][0]) + wcnt[2][0]) + wcnt[3][0];
+        o.n_inliers = ((wcnt[0][1] + wcnt[1][1]) + wcnt[2][1]) + wcnt[3][1];
+        o.rms = o.n_inliers > 0 ? sqrt(sum / (double)o.n_inliers) : 0.0;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) o.R[i] = R[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) o.t[i] = tv[i];
+        o.scale = sqrt((tv[0] * tv[0] + tv[1] * tv[1]) + tv[2] * tv[2]);
+        o.iters = it;
+        o.status = status;
+        a.pose[p] = o;
+    }
+}
+
 }  // namespace
 
 hipError_t launch_tracks(const TrackArgs& a, int pairs, hipStream_t s) {
@@ -182,12 +450,17 @@ hipError_t launch_tracks(const TrackArgs& a, int pairs, hipStream_t s) {
     if (!a.L.tmp || !a.L.tcnt || !a.mq || !a.mt || !a.rec || !a.table || !a.ratio || !a.lcnt || a.tiles < 1 ||
         a.kp_cap < 1 || a.idx_step < 1 || (!a.link && !a.scale) || (a.link && a.cap < 1))
         return hipErrorInvalidValue;
+    if (a.pose ? !a.scale || !a.corr || !a.pts_f || a.pose_iters < 1 || a.pose_iters > kTrackPoseMaxIters ||
+                     a.pose_min_points < 3 || !(a.huber_px > 0) || !(a.inlier_px > 0)
+               : a.corr != nullptr)
+        return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(a.table, 0x7f, (size_t)pairs * a.kp_cap * sizeof(int32_t), s);
     if (e != hipSuccess) return e;
     const dim3 grid((unsigned)a.tiles, (unsigned)pairs);
     hipLaunchKernelGGL(track_table_kernel, grid, dim3(kLandmarkTile), 0, s, a);
     hipLaunchKernelGGL(track_link_kernel, grid, dim3(kLandmarkTile), 0, s, a);
     if (a.scale) hipLaunchKernelGGL(track_select_kernel, dim3((unsigned)pairs), dim3(kSelNT), 0, s, a);
+    if (a.pose) hipLaunchKernelGGL(track_pose_kernel, dim3((unsigned)pairs), dim3(kPoseNT), 0, s, a);
     return hipGetLastError();
 }
 

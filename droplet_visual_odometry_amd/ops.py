@@ -1176,6 +1176,35 @@ def test_tracks(lm, count, mq, mt, m, rec, kp_cap, cap_out=None, link=None, ctx=
     return link, scale
 
 
+def test_track_poses(lm, count, mq, mt, m, rec, kp_cap, K, iters=10, huber_px=1.0, inlier_px=2.0, min_points=6,
+                     cap_out=None, link=None, ctx=None):
+    """test_tracks with the pose kernel (stream.TrackPoses): each landmark's x2, y2 are read too, K is
+    the camera matrix and the four parameters are bind_track_poses's (zero or negative: the default).
+    Returns (link, scale TRACK_SCALE_DTYPE[P], pose TRACK_POSE_DTYPE[P])."""
+    from ._native import LANDMARK_DTYPE, TRACK_POSE_DTYPE, TRACK_SCALE_DTYPE
+    c = _ctx(ctx)
+    mq = np.ascontiguousarray(mq, np.int32)
+    mt = np.ascontiguousarray(mt, np.int32)
+    count = np.ascontiguousarray(count, np.int32)
+    m = np.ascontiguousarray(m, np.int32)
+    if (lm.dtype != LANDMARK_DTYPE or lm.ndim != 2 or not lm.flags.c_contiguous or mq.ndim != 2 or mq.shape != mt.shape
+            or not (len(lm) == len(mq) == len(count) == len(m) == len(rec))):
+        raise DVOError(-1, "lm LANDMARK_DTYPE[P, cap], mq / mt int32[P, stride], count, m and rec [P] must agree")
+    rec = np.ascontiguousarray(rec, PAIR_RECORD_DTYPE)
+    K = np.ascontiguousarray(K, np.float64).reshape(9)
+    P, cap = lm.shape
+    cap_out = cap if cap_out is None else int(cap_out)
+    link = np.full((P, cap_out), -1, np.int32) if link is None else link
+    if link.dtype != np.int32 or link.shape != (P, cap_out) or not link.flags.c_contiguous:
+        raise DVOError(-1, "link must be a contiguous int32[P, cap_out] array")
+    scale = np.zeros(P, TRACK_SCALE_DTYPE)
+    pose = np.zeros(P, TRACK_POSE_DTYPE)
+    c.check(c.lib.dvo_test_track_poses(c.h, ptr(lm), ptr(count), ptr(mq), ptr(mt), ptr(m), ptr(rec), P, cap,
+                                       mq.shape[1], int(kp_cap), cap_out, ptr(K), int(iters), float(huber_px),
+                                       float(inlier_px), int(min_points), ptr(link), ptr(scale), ptr(pose)))
+    return link, scale, pose
+
+
 def test_flann_batch(desc, counts, trees=5, checks=50, rng_state=None, levels=0, ctx=None):
     """The batched kd-forest build and search of dvo_knn_stream_process's FLANN mode
     (stream.KnnFrameStream(matcher="flann")) on host arrays: desc float32[F, cap, dim] frame slots,

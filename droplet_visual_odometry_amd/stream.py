@@ -19,8 +19,8 @@ import ctypes
 import numpy as np
 import torch
 
-from ._native import (DMATCH_DTYPE, KEYPOINT_DTYPE, LANDMARK_DTYPE, PAIR_RECORD_DTYPE, TRACK_SCALE_DTYPE, Context,
-                      StreamConfig, _vp, orb_params, ptr)
+from ._native import (DMATCH_DTYPE, KEYPOINT_DTYPE, LANDMARK_DTYPE, PAIR_RECORD_DTYPE, TRACK_POSE_DTYPE,
+                      TRACK_SCALE_DTYPE, Context, StreamConfig, _vp, orb_params, ptr)
 
 
 class Landmarks:
@@ -103,21 +103,61 @@ def _bind_tracks(stream, setter, tr):
     return tr
 
 
-def carry_scale(anchor, scales) -> np.ndarray:
+class TrackPoses:
+    """Device buffer for one batch's track poses (dvo_stream_set_track_poses), the companion of a
+    Tracks: per pair the pose of its second camera refined on the previous pair's landmarks, whose
+    translation length `scale` is the baseline ratio without the error of the pair's own t
+    direction (see include/dvo.h).  poses: uint8 [n_pairs, 128] (TRACK_POSE_DTYPE).  Bind it with
+    bind_track_poses after bind_tracks; read it after the batch has retired and the stream is
+    synchronised."""
+
+    def __init__(self, n_pairs: int, device):
+        if n_pairs < 1:
+            raise ValueError("TrackPoses needs n_pairs >= 1")
+        self.n_pairs = int(n_pairs)
+        self.poses = torch.zeros((self.n_pairs, TRACK_POSE_DTYPE.itemsize), dtype=torch.uint8, device=device)
+
+    def numpy(self) -> np.ndarray:
+        """TRACK_POSE_DTYPE [n_pairs]: R, t, scale, rms, n_used, n_inliers, iters, status per pair."""
+        return self.poses.cpu().numpy().reshape(-1).view(TRACK_POSE_DTYPE).copy()
+
+
+def _bind_track_poses(stream, setter, tp, iters, huber_px, inlier_px, min_points):
+    """The one-shot pose binding of both stream classes; returns what to keep referenced."""
+    if tp is None:
+        stream.ctx.check(setter(stream.h, None, 0, 0.0, 0.0, 0))
+        return None
+    tr = stream._tr_next
+    if tr is None:
+        raise ValueError("bind_track_poses goes after bind_tracks: poses are a companion of a pending Tracks")
+    if not isinstance(tp, TrackPoses) or tp.poses.device != stream.device:
+        raise ValueError("bind_track_poses takes a TrackPoses on the stream's device (or None)")
+    if tp.n_pairs < tr.n_pairs:
+        raise ValueError(f"the TrackPoses ({tp.n_pairs} pairs) must have the bound Tracks' pairs ({tr.n_pairs})")
+    stream._after_torch()  # the buffer's fill ran on torch's stream: order the library's writes after it
+    stream.ctx.check(setter(stream.h, tp.poses.data_ptr(), int(iters), float(huber_px), float(inlier_px),
+                            int(min_points)))
+    return tp
+
+
+def carry_scale(anchor, scales, poses=None) -> np.ndarray:
     """Metric baseline length per pair of one batch: anchor float64 [pairs] holds the marker's scale
     where a marker was seen (the pose tail) and NaN elsewhere; scales is the batch's
     TRACK_SCALE_DTYPE [pairs] (Tracks.scales_numpy).  out[p] = anchor[p] where that is not NaN, else
     out[p - 1] * ratio[p] when n_common[p] >= 1 and out[p - 1] is not NaN, else NaN.  No threshold
-    of its own: filter on n_common, q1 and q3 first (set n_common to 0 where the ratio is not trusted)."""
+    of its own: filter on n_common, q1 and q3 first (set n_common to 0 where the ratio is not trusted).
+    poses: the batch's TRACK_POSE_DTYPE [pairs] (TrackPoses.numpy), or None: a pair whose pose has
+    status 0 multiplies by poses["scale"][p] instead of the ratio."""
     anchor = np.asarray(anchor, np.float64)
-    if anchor.ndim != 1 or len(scales) != len(anchor):
-        raise ValueError("anchor float64 [pairs] and scales [pairs] must agree")
+    if anchor.ndim != 1 or len(scales) != len(anchor) or (poses is not None and len(poses) != len(anchor)):
+        raise ValueError("anchor float64 [pairs], scales [pairs] and poses [pairs] must agree")
     out = np.full(len(anchor), np.nan)
     for p in range(len(anchor)):
         if not np.isnan(anchor[p]):
             out[p] = anchor[p]
         elif p >= 1 and scales["n_common"][p] >= 1 and not np.isnan(out[p - 1]):
-            out[p] = out[p - 1] * scales["ratio"][p]
+            refined = poses is not None and poses["status"][p] == 0
+            out[p] = out[p - 1] * (poses["scale"][p] if refined else scales["ratio"][p])
     return out
 
 
@@ -161,6 +201,7 @@ class FrameStream:
         self._lm_next = None  # bind_landmarks: the Landmarks the next batch takes
         self._lm_pending = {}  # Landmarks of batches not yet retired, by their records' device address
         self._tr_next = None  # bind_tracks: the Tracks the next batch takes with its Landmarks
+        self._tp_next = None  # bind_track_poses: the TrackPoses it takes with them
         self.width, self.height, self.max_frames, self.nfeatures = width, height, max_frames, nfeatures
         self.K = K.reshape(3, 3)
         if ratio:
@@ -188,7 +229,7 @@ class FrameStream:
         after it writes nothing.  None clears a binding no batch has taken yet."""
         self._lm_next = _bind_landmarks(self, self.ctx.lib.dvo_stream_set_landmarks, lm)
         if lm is None:
-            self._tr_next = None  # the library clears a pending tracks binding with it
+            self._tr_next = self._tp_next = None  # the library clears pending tracks and pose bindings with it
 
     def bind_tracks(self, tr: Tracks | None):
         """Have the next batch also write its tracks into `tr` (dvo_stream_set_tracks), after its
@@ -196,6 +237,17 @@ class FrameStream:
         same cap.  One-shot, like the landmark binding; None clears a pending binding.  Only for
         batches of consecutive frames: process_pairs / submit_pairs raise ValueError."""
         self._tr_next = _bind_tracks(self, self.ctx.lib.dvo_stream_set_tracks, tr)
+        self._tp_next = None  # the library's call cleared a pending pose binding: bind poses last
+
+    def bind_track_poses(self, tp: TrackPoses | None, iters: int = 10, huber_px: float = 1.0, inlier_px: float = 2.0,
+                         min_points: int = 6):
+        """Have the next batch also write its track poses into `tp` (dvo_stream_set_track_poses),
+        after its tracks.  Call it after bind_tracks (ValueError otherwise).  iters: Gauss-Newton
+        steps (at most 32); huber_px, inlier_px: the Huber width and the inlier bound in pixels;
+        min_points: shared landmarks a pair needs (at least 3).  One-shot; None clears a pending
+        binding, as bind_tracks and bind_landmarks(None) do."""
+        self._tp_next = _bind_track_poses(self, self.ctx.lib.dvo_stream_set_track_poses, tp, iters, huber_px,
+                                          inlier_px, min_points)
 
     def _lm_fits(self, pairs: int, shared: bool = True):
         if self._lm_next is not None and self._lm_next.n_pairs < pairs:
@@ -450,19 +502,22 @@ class FrameStream:
         # records (the newest pending ones) until the batch retires
         lm, self._lm_next = self._lm_next, None
         tr, self._tr_next = self._tr_next, None
+        tp, self._tp_next = self._tp_next, None
         if lm is not None and self._pending:
-            self._lm_pending[next(reversed(self._pending))] = (lm, tr)
+            self._lm_pending[next(reversed(self._pending))] = (lm, tr, tp)
         out, lms = [], []
         for i in range(min(n, cap)):
             t = self._pending.pop(recs[i], None)
             if t is None:
                 raise RuntimeError("retired records that were not submitted through this FrameStream")
             out.append((t, int(pairs[i])))
-            lm, tr = self._lm_pending.pop(recs[i], (None, None))
+            lm, tr, tp = self._lm_pending.pop(recs[i], (None, None, None))
             if lm is not None:
                 lms += [lm.entries, lm.counts]
             if tr is not None:
                 lms += [tr.links, tr.scales]
+            if tp is not None:
+                lms += [tp.poses]
         if out:
             # the retire kernels (records_kernel, the landmark kernels) writing these buffers are
             # queued on the library's stream by the call that retired them: keep the tensors alive
@@ -602,7 +657,7 @@ class FrameStream:
                 self._held.clear()
             self._last = ()
             self._pending = {}
-            self._lm_next, self._lm_pending, self._tr_next = None, {}, None
+            self._lm_next, self._lm_pending, self._tr_next, self._tp_next = None, {}, None, None
 
     def __del__(self):
         try:
@@ -712,6 +767,7 @@ class KnnFrameStream:
         self._pending = 0  # frames of the last detect() (sizes finish()'s records)
         self._lm_next = None  # bind_landmarks: the Landmarks the next process() / finish() takes
         self._tr_next = None  # bind_tracks: the Tracks it takes with them
+        self._tp_next = None  # bind_track_poses: and the TrackPoses
         self.width, self.height, self.max_frames = int(width), int(height), int(max_frames)
         self.dim = 64 if cfg.detector == 1 else 128
         self.K = K.reshape(3, 3)
@@ -729,13 +785,23 @@ class KnnFrameStream:
         that batch.  One-shot: the batch after it writes nothing.  None clears a pending binding."""
         self._lm_next = _bind_landmarks(self, self.ctx.lib.dvo_knn_stream_set_landmarks, lm)
         if lm is None:
-            self._tr_next = None  # the library clears a pending tracks binding with it
+            self._tr_next = self._tp_next = None  # the library clears pending tracks and pose bindings with it
 
     def bind_tracks(self, tr: Tracks | None):
         """Have the next batch also write its tracks into `tr` (dvo_knn_stream_set_tracks), after
         its landmarks.  Call it after bind_landmarks (ValueError otherwise), with a Tracks of the
         same cap.  One-shot; None clears a pending binding; detect*() alone does not take it."""
         self._tr_next = _bind_tracks(self, self.ctx.lib.dvo_knn_stream_set_tracks, tr)
+        self._tp_next = None  # the library's call cleared a pending pose binding: bind poses last
+
+    def bind_track_poses(self, tp: TrackPoses | None, iters: int = 10, huber_px: float = 1.0, inlier_px: float = 2.0,
+                         min_points: int = 6):
+        """Have the next batch also write its track poses into `tp` (dvo_knn_stream_set_track_poses),
+        after its tracks.  Call it after bind_tracks (ValueError otherwise); the parameters are
+        FrameStream.bind_track_poses's.  One-shot; None clears a pending binding; detect*() alone
+        does not take it."""
+        self._tp_next = _bind_track_poses(self, self.ctx.lib.dvo_knn_stream_set_track_poses, tp, iters, huber_px,
+                                          inlier_px, min_points)
 
     def _lm_fits(self, pairs: int):
         if self._lm_next is not None and self._lm_next.n_pairs < pairs:
@@ -745,7 +811,9 @@ class KnnFrameStream:
         """The tensors of the Landmarks the call just made took (to keep alive with its records)."""
         lm, self._lm_next = self._lm_next, None
         tr, self._tr_next = self._tr_next, None
-        return (() if lm is None else (lm.entries, lm.counts)) + (() if tr is None else (tr.links, tr.scales))
+        tp, self._tp_next = self._tp_next, None
+        return ((() if lm is None else (lm.entries, lm.counts)) + (() if tr is None else (tr.links, tr.scales))
+                + (() if tp is None else (tp.poses,)))
 
     def set_detect_group(self, group: int):
         """SIFT frames per detection launch from the next process() on (0: frame by frame).  Waits

@@ -1063,6 +1063,99 @@ int dvo_stream_set_tracks(dvo_stream* s, int32_t* d_link, dvo_track_scale* d_sca
  * alone consumes nothing. */
 int dvo_knn_stream_set_tracks(dvo_knn_stream* s, int32_t* d_link, dvo_track_scale* d_scale);
 
+/* ---------------------------------------------------------------------------
+ * Track poses: each pair's 6-DoF pose refined on the previous pair's landmarks.  An opt-in
+ * companion of a tracks binding.  The ratio above inherits the error of each pair's t
+ * direction; here camera j + 1 of pair p (frames j, j + 1) is fitted to 3-D to 2-D
+ * correspondences that use neither pair p's triangulation nor its t, and the length of the
+ * fitted translation is the baseline ratio.
+ *
+ * Correspondences.  For pair p they are its linked landmarks in ascending ordinal, k = 0..n-1
+ * with n = n_common.  Correspondence k has
+ *   Y = (y0, y1, y2)   the y_i of the ratio above, unchanged: the point in camera j, in units
+ *                      of pair p - 1's baseline;
+ *   (nu, nv)           the landmark's float x2, y2 normalised as the stream normalises them, in
+ *                      double: nu = x2 * ax + bx, nv = y2 * ay + by with ax = 1 / fx,
+ *                      bx = -cx * ax, ay = 1 / fy, by = -cy * ay.
+ *
+ * Start.  R = rec[p].R, t_i = scale[p].ratio * rec[p].t[i].
+ *
+ * One step.  In double, every operation rounded once, in the written order.  Per k:
+ *   P_i = ((R[i][0] * y0 + R[i][1] * y1) + R[i][2] * y2) + t[i]
+ *   a correspondence with !(P2 > 0) contributes +0.0 to every sum; otherwise
+ *   a = 1 / P2, u = P0 * a, v = P1 * a, ru = u - nu, rv = v - nv, e2 = ru * ru + rv * rv
+ *   w = 1 if e2 <= kh * kh, else kh / sqrt(e2), with kh = huber_px / ((fx + fy) / 2)
+ *   b = -(u * a), c = -(v * a)
+ *   Ju = (b * P1, a * P2 - b * P0, -(a * P1), a, 0, b)
+ *   Jv = (c * P1 - a * P2, -(c * P0), a * P0, 0, a, c)
+ * (the left perturbation P <- omega x P + dt, omega first).  The 21 terms of H are
+ * w * (Ju_i * Ju_j + Jv_i * Jv_j) for i <= j, the upper triangle row by row; the 6 terms of g
+ * are w * (Ju_i * ru + Jv_i * rv).
+ *
+ * Sum order, of each of the 27 terms alone:
+ *   1. lane l of 256 adds the terms of k = l, l + 256, ... in ascending k onto +0.0;
+ *   2. inside each group of 64 lanes, for s = 32, 16, 8, 4, 2, 1, lane l < s adds lane l + s;
+ *   3. the four group totals are added as ((g0 + g1) + g2) + g3.
+ *
+ * Solve H d = -g by LDL^T without pivoting, H[i][j] for i > j being H[j][i]:
+ *   for j = 0..5:  D[j] = H[j][j], then for k = 0..j-1: D[j] = D[j] - (L[j][k] * L[j][k]) * D[k]
+ *                  the step fails unless D[j] > 0
+ *                  for i = j+1..5: x = H[j][i], then for k = 0..j-1:
+ *                                  x = x - (L[i][k] * L[j][k]) * D[k];  L[i][j] = x / D[j]
+ *   for i = 0..5:  z[i] = -g[i], then for k = 0..i-1: z[i] = z[i] - L[i][k] * z[k]
+ *   for i = 0..5:  y[i] = z[i] / D[i]
+ *   for i = 5..0:  d[i] = y[i], then for k = i+1..5: d[i] = d[i] - L[k][i] * d[k]
+ *                  the step fails unless every d[i] is finite
+ * A step that fails ends the pair with status DEGENERATE and the pose of the step before.
+ *
+ * Update by the Cayley map (no transcendental function): v = d[0..3) * 0.5,
+ * vv = (vx * vx + vy * vy) + vz * vz,
+ *   C = [ (1 - vv) + 2 (vx vx)   2 (vx vy) - 2 vz       2 (vx vz) + 2 vy     ]
+ *       [ 2 (vx vy) + 2 vz       (1 - vv) + 2 (vy vy)   2 (vy vz) - 2 vx     ]
+ *       [ 2 (vx vz) - 2 vy       2 (vy vz) + 2 vx       (1 - vv) + 2 (vz vz) ]
+ * every entry then divided by 1 + vv; R <- C R and t <- C t + d[3..6), an entry of C R or C t
+ * formed as (x0 + x1) + x2 and d[3 + i] added last.
+ *
+ * Exactly `iters` steps are taken unless one fails: there is no convergence test, so the
+ * result depends on no tolerance and the loop's length on no data.
+ *
+ * Final pass, on the last pose, with P, a, u, v, ru, rv as above:
+ *   n_used     the correspondences with P2 > 0;
+ *   inlier     P2 > 0 and e = (fx * ru) * (fx * ru) + (fy * rv) * (fy * rv) <= inlier_px * inlier_px;
+ *   n_inliers  their number;
+ *   rms        sqrt(sum of the inliers' e in the order above (others +0.0) / n_inliers), 0.0 with none;
+ *   scale      sqrt((t0 * t0 + t1 * t1) + t2 * t2).
+ *
+ * Status.  DVO_TRACK_POSE_NONE: pair 0 of a batch and every pair with n_common < min_points (a
+ * pair whose record, or whose predecessor's record, failed has n_common 0).  Such a pair holds
+ * the start values in R, t and scale (all zero where n_common < 1: there is no ratio), and 0
+ * in rms, n_used, n_inliers, iters.  DVO_TRACK_POSE_DEGENERATE: see Solve; the final pass runs
+ * on the pose it kept.  iters is the number of steps taken.  Nothing depends on the landmark
+ * cap. */
+#define DVO_TRACK_POSE_OK 0
+#define DVO_TRACK_POSE_NONE 1
+#define DVO_TRACK_POSE_DEGENERATE 2
+typedef struct {              /* 128 bytes */
+    double R[9], t[3];        /* camera j + 1 from camera j: x' = R x + t, |t| in units of pair p - 1's baseline */
+    double scale, rms;        /* |t|: baseline p over baseline p - 1; pixels */
+    int32_t n_used, n_inliers, iters, status;
+} dvo_track_pose;
+/* Binds d_pose [pairs] for the NEXT batch only, beside the tracks binding pending for it:
+ * DVO_EINVAL unless a tracks binding with a non-NULL d_scale is pending (the start reads the
+ * ratio).  iters, huber_px, inlier_px, min_points: zero or negative means the default (10,
+ * 1.0, 2.0, 6); DVO_EINVAL for iters > 32, min_points 1 or 2, or a NaN.  huber_px = INFINITY
+ * weights every correspondence 1.  d_pose == NULL clears a pending binding, as clearing the
+ * landmark binding and every dvo_stream_set_tracks call do: bind poses last.  The binding
+ * travels with the batch and is written when it retires, after the tracks; a *_pairs call
+ * refuses it as it refuses tracks.  The first binding allocates 40 B per slot of the point
+ * buffer for every pair set, once; a stream that never binds poses launches and holds what it
+ * did before, and the landmark, link and scale bytes of a batch do not depend on the binding. */
+int dvo_stream_set_track_poses(dvo_stream* s, dvo_track_pose* d_pose, int iters, double huber_px, double inlier_px,
+                               int min_points);
+/* The same for a k-NN stream. */
+int dvo_knn_stream_set_track_poses(dvo_knn_stream* s, dvo_track_pose* d_pose, int iters, double huber_px,
+                                   double inlier_px, int min_points);
+
 /* Test hooks: exercise one device algorithm in isolation. */
 /* KeyPointsFilter::retainBest permutation on `n` float responses (GPU emulation
  * of libstdc++ nth_element + partition); depth < 0 = libstdc++ default. */
@@ -1176,6 +1269,13 @@ int dvo_test_landmarks(dvo_ctx* ctx, const float* pts, const int32_t* m, int pai
 int dvo_test_tracks(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* count, const int32_t* mq, const int32_t* mt,
                     const int32_t* m, const dvo_pair_record* rec, int pairs, int cap, int stride, int kp_cap,
                     int cap_out, int32_t* link, dvo_track_scale* scale);
+/* dvo_test_tracks with the pose kernel (dvo_stream_set_track_poses): each landmark's x2, y2 are
+ * read too (the pixel position in the pair's second frame), K [9] is the camera matrix and the
+ * four parameters are the binding's, defaults included.  pose [pairs]. */
+int dvo_test_track_poses(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* count, const int32_t* mq,
+                         const int32_t* mt, const int32_t* m, const dvo_pair_record* rec, int pairs, int cap, int stride,
+                         int kp_cap, int cap_out, const double* K, int iters, double huber_px, double inlier_px,
+                         int min_points, int32_t* link, dvo_track_scale* scale, dvo_track_pose* pose);
 
 #ifdef __cplusplus
 }
