@@ -5,8 +5,12 @@
 // restated from OpenCV 4.x (calibration.cpp cvGetOptimalNewCameraMatrix /
 // icvGetRectangles, undistort.dispatch.cpp cvUndistortPointsInternal,
 // cv::undistort, initUndistortRectifyMap, imgproc/imgwarp.cpp remapBilinear with
-// the 32x32 fixed-point bilinear table).  OpenCV itself is absent here, so this
-// path is "parity unpinned": the GPU is checked bit-exact against this file.
+// the 32x32 fixed-point bilinear table).  The GPU is checked bit-exact against
+// this file, and this file against the documented model in long double
+// (tests/undistort_reference.py, tests/test_undistort_anchors.py): the map to
+// half a 1/32-pixel quantum at every pixel, the remap on a plane image, the new
+// camera matrix against a converged inverse.  OpenCV itself is absent here, so
+// what stays unpinned is its own rounding order, not the formulas.
 // Restatement choices:
 //   * initUndistortRectifyMap follows the scalar per-row loop (x advanced by
 //     repeated addition of ir[0]); OpenCV >= 4.x may take a SIMD line routine

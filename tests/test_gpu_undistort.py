@@ -1,8 +1,16 @@
 """GPU undistortion (dvo_undistort_*, cv.undistort of visual_odometry_v3.py:120)
 vs the oracle restatement: remap table and remapped image bit-exact, for the
-reference's two calibration files, zero distortion and a rational model."""
+reference's two calibration files, zero distortion and a rational model.
+
+The device map is also compared with the documented model in long double
+(undistort_reference.py) directly, at the small cases test_undistort_anchors.py
+runs on the oracle, and dvo_undistort_apply / dvo_undistort_image are given every
+mono layout their ABI accepts (pitched, offset and unaligned sources and
+destinations, with guard bytes)."""
 import numpy as np
 import pytest
+
+import undistort_reference as ur
 
 pytestmark = pytest.mark.gpu
 
@@ -67,3 +75,104 @@ def test_stream_process_undistorted(gpu_ctx):
     for fs in (a, b):
         fs.close()
     u.close()
+
+
+@pytest.mark.parametrize("case", ur.SMALL_CASES, ids=[c[0] for c in ur.SMALL_CASES])
+def test_device_map_is_the_documented_model(gpu_ctx, oracle_mod, case):
+    """|(xy + frac / 32) - model| <= 1/64 + 1e-9 px on both axes at every pixel of the device's table (half
+    the 1/32 quantum; test_undistort_anchors.py derives the bound), against the long double model and not by
+    way of the oracle; then the table equals the oracle's bit for bit, and so do the remapped plane
+    I = 2x + 2y and a noise image."""
+    from droplet_visual_odometry_amd import cv, ops
+    cid, dist, (w, h), alpha = case
+    K = ur.camera(w, h)
+    newK, _ = cv.getOptimalNewCameraMatrix(K, dist, (w, h), alpha, (w, h))
+    mx, my = ur.model_map(K, dist, newK, w, h)
+    u = ops.Undistorter(K, dist, newK, w, h, ctx=gpu_ctx)
+    try:
+        xy, fr = u.map()
+        ex = np.abs(xy[..., 0] + (fr & 31) / 32.0 - mx).max()
+        ey = np.abs(xy[..., 1] + (fr >> 5) / 32.0 - my).max()
+        print(f"{cid}: device map max |dx| {ex:.10f} |dy| {ey:.10f}")
+        assert fr.max() < 1024
+        assert ex <= ur.MAP_BOUND and ey <= ur.MAP_BOUND
+        for img in (ur.plane_image(w, h)[0], ur.noise_image(w, h)):
+            want, xy_o, fr_o = oracle_mod.undistort(img, K, dist, newK)
+            np.testing.assert_array_equal(xy, xy_o)
+            np.testing.assert_array_equal(fr, fr_o)
+            np.testing.assert_array_equal(u.image(img), want)
+    finally:
+        u.close()
+
+
+def _strided(buf, off, shape, strides):
+    return np.lib.stride_tricks.as_strided(buf[off:], shape, strides)
+
+
+def _layout_undistorter(gpu_ctx, w, h):
+    from droplet_visual_odometry_amd import cv, ops
+    K, dist = ur.camera(w, h), np.array(ur.STRONG_BARREL)
+    newK, _ = cv.getOptimalNewCameraMatrix(K, dist, (w, h), 1, (w, h))
+    # the map has all three tap classes, so pads read as pixels or pixels skipped as pads would show
+    classes = ur.tap_classes(*ur.model_map(K, dist, newK, w, h), w, h)
+    assert all(c.any() for c in classes[:3])
+    return ops.Undistorter(K, dist, newK, w, h, ctx=gpu_ctx), (K, dist, newK)
+
+
+@pytest.mark.parametrize("size", [(36, 22), (37, 23), (50, 38), (67, 45)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_apply_layouts(gpu_ctx, oracle_mod, size):
+    """dvo_undistort_apply at w mod 4 = 0, 1, 2, 3 with every source pitch / base / frame count and
+    destination pitch / base: the word store (aligned rows of whole words), the byte store (the row tail,
+    unaligned rows) and the tail's guarded map reads.  The source pads hold noise; the destination's pad
+    bytes, the gaps between frames, the bytes before the base and a guard row after the last frame keep
+    their 0xA5.  Expected: the oracle's remap of each frame."""
+    import torch
+    w, h = size
+    rng = np.random.default_rng(w * 131 + h * 7)
+    u, (K, dist, newK) = _layout_undistorter(gpu_ctx, w, h)
+    try:
+        frames = rng.integers(0, 256, (3, h, w), dtype=np.uint8)
+        wants = np.stack([oracle_mod.undistort(f, K, dist, newK)[0] for f in frames])
+        for n in (1, 3):
+            for pitch in (w, w + 1, w + 5):
+                fstride = h * pitch + 5
+                fstride += fstride % 4 == 0  # never a multiple of 4: the frames of a batch start at different alignments
+                for off in (0, 1):
+                    host = rng.integers(0, 256, off + n * fstride, dtype=np.uint8)  # the pads hold noise
+                    _strided(host, off, (n, h, w), (fstride, pitch, 1))[...] = frames[:n]
+                    sbuf = torch.from_numpy(host).cuda()
+                    src = torch.as_strided(sbuf, (n, h, w), (fstride, pitch, 1), off)
+                    for dpitch in sorted({w, w + 3, (w + 4) & ~3}):
+                        dfstride = h * dpitch + 5
+                        for doff in (0, 1):
+                            want = np.full(doff + n * dfstride + dpitch, 0xA5, np.uint8)  # ends with the guard row
+                            _strided(want, doff, (n, h, w), (dfstride, dpitch, 1))[...] = wants[:n]
+                            dbuf = torch.full((want.size,), 0xA5, dtype=torch.uint8, device="cuda")
+                            dst = torch.as_strided(dbuf, (n, h, w), (dfstride, dpitch, 1), doff)
+                            u.apply(src, dst)
+                            torch.cuda.synchronize()
+                            np.testing.assert_array_equal(
+                                dbuf.cpu().numpy(), want,
+                                err_msg=f"n={n} pitch={pitch} off={off} dpitch={dpitch} doff={doff}")
+    finally:
+        u.close()
+
+
+def test_host_image_row_strided(gpu_ctx, oracle_mod):
+    """dvo_undistort_image on a row-strided host source and into a row-strided host destination (the
+    stride arguments of the ABI; Undistorter.image copies a view before the call), and Undistorter.image
+    on the same view.  The destination's pad columns keep their 0xA5."""
+    from droplet_visual_odometry_amd._native import ptr
+    w, h = 67, 45
+    u, (K, dist, newK) = _layout_undistorter(gpu_ctx, w, h)
+    try:
+        wide = np.random.default_rng(3).integers(0, 256, (h, w + 3), dtype=np.uint8)
+        view = wide[:, :w]
+        want = oracle_mod.undistort(np.ascontiguousarray(view), K, dist, newK)[0]
+        np.testing.assert_array_equal(u.image(view), want)
+        out = np.full((h, w + 5), 0xA5, np.uint8)
+        u.ctx.check(u.ctx.lib.dvo_undistort_image(u.h_, ptr(view), view.strides[0], ptr(out), out.strides[0]))
+        np.testing.assert_array_equal(out[:, :w], want)
+        assert (out[:, w:] == 0xA5).all()
+    finally:
+        u.close()
