@@ -57,6 +57,14 @@ TRACK_POSE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("scale", "
                              ("n_used", "<i4"), ("n_inliers", "<i4"), ("iters", "<i4"), ("status", "<i4")])
 assert TRACK_POSE_DTYPE.itemsize == 128
 TRACK_POSE_OK, TRACK_POSE_NONE, TRACK_POSE_DEGENERATE = 0, 1, 2
+# dvo_track_id, dvo_landmark_refined: a landmark's track and its multi-view position (dvo_stream_set_track_refine)
+TRACK_ID_DTYPE = np.dtype([("root_pair", "<i4"), ("root_ord", "<i4"), ("age", "<i4"), ("reserved", "<i4")])
+assert TRACK_ID_DTYPE.itemsize == 16
+LANDMARK_REFINED_DTYPE = np.dtype([("X", "<f8"), ("Y", "<f8"), ("Z", "<f8"), ("rms", "<f8"), ("views", "<i4"),
+                                   ("n_used", "<i4"), ("n_inliers", "<i4"), ("iters", "<i4"), ("status", "<i4"),
+                                   ("reserved", "<i4")])
+assert LANDMARK_REFINED_DTYPE.itemsize == 56
+TRACK_REFINE_OK, TRACK_REFINE_NONE, TRACK_REFINE_DEGENERATE = 0, 1, 2
 
 
 class DVOError(RuntimeError):
@@ -188,6 +196,10 @@ _SIGNATURES = {
     "dvo_knn_stream_set_track_poses": ([_vp, _vp, _c, _d, _d, _c], _c),
     "dvo_test_track_poses": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c, _c, _c, _c, _c, _vp, _c, _d, _d, _c, _vp, _vp,
                               _vp], _c),
+    "dvo_stream_set_track_refine": ([_vp, _vp, _vp, _c, _c, _d, _d], _c),
+    "dvo_knn_stream_set_track_refine": ([_vp, _vp, _vp, _c, _c, _d, _d], _c),
+    "dvo_test_track_refine": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c, _c, _c, _c, _c, _vp, _c, _d, _d, _c, _vp, _vp,
+                               _vp, _c, _c, _d, _d, _c, _vp, _vp], _c),
     "dvo_knn_pair_create": ([_vp, ctypes.POINTER(KnnPairConfig), ctypes.POINTER(_vp)], _c),
     "dvo_knn_pair_destroy": ([_vp], None),
     "dvo_knn_pair_run": ([_vp, _vp, _vp, _c, _c, ctypes.POINTER(ctypes.c_uint64), _vp], _c),

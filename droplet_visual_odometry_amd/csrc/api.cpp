@@ -122,6 +122,42 @@ inline bool track_pose_params(TrackPoseBinding& b, int iters, double huber_px, d
     return b.iters <= kTrackPoseMaxIters && b.min_points >= 3;
 }
 
+// The caller's buffers and parameters of a refine binding (dvo_stream_set_track_refine), beside a tracks binding.
+struct TrackRefineBinding {
+    dvo_landmark_refined* refined = nullptr;  // [pairs][the landmark binding's cap], or null
+    dvo_track_id* id = nullptr;               // the same, or null; both null: no binding
+    int views = 0, iters = 0;
+    double huber_px = 0, inlier_px = 0;
+    bool use_pose = false;  // a pose binding was pending when this one was made
+    explicit operator bool() const { return refined || id; }
+    // the refine fields of a retiring set's TrackArgs, from the set's GeomArgs and its part of the
+    // scratch: flink [pairs][pts_stride], rank two such buffers rank_stride apart
+    void fill(TrackArgs& a, const GeomArgs& g, int32_t* flink, TrackRank* rank, int64_t rank_stride) const {
+        a.pts_f = g.pts_f;
+        a.fx = g.fx, a.fy = g.fy, a.cx = g.cx, a.cy = g.cy;
+        a.flink = flink;
+        a.rank = rank;
+        a.rank_stride = rank_stride;
+        a.id = id;
+        a.refined = refined;
+        a.rf_views = views;
+        a.rf_iters = iters;
+        a.rf_use_pose = use_pose ? 1 : 0;
+        a.rf_huber_px = huber_px;
+        a.rf_inlier_px = inlier_px;
+    }
+};
+
+// The parameters of a refine binding with the defaults filled in; false: out of range.
+inline bool track_refine_params(TrackRefineBinding& b, int views, int iters, double huber_px, double inlier_px) {
+    if (std::isnan(huber_px) || std::isnan(inlier_px)) return false;
+    b.views = views > 0 ? views : 6;
+    b.iters = iters > 0 ? iters : 5;
+    b.huber_px = huber_px > 0 ? huber_px : 1.0;
+    b.inlier_px = inlier_px > 0 ? inlier_px : 2.0;
+    return b.views >= 3 && b.views <= kTrackRefineMaxViews && b.iters <= kTrackRefineMaxIters;
+}
+
 struct dvo_stream {
     dvo_ctx* ctx = nullptr;
     dvo_stream_config cfg{};
@@ -162,10 +198,12 @@ struct dvo_stream {
         LandmarkBinding lm;              // the batch's landmark binding, written when the set retires
         TracksBinding tr;                // its tracks binding (the set's index copy was taken at the match)
         TrackPoseBinding tp;             // its pose binding
+        TrackRefineBinding rf;           // its refine binding
     };
     LandmarkBinding lm_next;  // dvo_stream_set_landmarks: taken by the next batch
     TracksBinding tr_next;    // dvo_stream_set_tracks: taken with it
     TrackPoseBinding tp_next;  // dvo_stream_set_track_poses: taken with them
+    TrackRefineBinding rf_next;  // dvo_stream_set_track_refine: taken with them
     PairSet sets[kMaxSets];
     // their arrays: 1 set until the first submit, then kRansacRounds; pairs.all.g is the stream's GeomArgs
     PairSets pairs;
@@ -591,6 +629,7 @@ int retire_sets(dvo_stream* s) {
             a.cap = st.lm.cap;
             a.scale = st.tr.scale;
             if (st.tp.out) st.tp.fill(a, v.g, s->pairs.tr.corr + off);
+            if (st.rf) st.rf.fill(a, v.g, s->pairs.tr.flink + off, s->pairs.tr.rank + 2 * off, (int64_t)s->cfg.max_frames * s->plan.kp_cap);
             HIP_TRY(launch_tracks(a, st.pairs, s->hs));
         }
         s->retired_rec[s->retired] = st.rec;
@@ -620,6 +659,7 @@ int run_stream(dvo_stream* s, const uint8_t* d_frames, int n, int64_t fstride, i
     const LandmarkBinding lm = detect_only ? LandmarkBinding{} : std::exchange(s->lm_next, LandmarkBinding{});
     const TracksBinding tr = detect_only ? TracksBinding{} : std::exchange(s->tr_next, TracksBinding{});
     const TrackPoseBinding tp = detect_only ? TrackPoseBinding{} : std::exchange(s->tp_next, TrackPoseBinding{});
+    const TrackRefineBinding rf = detect_only ? TrackRefineBinding{} : std::exchange(s->rf_next, TrackRefineBinding{});
     if (tr && pair_step != 1)  // every binding is consumed
         return fail(ctx, DVO_EINVAL, "tracks need consecutive pairs: the pairs of a *_pairs call share no frame");
     const int want = drain ? 1 : kRansacRounds;
@@ -673,7 +713,7 @@ int run_stream(dvo_stream* s, const uint8_t* d_frames, int n, int64_t fstride, i
             HIP_TRY(hipMemcpyAsync(s->pairs.tr.it + off, s->buf.mt, nb, hipMemcpyDeviceToDevice, s->hs));
         }
         HIP_TRY(launch_geometry_args(s->pairs.view(k).g, pairs, kStageNormalize, s->hs));
-        s->sets[k] = dvo_stream::PairSet{true, 0, pairs, d_rec, lm, tr, tp};
+        s->sets[k] = dvo_stream::PairSet{true, 0, pairs, d_rec, lm, tr, tp, rf};
         s->last_set = k;
         // nsets >= 1 here: every path that matches has passed ensure_sets above
         s->next_set = (k + 1) % s->pairs.nsets;
@@ -1125,6 +1165,7 @@ int dvo_stream_set_landmarks(dvo_stream* s, dvo_landmark* d_out, int32_t* d_coun
         s->lm_next = LandmarkBinding{};
         s->tr_next = TracksBinding{};
         s->tp_next = TrackPoseBinding{};
+        s->rf_next = TrackRefineBinding{};
         return DVO_OK;
     }
     if (cap < 1 || !d_count) return fail(ctx, DVO_EINVAL, "landmarks need cap >= 1 and a count buffer");
@@ -1138,6 +1179,7 @@ int dvo_stream_set_tracks(dvo_stream* s, int32_t* d_link, dvo_track_scale* d_sca
     if (!s) return DVO_EINVAL;
     dvo_ctx* ctx = s->ctx;
     s->tp_next = TrackPoseBinding{};  // a pose binding goes after the tracks binding it reads
+    s->rf_next = TrackRefineBinding{};  // and a refine binding after both
     if (!d_link && !d_scale) {
         s->tr_next = TracksBinding{};
         return DVO_OK;
@@ -1154,6 +1196,7 @@ int dvo_stream_set_track_poses(dvo_stream* s, dvo_track_pose* d_pose, int iters,
                                int min_points) {
     if (!s) return DVO_EINVAL;
     dvo_ctx* ctx = s->ctx;
+    s->rf_next = TrackRefineBinding{};  // a refine binding goes after the pose binding it may read
     if (!d_pose) {
         s->tp_next = TrackPoseBinding{};
         return DVO_OK;
@@ -1167,6 +1210,28 @@ int dvo_stream_set_track_poses(dvo_stream* s, dvo_track_pose* d_pose, int iters,
     HIP_TRY(s->pairs.ensure_track_poses(s->cfg.max_frames, s->plan.kp_cap));  // the first binding sizes the scratch
     b.out = d_pose;
     s->tp_next = b;
+    return DVO_OK;
+}
+
+int dvo_stream_set_track_refine(dvo_stream* s, dvo_landmark_refined* d_refined, dvo_track_id* d_id, int views,
+                                int iters, double huber_px, double inlier_px) {
+    if (!s) return DVO_EINVAL;
+    dvo_ctx* ctx = s->ctx;
+    if (!d_refined && !d_id) {
+        s->rf_next = TrackRefineBinding{};
+        return DVO_OK;
+    }
+    if (!s->lm_next.out || !s->tr_next.link || !s->tr_next.scale)
+        return fail(ctx, DVO_EINVAL, "track refine goes with a pending tracks binding that has link and scale buffers");
+    TrackRefineBinding b;
+    if (!track_refine_params(b, views, iters, huber_px, inlier_px))
+        return fail(ctx, DVO_EINVAL, "track refine: views 3..8, iters <= 16, no NaN");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(s->pairs.ensure_track_refine(s->cfg.max_frames, s->plan.kp_cap));  // the first binding sizes the scratch
+    b.refined = d_refined;
+    b.id = d_id;
+    b.use_pose = s->tp_next.out != nullptr;
+    s->rf_next = b;
     return DVO_OK;
 }
 
@@ -2818,6 +2883,7 @@ struct dvo_knn_stream {
     LandmarkBinding lm_next;  // dvo_knn_stream_set_landmarks: taken by the next finish
     TracksBinding tr_next;    // dvo_knn_stream_set_tracks: taken with it
     TrackPoseBinding tp_next;  // dvo_knn_stream_set_track_poses: taken with them
+    TrackRefineBinding rf_next;  // dvo_knn_stream_set_track_refine: taken with them
     // A raw-input call records ev_in[k] before its input launch, k the one the last accepted call
     // does not use (first_ev; -1: that call began at ev[0]), so a refused call disturbs no figure.
     hipEvent_t ev_in[2] = {nullptr, nullptr};
@@ -3000,6 +3066,7 @@ int dvo_knn_stream_finish(dvo_knn_stream* st, dvo_pair_record* d_records, const 
     const LandmarkBinding lm = std::exchange(st->lm_next, LandmarkBinding{});  // for this batch alone
     const TracksBinding tr = std::exchange(st->tr_next, TracksBinding{});
     const TrackPoseBinding tp = std::exchange(st->tp_next, TrackPoseBinding{});
+    const TrackRefineBinding rf = std::exchange(st->rf_next, TrackRefineBinding{});
     const int pairs = n_frames - 1;
     const PairArrays& v = st->pairs.all;
     const bool flann = st->fl.trees > 0;
@@ -3025,6 +3092,7 @@ int dvo_knn_stream_finish(dvo_knn_stream* st, dvo_pair_record* d_records, const 
             a.cap = lm.cap;
             a.scale = tr.scale;
             if (tp.out) tp.fill(a, v.g, st->pairs.tr.corr);
+            if (rf) rf.fill(a, v.g, st->pairs.tr.flink, st->pairs.tr.rank, (int64_t)(b.F - 1 > 0 ? b.F - 1 : 1) * b.cap);
             HIP_TRY(launch_tracks(a, pairs, s));
         }
     }
@@ -3044,6 +3112,7 @@ int dvo_knn_stream_set_landmarks(dvo_knn_stream* s, dvo_landmark* d_out, int32_t
         s->lm_next = LandmarkBinding{};
         s->tr_next = TracksBinding{};
         s->tp_next = TrackPoseBinding{};
+        s->rf_next = TrackRefineBinding{};
         return DVO_OK;
     }
     if (cap < 1 || !d_count) return fail(ctx, DVO_EINVAL, "landmarks need cap >= 1 and a count buffer");
@@ -3057,6 +3126,7 @@ int dvo_knn_stream_set_tracks(dvo_knn_stream* s, int32_t* d_link, dvo_track_scal
     if (!s) return DVO_EINVAL;
     dvo_ctx* ctx = s->ctx;
     s->tp_next = TrackPoseBinding{};  // a pose binding goes after the tracks binding it reads
+    s->rf_next = TrackRefineBinding{};  // and a refine binding after both
     if (!d_link && !d_scale) {
         s->tr_next = TracksBinding{};
         return DVO_OK;
@@ -3072,6 +3142,7 @@ int dvo_knn_stream_set_track_poses(dvo_knn_stream* s, dvo_track_pose* d_pose, in
                                    double inlier_px, int min_points) {
     if (!s) return DVO_EINVAL;
     dvo_ctx* ctx = s->ctx;
+    s->rf_next = TrackRefineBinding{};  // a refine binding goes after the pose binding it may read
     if (!d_pose) {
         s->tp_next = TrackPoseBinding{};
         return DVO_OK;
@@ -3085,6 +3156,28 @@ int dvo_knn_stream_set_track_poses(dvo_knn_stream* s, dvo_track_pose* d_pose, in
     HIP_TRY(s->pairs.ensure_track_poses(s->b.F - 1, s->b.cap));  // the first binding sizes the scratch
     b.out = d_pose;
     s->tp_next = b;
+    return DVO_OK;
+}
+
+int dvo_knn_stream_set_track_refine(dvo_knn_stream* s, dvo_landmark_refined* d_refined, dvo_track_id* d_id, int views,
+                                    int iters, double huber_px, double inlier_px) {
+    if (!s) return DVO_EINVAL;
+    dvo_ctx* ctx = s->ctx;
+    if (!d_refined && !d_id) {
+        s->rf_next = TrackRefineBinding{};
+        return DVO_OK;
+    }
+    if (!s->lm_next.out || !s->tr_next.link || !s->tr_next.scale)
+        return fail(ctx, DVO_EINVAL, "track refine goes with a pending tracks binding that has link and scale buffers");
+    TrackRefineBinding b;
+    if (!track_refine_params(b, views, iters, huber_px, inlier_px))
+        return fail(ctx, DVO_EINVAL, "track refine: views 3..8, iters <= 16, no NaN");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(s->pairs.ensure_track_refine(s->b.F - 1, s->b.cap));  // the first binding sizes the scratch
+    b.refined = d_refined;
+    b.id = d_id;
+    b.use_pose = s->tp_next.out != nullptr;
+    s->rf_next = b;
     return DVO_OK;
 }
 
@@ -3786,11 +3879,13 @@ int dvo_test_landmarks(dvo_ctx* ctx, const float* pts, const int32_t* m, int pai
     return DVO_OK;
 }
 
-// dvo_test_tracks, and with tp (a binding without its buffer), K and pose dvo_test_track_poses
+// dvo_test_tracks, and with tp (a binding without its buffer), K and pose dvo_test_track_poses, and
+// with rf (its parameters and use_pose) dvo_test_track_refine, refined and id each optional
 static int test_tracks_run(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* count, const int32_t* mq,
                            const int32_t* mt, const int32_t* m, const dvo_pair_record* rec, int pairs, int cap, int stride,
                            int kp_cap, int cap_out, int32_t* link, dvo_track_scale* scale, const double* K,
-                           const TrackPoseBinding* tp, dvo_track_pose* pose) {
+                           const TrackPoseBinding* tp, dvo_track_pose* pose, const TrackRefineBinding* rf = nullptr,
+                           dvo_landmark_refined* refined = nullptr, dvo_track_id* id = nullptr) {
     if (!ctx || !lm || !count || !mq || !mt || !m || !rec || !link || !scale) return DVO_EINVAL;
     if (pairs < 1 || pairs > 65535 || cap < 1 || stride < 1 || kp_cap < 1 || cap_out < 1)
         return fail(ctx, DVO_EINVAL, "bad pair count, cap, stride, kp_cap or cap_out");
@@ -3839,6 +3934,10 @@ static int test_tracks_run(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* 
     float* dpts = tp ? mem.dev<float>(pts.size()) : nullptr;
     TrackCorr* dcorr = tp ? mem.dev<TrackCorr>(P * stride) : nullptr;
     dvo_track_pose* dpose = tp ? mem.dev<dvo_track_pose>(P) : nullptr;
+    int32_t* dflink = rf ? mem.dev<int32_t>(P * stride) : nullptr;
+    TrackRank* drank = rf ? mem.dev<TrackRank>(2 * P * stride) : nullptr;
+    dvo_landmark_refined* drefined = rf && refined ? mem.dev<dvo_landmark_refined>(P * cap_out) : nullptr;
+    dvo_track_id* did = rf && id ? mem.dev<dvo_track_id>(P * cap_out) : nullptr;
     HIP_TRY(mem.error());
     a.L.tmp = dtmp;
     a.L.tcnt = dtcnt;
@@ -3865,9 +3964,19 @@ static int test_tracks_run(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* 
         b.out = dpose;
         b.fill(a, g, dcorr);
         HIP_TRY(mem.put(dpts, pts.data(), pts.size() * sizeof(float)));
+        if (rf) {
+            TrackRefineBinding r = *rf;
+            r.refined = drefined;
+            r.id = did;
+            r.fill(a, g, dflink, drank, (int64_t)P * stride);
+            if (drefined) HIP_TRY(mem.put(drefined, refined, P * cap_out * sizeof(dvo_landmark_refined)));
+            if (did) HIP_TRY(mem.put(did, id, P * cap_out * sizeof(dvo_track_id)));
+        }
     }
     HIP_TRY(launch_tracks(a, pairs, ctx->stream));
-    uint8_t *hlink, *hscale, *hpose = nullptr;
+    uint8_t *hlink, *hscale, *hpose = nullptr, *hrefined = nullptr, *hid = nullptr;
+    if (drefined) HIP_TRY(mem.get(drefined, P * cap_out * sizeof(dvo_landmark_refined), &hrefined));
+    if (did) HIP_TRY(mem.get(did, P * cap_out * sizeof(dvo_track_id), &hid));
     HIP_TRY(mem.get(a.link, P * cap_out * 4, &hlink));
     HIP_TRY(mem.get(a.scale, P * sizeof(dvo_track_scale), &hscale));
     if (tp) HIP_TRY(mem.get(dpose, P * sizeof(dvo_track_pose), &hpose));
@@ -3875,6 +3984,8 @@ static int test_tracks_run(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* 
     std::memcpy(link, hlink, P * cap_out * 4);
     std::memcpy(scale, hscale, P * sizeof(dvo_track_scale));
     if (tp) std::memcpy(pose, hpose, P * sizeof(dvo_track_pose));
+    if (hrefined) std::memcpy(refined, hrefined, P * cap_out * sizeof(dvo_landmark_refined));
+    if (hid) std::memcpy(id, hid, P * cap_out * sizeof(dvo_track_id));
     return DVO_OK;
 }
 
@@ -3894,6 +4005,24 @@ int dvo_test_track_poses(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* co
     if (!track_pose_params(b, iters, huber_px, inlier_px, min_points))
         return fail(ctx, DVO_EINVAL, "track poses: iters <= 32, min_points >= 3, no NaN");
     return test_tracks_run(ctx, lm, count, mq, mt, m, rec, pairs, cap, stride, kp_cap, cap_out, link, scale, K, &b, pose);
+}
+
+int dvo_test_track_refine(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* count, const int32_t* mq,
+                          const int32_t* mt, const int32_t* m, const dvo_pair_record* rec, int pairs, int cap, int stride,
+                          int kp_cap, int cap_out, const double* K, int iters, double huber_px, double inlier_px,
+                          int min_points, int32_t* link, dvo_track_scale* scale, dvo_track_pose* pose, int rf_views,
+                          int rf_iters, double rf_huber_px, double rf_inlier_px, int use_poses,
+                          dvo_landmark_refined* refined, dvo_track_id* id) {
+    if (!ctx || !K || !pose || (!refined && !id)) return DVO_EINVAL;
+    TrackPoseBinding b;
+    if (!track_pose_params(b, iters, huber_px, inlier_px, min_points))
+        return fail(ctx, DVO_EINVAL, "track poses: iters <= 32, min_points >= 3, no NaN");
+    TrackRefineBinding r;
+    if (!track_refine_params(r, rf_views, rf_iters, rf_huber_px, rf_inlier_px))
+        return fail(ctx, DVO_EINVAL, "track refine: views 3..8, iters <= 16, no NaN");
+    r.use_pose = use_poses != 0;
+    return test_tracks_run(ctx, lm, count, mq, mt, m, rec, pairs, cap, stride, kp_cap, cap_out, link, scale, K, &b, pose,
+                           &r, refined, id);
 }
 
 int dvo_test_five_point(dvo_ctx* ctx, const double* q1, const double* q2, double* models, int* n) {

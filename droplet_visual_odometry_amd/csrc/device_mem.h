@@ -215,6 +215,26 @@ struct PairSets {
         tr.corr = c;
         return hipSuccess;
     }
+    // The full links and the id kernel's two rank buffers (dvo_stream_set_track_refine): 4 B and
+    // 16 B per slot, for the sets the track scratch was sized for.  Allocated by the first refine
+    // binding (after the track scratch: it needs a pending tracks binding) and never regrown.
+    // Set k's links start at flink + k F cap, its rank buffers at rank + 2 k F cap, F cap apart.
+    DeviceAllocs rf_mem;
+    hipError_t ensure_track_refine(int F_, int cap_) {
+        if (tr.flink) return hipSuccess;
+        if (!tr.table) return hipErrorInvalidValue;
+        const size_t n = (size_t)tr_sets * (F_ > 0 ? F_ : 1) * cap_;
+        DeviceAllocs fresh;
+        int32_t* l = nullptr;
+        TrackRank* r = nullptr;
+        hipError_t e = fresh.alloc(&l, n * sizeof(int32_t) + 256);
+        if (e == hipSuccess) e = fresh.alloc(&r, 2 * n * sizeof(TrackRank) + 256);
+        if (e != hipSuccess) return e;
+        rf_mem = std::move(fresh);
+        tr.flink = l;
+        tr.rank = r;
+        return hipSuccess;
+    }
     // Set k's part of it: the kernels' arguments but for the indices, the records and the caller's buffers
     // (and a pose binding's fields: TrackPoseBinding::fill in api.cpp).
     TrackArgs track_args(int k, int F_, int cap_) const {

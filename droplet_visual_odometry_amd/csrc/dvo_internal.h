@@ -412,6 +412,17 @@ constexpr int kTrackPoseMaxIters = 32;
 struct TrackCorr {  // 40 B
     double y[3], nu, nv;
 };
+// Track ids and refined landmarks (dvo_stream_set_track_refine): with TrackArgs::flink set, the link
+// kernel also writes every landmark's full link at its ordinal (the caller's d_link is capped and
+// cannot serve a walk); after the pose kernel the id kernel ranks the lists by pointer jumping
+// (1 + ceil(log2(pairs - 1)) launches, ping-pong over `rank`) and the refine kernel (grid as the
+// link kernel) forms the pair's window cameras in LDS, walks at most views - 2 links per landmark
+// and runs the header's Gauss-Newton steps from registers.
+constexpr int kTrackRefineMaxViews = 8;
+constexpr int kTrackRefineMaxIters = 16;
+struct TrackRank {  // 8 B: the links followed so far and the ordinal reached, in pair p - age
+    int32_t age, ord;
+};
 struct TrackScratch {
     int32_t* table = nullptr;  // [sets][pairs][kp_cap] smallest landmark ordinal per trainIdx
     double* ratio = nullptr;   // [sets][pairs][pts_stride] a tile's linked ratios from its first ordinal on
@@ -419,6 +430,8 @@ struct TrackScratch {
     int32_t* iq = nullptr;     // [sets][pairs][pts_stride] the ORB stream's copy of queryIdx, trainIdx
     int32_t* it = nullptr;
     TrackCorr* corr = nullptr;  // [sets][pairs][pts_stride] a tile's correspondences, as ratio (first pose binding)
+    int32_t* flink = nullptr;   // [sets][pairs][pts_stride] every landmark's full link at its ordinal (first refine binding)
+    TrackRank* rank = nullptr;  // [sets][2][pairs][pts_stride] the id kernel's ping-pong buffers (first refine binding)
 };
 struct TrackArgs {
     LandmarkScratch L;  // the set's full landmark lists
@@ -442,6 +455,15 @@ struct TrackArgs {
     TrackCorr* corr;  // [pairs][pts_stride]
     int pose_iters, pose_min_points;  // 1..kTrackPoseMaxIters, >= 3
     double huber_px, inlier_px;       // > 0
+    // track ids and refined landmarks; all unused while flink is null (pts_f and the camera are read too)
+    int32_t* flink;                 // [pairs][pts_stride]
+    TrackRank* rank;                // [2][pairs][pts_stride]; the second buffer starts at rank + rank_stride
+    int64_t rank_stride;
+    dvo_track_id* id;               // the caller's [pairs][cap], or null
+    dvo_landmark_refined* refined;  // the caller's [pairs][cap], or null
+    int rf_views, rf_iters;         // 3..kTrackRefineMaxViews, 1..kTrackRefineMaxIters
+    int rf_use_pose;                // the unit motions come from `pose` where its status is OK
+    double rf_huber_px, rf_inlier_px;  // > 0
 };
 hipError_t launch_tracks(const TrackArgs& a, int pairs, hipStream_t s);
 // five-point record blocks a merged round can need (sizes the stream's GeomArgs::fprec, dk_list)

@@ -14,6 +14,14 @@
 //   track_select_kernel  a workgroup per pair: the tiles' ratios moved together, then an exact
 //                        radix select on their 64-bit patterns (positive doubles order as
 //                        unsigned integers), most significant byte first, for the three ranks.
+// With a refine binding (dvo.h dvo_stream_set_track_refine) the link kernel also writes every
+// landmark's full link at its ordinal, and after the pose kernel:
+//   track_id_kernel      list ranking by pointer jumping: launch 0 turns a link into (age, ordinal
+//                        reached), launch r joins it with the state its ancestor had after launch
+//                        r - 1 (ping-pong), so ages double; the last launch writes the caller's ids;
+//   track_refine_kernel  per (tile, pair): thread 0 forms the pair's window cameras in LDS, then
+//                        each landmark walks at most views - 2 links, gathers its observations
+//                        into registers and runs the header's steps and final pass.
 // With a pose binding (dvo.h dvo_stream_set_track_poses) the link kernel also writes each linked
 // landmark's 3-D to 2-D correspondence beside its ratio, and a fourth kernel follows:
 //   track_pose_kernel    a workgroup per pair: the tiles' correspondences moved together, then
@@ -90,6 +98,7 @@ __global__ __launch_bounds__(kLandmarkTile) void track_link_kernel(TrackArgs a) 
         }
         const int o = first + tid;
         if (a.link && o < a.cap) a.link[(int64_t)p * a.cap + o] = lk;
+        if (a.flink) a.flink[(int64_t)p * a.pts_stride + o] = lk;  // o < the pair's landmarks <= pts_stride
     }
     const unsigned long long bal = __ballot(linked);
     const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
@@ -443,6 +452,280 @@ __global__ __launch_bounds__(kPoseNT) void track_pose_kernel(TrackArgs a) {
     }
 }
 
+// ---- track ids and refined landmarks (dvo.h dvo_stream_set_track_refine) --------------------------
+// Launch `round` of the list ranking.  A landmark of age g has followed g links and stands at
+// ordinal ord of pair p - g (g <= p: a link exists only from pair 1 on); joining it with that
+// landmark's state of the launch before adds the links that one had followed.  After launch r
+// every chain of up to 2^r links is ranked to its end and longer ones stand 2^r links back.
+__global__ __launch_bounds__(kLandmarkTile) void track_id_kernel(TrackArgs a, int round, int last) {
+    const int p = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
+    const int32_t* tc = a.L.tcnt + (int64_t)p * a.tiles;
+    if (tid >= tc[tile]) return;
+    int first = 0;
+    for (int t = 0; t < tile; ++t) first += tc[t];
+    const int o = first + tid;
+    const int64_t at = (int64_t)p * a.pts_stride + o;
+    TrackRank r;
+    if (round == 0) {
+        const int lk = a.flink[at];
+        r.age = lk >= 0 ? 1 : 0;
+        r.ord = lk >= 0 ? lk : o;
+    } else {
+        const TrackRank* src = a.rank + (int64_t)((round - 1) & 1) * a.rank_stride;
+        r = src[at];
+        if (r.age > 0) {
+            const TrackRank b = src[(int64_t)(p - r.age) * a.pts_stride + r.ord];
+            r.age += b.age;
+            r.ord = b.ord;
+        }
+    }
+    if (!last) {
+        (a.rank + (int64_t)(round & 1) * a.rank_stride)[at] = r;
+    } else if (o < a.cap) {
+        dvo_track_id id;
+        id.root_pair = p - r.age;
+        id.root_ord = r.ord;
+        id.age = r.age;
+        id.reserved = 0;
+        a.id[(int64_t)p * a.cap + o] = id;
+    }
+}
+
+// the unit motion of pair q (R row by row, d, rho)
+__device__ void refine_motion(const TrackArgs& a, int q, double* R, double* d, double* rho) {
+    if (a.rf_use_pose && a.pose[q].status == DVO_TRACK_POSE_OK) {
+        const dvo_track_pose& s = a.pose[q];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) R[i] = s.R[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) d[i] = s.t[i] / s.scale;
+        *rho = s.scale;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) R[i] = a.rec[q].R[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) d[i] = a.rec[q].t[i];
+        *rho = a.scale[q].ratio;
+    }
+}
+
+// H d = -g by the header's LDL^T at size 3, S the 6 + 3 sums; false: a pivot not > 0 or a non-finite d
+__device__ bool refine_solve(const double* S, double* d) {
+    double H[3][3], L[3][3], D[3], z[3];
+    {
+        int q = 0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = i; j < 3; ++j) H[i][j] = S[q++];
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        double dj = H[j][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) dj = dj - (L[j][k] * L[j][k]) * D[k];
+        if (!(dj > 0)) return false;
+        D[j] = dj;
+#pragma unroll
+        for (int i = j + 1; i < 3; ++i) {
+            double x = H[j][i];
+#pragma unroll
+            for (int k = 0; k < j; ++k) x = x - (L[i][k] * L[j][k]) * D[k];
+            L[i][j] = x / dj;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        double x = -S[6 + i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) x = x - L[i][k] * z[k];
+        z[i] = x;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) z[i] = z[i] / D[i];
+    bool finite = true;
+#pragma unroll
+    for (int i = 2; i >= 0; --i) {
+        double x = z[i];
+#pragma unroll
+        for (int k = i + 1; k < 3; ++k) x = x - L[k][i] * d[k];
+        d[i] = x;
+        finite = finite && isfinite(x);
+    }
+    return finite;
+}
+
+// Per (tile, pair).  The one barrier is reached by all 256 threads (an empty tile leaves before it
+// as a whole); after it every thread runs alone, its trip counts from the links, views and iters.
+__global__ __launch_bounds__(kLandmarkTile) void track_refine_kernel(TrackArgs a) {
+    __shared__ double cam[kTrackRefineMaxViews][12];  // view v: A row by row, then b
+    __shared__ int win;                               // the window's length W
+    const int p = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
+    const int32_t* tc = a.L.tcnt + (int64_t)p * a.tiles;
+    if (tc[tile] == 0) return;
+    if (tid == 0) {
+        double A[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, b[3] = {0, 0, 0}, sigma = 1, R[9], d[3], rho;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) cam[0][i] = A[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) cam[0][9 + i] = 0.0;
+        refine_motion(a, p, R, d, &rho);
+#pragma unroll
+        for (int i = 0; i < 9; ++i) cam[1][i] = R[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) cam[1][9 + i] = d[i];
+        int W = 0;
+        for (int k = 1; k <= a.rf_views - 2; ++k) {  // camera k goes to view k + 1 <= views - 1
+            const int q = p - k;
+            if (q < 0) break;
+            refine_motion(a, q + 1, R, d, &rho);
+            if (!(rho > 0)) break;  // also where pair q or q + 1 has no landmarks: pair q + 1 links nothing
+            sigma = sigma / rho;
+            if (!isfinite(sigma)) break;
+            refine_motion(a, q, R, d, &rho);
+            double An[9], c[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) An[3 * i + j] = (R[i] * A[j] + R[3 + i] * A[3 + j]) + R[6 + i] * A[6 + j];
+                c[i] = b[i] - sigma * d[i];
+            }
+#pragma unroll
+            for (int i = 0; i < 3; ++i) b[i] = (R[i] * c[0] + R[3 + i] * c[1]) + R[6 + i] * c[2];
+#pragma unroll
+            for (int i = 0; i < 9; ++i) cam[k + 1][i] = A[i] = An[i];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) cam[k + 1][9 + i] = b[i];
+            W = k;
+        }
+        win = W;
+    }
+    __syncthreads();
+    if (tid >= tc[tile]) return;
+    int first = 0;
+    for (int t = 0; t < tile; ++t) first += tc[t];
+    const int o = first + tid;
+    if (o >= a.cap) return;  // nothing but the slot is written
+    const LandmarkTmp e = track_entry(a, p, tile, tid);
+    const double ax = 1. / a.fx, ay = 1. / a.fy, bx = -a.cx * ax, by = -a.cy * ay;
+    double nu[kTrackRefineMaxViews], nv[kTrackRefineMaxViews];
+#pragma unroll
+    for (int v = 0; v < kTrackRefineMaxViews; ++v) nu[v] = nv[v] = 0.0;
+    {
+        const float* px = a.pts_f + ((int64_t)p * a.pts_stride + e.match) * 4;
+        nu[0] = (double)px[0] * ax + bx, nv[0] = (double)px[1] * ay + by;
+        nu[1] = (double)px[2] * ax + bx, nv[1] = (double)px[3] * ay + by;
+    }
+    int nviews = 2;
+    {
+        const int maxk = min(a.rf_views - 2, win);  // maxk <= p: the window stops at pair 0
+        int cur = o;                                // c_{k-1}'s ordinal in pair p - k + 1, -1 past the chain's end
+#pragma unroll
+        for (int k = 1; k <= kTrackRefineMaxViews - 2; ++k) {
+            if (k <= maxk && cur >= 0) {
+                cur = a.flink[(int64_t)(p - k + 1) * a.pts_stride + cur];
+                if (cur >= 0) {
+                    // ordinal cur of pair p - k: its tile and its place there, as the link kernel finds them
+                    const int32_t* tp = tc - (int64_t)k * a.tiles;
+                    int t = 0, rem = cur;
+                    while (t < a.tiles - 1 && rem >= tp[t]) rem -= tp[t++];
+                    const int mi = track_entry(a, p - k, t, min(rem, kLandmarkTile - 1)).match;  // (never clamps)
+                    const float* px = a.pts_f + ((int64_t)(p - k) * a.pts_stride + mi) * 4;
+                    nu[k + 1] = (double)px[0] * ax + bx, nv[k + 1] = (double)px[1] * ay + by;
+                    nviews = k + 2;
+                }
+            }
+        }
+    }
+    dvo_landmark_refined out;
+    out.rms = 0.0;
+    out.n_used = out.n_inliers = out.iters = 0;
+    out.reserved = 0;
+    double X[3] = {e.X, e.Y, e.Z};
+    if (nviews < 3) {
+        out.views = 2;
+        out.status = DVO_TRACK_REFINE_NONE;
+    } else {
+        const double kh = a.rf_huber_px / ((a.fx + a.fy) / 2), kh2 = kh * kh;
+        int status = DVO_TRACK_REFINE_OK, it = 0;
+        for (; it < a.rf_iters; ++it) {
+            int z = 0;  // opaque zero: the cameras are read from LDS every step, not held in 96 registers across the loop
+            asm volatile("" : "+v"(z));
+            double S[9];
+#pragma unroll
+            for (int q = 0; q < 9; ++q) S[q] = 0.0;
+#pragma unroll
+            for (int v = 0; v < kTrackRefineMaxViews; ++v) {
+                if (v < nviews) {
+                    const double* C = cam[v] + z;
+                    const double P0 = ((C[0] * X[0] + C[1] * X[1]) + C[2] * X[2]) + C[9];
+                    const double P1 = ((C[3] * X[0] + C[4] * X[1]) + C[5] * X[2]) + C[10];
+                    const double P2 = ((C[6] * X[0] + C[7] * X[1]) + C[8] * X[2]) + C[11];
+                    const bool ok = P2 > 0;
+                    const double ia = 1 / P2, u = P0 * ia, w_ = P1 * ia;
+                    const double ru = u - nu[v], rv = w_ - nv[v], e2 = ru * ru + rv * rv;
+                    const double w = e2 <= kh2 ? 1.0 : kh / sqrt(e2);
+                    double Ju[3], Jv[3];
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) {
+                        Ju[j] = ia * (C[j] - u * C[6 + j]);
+                        Jv[j] = ia * (C[3 + j] - w_ * C[6 + j]);
+                    }
+                    int q = 0;
+#pragma unroll
+                    for (int i = 0; i < 3; ++i)
+#pragma unroll
+                        for (int j = i; j < 3; ++j, ++q) {
+                            const double term = w * (Ju[i] * Ju[j] + Jv[i] * Jv[j]);
+                            S[q] = S[q] + (ok ? term : 0.0);
+                        }
+#pragma unroll
+                    for (int i = 0; i < 3; ++i, ++q) {
+                        const double term = w * (Ju[i] * ru + Jv[i] * rv);
+                        S[q] = S[q] + (ok ? term : 0.0);
+                    }
+                }
+            }
+            double d[3];
+            if (!refine_solve(S, d)) {
+                status = DVO_TRACK_REFINE_DEGENERATE;
+                break;
+            }
+#pragma unroll
+            for (int i = 0; i < 3; ++i) X[i] = X[i] + d[i];
+        }
+        // the final pass on the last X
+        double se = 0.0;
+        int used = 0, inl = 0;
+        const double in2 = a.rf_inlier_px * a.rf_inlier_px;
+#pragma unroll
+        for (int v = 0; v < kTrackRefineMaxViews; ++v) {
+            if (v < nviews) {
+                const double* C = cam[v];
+                const double P0 = ((C[0] * X[0] + C[1] * X[1]) + C[2] * X[2]) + C[9];
+                const double P1 = ((C[3] * X[0] + C[4] * X[1]) + C[5] * X[2]) + C[10];
+                const double P2 = ((C[6] * X[0] + C[7] * X[1]) + C[8] * X[2]) + C[11];
+                const bool ok = P2 > 0;
+                const double ia = 1 / P2, u = P0 * ia, w_ = P1 * ia;
+                const double ex = a.fx * (u - nu[v]), ey = a.fy * (w_ - nv[v]);
+                const double er = ex * ex + ey * ey;
+                const bool in = ok && er <= in2;
+                used += ok;
+                inl += in;
+                se = se + (in ? er : 0.0);
+            }
+        }
+        out.views = nviews;
+        out.n_used = used;
+        out.n_inliers = inl;
+        out.rms = inl > 0 ? sqrt(se / (double)inl) : 0.0;
+        out.iters = it;
+        out.status = status;
+    }
+    out.X = X[0], out.Y = X[1], out.Z = X[2];
+    a.refined[(int64_t)p * a.cap + o] = out;
+}
+
 }  // namespace
 
 hipError_t launch_tracks(const TrackArgs& a, int pairs, hipStream_t s) {
@@ -454,6 +737,11 @@ hipError_t launch_tracks(const TrackArgs& a, int pairs, hipStream_t s) {
                      a.pose_min_points < 3 || !(a.huber_px > 0) || !(a.inlier_px > 0)
                : a.corr != nullptr)
         return hipErrorInvalidValue;
+    if (a.flink && (!a.scale || !a.pts_f || a.cap < 1 || (!a.id && !a.refined) || (a.id && (!a.rank || a.rank_stride < 1)) ||
+                    a.rf_views < 3 || a.rf_views > kTrackRefineMaxViews || a.rf_iters < 1 ||
+                    a.rf_iters > kTrackRefineMaxIters || !(a.rf_huber_px > 0) || !(a.rf_inlier_px > 0) ||
+                    (a.rf_use_pose && !a.pose)))
+        return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(a.table, 0x7f, (size_t)pairs * a.kp_cap * sizeof(int32_t), s);
     if (e != hipSuccess) return e;
     const dim3 grid((unsigned)a.tiles, (unsigned)pairs);
@@ -461,6 +749,14 @@ hipError_t launch_tracks(const TrackArgs& a, int pairs, hipStream_t s) {
     hipLaunchKernelGGL(track_link_kernel, grid, dim3(kLandmarkTile), 0, s, a);
     if (a.scale) hipLaunchKernelGGL(track_select_kernel, dim3((unsigned)pairs), dim3(kSelNT), 0, s, a);
     if (a.pose) hipLaunchKernelGGL(track_pose_kernel, dim3((unsigned)pairs), dim3(kPoseNT), 0, s, a);
+    if (a.flink && a.id) {
+        // the longest chain has pairs - 1 links: launch r ranks chains of up to 2^r
+        int rounds = 0;
+        while ((1 << rounds) < pairs - 1) ++rounds;
+        for (int r = 0; r <= rounds; ++r)
+            hipLaunchKernelGGL(track_id_kernel, grid, dim3(kLandmarkTile), 0, s, a, r, r == rounds ? 1 : 0);
+    }
+    if (a.flink && a.refined) hipLaunchKernelGGL(track_refine_kernel, grid, dim3(kLandmarkTile), 0, s, a);
     return hipGetLastError();
 }
 

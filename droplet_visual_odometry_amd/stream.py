@@ -19,8 +19,8 @@ import ctypes
 import numpy as np
 import torch
 
-from ._native import (DMATCH_DTYPE, KEYPOINT_DTYPE, LANDMARK_DTYPE, PAIR_RECORD_DTYPE, TRACK_POSE_DTYPE,
-                      TRACK_SCALE_DTYPE, Context, StreamConfig, _vp, orb_params, ptr)
+from ._native import (DMATCH_DTYPE, KEYPOINT_DTYPE, LANDMARK_DTYPE, LANDMARK_REFINED_DTYPE, PAIR_RECORD_DTYPE,
+                      TRACK_ID_DTYPE, TRACK_POSE_DTYPE, TRACK_SCALE_DTYPE, Context, StreamConfig, _vp, orb_params, ptr)
 
 
 class Landmarks:
@@ -122,6 +122,53 @@ class TrackPoses:
         return self.poses.cpu().numpy().reshape(-1).view(TRACK_POSE_DTYPE).copy()
 
 
+class RefinedLandmarks:
+    """Device buffers for one batch's track ids and refined landmarks (dvo_stream_set_track_refine),
+    the companion of a Tracks, slot for slot beside the Landmarks of the same cap: per landmark the
+    root and age of its track, and its position re-estimated from up to `views` most recent frames
+    of the track (see include/dvo.h).  refined: uint8 [n_pairs, cap, 56] (LANDMARK_REFINED_DTYPE);
+    ids: uint8 [n_pairs, cap, 16] (TRACK_ID_DTYPE).  Bind it with bind_refine after bind_tracks (and
+    after bind_track_poses, where the poses are to feed it); read it after the batch has retired
+    and the stream is synchronised."""
+
+    def __init__(self, n_pairs: int, cap: int, device):
+        if n_pairs < 1 or cap < 1:
+            raise ValueError("RefinedLandmarks needs n_pairs >= 1 and cap >= 1")
+        self.n_pairs, self.cap = int(n_pairs), int(cap)
+        self.refined = torch.zeros((self.n_pairs, self.cap, LANDMARK_REFINED_DTYPE.itemsize), dtype=torch.uint8,
+                                   device=device)
+        self.ids = torch.zeros((self.n_pairs, self.cap, TRACK_ID_DTYPE.itemsize), dtype=torch.uint8, device=device)
+
+    def numpy(self, pair: int, count: int) -> np.ndarray:
+        """The pair's first min(count, cap) refined landmarks (count: Landmarks.count(pair))."""
+        n = min(int(count), self.cap)
+        return self.refined[pair, :n].cpu().numpy().reshape(-1).view(LANDMARK_REFINED_DTYPE).copy()
+
+    def ids_numpy(self, pair: int, count: int) -> np.ndarray:
+        """The track ids of the pair's first min(count, cap) landmarks."""
+        n = min(int(count), self.cap)
+        return self.ids[pair, :n].cpu().numpy().reshape(-1).view(TRACK_ID_DTYPE).copy()
+
+
+def _bind_refine(stream, setter, rf, views, iters, huber_px, inlier_px, ids, refined):
+    """The one-shot refine binding of both stream classes; returns what to keep referenced."""
+    if rf is None or not (ids or refined):
+        stream.ctx.check(setter(stream.h, None, None, 0, 0, 0.0, 0.0))
+        return None
+    lm, tr = stream._lm_next, stream._tr_next
+    if lm is None or tr is None:
+        raise ValueError("bind_refine goes after bind_tracks: it is a companion of a pending Tracks")
+    if not isinstance(rf, RefinedLandmarks) or rf.refined.device != stream.device or rf.ids.device != stream.device:
+        raise ValueError("bind_refine takes a RefinedLandmarks on the stream's device (or None)")
+    if rf.cap != lm.cap or rf.n_pairs < lm.n_pairs:
+        raise ValueError(f"the RefinedLandmarks ({rf.n_pairs} pairs, cap {rf.cap}) must have the bound Landmarks' cap "
+                         f"and pairs ({lm.n_pairs}, cap {lm.cap})")
+    stream._after_torch()  # the buffers' fill ran on torch's stream: order the library's writes after it
+    stream.ctx.check(setter(stream.h, rf.refined.data_ptr() if refined else None, rf.ids.data_ptr() if ids else None,
+                            int(views), int(iters), float(huber_px), float(inlier_px)))
+    return rf
+
+
 def _bind_track_poses(stream, setter, tp, iters, huber_px, inlier_px, min_points):
     """The one-shot pose binding of both stream classes; returns what to keep referenced."""
     if tp is None:
@@ -202,6 +249,7 @@ class FrameStream:
         self._lm_pending = {}  # Landmarks of batches not yet retired, by their records' device address
         self._tr_next = None  # bind_tracks: the Tracks the next batch takes with its Landmarks
         self._tp_next = None  # bind_track_poses: the TrackPoses it takes with them
+        self._rf_next = None  # bind_refine: and the RefinedLandmarks
         self.width, self.height, self.max_frames, self.nfeatures = width, height, max_frames, nfeatures
         self.K = K.reshape(3, 3)
         if ratio:
@@ -229,7 +277,7 @@ class FrameStream:
         after it writes nothing.  None clears a binding no batch has taken yet."""
         self._lm_next = _bind_landmarks(self, self.ctx.lib.dvo_stream_set_landmarks, lm)
         if lm is None:
-            self._tr_next = self._tp_next = None  # the library clears pending tracks and pose bindings with it
+            self._tr_next = self._tp_next = self._rf_next = None  # the library clears the companions with it
 
     def bind_tracks(self, tr: Tracks | None):
         """Have the next batch also write its tracks into `tr` (dvo_stream_set_tracks), after its
@@ -237,7 +285,7 @@ class FrameStream:
         same cap.  One-shot, like the landmark binding; None clears a pending binding.  Only for
         batches of consecutive frames: process_pairs / submit_pairs raise ValueError."""
         self._tr_next = _bind_tracks(self, self.ctx.lib.dvo_stream_set_tracks, tr)
-        self._tp_next = None  # the library's call cleared a pending pose binding: bind poses last
+        self._tp_next = self._rf_next = None  # the library's call cleared pending pose and refine bindings
 
     def bind_track_poses(self, tp: TrackPoses | None, iters: int = 10, huber_px: float = 1.0, inlier_px: float = 2.0,
                          min_points: int = 6):
@@ -246,8 +294,20 @@ class FrameStream:
         steps (at most 32); huber_px, inlier_px: the Huber width and the inlier bound in pixels;
         min_points: shared landmarks a pair needs (at least 3).  One-shot; None clears a pending
         binding, as bind_tracks and bind_landmarks(None) do."""
+        self._rf_next = None  # the library's call clears a pending refine binding: bind refine last
         self._tp_next = _bind_track_poses(self, self.ctx.lib.dvo_stream_set_track_poses, tp, iters, huber_px,
                                           inlier_px, min_points)
+
+    def bind_refine(self, rf: RefinedLandmarks | None, views: int = 6, iters: int = 5, huber_px: float = 1.0,
+                    inlier_px: float = 2.0, ids: bool = True, refined: bool = True):
+        """Have the next batch also write its track ids and refined landmarks into `rf`
+        (dvo_stream_set_track_refine), after its tracks and track poses.  Call it last: after
+        bind_tracks (ValueError otherwise) and after bind_track_poses where the refined poses are
+        to feed the fit.  views: frames of a track a landmark is fitted to (3..8); iters:
+        Gauss-Newton steps (at most 16); huber_px, inlier_px as for the poses; ids / refined:
+        which of the two outputs to write.  One-shot; None clears a pending binding."""
+        self._rf_next = _bind_refine(self, self.ctx.lib.dvo_stream_set_track_refine, rf, views, iters, huber_px,
+                                     inlier_px, ids, refined)
 
     def _lm_fits(self, pairs: int, shared: bool = True):
         if self._lm_next is not None and self._lm_next.n_pairs < pairs:
@@ -503,21 +563,24 @@ class FrameStream:
         lm, self._lm_next = self._lm_next, None
         tr, self._tr_next = self._tr_next, None
         tp, self._tp_next = self._tp_next, None
+        rf, self._rf_next = self._rf_next, None
         if lm is not None and self._pending:
-            self._lm_pending[next(reversed(self._pending))] = (lm, tr, tp)
+            self._lm_pending[next(reversed(self._pending))] = (lm, tr, tp, rf)
         out, lms = [], []
         for i in range(min(n, cap)):
             t = self._pending.pop(recs[i], None)
             if t is None:
                 raise RuntimeError("retired records that were not submitted through this FrameStream")
             out.append((t, int(pairs[i])))
-            lm, tr, tp = self._lm_pending.pop(recs[i], (None, None, None))
+            lm, tr, tp, rf = self._lm_pending.pop(recs[i], (None, None, None, None))
             if lm is not None:
                 lms += [lm.entries, lm.counts]
             if tr is not None:
                 lms += [tr.links, tr.scales]
             if tp is not None:
                 lms += [tp.poses]
+            if rf is not None:
+                lms += [rf.refined, rf.ids]
         if out:
             # the retire kernels (records_kernel, the landmark kernels) writing these buffers are
             # queued on the library's stream by the call that retired them: keep the tensors alive
@@ -657,7 +720,7 @@ class FrameStream:
                 self._held.clear()
             self._last = ()
             self._pending = {}
-            self._lm_next, self._lm_pending, self._tr_next, self._tp_next = None, {}, None, None
+            self._lm_next, self._lm_pending, self._tr_next, self._tp_next, self._rf_next = None, {}, None, None, None
 
     def __del__(self):
         try:
@@ -768,6 +831,7 @@ class KnnFrameStream:
         self._lm_next = None  # bind_landmarks: the Landmarks the next process() / finish() takes
         self._tr_next = None  # bind_tracks: the Tracks it takes with them
         self._tp_next = None  # bind_track_poses: and the TrackPoses
+        self._rf_next = None  # bind_refine: and the RefinedLandmarks
         self.width, self.height, self.max_frames = int(width), int(height), int(max_frames)
         self.dim = 64 if cfg.detector == 1 else 128
         self.K = K.reshape(3, 3)
@@ -785,14 +849,14 @@ class KnnFrameStream:
         that batch.  One-shot: the batch after it writes nothing.  None clears a pending binding."""
         self._lm_next = _bind_landmarks(self, self.ctx.lib.dvo_knn_stream_set_landmarks, lm)
         if lm is None:
-            self._tr_next = self._tp_next = None  # the library clears pending tracks and pose bindings with it
+            self._tr_next = self._tp_next = self._rf_next = None  # the library clears the companions with it
 
     def bind_tracks(self, tr: Tracks | None):
         """Have the next batch also write its tracks into `tr` (dvo_knn_stream_set_tracks), after
         its landmarks.  Call it after bind_landmarks (ValueError otherwise), with a Tracks of the
         same cap.  One-shot; None clears a pending binding; detect*() alone does not take it."""
         self._tr_next = _bind_tracks(self, self.ctx.lib.dvo_knn_stream_set_tracks, tr)
-        self._tp_next = None  # the library's call cleared a pending pose binding: bind poses last
+        self._tp_next = self._rf_next = None  # the library's call cleared pending pose and refine bindings
 
     def bind_track_poses(self, tp: TrackPoses | None, iters: int = 10, huber_px: float = 1.0, inlier_px: float = 2.0,
                          min_points: int = 6):
@@ -800,8 +864,18 @@ class KnnFrameStream:
         after its tracks.  Call it after bind_tracks (ValueError otherwise); the parameters are
         FrameStream.bind_track_poses's.  One-shot; None clears a pending binding; detect*() alone
         does not take it."""
+        self._rf_next = None  # the library's call clears a pending refine binding: bind refine last
         self._tp_next = _bind_track_poses(self, self.ctx.lib.dvo_knn_stream_set_track_poses, tp, iters, huber_px,
                                           inlier_px, min_points)
+
+    def bind_refine(self, rf: RefinedLandmarks | None, views: int = 6, iters: int = 5, huber_px: float = 1.0,
+                    inlier_px: float = 2.0, ids: bool = True, refined: bool = True):
+        """Have the next batch also write its track ids and refined landmarks into `rf`
+        (dvo_knn_stream_set_track_refine), after its tracks and track poses; the parameters are
+        FrameStream.bind_refine's.  Call it last.  One-shot; None clears a pending binding;
+        detect*() alone does not take it."""
+        self._rf_next = _bind_refine(self, self.ctx.lib.dvo_knn_stream_set_track_refine, rf, views, iters, huber_px,
+                                     inlier_px, ids, refined)
 
     def _lm_fits(self, pairs: int):
         if self._lm_next is not None and self._lm_next.n_pairs < pairs:
@@ -812,8 +886,9 @@ class KnnFrameStream:
         lm, self._lm_next = self._lm_next, None
         tr, self._tr_next = self._tr_next, None
         tp, self._tp_next = self._tp_next, None
+        rf, self._rf_next = self._rf_next, None
         return ((() if lm is None else (lm.entries, lm.counts)) + (() if tr is None else (tr.links, tr.scales))
-                + (() if tp is None else (tp.poses,)))
+                + (() if tp is None else (tp.poses,)) + (() if rf is None else (rf.refined, rf.ids)))
 
     def set_detect_group(self, group: int):
         """SIFT frames per detection launch from the next process() on (0: frame by frame).  Waits

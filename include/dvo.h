@@ -1156,6 +1156,107 @@ int dvo_stream_set_track_poses(dvo_stream* s, dvo_track_pose* d_pose, int iters,
 int dvo_knn_stream_set_track_poses(dvo_knn_stream* s, dvo_track_pose* d_pose, int iters, double huber_px,
                                    double inlier_px, int min_points);
 
+/* ---------------------------------------------------------------------------
+ * Track ids and refined landmarks: for every landmark the track it belongs to, and its position
+ * re-estimated from the most recent frames of that track.  An opt-in companion of a tracks
+ * binding.  A landmark's X, Y, Z is the two-view DLT point of one pair; under narrow-baseline
+ * motion its depth is the noisiest quantity a batch holds, and a point seen in several
+ * consecutive frames has wider parallax and more observations than any pair offers.  Both
+ * outputs are laid out [pairs][cap] in parallel with the landmark slots and computed on the full
+ * lists and full links: nothing depends on cap.  Slots [0, min(count, cap)) are written; bytes
+ * outside them are not touched.
+ *
+ * Chain.  link(p, o) is the link above, of the full list.  The chain of landmark (p, o) is
+ * c_0 = (p, o) and c_{k+1} = (p - k - 1, link(c_k)) while that link is >= 0.  By the link rule a
+ * landmark has at most one predecessor, and the smallest ordinal wins a shared one, so chains
+ * are simple paths; they never cross a failed or empty pair and never leave the batch.
+ *
+ * Ids.  age = the number of links to the chain's end (0 without a predecessor), root_pair =
+ * p - age, root_ord = the ordinal of the chain's last element in pair root_pair's full list (it
+ * may be >= cap, as a link may), reserved = 0.  Exact integers.
+ *
+ * Unit motion of pair q: (R_q, d_q, rho_q), camera q + 1 from camera q with |d_q| = 1 and rho_q =
+ * baseline q over baseline q - 1.  Where a track-poses binding was pending when this one was
+ * made and pose[q].status == DVO_TRACK_POSE_OK:  R_q = pose[q].R, d_q[i] = pose[q].t[i] /
+ * pose[q].scale, rho_q = pose[q].scale.  Otherwise R_q = rec[q].R, d_q = rec[q].t, rho_q =
+ * scale[q].ratio.
+ *
+ * Window cameras of pair p, the same for every landmark of the pair: camera p - k from the
+ * landmark's own frame p, in units of baseline p.  In double, every operation rounded once, in
+ * the written order.  A_0 = I, b_0 = 0, sigma_0 = 1; for k = 1, 2, ... with q = p - k:
+ *   the window ends before k if q < 0, if pair q or pair q + 1 has no landmarks, or if
+ *   !(rho_{q+1} > 0) (a pair that links nothing has ratio 0.0, so the first two follow from the
+ *   third);
+ *   sigma_k = sigma_{k-1} / rho_{q+1};  the window ends before k if sigma_k is not finite;
+ *   A_k[i][j] = (R_q[0][i] * A_{k-1}[0][j] + R_q[1][i] * A_{k-1}[1][j]) + R_q[2][i] * A_{k-1}[2][j]
+ *   c[i]      = b_{k-1}[i] - sigma_k * d_q[i]
+ *   b_k[i]    = (R_q[0][i] * c[0] + R_q[1][i] * c[1]) + R_q[2][i] * c[2]
+ * (A_k = R_q^T A_{k-1}, b_k = R_q^T (b_{k-1} - sigma_k d_q)).  W is the number of cameras k >= 1.
+ *
+ * Views of landmark (p, o).  n = min(chain length, views - 1, W + 1) chain elements give n + 1
+ * views: v = 0 is camera (I, 0) with (x1, y1) of c_0; v = 1 is camera (R_p, d_p) with (x2, y2)
+ * of c_0; v = k + 1 for k = 1..n-1 is camera (A_k, b_k) with (x1, y1) of c_k, the floats of the
+ * stream's point buffer at c_k's match.  Pixels go to double and are normalised as the track
+ * poses normalise them: nu = x * ax + bx, nv = y * ay + by.
+ *
+ * Fit.  X = the landmark's own (X, Y, Z).  One step, the views in ascending v, every sum
+ * starting at +0.0 and taking the views' terms in that order; per view with camera (A, b):
+ *   P_i = ((A[i][0] * X0 + A[i][1] * X1) + A[i][2] * X2) + b[i]
+ *   a view with !(P2 > 0) contributes nothing; otherwise
+ *   a = 1 / P2, u = P0 * a, v = P1 * a, ru = u - nu, rv = v - nv, e2 = ru * ru + rv * rv
+ *   w = 1 if e2 <= kh * kh, else kh / sqrt(e2), with kh = huber_px / ((fx + fy) / 2)
+ *   Ju[j] = a * (A[0][j] - u * A[2][j]),  Jv[j] = a * (A[1][j] - v * A[2][j])
+ * The 6 terms of H are w * (Ju[i] * Ju[j] + Jv[i] * Jv[j]) for i <= j, the upper triangle row by
+ * row; the 3 terms of g are w * (Ju[i] * ru + Jv[i] * rv).  H d = -g by the LDL^T of the track
+ * poses with 3 in place of 6, the same loops; the step fails unless every D[j] > 0 and every
+ * d[i] is finite.  X <- X + d, entry by entry.  Exactly `iters` steps are taken unless one fails:
+ * no convergence test.  A step that fails ends the landmark DEGENERATE on the X it started from.
+ *
+ * Final pass on the last X, with P, a, u, v, ru, rv as above: n_used = the views with P2 > 0;
+ * an inlier has P2 > 0 and e = (fx * ru) * (fx * ru) + (fy * rv) * (fy * rv) <= inlier_px *
+ * inlier_px; n_inliers their number; rms = sqrt(sum of the inliers' e in ascending v onto +0.0 /
+ * n_inliers), 0.0 with none.
+ *
+ * Status.  DVO_TRACK_REFINE_OK: X, Y, Z refined, views = n + 1, iters = the steps taken.
+ * DVO_TRACK_REFINE_NONE: fewer than 3 views (no predecessor, pair 0 of the batch, W = 0): the
+ * landmark's own X, Y, Z, views = 2, zero in rms, n_used, n_inliers, iters.
+ * DVO_TRACK_REFINE_DEGENERATE: a step failed; the final pass runs on the X that was kept.
+ * The refined point stands where the raw one stands: camera of frame p, units of baseline p. */
+#define DVO_TRACK_REFINE_OK 0
+#define DVO_TRACK_REFINE_NONE 1
+#define DVO_TRACK_REFINE_DEGENERATE 2
+typedef struct {              /* 16 bytes */
+    int32_t root_pair, root_ord, age, reserved;
+} dvo_track_id;
+typedef struct {              /* 56 bytes */
+    double X, Y, Z, rms;      /* rms in pixels */
+    int32_t views, n_used, n_inliers, iters, status, reserved;
+} dvo_landmark_refined;
+#ifdef __cplusplus
+static_assert(sizeof(dvo_track_id) == 16 && sizeof(dvo_landmark_refined) == 56, "layout");
+#else
+_Static_assert(sizeof(dvo_track_id) == 16 && sizeof(dvo_landmark_refined) == 56, "layout");
+#endif
+/* Binds d_refined and d_id, each [pairs][the landmark binding's cap], for the NEXT batch only.
+ * Either may be NULL (ids only, refined only); both NULL clears a pending binding.  DVO_EINVAL
+ * unless a tracks binding with non-NULL d_link and d_scale is pending.  A pose binding is
+ * optional and feeds the unit motions when it is pending at the time of this call.  views 3..8
+ * (default 6), iters 1..16 (default 5), huber_px (default 1.0; INFINITY weights every view 1),
+ * inlier_px (default 2.0): zero or negative means the default; DVO_EINVAL above the ranges, for
+ * views 1 or 2, or for a NaN.  Bind refine last: clearing the landmark binding and every
+ * dvo_stream_set_tracks and dvo_stream_set_track_poses call clear a pending refine binding.  It
+ * travels with the batch and is written when it retires, after the tracks and the track poses,
+ * on the stream's HIP stream with no read-back; a *_pairs call refuses it as it refuses tracks.
+ * The first binding allocates 20 B per slot of the point buffer for every pair set (4 B of full
+ * links, 16 B for the id kernel's two buffers), once; a stream that never binds it launches and
+ * holds what it did before, and the landmark, link, scale and pose bytes of a batch do not
+ * depend on the binding. */
+int dvo_stream_set_track_refine(dvo_stream* s, dvo_landmark_refined* d_refined, dvo_track_id* d_id, int views,
+                                int iters, double huber_px, double inlier_px);
+/* The same for a k-NN stream; a detect call alone consumes nothing. */
+int dvo_knn_stream_set_track_refine(dvo_knn_stream* s, dvo_landmark_refined* d_refined, dvo_track_id* d_id, int views,
+                                    int iters, double huber_px, double inlier_px);
+
 /* Test hooks: exercise one device algorithm in isolation. */
 /* KeyPointsFilter::retainBest permutation on `n` float responses (GPU emulation
  * of libstdc++ nth_element + partition); depth < 0 = libstdc++ default. */
@@ -1276,6 +1377,17 @@ int dvo_test_track_poses(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* co
                          const int32_t* mt, const int32_t* m, const dvo_pair_record* rec, int pairs, int cap, int stride,
                          int kp_cap, int cap_out, const double* K, int iters, double huber_px, double inlier_px,
                          int min_points, int32_t* link, dvo_track_scale* scale, dvo_track_pose* pose);
+/* dvo_test_track_poses with the id and refine kernels (dvo_stream_set_track_refine): each
+ * landmark's x1, y1 are read too, rf_views, rf_iters, rf_huber_px and rf_inlier_px are the
+ * binding's four parameters, defaults included, and use_poses says whether the poses feed the
+ * unit motions (a pose binding pending when refine was bound).  refined and id [pairs][cap_out]
+ * are copied up whole before the run and back whole after it; either may be NULL. */
+int dvo_test_track_refine(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* count, const int32_t* mq,
+                          const int32_t* mt, const int32_t* m, const dvo_pair_record* rec, int pairs, int cap, int stride,
+                          int kp_cap, int cap_out, const double* K, int iters, double huber_px, double inlier_px,
+                          int min_points, int32_t* link, dvo_track_scale* scale, dvo_track_pose* pose, int rf_views,
+                          int rf_iters, double rf_huber_px, double rf_inlier_px, int use_poses,
+                          dvo_landmark_refined* refined, dvo_track_id* id);
 
 #ifdef __cplusplus
 }
