@@ -18,6 +18,7 @@
 #include "dvo_internal.h"
 #include "jpeg_entropy.h"
 #include "jpeg_split.h"
+#include "pair_outputs.h"
 
 using namespace dvo;
 
@@ -80,84 +81,6 @@ struct dvo_ctx {
     int call_w = 0, call_h = 0, call_nf = 0;
 };
 
-// The caller's buffers of a landmark binding (dvo_stream_set_landmarks): [pairs][cap] entries, [pairs] counts.
-struct LandmarkBinding {
-    dvo_landmark* out = nullptr;  // null: no binding
-    int32_t* count = nullptr;
-    int cap = 0;
-};
-
-// The caller's buffers of a tracks binding (dvo_stream_set_tracks), beside a landmark binding.
-struct TracksBinding {
-    int32_t* link = nullptr;  // [pairs][the landmark binding's cap], or null
-    dvo_track_scale* scale = nullptr;  // [pairs], or null; both null: no binding
-    explicit operator bool() const { return link || scale; }
-};
-
-// The caller's buffer and parameters of a pose binding (dvo_stream_set_track_poses), beside a tracks binding.
-struct TrackPoseBinding {
-    dvo_track_pose* out = nullptr;  // [pairs]; null: no binding
-    int iters = 0, min_points = 0;
-    double huber_px = 0, inlier_px = 0;
-    // the pose fields of a retiring set's TrackArgs, from the set's GeomArgs and its part of the scratch
-    void fill(TrackArgs& a, const GeomArgs& g, TrackCorr* corr) const {
-        a.pose = out;
-        a.pts_f = g.pts_f;
-        a.fx = g.fx, a.fy = g.fy, a.cx = g.cx, a.cy = g.cy;
-        a.corr = corr;
-        a.pose_iters = iters;
-        a.pose_min_points = min_points;
-        a.huber_px = huber_px;
-        a.inlier_px = inlier_px;
-    }
-};
-
-// The parameters of a pose binding with the defaults filled in; false: out of range.
-inline bool track_pose_params(TrackPoseBinding& b, int iters, double huber_px, double inlier_px, int min_points) {
-    if (std::isnan(huber_px) || std::isnan(inlier_px)) return false;
-    b.iters = iters > 0 ? iters : 10;
-    b.huber_px = huber_px > 0 ? huber_px : 1.0;
-    b.inlier_px = inlier_px > 0 ? inlier_px : 2.0;
-    b.min_points = min_points > 0 ? min_points : 6;
-    return b.iters <= kTrackPoseMaxIters && b.min_points >= 3;
-}
-
-// The caller's buffers and parameters of a refine binding (dvo_stream_set_track_refine), beside a tracks binding.
-struct TrackRefineBinding {
-    dvo_landmark_refined* refined = nullptr;  // [pairs][the landmark binding's cap], or null
-    dvo_track_id* id = nullptr;               // the same, or null; both null: no binding
-    int views = 0, iters = 0;
-    double huber_px = 0, inlier_px = 0;
-    bool use_pose = false;  // a pose binding was pending when this one was made
-    explicit operator bool() const { return refined || id; }
-    // the refine fields of a retiring set's TrackArgs, from the set's GeomArgs and its part of the
-    // scratch: flink [pairs][pts_stride], rank two such buffers rank_stride apart
-    void fill(TrackArgs& a, const GeomArgs& g, int32_t* flink, TrackRank* rank, int64_t rank_stride) const {
-        a.pts_f = g.pts_f;
-        a.fx = g.fx, a.fy = g.fy, a.cx = g.cx, a.cy = g.cy;
-        a.flink = flink;
-        a.rank = rank;
-        a.rank_stride = rank_stride;
-        a.id = id;
-        a.refined = refined;
-        a.rf_views = views;
-        a.rf_iters = iters;
-        a.rf_use_pose = use_pose ? 1 : 0;
-        a.rf_huber_px = huber_px;
-        a.rf_inlier_px = inlier_px;
-    }
-};
-
-// The parameters of a refine binding with the defaults filled in; false: out of range.
-inline bool track_refine_params(TrackRefineBinding& b, int views, int iters, double huber_px, double inlier_px) {
-    if (std::isnan(huber_px) || std::isnan(inlier_px)) return false;
-    b.views = views > 0 ? views : 6;
-    b.iters = iters > 0 ? iters : 5;
-    b.huber_px = huber_px > 0 ? huber_px : 1.0;
-    b.inlier_px = inlier_px > 0 ? inlier_px : 2.0;
-    return b.views >= 3 && b.views <= kTrackRefineMaxViews && b.iters <= kTrackRefineMaxIters;
-}
-
 struct dvo_stream {
     dvo_ctx* ctx = nullptr;
     dvo_stream_config cfg{};
@@ -195,15 +118,9 @@ struct dvo_stream {
         int round = 0;  // the round this set runs next
         int pairs = 0;
         dvo_pair_record* rec = nullptr;  // the caller's records of the batch
-        LandmarkBinding lm;              // the batch's landmark binding, written when the set retires
-        TracksBinding tr;                // its tracks binding (the set's index copy was taken at the match)
-        TrackPoseBinding tp;             // its pose binding
-        TrackRefineBinding rf;           // its refine binding
+        PairOutputs out;  // the batch's bindings, written when the set retires (with tracks, the set's index copy was taken at the match)
     };
-    LandmarkBinding lm_next;  // dvo_stream_set_landmarks: taken by the next batch
-    TracksBinding tr_next;    // dvo_stream_set_tracks: taken with it
-    TrackPoseBinding tp_next;  // dvo_stream_set_track_poses: taken with them
-    TrackRefineBinding rf_next;  // dvo_stream_set_track_refine: taken with them
+    PairOutputs next;  // dvo_stream_set_landmarks / _tracks / _track_poses / _track_refine: taken by the next batch
     PairSet sets[kMaxSets];
     // their arrays: 1 set until the first submit, then kRansacRounds; pairs.all.g is the stream's GeomArgs
     PairSets pairs;
@@ -244,6 +161,12 @@ namespace {
 int fail(dvo_ctx* ctx, int code, const std::string& msg) {
     if (ctx) ctx->err = msg;
     return code;
+}
+
+// What a PairOutputs setter answered, as an entry point returns it.
+int bind_status(dvo_ctx* ctx, const BindResult& r) {
+    if (r.code == DVO_EHIP) return fail(ctx, r.code, std::string(r.what) + ": " + hipGetErrorString(r.hip));
+    return r.code == DVO_OK ? DVO_OK : fail(ctx, r.code, r.what);
 }
 
 int cv_round_f(float v) { return (int)lrintf(v); }
@@ -467,8 +390,69 @@ size_t hyp_cap(const dvo_stream* s) { return (size_t)(s->cfg.max_iters > 1 ? s->
 // next call that needs one allocates it.
 int ensure_sets(dvo_stream* s, int want) {
     dvo_ctx* ctx = s->ctx;
-    HIP_TRY(s->pairs.ensure(want, s->cfg.max_frames, s->plan.kp_cap, hyp_cap(s)));
+    HIP_TRY(s->pairs.ensure(want));
     return DVO_OK;
+}
+
+// A stream's geometry, for both frame streams (cfg: its configuration): the shape of its pair sets
+// (F pairs per set of cap points and hc hypotheses; track_sets, own_idx: PairSets::shape), the
+// configuration of its GeomArgs (sets.all.g), the first pair set, and into `mem` the round-local
+// arrays: the five-point records and parked Durand-Kerner lists of one merged round (a bound over
+// any number of sets: one set at each round).
+template <class Config>
+hipError_t stream_geometry(PairSets& sets, DeviceAllocs& mem, const Config& cfg, int F, int cap, size_t hc, int track_sets,
+                           bool own_idx, hipStream_t hs) {
+    sets.shape(F, cap, hc, track_sets, own_idx);
+    sets.stream = hs;
+    GeomArgs& g = sets.all.g;
+    g.pts_stride = cap;
+    set_camera(g, cfg.K);
+    g.prob = cfg.prob;
+    g.threshold = cfg.threshold;
+    g.max_iters = cfg.max_iters;
+    g.dist_thresh = cfg.dist_thresh;
+    g.hyp_cap = (int)hc;
+    g.dk_list_cap = std::max<int64_t>(round_items_bound(F, (int)hc), (int64_t)hc);
+    const size_t blocks = (size_t)std::max<int64_t>(round_blocks_bound(F, (int)hc), (int64_t)(hc + 63) / 64);
+    hipError_t e = sets.ensure(1);
+    if (e == hipSuccess) e = mem.alloc(&g.fprec, blocks * 128 * 64 * sizeof(double) + 256);
+    if (e == hipSuccess) e = mem.alloc(&g.dk_ctl, (size_t)(2 + kDkMaxPasses) * sizeof(int32_t) + 256);
+    if (e == hipSuccess) e = mem.alloc(&g.dk_list, (size_t)(kDkMaxPasses - 1) * g.dk_list_cap * sizeof(int32_t) + 256);
+    return e;
+}
+
+// The geometry arrays of a per-call entry point, from its CallMem, for `pairs` pairs of `pts`
+// points and hc hypotheses each, a group on request.  kGeomRansac: what the normalize and RANSAC
+// stages use and leave (E, info), with hyp_cap and dk_list_cap; fprec has `blocks` five-point
+// blocks, by default what one round over every hypothesis of every pair needs, each pair's
+// hypotheses rounded up to whole blocks.  kGeomPose: what recoverPose leaves.
+constexpr int kGeomRansac = 1, kGeomPose = 2;
+void call_geometry(GeomArgs& g, CallMem& mem, int groups, size_t pairs, size_t pts, size_t hc, size_t blocks = 0) {
+    const size_t PH = pairs * hc;
+    if (groups & kGeomRansac) {
+        g.npts = mem.dev<double>(pairs * pts * 4);
+        g.models = mem.dev<double>(PH * 90);
+        g.nmod = mem.dev<int32_t>(PH);
+        g.cnt = mem.dev<int32_t>(PH * 10);
+        g.subsets = mem.dev<int32_t>(PH * 5);
+        g.rs = mem.dev<RansacState>(pairs);
+        g.fprec = mem.dev<double>((blocks ? blocks : (PH + 63) / 64 + pairs - 1) * 128 * 64);
+        g.dk_off = mem.dev<int32_t>(pairs + 1);
+        g.a_off = mem.dev<int32_t>(pairs + 1);
+        g.s_off = mem.dev<int32_t>(pairs + 1);
+        g.dk_ctl = mem.dev<int32_t>(2 + kDkMaxPasses);
+        g.dk_list_cap = (int64_t)PH;
+        g.dk_list = mem.dev<int32_t>((size_t)(kDkMaxPasses - 1) * PH);
+        g.hyp_cap = (int)hc;
+        g.E = mem.dev<double>(pairs * 90);
+        g.info = mem.dev<int32_t>(pairs * 4);
+    }
+    if (groups & kGeomPose) {
+        g.Rt = mem.dev<double>(pairs * 12);
+        g.good = mem.dev<int32_t>(pairs);
+        g.pose_P = mem.dev<double>(pairs * 72);
+        g.pose_cnt = mem.dev<int32_t>(pairs * 5);
+    }
 }
 
 int stream_alloc(dvo_stream* s) {
@@ -498,26 +482,10 @@ int stream_alloc(dvo_stream* s) {
     A(b.mq, (size_t)F * cap);
     A(b.mt, (size_t)F * cap);
     A(b.md, (size_t)F * cap);
-    const size_t hc = hyp_cap(s);
-    // the stream's GeomArgs: configuration and the round-local arrays here, once; the per-pair
-    // pointers are PairSets::ensure's
-    const dvo_stream_config& c = s->cfg;
-    GeomArgs& g = s->pairs.all.g;
-    g.pts_stride = cap;
-    set_camera(g, c.K);
-    g.prob = c.prob;
-    g.threshold = c.threshold;
-    g.max_iters = c.max_iters;
-    g.dist_thresh = c.dist_thresh;
-    g.hyp_cap = (int)hc;
-    g.dk_list_cap = std::max<int64_t>(round_items_bound(F, (int)hc), (int64_t)hc);
-    s->pairs.stream = s->hs;
-    if ((rc = ensure_sets(s, 1))) return rc;
-    // five-point records and parked Durand-Kerner lists of one merged round (a bound over any
-    // number of sets: one set at each round)
-    A(g.fprec, (size_t)std::max<int64_t>(round_blocks_bound(F, (int)hc), (int64_t)(hc + 63) / 64) * 128 * 64);
-    A(g.dk_ctl, (size_t)2 + kDkMaxPasses);
-    A(g.dk_list, (size_t)(kDkMaxPasses - 1) * g.dk_list_cap);
+    // the stream's GeomArgs and its round-local arrays, once; the track scratch covers every set a
+    // pipelined stream will hold, each with its own copy of the match indices
+    dvo_ctx* ctx = s->ctx;
+    HIP_TRY(stream_geometry(s->pairs, s->mem, s->cfg, F, cap, hyp_cap(s), kRansacRounds, true, s->hs));
     A(b.status, (size_t)F);
     A(s->d_frames, (size_t)F * frame_pitch(s) * s->cfg.height);
     A(s->d_carry, (size_t)28);
@@ -615,23 +583,7 @@ int retire_sets(dvo_stream* s) {
         const PairArrays v = s->pairs.view(k);
         HIP_TRY(launch_retire(v.g, st.pairs, v.hdr, st.rec, s->hs));
         if (s->ratio > 0) HIP_TRY(launch_hamming_ratio_status(v.hdr, st.pairs, st.rec, nullptr, s->hs));
-        if (st.lm.out)  // after the records are final: a landmark pair is one whose record got through
-            HIP_TRY(launch_landmarks(v.g, st.pairs, st.rec, s->pairs.lm, st.lm.out, st.lm.count, st.lm.cap, s->hs));
-        if (st.lm.out && st.tr) {  // on the lists the landmark kernels just left, with the set's own indices
-            TrackArgs a = s->pairs.track_args(k, s->cfg.max_frames, s->plan.kp_cap);
-            const size_t off = (size_t)k * s->cfg.max_frames * s->plan.kp_cap;
-            a.mq = s->pairs.tr.iq + off;
-            a.mt = s->pairs.tr.it + off;
-            a.idx_stride = s->plan.kp_cap;
-            a.idx_step = 1;
-            a.rec = st.rec;
-            a.link = st.tr.link;
-            a.cap = st.lm.cap;
-            a.scale = st.tr.scale;
-            if (st.tp.out) st.tp.fill(a, v.g, s->pairs.tr.corr + off);
-            if (st.rf) st.rf.fill(a, v.g, s->pairs.tr.flink + off, s->pairs.tr.rank + 2 * off, (int64_t)s->cfg.max_frames * s->plan.kp_cap);
-            HIP_TRY(launch_tracks(a, st.pairs, s->hs));
-        }
+        HIP_TRY(launch_pair_outputs(st.out, s->pairs, k, v.g, st.pairs, st.rec, nullptr, s->hs));  // with the set's own indices
         s->retired_rec[s->retired] = st.rec;
         s->retired_pairs[s->retired] = st.pairs;
         ++s->retired;
@@ -655,12 +607,9 @@ bool sets_pending(const dvo_stream* s) {
 int run_stream(dvo_stream* s, const uint8_t* d_frames, int n, int64_t fstride, int pitch, dvo_pair_record* d_rec,
                bool detect_only, int pair_step = 1, bool drain = true) {
     dvo_ctx* ctx = s->ctx;
-    // a landmark binding is for this batch alone, whether or not the call gets as far as its pairs
-    const LandmarkBinding lm = detect_only ? LandmarkBinding{} : std::exchange(s->lm_next, LandmarkBinding{});
-    const TracksBinding tr = detect_only ? TracksBinding{} : std::exchange(s->tr_next, TracksBinding{});
-    const TrackPoseBinding tp = detect_only ? TrackPoseBinding{} : std::exchange(s->tp_next, TrackPoseBinding{});
-    const TrackRefineBinding rf = detect_only ? TrackRefineBinding{} : std::exchange(s->rf_next, TrackRefineBinding{});
-    if (tr && pair_step != 1)  // every binding is consumed
+    // the bindings are for this batch alone, whether or not the call gets as far as its pairs
+    const PairOutputs out = detect_only ? PairOutputs{} : s->next.take();
+    if (out.tr && pair_step != 1)  // every binding is consumed
         return fail(ctx, DVO_EINVAL, "tracks need consecutive pairs: the pairs of a *_pairs call share no frame");
     const int want = drain ? 1 : kRansacRounds;
     if (!detect_only && s->pairs.nsets < want) {
@@ -705,15 +654,15 @@ int run_stream(dvo_stream* s, const uint8_t* d_frames, int n, int64_t fstride, i
         else
             HIP_TRY(launch_match(P, s->cfg.cross_check, s->hs, ev));
         HIP_TRY(launch_pair_header(P, P.buf.hdr, s->hs));
-        if (lm.out && tr) {
+        if (out.lm.out && out.tr) {
             // the match indices are the stream's, not the set's: a later batch overwrites them
             // before this one retires, so a batch with tracks keeps its own copy
-            const size_t off = (size_t)k * s->cfg.max_frames * s->plan.kp_cap, nb = (size_t)pairs * s->plan.kp_cap * 4;
+            const size_t off = (size_t)k * s->pairs.set_slots(), nb = (size_t)pairs * s->plan.kp_cap * 4;
             HIP_TRY(hipMemcpyAsync(s->pairs.tr.iq + off, s->buf.mq, nb, hipMemcpyDeviceToDevice, s->hs));
             HIP_TRY(hipMemcpyAsync(s->pairs.tr.it + off, s->buf.mt, nb, hipMemcpyDeviceToDevice, s->hs));
         }
         HIP_TRY(launch_geometry_args(s->pairs.view(k).g, pairs, kStageNormalize, s->hs));
-        s->sets[k] = dvo_stream::PairSet{true, 0, pairs, d_rec, lm, tr, tp, rf};
+        s->sets[k] = dvo_stream::PairSet{true, 0, pairs, d_rec, out};
         s->last_set = k;
         // nsets >= 1 here: every path that matches has passed ensure_sets above
         s->next_set = (k + 1) % s->pairs.nsets;
@@ -1160,79 +1109,25 @@ int dvo_stream_set_ratio_test(dvo_stream* s, double ratio) {
 
 int dvo_stream_set_landmarks(dvo_stream* s, dvo_landmark* d_out, int32_t* d_count, int cap) {
     if (!s) return DVO_EINVAL;
-    dvo_ctx* ctx = s->ctx;
-    if (!d_out) {
-        s->lm_next = LandmarkBinding{};
-        s->tr_next = TracksBinding{};
-        s->tp_next = TrackPoseBinding{};
-        s->rf_next = TrackRefineBinding{};
-        return DVO_OK;
-    }
-    if (cap < 1 || !d_count) return fail(ctx, DVO_EINVAL, "landmarks need cap >= 1 and a count buffer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(s->pairs.ensure_landmarks(s->cfg.max_frames, s->plan.kp_cap));  // the first binding sizes the scratch
-    s->lm_next = LandmarkBinding{d_out, d_count, cap};
-    return DVO_OK;
+    return bind_status(s->ctx, s->next.set_landmarks(s->pairs, s->ctx->device, d_out, d_count, cap));
 }
 
 int dvo_stream_set_tracks(dvo_stream* s, int32_t* d_link, dvo_track_scale* d_scale) {
     if (!s) return DVO_EINVAL;
-    dvo_ctx* ctx = s->ctx;
-    s->tp_next = TrackPoseBinding{};  // a pose binding goes after the tracks binding it reads
-    s->rf_next = TrackRefineBinding{};  // and a refine binding after both
-    if (!d_link && !d_scale) {
-        s->tr_next = TracksBinding{};
-        return DVO_OK;
-    }
-    if (!s->lm_next.out) return fail(ctx, DVO_EINVAL, "tracks go with a pending landmark binding");
-    HIP_TRY(hipSetDevice(ctx->device));
-    // the first binding sizes the scratch, for every set a pipelined stream will hold
-    HIP_TRY(s->pairs.ensure_tracks(kRansacRounds, s->cfg.max_frames, s->plan.kp_cap, true));
-    s->tr_next = TracksBinding{d_link, d_scale};
-    return DVO_OK;
+    return bind_status(s->ctx, s->next.set_tracks(s->pairs, s->ctx->device, d_link, d_scale));
 }
 
 int dvo_stream_set_track_poses(dvo_stream* s, dvo_track_pose* d_pose, int iters, double huber_px, double inlier_px,
                                int min_points) {
     if (!s) return DVO_EINVAL;
-    dvo_ctx* ctx = s->ctx;
-    s->rf_next = TrackRefineBinding{};  // a refine binding goes after the pose binding it may read
-    if (!d_pose) {
-        s->tp_next = TrackPoseBinding{};
-        return DVO_OK;
-    }
-    if (!s->lm_next.out || !s->tr_next.scale)
-        return fail(ctx, DVO_EINVAL, "track poses go with a pending tracks binding that has a scale buffer");
-    TrackPoseBinding b;
-    if (!track_pose_params(b, iters, huber_px, inlier_px, min_points))
-        return fail(ctx, DVO_EINVAL, "track poses: iters <= 32, min_points >= 3, no NaN");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(s->pairs.ensure_track_poses(s->cfg.max_frames, s->plan.kp_cap));  // the first binding sizes the scratch
-    b.out = d_pose;
-    s->tp_next = b;
-    return DVO_OK;
+    return bind_status(s->ctx, s->next.set_track_poses(s->pairs, s->ctx->device, d_pose, iters, huber_px, inlier_px, min_points));
 }
 
 int dvo_stream_set_track_refine(dvo_stream* s, dvo_landmark_refined* d_refined, dvo_track_id* d_id, int views,
                                 int iters, double huber_px, double inlier_px) {
     if (!s) return DVO_EINVAL;
-    dvo_ctx* ctx = s->ctx;
-    if (!d_refined && !d_id) {
-        s->rf_next = TrackRefineBinding{};
-        return DVO_OK;
-    }
-    if (!s->lm_next.out || !s->tr_next.link || !s->tr_next.scale)
-        return fail(ctx, DVO_EINVAL, "track refine goes with a pending tracks binding that has link and scale buffers");
-    TrackRefineBinding b;
-    if (!track_refine_params(b, views, iters, huber_px, inlier_px))
-        return fail(ctx, DVO_EINVAL, "track refine: views 3..8, iters <= 16, no NaN");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(s->pairs.ensure_track_refine(s->cfg.max_frames, s->plan.kp_cap));  // the first binding sizes the scratch
-    b.refined = d_refined;
-    b.id = d_id;
-    b.use_pose = s->tp_next.out != nullptr;
-    s->rf_next = b;
-    return DVO_OK;
+    return bind_status(s->ctx,
+                       s->next.set_track_refine(s->pairs, s->ctx->device, d_refined, d_id, views, iters, huber_px, inlier_px));
 }
 
 int dvo_stream_sync(dvo_stream* s) {
@@ -2330,23 +2225,8 @@ int dvo_find_essential_mat(dvo_ctx* ctx, const double* p1, const double* p2, int
     g.prob = prob;
     g.threshold = threshold;
     g.max_iters = max_iters;
-    g.npts = mem.dev<double>((size_t)m * 4);
-    g.models = mem.dev<double>(hc * 90);
-    g.E = mem.dev<double>(90);
-    g.info = mem.dev<int32_t>(4);
+    call_geometry(g, mem, kGeomRansac, 1, (size_t)m, hc);
     g.mask = mem.dev<uint8_t>(m);
-    g.nmod = mem.dev<int32_t>(hc);
-    g.cnt = mem.dev<int32_t>(hc * 10);
-    g.subsets = mem.dev<int32_t>(hc * 5);
-    g.rs = mem.dev<RansacState>(1);
-    g.fprec = mem.dev<double>(((hc + 63) / 64) * 128 * 64);
-    g.dk_off = mem.dev<int32_t>(2);
-    g.a_off = mem.dev<int32_t>(2);
-    g.s_off = mem.dev<int32_t>(2);
-    g.dk_ctl = mem.dev<int32_t>(2 + kDkMaxPasses);
-    g.dk_list = mem.dev<int32_t>(hc * 2);
-    g.dk_list_cap = (int64_t)hc;
-    g.hyp_cap = (int)hc;
     int rc = upload_points(ctx, mem, p1, p2, m, &g.pts_d);
     if (rc) return rc;
     HIP_TRY(launch_geometry_args(g, 1, kStageNormalize | kStageRansac | kStageOneRound, ctx->stream));
@@ -2379,15 +2259,14 @@ int dvo_recover_pose(dvo_ctx* ctx, const double* E, int e_rows, const double* p1
     g.pts_stride = mm;
     set_camera(g, K);
     g.dist_thresh = dist_thresh;
+    call_geometry(g, mem, kGeomPose, 1, (size_t)mm, 0);
+    // no RANSAC here: of that group only the normalised points, and E and info as inputs; and what
+    // only this entry point has: the chosen decomposition, the four masks, the caller's mask
     g.npts = mem.dev<double>((size_t)mm * 4);
     g.E = mem.dev<double>(90);
     g.info = mem.dev<int32_t>(4);
-    g.Rt = mem.dev<double>(12);
-    g.good = mem.dev<int32_t>(2);
     g.pick = mem.dev<int32_t>(2);
     g.pose_mask = mem.dev<uint8_t>((size_t)mm * 4);
-    g.pose_P = mem.dev<double>(72);
-    g.pose_cnt = mem.dev<int32_t>(5);
     uint8_t* dmin = mask_in ? mem.dev<uint8_t>(mm) : nullptr;
     g.mask_in = dmin;
     int rc = upload_points(ctx, mem, p1, p2, m, &g.pts_d);
@@ -2653,26 +2532,7 @@ int dvo_knn_pair_run(dvo_knn_pair* p, const uint8_t* prev_img, const uint8_t* cu
         g.threshold = c.threshold;
         g.max_iters = c.max_iters;
         g.dist_thresh = c.dist_thresh;
-        g.npts = mem.dev<double>((size_t)nq * 4);
-        g.models = mem.dev<double>(hc * 90);
-        g.E = mem.dev<double>(90);
-        g.info = mem.dev<int32_t>(4);
-        g.nmod = mem.dev<int32_t>(hc);
-        g.cnt = mem.dev<int32_t>(hc * 10);
-        g.subsets = mem.dev<int32_t>(hc * 5);
-        g.rs = mem.dev<RansacState>(1);
-        g.fprec = mem.dev<double>(((hc + 63) / 64) * 128 * 64);
-        g.dk_off = mem.dev<int32_t>(2);
-        g.a_off = mem.dev<int32_t>(2);
-        g.s_off = mem.dev<int32_t>(2);
-        g.dk_ctl = mem.dev<int32_t>(2 + kDkMaxPasses);
-        g.dk_list = mem.dev<int32_t>(hc * 2);
-        g.dk_list_cap = (int64_t)hc;
-        g.hyp_cap = (int)hc;
-        g.Rt = mem.dev<double>(12);
-        g.good = mem.dev<int32_t>(2);
-        g.pose_P = mem.dev<double>(72);
-        g.pose_cnt = mem.dev<int32_t>(5);
+        call_geometry(g, mem, kGeomRansac | kGeomPose, 1, (size_t)nq, hc);
         HIP_TRY(mem.error());
         HIP_TRY(launch_geometry_args(g, 1, kStageNormalize | kStageRansac | kStageOneRound, s));
         HIP_TRY(launch_retire(g, 1, p->hdr, p->rec, s));  // kStagePose and the record
@@ -2880,10 +2740,7 @@ struct dvo_knn_stream {
     DeviceAllocs raw_mem;
     uint8_t* raw = nullptr;
     int raw_pitch = 0;
-    LandmarkBinding lm_next;  // dvo_knn_stream_set_landmarks: taken by the next finish
-    TracksBinding tr_next;    // dvo_knn_stream_set_tracks: taken with it
-    TrackPoseBinding tp_next;  // dvo_knn_stream_set_track_poses: taken with them
-    TrackRefineBinding rf_next;  // dvo_knn_stream_set_track_refine: taken with them
+    PairOutputs next;  // dvo_knn_stream_set_landmarks / _tracks / _track_poses / _track_refine: taken by the next finish
     // A raw-input call records ev_in[k] before its input launch, k the one the last accepted call
     // does not use (first_ev; -1: that call began at ev[0]), so a refused call disturbs no figure.
     hipEvent_t ev_in[2] = {nullptr, nullptr};
@@ -2933,24 +2790,8 @@ int dvo_knn_stream_create(dvo_ctx* ctx, const dvo_knn_stream_config* cfg, dvo_kn
         return he == hipSuccess;
     });
     HIP_TRY(he);
-    // the geometry as a dvo_stream allocates it (stream_alloc): the per-pair arrays from PairSets,
-    // the round-local ones sized for the largest round of P pairs
-    const size_t hc = (size_t)cfg->max_iters;
-    GeomArgs& g = s->pairs.all.g;
-    g.pts_stride = cap;
-    set_camera(g, cfg->K);
-    g.prob = cfg->prob;
-    g.threshold = cfg->threshold;
-    g.max_iters = cfg->max_iters;
-    g.dist_thresh = cfg->dist_thresh;
-    g.hyp_cap = (int)hc;
-    g.dk_list_cap = std::max<int64_t>(round_items_bound(P, (int)hc), (int64_t)hc);
-    s->pairs.stream = ctx->stream;
-    HIP_TRY(s->pairs.ensure(1, P, cap, hc));
-    const size_t blocks = (size_t)std::max<int64_t>(round_blocks_bound(P, (int)hc), (int64_t)(hc + 63) / 64);
-    HIP_TRY(s->mem.alloc(&g.fprec, blocks * 128 * 64 * sizeof(double) + 256));
-    HIP_TRY(s->mem.alloc(&g.dk_ctl, (size_t)(2 + kDkMaxPasses) * sizeof(int32_t) + 256));
-    HIP_TRY(s->mem.alloc(&g.dk_list, (size_t)(kDkMaxPasses - 1) * g.dk_list_cap * sizeof(int32_t) + 256));
+    // the geometry as a dvo_stream has it: one set of P pairs, whose tracks read the batch's DMatch array
+    HIP_TRY(stream_geometry(s->pairs, s->mem, *cfg, P, cap, (size_t)cfg->max_iters, 1, false, ctx->stream));
     *out = s.release();
     return DVO_OK;
 }
@@ -3063,10 +2904,7 @@ int dvo_knn_stream_finish(dvo_knn_stream* st, dvo_pair_record* d_records, const 
     const KnnBatch& b = st->b;
     hipEvent_t* ev = st->profiling && st->pending_timed ? st->ev : nullptr;
     st->pending = 0;
-    const LandmarkBinding lm = std::exchange(st->lm_next, LandmarkBinding{});  // for this batch alone
-    const TracksBinding tr = std::exchange(st->tr_next, TracksBinding{});
-    const TrackPoseBinding tp = std::exchange(st->tp_next, TrackPoseBinding{});
-    const TrackRefineBinding rf = std::exchange(st->rf_next, TrackRefineBinding{});
+    const PairOutputs out = st->next.take();  // for this batch alone
     const int pairs = n_frames - 1;
     const PairArrays& v = st->pairs.all;
     const bool flann = st->fl.trees > 0;
@@ -3079,22 +2917,9 @@ int dvo_knn_stream_finish(dvo_knn_stream* st, dvo_pair_record* d_records, const 
         HIP_TRY(launch_geometry_args(v.g, pairs, kStageNormalize | kStageRansac, s));
         HIP_TRY(launch_retire(v.g, pairs, v.hdr, d_records, s));
         HIP_TRY(launch_knn_status(b.n, b.fstate, b.missing, pairs, d_records, s));
-        if (lm.out)  // after the records are final: a landmark pair is one whose record got through
-            HIP_TRY(launch_landmarks(v.g, pairs, d_records, st->pairs.lm, lm.out, lm.count, lm.cap, s));
-        if (lm.out && tr) {  // on the lists the landmark kernels just left; the batch's DMatch array is still its own
-            TrackArgs a = st->pairs.track_args(0, b.F - 1, b.cap);
-            a.mq = &b.matches->queryIdx;
-            a.mt = &b.matches->trainIdx;
-            a.idx_stride = b.cap;
-            a.idx_step = (int)(sizeof(dvo_dmatch) / sizeof(int32_t));
-            a.rec = d_records;
-            a.link = tr.link;
-            a.cap = lm.cap;
-            a.scale = tr.scale;
-            if (tp.out) tp.fill(a, v.g, st->pairs.tr.corr);
-            if (rf) rf.fill(a, v.g, st->pairs.tr.flink, st->pairs.tr.rank, (int64_t)(b.F - 1 > 0 ? b.F - 1 : 1) * b.cap);
-            HIP_TRY(launch_tracks(a, pairs, s));
-        }
+        // the batch's DMatch array is still its own
+        const TrackIndex idx{&b.matches->queryIdx, &b.matches->trainIdx, b.cap, (int)(sizeof(dvo_dmatch) / sizeof(int32_t))};
+        HIP_TRY(launch_pair_outputs(out, st->pairs, 0, v.g, pairs, d_records, &idx, s));
     }
     if (ev) {
         HIP_TRY(hipEventRecord(ev[3], s));
@@ -3107,78 +2932,25 @@ int dvo_knn_stream_finish(dvo_knn_stream* st, dvo_pair_record* d_records, const 
 
 int dvo_knn_stream_set_landmarks(dvo_knn_stream* s, dvo_landmark* d_out, int32_t* d_count, int cap) {
     if (!s) return DVO_EINVAL;
-    dvo_ctx* ctx = s->ctx;
-    if (!d_out) {
-        s->lm_next = LandmarkBinding{};
-        s->tr_next = TracksBinding{};
-        s->tp_next = TrackPoseBinding{};
-        s->rf_next = TrackRefineBinding{};
-        return DVO_OK;
-    }
-    if (cap < 1 || !d_count) return fail(ctx, DVO_EINVAL, "landmarks need cap >= 1 and a count buffer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(s->pairs.ensure_landmarks(s->b.F - 1, s->b.cap));  // the first binding sizes the scratch
-    s->lm_next = LandmarkBinding{d_out, d_count, cap};
-    return DVO_OK;
+    return bind_status(s->ctx, s->next.set_landmarks(s->pairs, s->ctx->device, d_out, d_count, cap));
 }
 
 int dvo_knn_stream_set_tracks(dvo_knn_stream* s, int32_t* d_link, dvo_track_scale* d_scale) {
     if (!s) return DVO_EINVAL;
-    dvo_ctx* ctx = s->ctx;
-    s->tp_next = TrackPoseBinding{};  // a pose binding goes after the tracks binding it reads
-    s->rf_next = TrackRefineBinding{};  // and a refine binding after both
-    if (!d_link && !d_scale) {
-        s->tr_next = TracksBinding{};
-        return DVO_OK;
-    }
-    if (!s->lm_next.out) return fail(ctx, DVO_EINVAL, "tracks go with a pending landmark binding");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(s->pairs.ensure_tracks(1, s->b.F - 1, s->b.cap, false));  // the first binding sizes the scratch
-    s->tr_next = TracksBinding{d_link, d_scale};
-    return DVO_OK;
+    return bind_status(s->ctx, s->next.set_tracks(s->pairs, s->ctx->device, d_link, d_scale));
 }
 
 int dvo_knn_stream_set_track_poses(dvo_knn_stream* s, dvo_track_pose* d_pose, int iters, double huber_px,
                                    double inlier_px, int min_points) {
     if (!s) return DVO_EINVAL;
-    dvo_ctx* ctx = s->ctx;
-    s->rf_next = TrackRefineBinding{};  // a refine binding goes after the pose binding it may read
-    if (!d_pose) {
-        s->tp_next = TrackPoseBinding{};
-        return DVO_OK;
-    }
-    if (!s->lm_next.out || !s->tr_next.scale)
-        return fail(ctx, DVO_EINVAL, "track poses go with a pending tracks binding that has a scale buffer");
-    TrackPoseBinding b;
-    if (!track_pose_params(b, iters, huber_px, inlier_px, min_points))
-        return fail(ctx, DVO_EINVAL, "track poses: iters <= 32, min_points >= 3, no NaN");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(s->pairs.ensure_track_poses(s->b.F - 1, s->b.cap));  // the first binding sizes the scratch
-    b.out = d_pose;
-    s->tp_next = b;
-    return DVO_OK;
+    return bind_status(s->ctx, s->next.set_track_poses(s->pairs, s->ctx->device, d_pose, iters, huber_px, inlier_px, min_points));
 }
 
 int dvo_knn_stream_set_track_refine(dvo_knn_stream* s, dvo_landmark_refined* d_refined, dvo_track_id* d_id, int views,
                                     int iters, double huber_px, double inlier_px) {
     if (!s) return DVO_EINVAL;
-    dvo_ctx* ctx = s->ctx;
-    if (!d_refined && !d_id) {
-        s->rf_next = TrackRefineBinding{};
-        return DVO_OK;
-    }
-    if (!s->lm_next.out || !s->tr_next.link || !s->tr_next.scale)
-        return fail(ctx, DVO_EINVAL, "track refine goes with a pending tracks binding that has link and scale buffers");
-    TrackRefineBinding b;
-    if (!track_refine_params(b, views, iters, huber_px, inlier_px))
-        return fail(ctx, DVO_EINVAL, "track refine: views 3..8, iters <= 16, no NaN");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(s->pairs.ensure_track_refine(s->b.F - 1, s->b.cap));  // the first binding sizes the scratch
-    b.refined = d_refined;
-    b.id = d_id;
-    b.use_pose = s->tp_next.out != nullptr;
-    s->rf_next = b;
-    return DVO_OK;
+    return bind_status(s->ctx,
+                       s->next.set_track_refine(s->pairs, s->ctx->device, d_refined, d_id, views, iters, huber_px, inlier_px));
 }
 
 int dvo_knn_stream_sync(dvo_knn_stream* s) {
@@ -3714,22 +3486,7 @@ int dvo_test_ransac_hypotheses(dvo_ctx* ctx, const double* pts, const int32_t* m
     g.prob = prob;
     g.threshold = threshold;
     g.max_iters = n_hyp;
-    g.hyp_cap = n_hyp;
-    g.npts = mem.dev<double>(npt);
-    g.models = mem.dev<double>(PH * 90);
-    g.E = mem.dev<double>((size_t)P * 90);
-    g.info = mem.dev<int32_t>((size_t)P * 4);
-    g.nmod = mem.dev<int32_t>(PH);
-    g.cnt = mem.dev<int32_t>(PH * 10);
-    g.subsets = mem.dev<int32_t>(PH * 5);
-    g.rs = mem.dev<RansacState>(P);
-    g.fprec = mem.dev<double>(nrec);
-    g.dk_off = mem.dev<int32_t>((size_t)P + 1);
-    g.a_off = mem.dev<int32_t>((size_t)P + 1);
-    g.s_off = mem.dev<int32_t>((size_t)P + 1);
-    g.dk_ctl = mem.dev<int32_t>(2 + kDkMaxPasses);
-    g.dk_list = mem.dev<int32_t>((size_t)(kDkMaxPasses - 1) * PH);
-    g.dk_list_cap = (int64_t)PH;
+    call_geometry(g, mem, kGeomRansac, (size_t)P, (size_t)stride, hc, nblocks);  // fprec: the nrec records read back below
     HIP_TRY(mem.error());
     HIP_TRY(mem.put(dpts, pts, npt * 8));
     HIP_TRY(mem.put(dm, m, (size_t)P * 4));
@@ -3818,26 +3575,7 @@ int dvo_test_landmarks(dvo_ctx* ctx, const float* pts, const int32_t* m, int pai
     g.threshold = threshold;
     g.max_iters = max_iters;
     g.dist_thresh = dist_thresh;
-    g.hyp_cap = max_iters;
-    g.npts = mem.dev<double>(npt);
-    g.models = mem.dev<double>(PH * 90);
-    g.nmod = mem.dev<int32_t>(PH);
-    g.cnt = mem.dev<int32_t>(PH * 10);
-    g.subsets = mem.dev<int32_t>(PH * 5);
-    g.rs = mem.dev<RansacState>(P);
-    g.fprec = mem.dev<double>(((PH + 63) / 64 + P) * 128 * 64);
-    g.dk_off = mem.dev<int32_t>(P + 1);
-    g.a_off = mem.dev<int32_t>(P + 1);
-    g.s_off = mem.dev<int32_t>(P + 1);
-    g.dk_ctl = mem.dev<int32_t>(2 + kDkMaxPasses);
-    g.dk_list = mem.dev<int32_t>((size_t)(kDkMaxPasses - 1) * PH);
-    g.dk_list_cap = (int64_t)PH;
-    g.E = mem.dev<double>(P * 90);
-    g.info = mem.dev<int32_t>(P * 4);
-    g.Rt = mem.dev<double>(P * 12);
-    g.good = mem.dev<int32_t>(P);
-    g.pose_P = mem.dev<double>(P * 72);
-    g.pose_cnt = mem.dev<int32_t>(P * 5);
+    call_geometry(g, mem, kGeomRansac | kGeomPose, P, (size_t)stride, hc);
     PairHeader* dhdr = mem.dev<PairHeader>(P);
     dvo_pair_record* drec = mem.dev<dvo_pair_record>(P);
     LandmarkScratch L;
@@ -3939,6 +3677,7 @@ static int test_tracks_run(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* 
     dvo_landmark_refined* drefined = rf && refined ? mem.dev<dvo_landmark_refined>(P * cap_out) : nullptr;
     dvo_track_id* did = rf && id ? mem.dev<dvo_track_id>(P * cap_out) : nullptr;
     HIP_TRY(mem.error());
+    // the scratch side by hand (what PairSets::track_args gives a stream), the caller's side as the streams fill it
     a.L.tmp = dtmp;
     a.L.tcnt = dtcnt;
     a.tiles = (int)tiles;
@@ -3946,33 +3685,30 @@ static int test_tracks_run(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* 
     a.mt = dt;
     a.idx_stride = stride;
     a.idx_step = 1;
-    a.rec = drec;
     a.kp_cap = kp_cap;
     a.pts_stride = stride;
-    a.cap = cap_out;
+    a.corr = dcorr;
+    a.flink = dflink;
+    a.rank = drank;
+    a.rank_stride = (int64_t)P * stride;
+    PairOutputs o;
+    o.lm.cap = cap_out;
+    o.tr = TracksBinding{a.link, a.scale};
+    if (tp) o.tp = *tp, o.tp.out = dpose;
+    if (rf) o.rf = *rf, o.rf.refined = drefined, o.rf.id = did;
+    GeomArgs g{};
+    g.pts_f = dpts;
+    if (tp) set_camera(g, K);
+    o.fill(a, g, drec);
     HIP_TRY(mem.put(dtmp, tmp.data(), tmp.size() * sizeof(LandmarkTmp)));
     HIP_TRY(mem.put(dtcnt, tcnt.data(), tcnt.size() * 4));
     HIP_TRY(mem.put(dq, mq, P * stride * 4));
     HIP_TRY(mem.put(dt, mt, P * stride * 4));
     HIP_TRY(mem.put(drec, rec, P * sizeof(dvo_pair_record)));
     HIP_TRY(mem.put(a.link, link, P * cap_out * 4));
-    if (tp) {
-        GeomArgs g{};
-        g.pts_f = dpts;
-        set_camera(g, K);
-        TrackPoseBinding b = *tp;
-        b.out = dpose;
-        b.fill(a, g, dcorr);
-        HIP_TRY(mem.put(dpts, pts.data(), pts.size() * sizeof(float)));
-        if (rf) {
-            TrackRefineBinding r = *rf;
-            r.refined = drefined;
-            r.id = did;
-            r.fill(a, g, dflink, drank, (int64_t)P * stride);
-            if (drefined) HIP_TRY(mem.put(drefined, refined, P * cap_out * sizeof(dvo_landmark_refined)));
-            if (did) HIP_TRY(mem.put(did, id, P * cap_out * sizeof(dvo_track_id)));
-        }
-    }
+    if (tp) HIP_TRY(mem.put(dpts, pts.data(), pts.size() * sizeof(float)));
+    if (drefined) HIP_TRY(mem.put(drefined, refined, P * cap_out * sizeof(dvo_landmark_refined)));
+    if (did) HIP_TRY(mem.put(did, id, P * cap_out * sizeof(dvo_track_id)));
     HIP_TRY(launch_tracks(a, pairs, ctx->stream));
     uint8_t *hlink, *hscale, *hpose = nullptr, *hrefined = nullptr, *hid = nullptr;
     if (drefined) HIP_TRY(mem.get(drefined, P * cap_out * sizeof(dvo_landmark_refined), &hrefined));

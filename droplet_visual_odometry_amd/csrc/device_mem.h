@@ -1,5 +1,6 @@
 // Host-side ownership of the library's device memory (api.cpp): DeviceAllocs frees what it
-// allocated, PairSets owns a stream's per-pair arrays and describes them once.  Host code only.
+// allocated, PairSets owns a stream's per-pair arrays and the scratches of its pair outputs
+// (pair_outputs.h) and describes them once.  Host code only.
 #pragma once
 
 #include <cstring>
@@ -91,10 +92,22 @@ struct PairArrays {
 struct PairSets {
     PairArrays all;  // null pointers while nsets == 0
     int nsets = 0;   // sets allocated (0: none)
+    // The stream's shape, stated once at its creation (shape()) and fixed for life: F pairs per set
+    // of cap points and hc hypotheses each; the sets its track scratch covers (the most the stream
+    // will ever hold) and whether a set keeps its own copy of the match indices there.
     int F = 0, cap = 0;
     size_t hc = 0;
+    int tr_sets = 0;
+    bool own_idx = false;
     hipStream_t stream = nullptr;  // the stream whose kernels use the arrays (ensure waits for it)
     DeviceAllocs mem;
+
+    void shape(int F_, int cap_, size_t hc_, int track_sets, bool own_idx_) {
+        F = F_, cap = cap_, hc = hc_, tr_sets = track_sets, own_idx = own_idx_;
+    }
+    // A set's slots in the scratches below: its pairs (one at least) of cap points.
+    size_t scratch_pairs() const { return (size_t)(F > 0 ? F : 1); }
+    size_t set_slots() const { return scratch_pairs() * cap; }
 
     // The one description of the arrays: f(pointer, elements per pair, whole-launch) per array, in
     // allocation order.  A whole-launch array has sets F + 1 elements and is not offset in a view.
@@ -129,18 +142,15 @@ struct PairSets {
         nsets = 0;
     }
 
-    // At least `want` sets of F pairs (kp_cap cap, hc hypotheses per pair).  Growing waits for the
-    // stream, frees the old sets, then allocates the new ones (never both at once: batches are
-    // sized to fill the card), each array n * sizeof(T) + 256 bytes.  On failure no set is left:
-    // nsets == 0 and every pointer is null, and a later ensure() starts afresh.
-    hipError_t ensure(int want, int F_, int cap_, size_t hc_) {
+    // At least `want` sets of the stream's shape.  Growing waits for the stream, frees the old
+    // sets, then allocates the new ones (never both at once: batches are sized to fill the card),
+    // each array n * sizeof(T) + 256 bytes.  On failure no set is left: nsets == 0 and every
+    // pointer is null, and a later ensure() starts afresh.
+    hipError_t ensure(int want) {
         if (nsets >= want) return hipSuccess;
         hipError_t e = hipSuccess;
         if (!mem.empty() && (e = hipStreamSynchronize(stream)) != hipSuccess) return e;
         release();
-        F = F_;
-        cap = cap_;
-        hc = hc_;
         const size_t SF = (size_t)want * F;
         rows(all, cap, hc, [&](auto*& p, size_t per_pair, bool whole) {
             if (e == hipSuccess) e = mem.alloc(&p, (whole ? SF + 1 : SF * per_pair) * sizeof(*p) + 256);
@@ -156,16 +166,16 @@ struct PairSets {
     }
 
     // The landmark kernels' scratch (launch_landmarks): empty until the stream's first binding
-    // (dvo_stream_set_landmarks), then one copy for F pairs of cap points whatever the number of
-    // sets, since it is live only between the two launches of one set's retire.  It does not
-    // depend on the sets' arrays: ensure() and release() leave it alone, and because F and cap
-    // are the stream's for life it is allocated once and never regrown (nothing is freed, no
-    // pointer a queued kernel holds goes stale).  A failure leaves it empty.
+    // (PairOutputs::set_landmarks), then one copy for a set's pairs whatever the number of sets,
+    // since it is live only between the two launches of one set's retire.  It does not depend on
+    // the sets' arrays: ensure() and release() leave it alone, and because the shape is the
+    // stream's for life it is allocated once and never regrown (nothing is freed, no pointer a
+    // queued kernel holds goes stale).  A failure leaves it empty.
     LandmarkScratch lm;
     DeviceAllocs lm_mem;
-    hipError_t ensure_landmarks(int F_, int cap_) {
+    hipError_t ensure_landmarks() {
         if (lm.tmp) return hipSuccess;
-        const size_t tiles = (size_t)landmark_tiles(cap_), n = (size_t)(F_ > 0 ? F_ : 1) * tiles;
+        const size_t n = scratch_pairs() * landmark_tiles(cap);
         DeviceAllocs fresh;
         LandmarkScratch l;
         hipError_t e = fresh.alloc(&l.tmp, n * kLandmarkTile * sizeof(LandmarkTmp) + 256);
@@ -177,53 +187,49 @@ struct PairSets {
     }
 
     // The track kernels' scratch (launch_tracks): empty until the stream's first tracks binding
-    // (dvo_stream_set_tracks), then `sets` copies for F pairs of cap points, sets being the most
-    // the stream will ever hold: like the landmark scratch it is allocated once, whatever ensure()
-    // does later, and never regrown.  own_idx: the ORB stream's per-set copy of its match indices.
+    // (PairOutputs::set_tracks), then tr_sets copies of a set's slots: like the landmark scratch it
+    // is allocated once, whatever ensure() does later, and never regrown.  With own_idx, iq and it:
+    // the ORB stream's per-set copy of its match indices.
     TrackScratch tr;
-    int tr_sets = 0;
     DeviceAllocs tr_mem;
-    hipError_t ensure_tracks(int sets, int F_, int cap_, bool own_idx) {
+    hipError_t ensure_tracks() {
         if (tr.table) return hipSuccess;
-        const size_t P = (size_t)sets * (F_ > 0 ? F_ : 1), n = P * cap_;
+        const size_t P = tr_sets * scratch_pairs(), n = tr_sets * set_slots();
         DeviceAllocs fresh;
         TrackScratch t;
         hipError_t e = fresh.alloc(&t.table, n * sizeof(int32_t) + 256);
         if (e == hipSuccess) e = fresh.alloc(&t.ratio, n * sizeof(double) + 256);
-        if (e == hipSuccess) e = fresh.alloc(&t.lcnt, P * landmark_tiles(cap_) * sizeof(int32_t) + 256);
+        if (e == hipSuccess) e = fresh.alloc(&t.lcnt, P * landmark_tiles(cap) * sizeof(int32_t) + 256);
         if (e == hipSuccess && own_idx) e = fresh.alloc(&t.iq, n * sizeof(int32_t) + 256);
         if (e == hipSuccess && own_idx) e = fresh.alloc(&t.it, n * sizeof(int32_t) + 256);
         if (e != hipSuccess) return e;
         tr_mem = std::move(fresh);
         tr = t;
-        tr_sets = sets;
         return hipSuccess;
     }
-    // The pose kernel's correspondences (dvo_stream_set_track_poses): 40 B per slot beside the
-    // ratios, for the sets the track scratch was sized for.  Allocated by the first pose binding
-    // (after the track scratch: a pose binding needs a pending tracks binding) and never regrown.
+    // The pose kernel's correspondences (PairOutputs::set_track_poses): 40 B per slot beside the
+    // ratios.  Allocated by the first pose binding (after the track scratch: a pose binding needs a
+    // pending tracks binding) and never regrown.
     DeviceAllocs tp_mem;
-    hipError_t ensure_track_poses(int F_, int cap_) {
+    hipError_t ensure_track_poses() {
         if (tr.corr) return hipSuccess;
         if (!tr.table) return hipErrorInvalidValue;
-        const size_t n = (size_t)tr_sets * (F_ > 0 ? F_ : 1) * cap_;
         DeviceAllocs fresh;
         TrackCorr* c = nullptr;
-        const hipError_t e = fresh.alloc(&c, n * sizeof(TrackCorr) + 256);
+        const hipError_t e = fresh.alloc(&c, tr_sets * set_slots() * sizeof(TrackCorr) + 256);
         if (e != hipSuccess) return e;
         tp_mem = std::move(fresh);
         tr.corr = c;
         return hipSuccess;
     }
-    // The full links and the id kernel's two rank buffers (dvo_stream_set_track_refine): 4 B and
-    // 16 B per slot, for the sets the track scratch was sized for.  Allocated by the first refine
-    // binding (after the track scratch: it needs a pending tracks binding) and never regrown.
-    // Set k's links start at flink + k F cap, its rank buffers at rank + 2 k F cap, F cap apart.
+    // The full links and the id kernel's two rank buffers (PairOutputs::set_track_refine): 4 B and
+    // 16 B per slot.  Allocated by the first refine binding (after the track scratch: it needs a
+    // pending tracks binding) and never regrown.
     DeviceAllocs rf_mem;
-    hipError_t ensure_track_refine(int F_, int cap_) {
+    hipError_t ensure_track_refine() {
         if (tr.flink) return hipSuccess;
         if (!tr.table) return hipErrorInvalidValue;
-        const size_t n = (size_t)tr_sets * (F_ > 0 ? F_ : 1) * cap_;
+        const size_t n = tr_sets * set_slots();
         DeviceAllocs fresh;
         int32_t* l = nullptr;
         TrackRank* r = nullptr;
@@ -235,18 +241,23 @@ struct PairSets {
         tr.rank = r;
         return hipSuccess;
     }
-    // Set k's part of it: the kernels' arguments but for the indices, the records and the caller's buffers
-    // (and a pose binding's fields: TrackPoseBinding::fill in api.cpp).
-    TrackArgs track_args(int k, int F_, int cap_) const {
-        const size_t P = (size_t)k * (F_ > 0 ? F_ : 1), n = P * cap_;
+    // Set k's part of every scratch there is, as the track kernels' arguments: all of a TrackArgs
+    // but the records and the caller's side (PairOutputs::fill in pair_outputs.h).  Set k's slots
+    // start k set_slots() into each array, its two rank buffers at rank + 2 k set_slots(), one
+    // set's slots apart; an own-index scratch is the set's index source.
+    TrackArgs track_args(int k) const {
+        const size_t n = k * set_slots();
         TrackArgs a{};
         a.L = lm;
-        a.tiles = landmark_tiles(cap_);
+        a.tiles = landmark_tiles(cap);
         a.table = tr.table + n;
-        a.kp_cap = cap_;
+        a.kp_cap = cap;
         a.ratio = tr.ratio + n;
-        a.pts_stride = cap_;
-        a.lcnt = tr.lcnt + P * a.tiles;
+        a.pts_stride = cap;
+        a.lcnt = tr.lcnt + k * scratch_pairs() * a.tiles;
+        if (tr.iq) a.mq = tr.iq + n, a.mt = tr.it + n, a.idx_stride = cap, a.idx_step = 1;
+        if (tr.corr) a.corr = tr.corr + n;
+        if (tr.flink) a.flink = tr.flink + n, a.rank = tr.rank + 2 * n, a.rank_stride = (int64_t)set_slots();
         return a;
     }
 

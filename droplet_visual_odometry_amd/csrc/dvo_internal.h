@@ -371,7 +371,8 @@ hipError_t launch_geometry(const StreamParams& P, const GeomArgs& g, dvo_pair_re
                            hipEvent_t* ev = nullptr, bool one_round = false);
 hipError_t launch_geometry_args(const GeomArgs& g, int pairs, int stages, hipStream_t s);
 // Stream batches (api.cpp dvo_stream_submit): the per-set pieces.  g_all spans every set (pairs
-// [0, nsets F)); g_set is one set's view (PairSets::view).
+// [0, nsets F)); g_set is one set's view (PairSets::view).  Both frame streams launch a retiring
+// set's landmarks and tracks through launch_pair_outputs (pair_outputs.h).
 hipError_t launch_pair_header(const StreamParams& P, PairHeader* hdr, hipStream_t s);
 hipError_t launch_ransac_round(const GeomArgs& g_all, const RoundSpec& spec, hipStream_t s);
 hipError_t launch_retire(const GeomArgs& g_set, int pairs, const PairHeader* hdr, dvo_pair_record* records,

@@ -1,70 +1,12 @@
 // Host check of csrc/device_mem.h (tests/test_device_mem_host.py builds it with the address and
 // undefined-behaviour sanitizers and runs it; no GPU).  The HIP allocation calls the header uses
-// are defined here: a fake allocator that records sizes, can fail the n-th hipMalloc, and aborts
+// are fake_hip.h's: a fake allocator that records sizes, can fail the n-th hipMalloc, and aborts
 // when asked to free a pointer it does not hold.
-#include <cstdio>
-#include <cstdlib>
-#include <map>
-#include <vector>
+#include "fake_hip.h"
 
 #include "../droplet_visual_odometry_amd/csrc/device_mem.h"
 
 using namespace dvo;
-
-namespace {
-std::map<void*, size_t> g_dev, g_pin;  // live allocations
-std::vector<size_t> g_mallocs;         // byte counts of the hipMalloc calls, in order (failed ones too)
-int g_fail_at = -1;                    // fail the hipMalloc call with this index in g_mallocs
-int g_syncs = 0, g_frees = 0;
-
-[[noreturn]] void die(const char* what, int line) {
-    std::fprintf(stderr, "device_mem_check: %s (line %d)\n", what, line);
-    std::abort();
-}
-#define CHECK(c) \
-    if (!(c)) die(#c, __LINE__)
-
-void reset_log() {
-    g_mallocs.clear();
-    g_fail_at = -1;
-    g_syncs = g_frees = 0;
-}
-}  // namespace
-
-extern "C" {
-hipError_t hipMalloc(void** p, size_t n) {
-    const bool fail = (int)g_mallocs.size() == g_fail_at;
-    g_mallocs.push_back(n);
-    if (fail) return hipErrorOutOfMemory;
-    *p = std::malloc(n ? n : 1);
-    g_dev[*p] = n;
-    return hipSuccess;
-}
-hipError_t hipFree(void* p) {
-    if (!g_dev.erase(p)) die("hipFree of a pointer that is not live", __LINE__);
-    std::free(p);
-    ++g_frees;
-    return hipSuccess;
-}
-hipError_t hipHostMalloc(void** p, size_t n, unsigned int) {
-    *p = std::malloc(n ? n : 1);
-    g_pin[*p] = n;
-    return hipSuccess;
-}
-hipError_t hipHostFree(void* p) {
-    if (!g_pin.erase(p)) die("hipHostFree of a pointer that is not live", __LINE__);
-    std::free(p);
-    return hipSuccess;
-}
-hipError_t hipStreamSynchronize(hipStream_t) {
-    ++g_syncs;
-    return hipSuccess;
-}
-hipError_t hipMemcpyAsync(void* dst, const void* src, size_t n, hipMemcpyKind, hipStream_t) {
-    std::memcpy(dst, src, n);
-    return hipSuccess;
-}
-}
 
 namespace {
 constexpr int F = 3, CAP = 7;
@@ -94,12 +36,13 @@ std::vector<const char*> pointers(const PairArrays& a) {
 void check_sizes_and_views() {
     static_assert(sizeof(RansacState) == 48 && sizeof(PairHeader) == 16, "the size table below assumes these");
     PairSets ps;
+    ps.shape(F, CAP, HC, 1, false);
     reset_log();
-    CHECK(ps.ensure(1, F, CAP, HC) == hipSuccess);
+    CHECK(ps.ensure(1) == hipSuccess);
     CHECK(ps.nsets == 1 && g_mallocs == expected_sizes(1) && g_syncs == 0 && g_frees == 0);
-    CHECK(ps.ensure(1, F, CAP, HC) == hipSuccess && g_mallocs.size() == 18);  // enough already: no call
+    CHECK(ps.ensure(1) == hipSuccess && g_mallocs.size() == 18);  // enough already: no call
     reset_log();
-    CHECK(ps.ensure(5, F, CAP, HC) == hipSuccess);
+    CHECK(ps.ensure(5) == hipSuccess);
     CHECK(ps.nsets == 5 && g_mallocs == expected_sizes(5));
     CHECK(g_syncs == 1 && g_frees == 18 && g_dev.size() == 18);  // waited, freed the old set first
     // bytes per pair of each per-set array (element size x elements per pair); 0: not offset
@@ -120,18 +63,19 @@ void check_sizes_and_views() {
 void check_failed_grow() {
     for (int n = 0; n < 18; ++n) {
         PairSets ps;
+        ps.shape(F, CAP, HC, 1, false);
         ps.all.g.fprec = reinterpret_cast<double*>(&ps);  // the stream's own members of g are not the sets'
         ps.all.g.hyp_cap = (int)HC;
-        CHECK(ps.ensure(1, F, CAP, HC) == hipSuccess);
+        CHECK(ps.ensure(1) == hipSuccess);
         reset_log();
         g_fail_at = n;
-        CHECK(ps.ensure(5, F, CAP, HC) != hipSuccess);
+        CHECK(ps.ensure(5) != hipSuccess);
         CHECK(ps.nsets == 0 && g_dev.empty() && (int)g_mallocs.size() == n + 1);
         for (const char* p : pointers(ps.all)) CHECK(p == nullptr);
         CHECK(ps.all.g.pts_f == nullptr && ps.all.g.m_arr == nullptr);
         CHECK(ps.all.g.fprec == reinterpret_cast<double*>(&ps) && ps.all.g.hyp_cap == (int)HC);
         reset_log();
-        CHECK(ps.ensure(1, F, CAP, HC) == hipSuccess);  // usable again: one set
+        CHECK(ps.ensure(1) == hipSuccess);  // usable again: one set
         CHECK(ps.nsets == 1 && g_mallocs == expected_sizes(1) && g_dev.size() == 18);
     }
     CHECK(g_dev.empty());
