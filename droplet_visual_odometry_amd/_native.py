@@ -65,6 +65,12 @@ LANDMARK_REFINED_DTYPE = np.dtype([("X", "<f8"), ("Y", "<f8"), ("Z", "<f8"), ("r
                                    ("reserved", "<i4")])
 assert LANDMARK_REFINED_DTYPE.itemsize == 56
 TRACK_REFINE_OK, TRACK_REFINE_NONE, TRACK_REFINE_DEGENERATE = 0, 1, 2
+# dvo_track_bundle: a pair's window cameras and landmarks fitted jointly (dvo_stream_set_track_bundle)
+TRACK_BUNDLE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("ratio", "<f8"), ("cost0", "<f8"),
+                               ("cost", "<f8"), ("rms0", "<f8"), ("rms", "<f8"), ("n_points", "<i4"), ("n_obs", "<i4"),
+                               ("n_inliers", "<i4"), ("n_cams", "<i4"), ("iters", "<i4"), ("status", "<i4")])
+assert TRACK_BUNDLE_DTYPE.itemsize == 160
+TRACK_BUNDLE_OK, TRACK_BUNDLE_NONE, TRACK_BUNDLE_DEGENERATE, TRACK_BUNDLE_NOT_IMPROVED = 0, 1, 2, 3
 
 
 class DVOError(RuntimeError):
@@ -200,6 +206,10 @@ _SIGNATURES = {
     "dvo_knn_stream_set_track_refine": ([_vp, _vp, _vp, _c, _c, _d, _d], _c),
     "dvo_test_track_refine": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c, _c, _c, _c, _c, _vp, _c, _d, _d, _c, _vp, _vp,
                                _vp, _c, _c, _d, _d, _c, _vp, _vp], _c),
+    "dvo_stream_set_track_bundle": ([_vp, _vp, _vp, _c, _c, _d, _d, _d, _c], _c),
+    "dvo_knn_stream_set_track_bundle": ([_vp, _vp, _vp, _c, _c, _d, _d, _d, _c], _c),
+    "dvo_test_track_bundle": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c, _c, _c, _c, _c, _vp, _c, _d, _d, _c, _vp, _vp,
+                               _vp, _c, _c, _d, _d, _d, _c, _c, _vp, _vp], _c),
     "dvo_knn_pair_create": ([_vp, ctypes.POINTER(KnnPairConfig), ctypes.POINTER(_vp)], _c),
     "dvo_knn_pair_destroy": ([_vp], None),
     "dvo_knn_pair_run": ([_vp, _vp, _vp, _c, _c, ctypes.POINTER(ctypes.c_uint64), _vp], _c),

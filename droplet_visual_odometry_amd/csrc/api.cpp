@@ -120,7 +120,7 @@ struct dvo_stream {
         dvo_pair_record* rec = nullptr;  // the caller's records of the batch
         PairOutputs out;  // the batch's bindings, written when the set retires (with tracks, the set's index copy was taken at the match)
     };
-    PairOutputs next;  // dvo_stream_set_landmarks / _tracks / _track_poses / _track_refine: taken by the next batch
+    PairOutputs next;  // dvo_stream_set_landmarks / _tracks / _track_poses / _track_refine / _track_bundle: taken by the next batch
     PairSet sets[kMaxSets];
     // their arrays: 1 set until the first submit, then kRansacRounds; pairs.all.g is the stream's GeomArgs
     PairSets pairs;
@@ -1128,6 +1128,13 @@ int dvo_stream_set_track_refine(dvo_stream* s, dvo_landmark_refined* d_refined, 
     if (!s) return DVO_EINVAL;
     return bind_status(s->ctx,
                        s->next.set_track_refine(s->pairs, s->ctx->device, d_refined, d_id, views, iters, huber_px, inlier_px));
+}
+
+int dvo_stream_set_track_bundle(dvo_stream* s, dvo_track_bundle* d_bundle, dvo_landmark_refined* d_points, int views,
+                                int iters, double lambda, double huber_px, double inlier_px, int min_points) {
+    if (!s) return DVO_EINVAL;
+    return bind_status(s->ctx, s->next.set_track_bundle(s->pairs, s->ctx->device, d_bundle, d_points, views, iters, lambda,
+                                                        huber_px, inlier_px, min_points));
 }
 
 int dvo_stream_sync(dvo_stream* s) {
@@ -2740,7 +2747,7 @@ struct dvo_knn_stream {
     DeviceAllocs raw_mem;
     uint8_t* raw = nullptr;
     int raw_pitch = 0;
-    PairOutputs next;  // dvo_knn_stream_set_landmarks / _tracks / _track_poses / _track_refine: taken by the next finish
+    PairOutputs next;  // dvo_knn_stream_set_landmarks / _tracks / _track_poses / _track_refine / _track_bundle: taken by the next finish
     // A raw-input call records ev_in[k] before its input launch, k the one the last accepted call
     // does not use (first_ev; -1: that call began at ev[0]), so a refused call disturbs no figure.
     hipEvent_t ev_in[2] = {nullptr, nullptr};
@@ -2951,6 +2958,14 @@ int dvo_knn_stream_set_track_refine(dvo_knn_stream* s, dvo_landmark_refined* d_r
     if (!s) return DVO_EINVAL;
     return bind_status(s->ctx,
                        s->next.set_track_refine(s->pairs, s->ctx->device, d_refined, d_id, views, iters, huber_px, inlier_px));
+}
+
+int dvo_knn_stream_set_track_bundle(dvo_knn_stream* s, dvo_track_bundle* d_bundle, dvo_landmark_refined* d_points,
+                                    int views, int iters, double lambda, double huber_px, double inlier_px,
+                                    int min_points) {
+    if (!s) return DVO_EINVAL;
+    return bind_status(s->ctx, s->next.set_track_bundle(s->pairs, s->ctx->device, d_bundle, d_points, views, iters, lambda,
+                                                        huber_px, inlier_px, min_points));
 }
 
 int dvo_knn_stream_sync(dvo_knn_stream* s) {
@@ -3618,12 +3633,15 @@ int dvo_test_landmarks(dvo_ctx* ctx, const float* pts, const int32_t* m, int pai
 }
 
 // dvo_test_tracks, and with tp (a binding without its buffer), K and pose dvo_test_track_poses, and
-// with rf (its parameters and use_pose) dvo_test_track_refine, refined and id each optional
+// with rf (its parameters and use_pose) dvo_test_track_refine, refined and id each optional, and
+// with bd (its parameters and use_pose) dvo_test_track_bundle, bundle and points each optional
 static int test_tracks_run(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* count, const int32_t* mq,
                            const int32_t* mt, const int32_t* m, const dvo_pair_record* rec, int pairs, int cap, int stride,
                            int kp_cap, int cap_out, int32_t* link, dvo_track_scale* scale, const double* K,
                            const TrackPoseBinding* tp, dvo_track_pose* pose, const TrackRefineBinding* rf = nullptr,
-                           dvo_landmark_refined* refined = nullptr, dvo_track_id* id = nullptr) {
+                           dvo_landmark_refined* refined = nullptr, dvo_track_id* id = nullptr,
+                           const TrackBundleBinding* bd = nullptr, dvo_track_bundle* bundle = nullptr,
+                           dvo_landmark_refined* points = nullptr) {
     if (!ctx || !lm || !count || !mq || !mt || !m || !rec || !link || !scale) return DVO_EINVAL;
     if (pairs < 1 || pairs > 65535 || cap < 1 || stride < 1 || kp_cap < 1 || cap_out < 1)
         return fail(ctx, DVO_EINVAL, "bad pair count, cap, stride, kp_cap or cap_out");
@@ -3672,10 +3690,13 @@ static int test_tracks_run(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* 
     float* dpts = tp ? mem.dev<float>(pts.size()) : nullptr;
     TrackCorr* dcorr = tp ? mem.dev<TrackCorr>(P * stride) : nullptr;
     dvo_track_pose* dpose = tp ? mem.dev<dvo_track_pose>(P) : nullptr;
-    int32_t* dflink = rf ? mem.dev<int32_t>(P * stride) : nullptr;
+    int32_t* dflink = rf || bd ? mem.dev<int32_t>(P * stride) : nullptr;
     TrackRank* drank = rf ? mem.dev<TrackRank>(2 * P * stride) : nullptr;
     dvo_landmark_refined* drefined = rf && refined ? mem.dev<dvo_landmark_refined>(P * cap_out) : nullptr;
     dvo_track_id* did = rf && id ? mem.dev<dvo_track_id>(P * cap_out) : nullptr;
+    BundlePoint* dbx = bd ? mem.dev<BundlePoint>(P * stride) : nullptr;
+    dvo_track_bundle* dbundle = bd && bundle ? mem.dev<dvo_track_bundle>(P) : nullptr;
+    dvo_landmark_refined* dpoints = bd && points ? mem.dev<dvo_landmark_refined>(P * cap_out) : nullptr;
     HIP_TRY(mem.error());
     // the scratch side by hand (what PairSets::track_args gives a stream), the caller's side as the streams fill it
     a.L.tmp = dtmp;
@@ -3691,11 +3712,13 @@ static int test_tracks_run(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* 
     a.flink = dflink;
     a.rank = drank;
     a.rank_stride = (int64_t)P * stride;
+    a.bd_x = dbx;
     PairOutputs o;
     o.lm.cap = cap_out;
     o.tr = TracksBinding{a.link, a.scale};
     if (tp) o.tp = *tp, o.tp.out = dpose;
     if (rf) o.rf = *rf, o.rf.refined = drefined, o.rf.id = did;
+    if (bd) o.bd = *bd, o.bd.out = dbundle, o.bd.points = dpoints;
     GeomArgs g{};
     g.pts_f = dpts;
     if (tp) set_camera(g, K);
@@ -3709,8 +3732,12 @@ static int test_tracks_run(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* 
     if (tp) HIP_TRY(mem.put(dpts, pts.data(), pts.size() * sizeof(float)));
     if (drefined) HIP_TRY(mem.put(drefined, refined, P * cap_out * sizeof(dvo_landmark_refined)));
     if (did) HIP_TRY(mem.put(did, id, P * cap_out * sizeof(dvo_track_id)));
+    if (dbundle) HIP_TRY(mem.put(dbundle, bundle, P * sizeof(dvo_track_bundle)));
+    if (dpoints) HIP_TRY(mem.put(dpoints, points, P * cap_out * sizeof(dvo_landmark_refined)));
     HIP_TRY(launch_tracks(a, pairs, ctx->stream));
-    uint8_t *hlink, *hscale, *hpose = nullptr, *hrefined = nullptr, *hid = nullptr;
+    uint8_t *hlink, *hscale, *hpose = nullptr, *hrefined = nullptr, *hid = nullptr, *hbundle = nullptr, *hpoints = nullptr;
+    if (dbundle) HIP_TRY(mem.get(dbundle, P * sizeof(dvo_track_bundle), &hbundle));
+    if (dpoints) HIP_TRY(mem.get(dpoints, P * cap_out * sizeof(dvo_landmark_refined), &hpoints));
     if (drefined) HIP_TRY(mem.get(drefined, P * cap_out * sizeof(dvo_landmark_refined), &hrefined));
     if (did) HIP_TRY(mem.get(did, P * cap_out * sizeof(dvo_track_id), &hid));
     HIP_TRY(mem.get(a.link, P * cap_out * 4, &hlink));
@@ -3722,6 +3749,8 @@ static int test_tracks_run(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* 
     if (tp) std::memcpy(pose, hpose, P * sizeof(dvo_track_pose));
     if (hrefined) std::memcpy(refined, hrefined, P * cap_out * sizeof(dvo_landmark_refined));
     if (hid) std::memcpy(id, hid, P * cap_out * sizeof(dvo_track_id));
+    if (hbundle) std::memcpy(bundle, hbundle, P * sizeof(dvo_track_bundle));
+    if (hpoints) std::memcpy(points, hpoints, P * cap_out * sizeof(dvo_landmark_refined));
     return DVO_OK;
 }
 
@@ -3759,6 +3788,24 @@ int dvo_test_track_refine(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* c
     r.use_pose = use_poses != 0;
     return test_tracks_run(ctx, lm, count, mq, mt, m, rec, pairs, cap, stride, kp_cap, cap_out, link, scale, K, &b, pose,
                            &r, refined, id);
+}
+
+int dvo_test_track_bundle(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* count, const int32_t* mq,
+                          const int32_t* mt, const int32_t* m, const dvo_pair_record* rec, int pairs, int cap, int stride,
+                          int kp_cap, int cap_out, const double* K, int iters, double huber_px, double inlier_px,
+                          int min_points, int32_t* link, dvo_track_scale* scale, dvo_track_pose* pose, int bd_views,
+                          int bd_iters, double bd_lambda, double bd_huber_px, double bd_inlier_px, int bd_min_points,
+                          int use_poses, dvo_track_bundle* bundle, dvo_landmark_refined* points) {
+    if (!ctx || !K || !pose || (!bundle && !points)) return DVO_EINVAL;
+    TrackPoseBinding b;
+    if (!track_pose_params(b, iters, huber_px, inlier_px, min_points))
+        return fail(ctx, DVO_EINVAL, "track poses: iters <= 32, min_points >= 3, no NaN");
+    TrackBundleBinding d;
+    if (!track_bundle_params(d, bd_views, bd_iters, bd_lambda, bd_huber_px, bd_inlier_px, bd_min_points))
+        return fail(ctx, DVO_EINVAL, "track bundle: views 2..8, iters <= 16, min_points >= 6, no NaN");
+    d.use_pose = use_poses != 0;
+    return test_tracks_run(ctx, lm, count, mq, mt, m, rec, pairs, cap, stride, kp_cap, cap_out, link, scale, K, &b, pose,
+                           nullptr, nullptr, nullptr, &d, bundle, points);
 }
 
 int dvo_test_five_point(dvo_ctx* ctx, const double* q1, const double* q2, double* models, int* n) {

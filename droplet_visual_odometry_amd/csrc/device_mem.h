@@ -241,10 +241,29 @@ struct PairSets {
         tr.rank = r;
         return hipSuccess;
     }
+    // The bundle kernel's points and full links of its own (PairOutputs::set_track_bundle): 32 B and
+    // 4 B per slot, one allocation, the links behind the points.  Allocated by the first bundle
+    // binding (after the track scratch: it needs a pending tracks binding) and never regrown.  The
+    // links are used where no refine binding has brought its own.
+    DeviceAllocs bd_mem;
+    hipError_t ensure_track_bundle() {
+        if (tr.bx) return hipSuccess;
+        if (!tr.table) return hipErrorInvalidValue;
+        const size_t n = tr_sets * set_slots();
+        DeviceAllocs fresh;
+        BundlePoint* b = nullptr;
+        const hipError_t e = fresh.alloc(&b, n * (sizeof(BundlePoint) + sizeof(int32_t)) + 256);
+        if (e != hipSuccess) return e;
+        bd_mem = std::move(fresh);
+        tr.bx = b;
+        tr.blink = reinterpret_cast<int32_t*>(b + n);
+        return hipSuccess;
+    }
     // Set k's part of every scratch there is, as the track kernels' arguments: all of a TrackArgs
     // but the records and the caller's side (PairOutputs::fill in pair_outputs.h).  Set k's slots
     // start k set_slots() into each array, its two rank buffers at rank + 2 k set_slots(), one
-    // set's slots apart; an own-index scratch is the set's index source.
+    // set's slots apart; an own-index scratch is the set's index source; the full links are the
+    // refine scratch's where there is one, else the bundle scratch's own.
     TrackArgs track_args(int k) const {
         const size_t n = k * set_slots();
         TrackArgs a{};
@@ -258,6 +277,8 @@ struct PairSets {
         if (tr.iq) a.mq = tr.iq + n, a.mt = tr.it + n, a.idx_stride = cap, a.idx_step = 1;
         if (tr.corr) a.corr = tr.corr + n;
         if (tr.flink) a.flink = tr.flink + n, a.rank = tr.rank + 2 * n, a.rank_stride = (int64_t)set_slots();
+        if (tr.bx) a.bd_x = tr.bx + n;
+        if (tr.bx && !a.flink) a.flink = tr.blink + n;
         return a;
     }
 

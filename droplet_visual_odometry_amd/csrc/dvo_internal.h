@@ -424,6 +424,17 @@ constexpr int kTrackRefineMaxIters = 16;
 struct TrackRank {  // 8 B: the links followed so far and the ordinal reached, in pair p - age
     int32_t age, ord;
 };
+// Track bundle (dvo_stream_set_track_bundle): with TrackArgs::bd_x set the link kernel writes the
+// full links as for a refine binding, and after the refine kernel the bundle kernel (a workgroup per
+// pair) fits the pair's window cameras and all its landmarks jointly: per step the landmarks are
+// linearised kBundleTile at a time into LDS, every entry of the reduced system is summed by its
+// owner lane in ordinal order, the system is factored across lanes and solved on lane 0, and the
+// landmarks back-substitute.  A landmark's current X and the steps that moved it live in bd_x.
+constexpr int kTrackBundleMaxIters = 16;
+struct BundlePoint {  // 32 B
+    double X[3];
+    int32_t steps, pad;
+};
 struct TrackScratch {
     int32_t* table = nullptr;  // [sets][pairs][kp_cap] smallest landmark ordinal per trainIdx
     double* ratio = nullptr;   // [sets][pairs][pts_stride] a tile's linked ratios from its first ordinal on
@@ -433,6 +444,8 @@ struct TrackScratch {
     TrackCorr* corr = nullptr;  // [sets][pairs][pts_stride] a tile's correspondences, as ratio (first pose binding)
     int32_t* flink = nullptr;   // [sets][pairs][pts_stride] every landmark's full link at its ordinal (first refine binding)
     TrackRank* rank = nullptr;  // [sets][2][pairs][pts_stride] the id kernel's ping-pong buffers (first refine binding)
+    BundlePoint* bx = nullptr;  // [sets][pairs][pts_stride] the bundle kernel's points (first bundle binding)
+    int32_t* blink = nullptr;   // [sets][pairs][pts_stride] full links of its own, behind bx in the same allocation
 };
 struct TrackArgs {
     LandmarkScratch L;  // the set's full landmark lists
@@ -465,6 +478,13 @@ struct TrackArgs {
     int rf_views, rf_iters;         // 3..kTrackRefineMaxViews, 1..kTrackRefineMaxIters
     int rf_use_pose;                // the unit motions come from `pose` where its status is OK
     double rf_huber_px, rf_inlier_px;  // > 0
+    // track bundle; all unused while bd_x is null (flink, pts_f, scale and the camera are read too)
+    BundlePoint* bd_x;                // [pairs][pts_stride]
+    dvo_track_bundle* bundle;         // the caller's [pairs], or null
+    dvo_landmark_refined* bd_points;  // the caller's [pairs][cap], or null
+    int bd_views, bd_iters;           // 2..kTrackRefineMaxViews, 1..kTrackBundleMaxIters
+    int bd_min_points, bd_use_pose;   // >= 6; the unit motions come from `pose` where its status is OK
+    double bd_lambda, bd_huber_px, bd_inlier_px;  // > 0
 };
 hipError_t launch_tracks(const TrackArgs& a, int pairs, hipStream_t s);
 // five-point record blocks a merged round can need (sizes the stream's GeomArgs::fprec, dk_list)

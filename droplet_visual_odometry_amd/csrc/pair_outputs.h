@@ -1,5 +1,5 @@
-// Host-side ownership of a stream's pair outputs (api.cpp): the caller's landmark, tracks, pose
-// and refine bindings of a batch, the rules of setting them, and the one launch of what they ask
+// Host-side ownership of a stream's pair outputs (api.cpp): the caller's landmark, tracks, pose,
+// refine and bundle bindings of a batch, the rules of setting them, and the one launch of what they ask
 // for when the batch's pair set retires.  Both frame streams use it.  Host code only.
 #pragma once
 
@@ -62,6 +62,29 @@ inline bool track_refine_params(TrackRefineBinding& b, int views, int iters, dou
     return b.views >= 3 && b.views <= kTrackRefineMaxViews && b.iters <= kTrackRefineMaxIters;
 }
 
+// The caller's buffers and parameters of a bundle binding (dvo_stream_set_track_bundle), beside a tracks binding.
+struct TrackBundleBinding {
+    dvo_track_bundle* out = nullptr;         // [pairs], or null
+    dvo_landmark_refined* points = nullptr;  // [pairs][the landmark binding's cap], or null; both null: no binding
+    int views = 0, iters = 0, min_points = 0;
+    double lambda = 0, huber_px = 0, inlier_px = 0;
+    bool use_pose = false;  // a pose binding was pending when this one was made
+    explicit operator bool() const { return out || points; }
+};
+
+// The parameters of a bundle binding with the defaults filled in; false: out of range.
+inline bool track_bundle_params(TrackBundleBinding& b, int views, int iters, double lambda, double huber_px,
+                                double inlier_px, int min_points) {
+    if (std::isnan(lambda) || std::isnan(huber_px) || std::isnan(inlier_px)) return false;
+    b.views = views > 0 ? views : 6;
+    b.iters = iters > 0 ? iters : 5;
+    b.lambda = lambda > 0 ? lambda : DVO_TRACK_BUNDLE_LAMBDA;
+    b.huber_px = huber_px > 0 ? huber_px : 1.0;
+    b.inlier_px = inlier_px > 0 ? inlier_px : 2.0;
+    b.min_points = min_points > 0 ? min_points : 8;
+    return b.views >= 2 && b.views <= kTrackRefineMaxViews && b.iters <= kTrackBundleMaxIters && b.min_points >= 6;
+}
+
 // What a setter answers.  DVO_OK; DVO_EINVAL and the message; or DVO_EHIP, the call that failed
 // and its error.
 struct BindResult {
@@ -70,7 +93,7 @@ struct BindResult {
     hipError_t hip = hipSuccess;
 };
 
-// The four bindings of one batch: pending in a stream until its next batch takes them, then the
+// The five bindings of one batch: pending in a stream until its next batch takes them, then the
 // batch's until its pair set retires.  The setters are the dvo_stream_set_* / dvo_knn_stream_set_*
 // entry points after their handle check: a later binding reads an earlier one, so setting an
 // earlier one clears the later ones, and each first binding sizes its scratch in `sets` (on
@@ -80,6 +103,7 @@ struct PairOutputs {
     TracksBinding tr;
     TrackPoseBinding tp;
     TrackRefineBinding rf;
+    TrackBundleBinding bd;
 
     PairOutputs take() { return std::exchange(*this, PairOutputs{}); }
 
@@ -97,6 +121,7 @@ struct PairOutputs {
     BindResult set_tracks(PairSets& sets, int device, int32_t* link, dvo_track_scale* scale) {
         tp = TrackPoseBinding{};    // a pose binding goes after the tracks binding it reads
         rf = TrackRefineBinding{};  // and a refine binding after both
+        bd = TrackBundleBinding{};  // and a bundle binding last
         if (!link && !scale) {
             tr = TracksBinding{};
             return {};
@@ -110,6 +135,7 @@ struct PairOutputs {
     BindResult set_track_poses(PairSets& sets, int device, dvo_track_pose* pose, int iters, double huber_px,
                                double inlier_px, int min_points) {
         rf = TrackRefineBinding{};  // a refine binding goes after the pose binding it may read
+        bd = TrackBundleBinding{};  // and so does a bundle binding
         if (!pose) {
             tp = TrackPoseBinding{};
             return {};
@@ -127,6 +153,7 @@ struct PairOutputs {
 
     BindResult set_track_refine(PairSets& sets, int device, dvo_landmark_refined* refined, dvo_track_id* id, int views,
                                 int iters, double huber_px, double inlier_px) {
+        bd = TrackBundleBinding{};  // a bundle binding goes last
         if (!refined && !id) {
             rf = TrackRefineBinding{};
             return {};
@@ -144,16 +171,36 @@ struct PairOutputs {
         return r;
     }
 
+    BindResult set_track_bundle(PairSets& sets, int device, dvo_track_bundle* bundle, dvo_landmark_refined* points,
+                                int views, int iters, double lambda, double huber_px, double inlier_px, int min_points) {
+        if (!bundle && !points) {
+            bd = TrackBundleBinding{};
+            return {};
+        }
+        if (!lm.out || !tr.link || !tr.scale)
+            return {DVO_EINVAL, "track bundle goes with a pending tracks binding that has link and scale buffers"};
+        TrackBundleBinding b;
+        if (!track_bundle_params(b, views, iters, lambda, huber_px, inlier_px, min_points))
+            return {DVO_EINVAL, "track bundle: views 2..8, iters <= 16, min_points >= 6, no NaN"};
+        const BindResult r = scratch(sets, device, &PairSets::ensure_track_bundle, "PairSets::ensure_track_bundle");
+        b.out = bundle;
+        b.points = points;
+        b.use_pose = tp.out != nullptr;
+        if (r.code == DVO_OK) bd = b;
+        return r;
+    }
+
     // The caller's side of a retiring set's TrackArgs, over the scratch side (PairSets::track_args,
     // or a test hook's own): the records, the buffers, the parameters, and for a pose or refine
-    // binding the points and camera of the set's GeomArgs.  The kernels take corr and flink for
-    // "a pose binding" and "a refine binding", so the scratch of an absent binding is taken out.
+    // binding the points and camera of the set's GeomArgs.  The kernels take corr, id / refined and
+    // bd_x for "a pose binding", "a refine binding" and "a bundle binding", so the scratch of an
+    // absent binding is taken out; the full links stay where either of the last two is there.
     void fill(TrackArgs& a, const GeomArgs& g, const dvo_pair_record* rec) const {
         a.rec = rec;
         a.link = tr.link;
         a.cap = lm.cap;
         a.scale = tr.scale;
-        if (tp.out || rf) {
+        if (tp.out || rf || bd) {
             a.pts_f = g.pts_f;
             a.fx = g.fx, a.fy = g.fy, a.cx = g.cx, a.cy = g.cy;
         }
@@ -175,9 +222,22 @@ struct PairOutputs {
             a.rf_huber_px = rf.huber_px;
             a.rf_inlier_px = rf.inlier_px;
         } else {
-            a.flink = nullptr;
+            if (!bd) a.flink = nullptr;
             a.rank = nullptr;
             a.rank_stride = 0;
+        }
+        if (bd) {
+            a.bundle = bd.out;
+            a.bd_points = bd.points;
+            a.bd_views = bd.views;
+            a.bd_iters = bd.iters;
+            a.bd_min_points = bd.min_points;
+            a.bd_use_pose = bd.use_pose ? 1 : 0;
+            a.bd_lambda = bd.lambda;
+            a.bd_huber_px = bd.huber_px;
+            a.bd_inlier_px = bd.inlier_px;
+        } else {
+            a.bd_x = nullptr;
         }
     }
 

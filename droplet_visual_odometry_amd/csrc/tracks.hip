@@ -29,6 +29,18 @@
 //                        sums per step (lane sums, shuffles inside a wave, the four wave totals
 //                        through LDS), the 6 x 6 LDL^T solve and the Cayley update on lane 0, the
 //                        new pose and a stop flag broadcast through LDS; then the final pass.
+// With a bundle binding (dvo.h dvo_stream_set_track_bundle) the link kernel writes the full links
+// too, and last of all:
+//   track_bundle_kernel  a workgroup per pair: thread 0 forms the window cameras in LDS; per step
+//                        the landmarks are linearised 32 at a time, lane per landmark, their blocks
+//                        (W, Y = W V^-1, the U and h terms, g) left in LDS, and every entry of the
+//                        reduced system S, r (up to 903 + 42, four per lane) adds the tile's
+//                        landmarks in ordinal order onto the value it keeps in registers; then the
+//                        LDL^T of S column by column across lanes, the two triangular solves on
+//                        lane 0, the landmarks' back-substitution (lane per landmark, the blocks
+//                        formed again) and the cameras' Cayley updates; the cost before and after,
+//                        the guard, the gauge division and the final pass, lane per landmark with
+//                        the pair's sums added in ordinal order by one lane each.
 // The arithmetic is the header's, one rounding per operation (-ffp-contract=off).
 #include "dvo_internal.h"
 
@@ -492,8 +504,8 @@ __global__ __launch_bounds__(kLandmarkTile) void track_id_kernel(TrackArgs a, in
 }
 
 // the unit motion of pair q (R row by row, d, rho)
-__device__ void refine_motion(const TrackArgs& a, int q, double* R, double* d, double* rho) {
-    if (a.rf_use_pose && a.pose[q].status == DVO_TRACK_POSE_OK) {
+__device__ void refine_motion(const TrackArgs& a, int use_pose, int q, double* R, double* d, double* rho) {
+    if (use_pose && a.pose[q].status == DVO_TRACK_POSE_OK) {
         const dvo_track_pose& s = a.pose[q];
 #pragma unroll
         for (int i = 0; i < 9; ++i) R[i] = s.R[i];
@@ -507,6 +519,47 @@ __device__ void refine_motion(const TrackArgs& a, int q, double* R, double* d, d
         for (int i = 0; i < 3; ++i) d[i] = a.rec[q].t[i];
         *rho = a.scale[q].ratio;
     }
+}
+
+// The header's window cameras of pair p into cam (view v: A row by row, then b): view 0 the
+// identity, view 1 the pair's unit motion, view k + 1 camera (A_k, b_k) for k = 1..W <= views - 2.
+// Returns W; *rho_p: the pair's own rho.
+__device__ int window_cameras(const TrackArgs& a, int p, int views, int use_pose, double (*cam)[12], double* rho_p) {
+    double A[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, b[3] = {0, 0, 0}, sigma = 1, R[9], d[3], rho;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) cam[0][i] = A[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) cam[0][9 + i] = 0.0;
+    refine_motion(a, use_pose, p, R, d, rho_p);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) cam[1][i] = R[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) cam[1][9 + i] = d[i];
+    int W = 0;
+    for (int k = 1; k <= views - 2; ++k) {  // camera k goes to view k + 1 <= views - 1
+        const int q = p - k;
+        if (q < 0) break;
+        refine_motion(a, use_pose, q + 1, R, d, &rho);
+        if (!(rho > 0)) break;  // also where pair q or q + 1 has no landmarks: pair q + 1 links nothing
+        sigma = sigma / rho;
+        if (!isfinite(sigma)) break;
+        refine_motion(a, use_pose, q, R, d, &rho);
+        double An[9], c[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) An[3 * i + j] = (R[i] * A[j] + R[3 + i] * A[3 + j]) + R[6 + i] * A[6 + j];
+            c[i] = b[i] - sigma * d[i];
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) b[i] = (R[i] * c[0] + R[3 + i] * c[1]) + R[6 + i] * c[2];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) cam[k + 1][i] = A[i] = An[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) cam[k + 1][9 + i] = b[i];
+        W = k;
+    }
+    return W;
 }
 
 // H d = -g by the header's LDL^T at size 3, S the 6 + 3 sums; false: a pivot not > 0 or a non-finite d
@@ -564,41 +617,8 @@ __global__ __launch_bounds__(kLandmarkTile) void track_refine_kernel(TrackArgs a
     const int32_t* tc = a.L.tcnt + (int64_t)p * a.tiles;
     if (tc[tile] == 0) return;
     if (tid == 0) {
-        double A[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, b[3] = {0, 0, 0}, sigma = 1, R[9], d[3], rho;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) cam[0][i] = A[i];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) cam[0][9 + i] = 0.0;
-        refine_motion(a, p, R, d, &rho);
-#pragma unroll
-        for (int i = 0; i < 9; ++i) cam[1][i] = R[i];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) cam[1][9 + i] = d[i];
-        int W = 0;
-        for (int k = 1; k <= a.rf_views - 2; ++k) {  // camera k goes to view k + 1 <= views - 1
-            const int q = p - k;
-            if (q < 0) break;
-            refine_motion(a, q + 1, R, d, &rho);
-            if (!(rho > 0)) break;  // also where pair q or q + 1 has no landmarks: pair q + 1 links nothing
-            sigma = sigma / rho;
-            if (!isfinite(sigma)) break;
-            refine_motion(a, q, R, d, &rho);
-            double An[9], c[3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-#pragma unroll
-                for (int j = 0; j < 3; ++j) An[3 * i + j] = (R[i] * A[j] + R[3 + i] * A[3 + j]) + R[6 + i] * A[6 + j];
-                c[i] = b[i] - sigma * d[i];
-            }
-#pragma unroll
-            for (int i = 0; i < 3; ++i) b[i] = (R[i] * c[0] + R[3 + i] * c[1]) + R[6 + i] * c[2];
-#pragma unroll
-            for (int i = 0; i < 9; ++i) cam[k + 1][i] = A[i] = An[i];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) cam[k + 1][9 + i] = b[i];
-            W = k;
-        }
-        win = W;
+        double rho;
+        win = window_cameras(a, p, a.rf_views, a.rf_use_pose, cam, &rho);
     }
     __syncthreads();
     if (tid >= tc[tile]) return;
@@ -726,6 +746,564 @@ __global__ __launch_bounds__(kLandmarkTile) void track_refine_kernel(TrackArgs a
     a.refined[(int64_t)p * a.cap + o] = out;
 }
 
+// ---- track bundle (dvo.h dvo_stream_set_track_bundle) ---------------------------------------------
+constexpr int kBundleNT = 256;
+constexpr int kBundleTile = 32;                      // landmarks linearised per tile
+constexpr int kBundleCamF = 63;                      // per camera c >= 1: W 18, Y 18, U terms 21, h terms 6
+constexpr int kBundleG = 7 * kBundleCamF;            // then g 3
+constexpr int kBundleF = kBundleG + 4;               // 445 doubles per landmark: odd, so a tile's lanes spread over the banks
+constexpr int kBundleMaxN = 6 * (kTrackRefineMaxViews - 1);  // 42 unknowns
+constexpr int kBundleLd = kBundleMaxN + 1;
+constexpr int kBundleEnt = 4;                        // entries per lane: 903 + 42 <= 4 * 256
+static_assert(kBundleMaxN * (kBundleMaxN + 1) / 2 + kBundleMaxN <= kBundleEnt * kBundleNT, "entries");
+static_assert(2 * kBundleNT <= kBundleTile * kBundleF, "the evaluation's two columns lie in the tile's blocks");
+
+// landmark o of pair p's full list
+__device__ __forceinline__ const LandmarkTmp& track_ordinal(const TrackArgs& a, int p, int o) {
+    const int32_t* tp = a.L.tcnt + (int64_t)p * a.tiles;
+    int t = 0, rem = o;
+    while (t < a.tiles - 1 && rem >= tp[t]) rem -= tp[t++];
+    return track_entry(a, p, t, min(rem, kLandmarkTile - 1));  // (never clamps: o is an ordinal)
+}
+
+// The views of landmark o of pair p over V cameras, as track_refine_kernel gathers them; returns their number.
+__device__ __forceinline__ int bundle_views(const TrackArgs& a, int p, int o, int match, int V, double* nu, double* nv) {
+    const double ax = 1. / a.fx, ay = 1. / a.fy, bx = -a.cx * ax, by = -a.cy * ay;
+#pragma unroll
+    for (int v = 0; v < kTrackRefineMaxViews; ++v) nu[v] = nv[v] = 0.0;
+    {
+        const float* px = a.pts_f + ((int64_t)p * a.pts_stride + match) * 4;
+        nu[0] = (double)px[0] * ax + bx, nv[0] = (double)px[1] * ay + by;
+        nu[1] = (double)px[2] * ax + bx, nv[1] = (double)px[3] * ay + by;
+    }
+    int nviews = 2, cur = o;
+#pragma unroll
+    for (int k = 1; k <= kTrackRefineMaxViews - 2; ++k) {
+        if (k <= V - 2 && cur >= 0) {  // V - 2 <= p: the window stops at pair 0
+            cur = a.flink[(int64_t)(p - k + 1) * a.pts_stride + cur];
+            if (cur >= 0) {
+                const int mi = track_ordinal(a, p - k, cur).match;
+                const float* px = a.pts_f + ((int64_t)(p - k) * a.pts_stride + mi) * 4;
+                nu[k + 1] = (double)px[0] * ax + bx, nv[k + 1] = (double)px[1] * ay + by;
+                nviews = k + 2;
+            }
+        }
+    }
+    return nviews;
+}
+
+struct BundleView {
+    double P0, P1, P2, ia, u, v, ru, rv, e2, w;
+    bool ok;
+};
+
+__device__ __forceinline__ BundleView bundle_view(const double* C, const double* X, double nu, double nv, double kh,
+                                                  double kh2) {
+    BundleView r;
+    r.P0 = ((C[0] * X[0] + C[1] * X[1]) + C[2] * X[2]) + C[9];
+    r.P1 = ((C[3] * X[0] + C[4] * X[1]) + C[5] * X[2]) + C[10];
+    r.P2 = ((C[6] * X[0] + C[7] * X[1]) + C[8] * X[2]) + C[11];
+    r.ok = r.P2 > 0;
+    r.ia = 1 / r.P2, r.u = r.P0 * r.ia, r.v = r.P1 * r.ia;
+    r.ru = r.u - nu, r.rv = r.v - nv, r.e2 = r.ru * r.ru + r.rv * r.rv;
+    r.w = r.e2 <= kh2 ? 1.0 : kh / sqrt(r.e2);
+    return r;
+}
+
+// the point and camera Jacobians of a view
+__device__ __forceinline__ void bundle_jx(const double* C, const BundleView& q, double* Ju, double* Jv) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        Ju[j] = q.ia * (C[j] - q.u * C[6 + j]);
+        Jv[j] = q.ia * (C[3 + j] - q.v * C[6 + j]);
+    }
+}
+__device__ __forceinline__ void bundle_jc(const BundleView& q, double* Ju, double* Jv) {
+    const double b = -(q.u * q.ia), c = -(q.v * q.ia);
+    Ju[0] = b * q.P1, Ju[1] = q.ia * q.P2 - b * q.P0, Ju[2] = -(q.ia * q.P1), Ju[3] = q.ia, Ju[4] = 0.0, Ju[5] = b;
+    Jv[0] = c * q.P1 - q.ia * q.P2, Jv[1] = -(c * q.P0), Jv[2] = q.ia * q.P0, Jv[3] = 0.0, Jv[4] = q.ia, Jv[5] = c;
+}
+
+// the header's LDL^T at size 3 of the damped V (upper triangle row by row): L10, L20, L21, D; false: a pivot not > 0
+struct BundleLdl3 {
+    double L10, L20, L21, D0, D1, D2;
+};
+__device__ __forceinline__ bool bundle_factor3(const double* V, BundleLdl3* f) {
+    f->D0 = V[0];
+    f->L10 = V[1] / f->D0;
+    f->L20 = V[2] / f->D0;
+    f->D1 = V[3] - (f->L10 * f->L10) * f->D0;
+    f->L21 = (V[4] - (f->L20 * f->L10) * f->D0) / f->D1;
+    f->D2 = (V[5] - (f->L20 * f->L20) * f->D0) - (f->L21 * f->L21) * f->D1;
+    return f->D0 > 0 && f->D1 > 0 && f->D2 > 0;
+}
+// V x = q by the factor's two triangular solves
+__device__ __forceinline__ void bundle_apply3(const BundleLdl3& f, double q0, double q1, double q2, double* x) {
+    const double z0 = q0, z1 = q1 - f.L10 * z0, z2 = (q2 - f.L20 * z0) - f.L21 * z1;
+    const double y0 = z0 / f.D0, y1 = z1 / f.D1, y2 = z2 / f.D2;
+    x[2] = y2;
+    x[1] = y1 - f.L21 * x[2];
+    x[0] = (y0 - f.L10 * x[1]) - f.L20 * x[2];
+}
+
+struct BundleShared {
+    double blk[kBundleTile * kBundleF];        // a tile's blocks; the evaluation's two columns
+    double S[kBundleMaxN * kBundleLd];         // the reduced system's upper triangle, L below it
+    double D[kBundleMaxN], r[kBundleMaxN], y[kBundleMaxN], d[kBundleMaxN];
+    double cam[kTrackRefineMaxViews][12], cam0[kTrackRefineMaxViews][12];
+    double res[2], rho;
+    int lnv[kBundleTile];  // a tile landmark's views, 0 where its factorisation failed
+    int cnt[2], win, fail;
+};
+
+// The Huber cost and the final-pass sums of a state into sh.res (cost, the inliers' squared pixels)
+// and sh.cnt (views, inliers): lane per landmark, 256 at a time, their values added in ordinal order
+// by lane 0 and lane 64.  raw: the landmarks' own X, else bd_x.  write: also the caller's slots
+// (kept: the steps and status of a kept fit).  Every barrier is reached by all threads.
+__device__ void bundle_eval(const TrackArgs& a, BundleShared& sh, int p, int n, int V, double kh, double kh2, bool raw,
+                            bool write, bool kept, int taken) {
+    const int tid = threadIdx.x;
+    double* evc = sh.blk;
+    double* evs = sh.blk + kBundleNT;
+    if (tid == 0) sh.cnt[0] = sh.cnt[1] = 0;
+    __syncthreads();
+    BundlePoint* bx = a.bd_x + (int64_t)p * a.pts_stride;
+    const double in2 = a.bd_inlier_px * a.bd_inlier_px;
+    double acc = 0.0;
+    for (int base = 0; base < n; base += kBundleNT) {
+        const int o = base + tid;
+        if (o < n) {
+            const LandmarkTmp e = track_ordinal(a, p, o);
+            double X[3] = {e.X, e.Y, e.Z};
+            int steps = 0;
+            if (!raw) {
+                const BundlePoint b = bx[o];
+                X[0] = b.X[0], X[1] = b.X[1], X[2] = b.X[2];
+                steps = b.steps;
+            }
+            double nu[kTrackRefineMaxViews], nv[kTrackRefineMaxViews];
+            const int nviews = bundle_views(a, p, o, e.match, V, nu, nv);
+            double ci = 0.0, se = 0.0;
+            int used = 0, inl = 0;
+#pragma unroll
+            for (int v = 0; v < kTrackRefineMaxViews; ++v) {
+                if (v < nviews) {
+                    const BundleView q = bundle_view(sh.cam[v], X, nu[v], nv[v], kh, kh2);
+                    const double rho = q.e2 <= kh2 ? q.e2 : (2 * kh) * sqrt(q.e2) - kh * kh;
+                    ci = ci + (q.ok ? rho : 0.0);
+                    const double ex = a.fx * q.ru, ey = a.fy * q.rv;
+                    const double er = ex * ex + ey * ey;
+                    const bool in = q.ok && er <= in2;
+                    used += q.ok;
+                    inl += in;
+                    se = se + (in ? er : 0.0);
+                }
+            }
+            evc[tid] = ci;
+            evs[tid] = se;
+            atomicAdd(&sh.cnt[0], nviews);
+            atomicAdd(&sh.cnt[1], inl);
+            if (write && a.bd_points && o < a.cap) {
+                dvo_landmark_refined out;
+                out.X = X[0], out.Y = X[1], out.Z = X[2];
+                out.rms = inl > 0 ? sqrt(se / (double)inl) : 0.0;
+                out.views = nviews;
+                out.n_used = used;
+                out.n_inliers = inl;
+                out.iters = kept ? steps : 0;
+                out.status = !kept ? DVO_TRACK_REFINE_NONE : steps == taken ? DVO_TRACK_REFINE_OK : DVO_TRACK_REFINE_DEGENERATE;
+                out.reserved = 0;
+                a.bd_points[(int64_t)p * a.cap + o] = out;
+            }
+        }
+        __syncthreads();
+        const int c = min(kBundleNT, n - base);
+        if (tid == 0)
+            for (int j = 0; j < c; ++j) acc = acc + evc[j];
+        if (tid == 64)
+            for (int j = 0; j < c; ++j) acc = acc + evs[j];
+        __syncthreads();
+    }
+    if (tid == 0) sh.res[0] = acc;
+    if (tid == 64) sh.res[1] = acc;
+    __syncthreads();
+}
+
+// A workgroup per pair.  Every barrier is reached by all 256 threads: a NONE pair leaves before the
+// first as a whole, and the trip counts come from the pair's count, V, iters and the failure flag
+// read after a barrier.
+__global__ __launch_bounds__(kBundleNT) void track_bundle_kernel(TrackArgs a) {
+    __shared__ BundleShared sh;
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int32_t* tc = a.L.tcnt + (int64_t)p * a.tiles;
+    int n = 0;
+    for (int t = 0; t < a.tiles; ++t) n += tc[t];
+    if (n == 0 || n < a.bd_min_points) {
+        if (tid == 0 && a.bundle) {
+            dvo_track_bundle o;
+            double rho;
+            refine_motion(a, a.bd_use_pose, p, o.R, o.t, &rho);
+            o.ratio = o.cost0 = o.cost = o.rms0 = o.rms = 0.0;
+            o.n_points = o.n_obs = o.n_inliers = o.n_cams = o.iters = 0;
+            o.status = DVO_TRACK_BUNDLE_NONE;
+            a.bundle[p] = o;
+        }
+        if (a.bd_points)
+            for (int o = tid; o < min(n, a.cap); o += kBundleNT) {
+                const LandmarkTmp e = track_ordinal(a, p, o);
+                dvo_landmark_refined out;
+                out.X = e.X, out.Y = e.Y, out.Z = e.Z;
+                out.rms = 0.0;
+                out.views = 2;
+                out.n_used = out.n_inliers = out.iters = 0;
+                out.status = DVO_TRACK_REFINE_NONE;
+                out.reserved = 0;
+                a.bd_points[(int64_t)p * a.cap + o] = out;
+            }
+        return;
+    }
+    BundlePoint* bx = a.bd_x + (int64_t)p * a.pts_stride;
+    if (tid == 0) {
+        double rho;
+        sh.win = window_cameras(a, p, a.bd_views, a.bd_use_pose, sh.cam, &rho);
+        sh.rho = rho;
+        for (int v = 0; v < kTrackRefineMaxViews; ++v)
+            for (int i = 0; i < 12; ++i) sh.cam0[v][i] = v <= sh.win + 1 ? sh.cam[v][i] : 0.0;
+    }
+    for (int o = tid; o < n; o += kBundleNT) {
+        const LandmarkTmp e = track_ordinal(a, p, o);
+        BundlePoint b;
+        b.X[0] = e.X, b.X[1] = e.Y, b.X[2] = e.Z;
+        b.steps = b.pad = 0;
+        bx[o] = b;
+    }
+    __syncthreads();
+    const int V = sh.win + 2, n6 = 6 * (V - 1), nS = n6 * (n6 + 1) / 2;
+    const double kh = a.bd_huber_px / ((a.fx + a.fy) / 2), kh2 = kh * kh, lam = a.bd_lambda;
+    bundle_eval(a, sh, p, n, V, kh, kh2, true, false, false, 0);
+    const double cost0 = sh.res[0], se0 = sh.res[1];
+    const int inl0 = sh.cnt[1];
+    // this lane's entries of S (upper triangle, row by row) and r: where Y's row, the second factor's
+    // row, and the U / h term stand in a landmark's blocks
+    int eY[kBundleEnt], eB[kBundleEnt], eU[kBundleEnt], eNeed[kBundleEnt], eKind[kBundleEnt], eDst[kBundleEnt];
+#pragma unroll
+    for (int q = 0; q < kBundleEnt; ++q) {
+        const int e = tid + q * kBundleNT;
+        eY[q] = eB[q] = eU[q] = eNeed[q] = eDst[q] = 0;
+        eKind[q] = -1;
+        if (e < nS) {
+            int row = 0, rem = e;
+            while (rem >= n6 - row) rem -= n6 - row, ++row;
+            const int col = row + rem;
+            const int c = row / 6, r = row % 6, c2 = col / 6, s = col % 6;  // cameras c + 1, c2 + 1
+            eY[q] = c * kBundleCamF + 18 + r * 3;
+            eB[q] = c2 * kBundleCamF + s * 3;
+            eNeed[q] = c2 + 1;
+            eDst[q] = row * kBundleLd + col;
+            if (c == c2) {
+                eU[q] = c * kBundleCamF + 36 + (r * 6 - r * (r - 1) / 2 + (s - r));
+                eKind[q] = r == s ? 2 : 1;
+            } else {
+                eKind[q] = 0;
+            }
+        } else if (e < nS + n6) {
+            const int row = e - nS, c = row / 6, r = row % 6;
+            eY[q] = c * kBundleCamF + 18 + r * 3;
+            eB[q] = kBundleG;
+            eU[q] = c * kBundleCamF + 57 + r;
+            eNeed[q] = c + 1;
+            eDst[q] = row;
+            eKind[q] = 3;
+        }
+    }
+    int status = DVO_TRACK_BUNDLE_OK, it = 0;
+    for (; it < a.bd_iters; ++it) {
+        double accT[kBundleEnt], accU[kBundleEnt];
+#pragma unroll
+        for (int q = 0; q < kBundleEnt; ++q) accT[q] = accU[q] = 0.0;
+        if (tid == 0) sh.fail = 0;
+        for (int base = 0; base < n; base += kBundleTile) {
+            const int cnt = min(kBundleTile, n - base);
+            // 1. lane per landmark: linearise, factor V, form Y, leave the blocks in LDS
+            if (tid < cnt) {
+                const int o = base + tid;
+                const LandmarkTmp e = track_ordinal(a, p, o);
+                const BundlePoint bp = bx[o];
+                const double X[3] = {bp.X[0], bp.X[1], bp.X[2]};
+                double nu[kTrackRefineMaxViews], nv[kTrackRefineMaxViews];
+                const int nviews = bundle_views(a, p, o, e.match, V, nu, nv);
+                double* B = sh.blk + tid * kBundleF;
+                double Vt[6], g[3];
+#pragma unroll
+                for (int i = 0; i < 6; ++i) Vt[i] = 0.0;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) g[i] = 0.0;
+#pragma unroll
+                for (int v = 0; v < kTrackRefineMaxViews; ++v) {
+                    if (v < nviews) {
+                        const double* C = sh.cam[v];
+                        const BundleView q = bundle_view(C, X, nu[v], nv[v], kh, kh2);
+                        double Ju[3], Jv[3];
+                        bundle_jx(C, q, Ju, Jv);
+                        int k = 0;
+#pragma unroll
+                        for (int i = 0; i < 3; ++i)
+#pragma unroll
+                            for (int j = i; j < 3; ++j, ++k) {
+                                const double term = q.w * (Ju[i] * Ju[j] + Jv[i] * Jv[j]);
+                                Vt[k] = Vt[k] + (q.ok ? term : 0.0);
+                            }
+#pragma unroll
+                        for (int i = 0; i < 3; ++i) {
+                            const double term = q.w * (Ju[i] * q.ru + Jv[i] * q.rv);
+                            g[i] = g[i] + (q.ok ? term : 0.0);
+                        }
+                        if (v >= 1) {
+                            double Cu[6], Cv[6];
+                            bundle_jc(q, Cu, Cv);
+                            double* Bc = B + (v - 1) * kBundleCamF;
+#pragma unroll
+                            for (int r = 0; r < 6; ++r)
+#pragma unroll
+                                for (int j = 0; j < 3; ++j) {
+                                    const double term = q.w * (Cu[r] * Ju[j] + Cv[r] * Jv[j]);
+                                    Bc[r * 3 + j] = q.ok ? term : 0.0;
+                                }
+                            k = 36;
+#pragma unroll
+                            for (int r = 0; r < 6; ++r)
+#pragma unroll
+                                for (int s = r; s < 6; ++s, ++k) {
+                                    const double term = q.w * (Cu[r] * Cu[s] + Cv[r] * Cv[s]);
+                                    Bc[k] = q.ok ? term : 0.0;
+                                }
+#pragma unroll
+                            for (int r = 0; r < 6; ++r) {
+                                const double term = q.w * (Cu[r] * q.ru + Cv[r] * q.rv);
+                                Bc[57 + r] = q.ok ? term : 0.0;
+                            }
+                        }
+                    }
+                }
+                Vt[0] = Vt[0] + lam * Vt[0];
+                Vt[3] = Vt[3] + lam * Vt[3];
+                Vt[5] = Vt[5] + lam * Vt[5];
+                BundleLdl3 f;
+                const bool good = bundle_factor3(Vt, &f);
+                for (int v = 1; v < nviews; ++v) {
+                    double* Bc = B + (v - 1) * kBundleCamF;
+                    for (int r = 0; r < 6; ++r) {
+                        double x[3];
+                        bundle_apply3(f, Bc[r * 3], Bc[r * 3 + 1], Bc[r * 3 + 2], x);
+                        Bc[18 + r * 3] = x[0], Bc[18 + r * 3 + 1] = x[1], Bc[18 + r * 3 + 2] = x[2];
+                    }
+                }
+                B[kBundleG] = g[0], B[kBundleG + 1] = g[1], B[kBundleG + 2] = g[2];
+                sh.lnv[tid] = good ? nviews : 0;
+            }
+            __syncthreads();
+            // 2. lane per entry: the tile's landmarks in ascending ordinal onto the running value
+            for (int l = 0; l < cnt; ++l) {
+                const int nvl = sh.lnv[l];
+                const double* B = sh.blk + l * kBundleF;
+#pragma unroll
+                for (int q = 0; q < kBundleEnt; ++q) {
+                    if (eKind[q] >= 0 && nvl > eNeed[q]) {
+                        const double* Y = B + eY[q];
+                        const double* W = B + eB[q];
+                        accT[q] = accT[q] + ((Y[0] * W[0] + Y[1] * W[1]) + Y[2] * W[2]);
+                        if (eKind[q] != 0) accU[q] = accU[q] + B[eU[q]];
+                    }
+                }
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int q = 0; q < kBundleEnt; ++q) {
+            if (eKind[q] == 0) sh.S[eDst[q]] = -accT[q];
+            if (eKind[q] == 1) sh.S[eDst[q]] = accU[q] - accT[q];
+            if (eKind[q] == 2) sh.S[eDst[q]] = (accU[q] + lam * accU[q]) - accT[q];
+            if (eKind[q] == 3) sh.r[eDst[q]] = accU[q] - accT[q];
+        }
+        __syncthreads();
+        // 3. the LDL^T of S: for column j, lane i - j runs row i's k loop in the header's order
+        for (int j = 0; j < n6; ++j) {
+            const int i = j + tid;
+            double x = 0.0;
+            if (i < n6) {
+                x = sh.S[j * kBundleLd + i];
+                for (int k = 0; k < j; ++k) x = x - (sh.S[i * kBundleLd + k] * sh.S[j * kBundleLd + k]) * sh.D[k];
+                if (tid == 0) {
+                    sh.D[j] = x;
+                    if (!(x > 0)) sh.fail = 1;
+                }
+            }
+            __syncthreads();
+            if (i < n6 && tid > 0) sh.S[i * kBundleLd + j] = x / sh.D[j];
+            __syncthreads();
+        }
+        if (tid == 0) {
+            for (int i = 0; i < n6; ++i) {
+                double x = -sh.r[i];
+                for (int k = 0; k < i; ++k) x = x - sh.S[i * kBundleLd + k] * sh.y[k];
+                sh.y[i] = x;
+            }
+            for (int i = 0; i < n6; ++i) sh.y[i] = sh.y[i] / sh.D[i];
+            bool finite = true;
+            for (int i = n6 - 1; i >= 0; --i) {
+                double x = sh.y[i];
+                for (int k = i + 1; k < n6; ++k) x = x - sh.S[k * kBundleLd + i] * sh.d[k];
+                sh.d[i] = x;
+                finite = finite && isfinite(x);
+            }
+            if (!finite) sh.fail = 1;
+        }
+        __syncthreads();
+        if (sh.fail) {  // the same for every thread; the next write to it lies behind the next barrier
+            status = DVO_TRACK_BUNDLE_DEGENERATE;
+            break;
+        }
+        // the landmarks back-substitute on the step's cameras: lane per landmark, the blocks formed again
+        for (int o = tid; o < n; o += kBundleNT) {
+            const LandmarkTmp e = track_ordinal(a, p, o);
+            BundlePoint bp = bx[o];
+            const double X[3] = {bp.X[0], bp.X[1], bp.X[2]};
+            double nu[kTrackRefineMaxViews], nv[kTrackRefineMaxViews];
+            const int nviews = bundle_views(a, p, o, e.match, V, nu, nv);
+            double Vt[6], g[3], tw[kTrackRefineMaxViews][3];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) Vt[i] = 0.0;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) g[i] = 0.0;
+#pragma unroll
+            for (int v = 0; v < kTrackRefineMaxViews; ++v) {
+                tw[v][0] = tw[v][1] = tw[v][2] = 0.0;
+                if (v < nviews) {
+                    const double* C = sh.cam[v];
+                    const BundleView q = bundle_view(C, X, nu[v], nv[v], kh, kh2);
+                    double Ju[3], Jv[3];
+                    bundle_jx(C, q, Ju, Jv);
+                    int k = 0;
+#pragma unroll
+                    for (int i = 0; i < 3; ++i)
+#pragma unroll
+                        for (int j = i; j < 3; ++j, ++k) {
+                            const double term = q.w * (Ju[i] * Ju[j] + Jv[i] * Jv[j]);
+                            Vt[k] = Vt[k] + (q.ok ? term : 0.0);
+                        }
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) {
+                        const double term = q.w * (Ju[i] * q.ru + Jv[i] * q.rv);
+                        g[i] = g[i] + (q.ok ? term : 0.0);
+                    }
+                    if (v >= 1) {
+                        double Cu[6], Cv[6];
+                        bundle_jc(q, Cu, Cv);
+                        const double* dc = sh.d + 6 * (v - 1);
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) {
+                            double t = 0.0;
+#pragma unroll
+                            for (int r = 0; r < 6; ++r) {
+                                const double term = q.w * (Cu[r] * Ju[j] + Cv[r] * Jv[j]);
+                                const double wd = (q.ok ? term : 0.0) * dc[r];
+                                t = r == 0 ? wd : t + wd;
+                            }
+                            tw[v][j] = t;
+                        }
+                    }
+                }
+            }
+            Vt[0] = Vt[0] + lam * Vt[0];
+            Vt[3] = Vt[3] + lam * Vt[3];
+            Vt[5] = Vt[5] + lam * Vt[5];
+            BundleLdl3 f;
+            if (bundle_factor3(Vt, &f)) {
+                double qv[3] = {-g[0], -g[1], -g[2]}, x[3];
+#pragma unroll
+                for (int v = 1; v < kTrackRefineMaxViews; ++v)
+                    if (v < nviews) {
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) qv[j] = qv[j] - tw[v][j];
+                    }
+                bundle_apply3(f, qv[0], qv[1], qv[2], x);
+#pragma unroll
+                for (int j = 0; j < 3; ++j) bp.X[j] = X[j] + x[j];
+                ++bp.steps;
+                bx[o] = bp;
+            }
+        }
+        __syncthreads();
+        if (tid >= 1 && tid < V) {
+            double R[9], t[3], d[6], o[12];
+#pragma unroll
+            for (int i = 0; i < 9; ++i) R[i] = sh.cam[tid][i];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) t[i] = sh.cam[tid][9 + i];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) d[i] = sh.d[6 * (tid - 1) + i];
+            pose_update(R, t, d, o);
+#pragma unroll
+            for (int i = 0; i < 12; ++i) sh.cam[tid][i] = o[i];
+        }
+        __syncthreads();
+    }
+    // the guard and the gauge
+    bundle_eval(a, sh, p, n, V, kh, kh2, false, false, false, it);
+    const double cost = sh.res[0];
+    const double b0 = sh.cam[1][9], b1 = sh.cam[1][10], b2 = sh.cam[1][11];
+    const double s = sqrt((b0 * b0 + b1 * b1) + b2 * b2);
+    const bool gauge = s > 0 && isfinite(1.0 / s);
+    if (status == DVO_TRACK_BUNDLE_OK && !gauge)
+        status = DVO_TRACK_BUNDLE_DEGENERATE;
+    else if (status == DVO_TRACK_BUNDLE_OK && !(cost <= cost0))
+        status = DVO_TRACK_BUNDLE_NOT_IMPROVED;
+    const bool keep = it > 0 && gauge && cost <= cost0;
+    __syncthreads();  // every thread has read cam[1] and res
+    if (keep) {
+        for (int o = tid; o < n; o += kBundleNT) {
+            BundlePoint bp = bx[o];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) bp.X[j] = bp.X[j] / s;
+            bx[o] = bp;
+        }
+        if (tid >= 1 && tid < V) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) sh.cam[tid][9 + i] = sh.cam[tid][9 + i] / s;
+        }
+    } else if (tid < kTrackRefineMaxViews * 12) {
+        sh.cam[tid / 12][tid % 12] = sh.cam0[tid / 12][tid % 12];
+    }
+    __syncthreads();
+    bundle_eval(a, sh, p, n, V, kh, kh2, !keep, true, keep, it);
+    if (tid == 0 && a.bundle) {
+        dvo_track_bundle o;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) o.R[i] = sh.cam[1][i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) o.t[i] = sh.cam[1][9 + i];
+        if (V < 3) {
+            o.ratio = 0.0;
+        } else if (keep) {
+            const double c0 = sh.cam[2][9], c1 = sh.cam[2][10], c2 = sh.cam[2][11];
+            o.ratio = 1.0 / sqrt((c0 * c0 + c1 * c1) + c2 * c2);
+        } else {
+            o.ratio = sh.rho;
+        }
+        o.cost0 = cost0;
+        o.cost = cost;
+        o.rms0 = inl0 > 0 ? sqrt(se0 / (double)inl0) : 0.0;
+        o.rms = sh.cnt[1] > 0 ? sqrt(sh.res[1] / (double)sh.cnt[1]) : 0.0;
+        o.n_points = n;
+        o.n_obs = sh.cnt[0];
+        o.n_inliers = sh.cnt[1];
+        o.n_cams = V;
+        o.iters = it;
+        o.status = status;
+        a.bundle[p] = o;
+    }
+}
+
 }  // namespace
 
 hipError_t launch_tracks(const TrackArgs& a, int pairs, hipStream_t s) {
@@ -737,10 +1315,16 @@ hipError_t launch_tracks(const TrackArgs& a, int pairs, hipStream_t s) {
                      a.pose_min_points < 3 || !(a.huber_px > 0) || !(a.inlier_px > 0)
                : a.corr != nullptr)
         return hipErrorInvalidValue;
-    if (a.flink && (!a.scale || !a.pts_f || a.cap < 1 || (!a.id && !a.refined) || (a.id && (!a.rank || a.rank_stride < 1)) ||
-                    a.rf_views < 3 || a.rf_views > kTrackRefineMaxViews || a.rf_iters < 1 ||
-                    a.rf_iters > kTrackRefineMaxIters || !(a.rf_huber_px > 0) || !(a.rf_inlier_px > 0) ||
-                    (a.rf_use_pose && !a.pose)))
+    const bool refine = a.id || a.refined;  // a refine binding; a bundle binding is bd_x
+    if (a.flink ? !a.scale || !a.pts_f || a.cap < 1 || (!refine && !a.bd_x) : refine || a.bd_x != nullptr)
+        return hipErrorInvalidValue;
+    if (refine && ((a.id && (!a.rank || a.rank_stride < 1)) || a.rf_views < 3 || a.rf_views > kTrackRefineMaxViews ||
+                   a.rf_iters < 1 || a.rf_iters > kTrackRefineMaxIters || !(a.rf_huber_px > 0) ||
+                   !(a.rf_inlier_px > 0) || (a.rf_use_pose && !a.pose)))
+        return hipErrorInvalidValue;
+    if (a.bd_x && ((!a.bundle && !a.bd_points) || a.bd_views < 2 || a.bd_views > kTrackRefineMaxViews || a.bd_iters < 1 ||
+                   a.bd_iters > kTrackBundleMaxIters || a.bd_min_points < 6 || !(a.bd_lambda > 0) ||
+                   !(a.bd_huber_px > 0) || !(a.bd_inlier_px > 0) || (a.bd_use_pose && !a.pose)))
         return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(a.table, 0x7f, (size_t)pairs * a.kp_cap * sizeof(int32_t), s);
     if (e != hipSuccess) return e;
@@ -757,6 +1341,7 @@ hipError_t launch_tracks(const TrackArgs& a, int pairs, hipStream_t s) {
             hipLaunchKernelGGL(track_id_kernel, grid, dim3(kLandmarkTile), 0, s, a, r, r == rounds ? 1 : 0);
     }
     if (a.flink && a.refined) hipLaunchKernelGGL(track_refine_kernel, grid, dim3(kLandmarkTile), 0, s, a);
+    if (a.bd_x) hipLaunchKernelGGL(track_bundle_kernel, dim3((unsigned)pairs), dim3(kBundleNT), 0, s, a);
     return hipGetLastError();
 }
 

@@ -1248,6 +1248,53 @@ def test_track_refine(lm, count, mq, mt, m, rec, kp_cap, K, views=6, iters=5, hu
     return link, scale, pose, refined if want_refined else None, ids if want_ids else None
 
 
+def test_track_bundle(lm, count, mq, mt, m, rec, kp_cap, K, views=6, iters=5, lam=0.0, huber_px=1.0, inlier_px=2.0,
+                      min_points=8, use_poses=False, pose_params=(10, 1.0, 2.0, 6), cap_out=None, link=None, bundle=None,
+                      points=None, want_bundle=True, want_points=True, ctx=None):
+    """test_track_poses with the bundle kernel (stream.TrackBundle) and no refine binding: each
+    landmark's x1, y1 are read too; views, iters, lam, huber_px, inlier_px, min_points are
+    bind_bundle's (zero or negative: the default), use_poses whether the poses feed the unit motions,
+    pose_params bind_track_poses's four.  bundle TRACK_BUNDLE_DTYPE[P] and points
+    LANDMARK_REFINED_DTYPE[P, cap_out] keep their bytes outside what is written (default: 0xff
+    fill); want_bundle / want_points False passes NULL for that output.
+    Returns (link, scale, pose, bundle or None, points or None)."""
+    from ._native import (LANDMARK_DTYPE, LANDMARK_REFINED_DTYPE, TRACK_BUNDLE_DTYPE, TRACK_POSE_DTYPE,
+                          TRACK_SCALE_DTYPE)
+    c = _ctx(ctx)
+    mq = np.ascontiguousarray(mq, np.int32)
+    mt = np.ascontiguousarray(mt, np.int32)
+    count = np.ascontiguousarray(count, np.int32)
+    m = np.ascontiguousarray(m, np.int32)
+    if (lm.dtype != LANDMARK_DTYPE or lm.ndim != 2 or not lm.flags.c_contiguous or mq.ndim != 2 or mq.shape != mt.shape
+            or not (len(lm) == len(mq) == len(count) == len(m) == len(rec))):
+        raise DVOError(-1, "lm LANDMARK_DTYPE[P, cap], mq / mt int32[P, stride], count, m and rec [P] must agree")
+    rec = np.ascontiguousarray(rec, PAIR_RECORD_DTYPE)
+    K = np.ascontiguousarray(K, np.float64).reshape(9)
+    P, cap = lm.shape
+    cap_out = cap if cap_out is None else int(cap_out)
+    link = np.full((P, cap_out), -1, np.int32) if link is None else link
+    if link.dtype != np.int32 or link.shape != (P, cap_out) or not link.flags.c_contiguous:
+        raise DVOError(-1, "link must be a contiguous int32[P, cap_out] array")
+    if want_bundle and bundle is None:
+        bundle = np.frombuffer(b"\xff" * (P * 160), TRACK_BUNDLE_DTYPE).copy()
+    if want_points and points is None:
+        points = np.frombuffer(b"\xff" * (P * cap_out * 56), LANDMARK_REFINED_DTYPE).reshape(P, cap_out).copy()
+    if bundle is not None and (bundle.dtype != TRACK_BUNDLE_DTYPE or bundle.shape != (P,) or not bundle.flags.c_contiguous):
+        raise DVOError(-1, "bundle must be a contiguous TRACK_BUNDLE_DTYPE[P] array")
+    if points is not None and (points.dtype != LANDMARK_REFINED_DTYPE or points.shape != (P, cap_out)
+                               or not points.flags.c_contiguous):
+        raise DVOError(-1, "points must be a contiguous LANDMARK_REFINED_DTYPE[P, cap_out] array")
+    scale = np.zeros(P, TRACK_SCALE_DTYPE)
+    pose = np.zeros(P, TRACK_POSE_DTYPE)
+    pi, ph, pin, pm = pose_params
+    c.check(c.lib.dvo_test_track_bundle(c.h, ptr(lm), ptr(count), ptr(mq), ptr(mt), ptr(m), ptr(rec), P, cap,
+                                        mq.shape[1], int(kp_cap), cap_out, ptr(K), int(pi), float(ph), float(pin),
+                                        int(pm), ptr(link), ptr(scale), ptr(pose), int(views), int(iters), float(lam),
+                                        float(huber_px), float(inlier_px), int(min_points), int(bool(use_poses)),
+                                        ptr(bundle) if want_bundle else None, ptr(points) if want_points else None))
+    return link, scale, pose, bundle if want_bundle else None, points if want_points else None
+
+
 def test_flann_batch(desc, counts, trees=5, checks=50, rng_state=None, levels=0, ctx=None):
     """The batched kd-forest build and search of dvo_knn_stream_process's FLANN mode
     (stream.KnnFrameStream(matcher="flann")) on host arrays: desc float32[F, cap, dim] frame slots,

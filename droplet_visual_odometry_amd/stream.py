@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from ._native import (DMATCH_DTYPE, KEYPOINT_DTYPE, LANDMARK_DTYPE, LANDMARK_REFINED_DTYPE, PAIR_RECORD_DTYPE,
-                      TRACK_ID_DTYPE, TRACK_POSE_DTYPE, TRACK_SCALE_DTYPE, Context, StreamConfig, _vp, orb_params, ptr)
+                      TRACK_BUNDLE_DTYPE, TRACK_ID_DTYPE, TRACK_POSE_DTYPE, TRACK_SCALE_DTYPE, Context, StreamConfig, _vp, orb_params, ptr)
 
 
 class Landmarks:
@@ -169,6 +169,51 @@ def _bind_refine(stream, setter, rf, views, iters, huber_px, inlier_px, ids, ref
     return rf
 
 
+class TrackBundle:
+    """Device buffers for one batch's track bundle (dvo_stream_set_track_bundle), the companion of a
+    Tracks: per pair the pose, baseline ratio and costs of the joint fit of its window cameras and
+    landmarks, and slot for slot beside the Landmarks of the same cap each landmark's fitted
+    position (see include/dvo.h).  bundle: uint8 [n_pairs, 160] (TRACK_BUNDLE_DTYPE); points: uint8
+    [n_pairs, cap, 56] (LANDMARK_REFINED_DTYPE).  Bind it with bind_bundle, last; read it after the
+    batch has retired and the stream is synchronised."""
+
+    def __init__(self, n_pairs: int, cap: int, device):
+        if n_pairs < 1 or cap < 1:
+            raise ValueError("TrackBundle needs n_pairs >= 1 and cap >= 1")
+        self.n_pairs, self.cap = int(n_pairs), int(cap)
+        self.bundle = torch.zeros((self.n_pairs, TRACK_BUNDLE_DTYPE.itemsize), dtype=torch.uint8, device=device)
+        self.points = torch.zeros((self.n_pairs, self.cap, LANDMARK_REFINED_DTYPE.itemsize), dtype=torch.uint8,
+                                  device=device)
+
+    def numpy(self) -> np.ndarray:
+        """TRACK_BUNDLE_DTYPE [n_pairs]: R, t, ratio, cost0, cost, rms0, rms and the counts per pair."""
+        return self.bundle.cpu().numpy().reshape(-1).view(TRACK_BUNDLE_DTYPE).copy()
+
+    def points_numpy(self, pair: int, count: int) -> np.ndarray:
+        """The pair's first min(count, cap) fitted landmarks (count: Landmarks.count(pair))."""
+        n = min(int(count), self.cap)
+        return self.points[pair, :n].cpu().numpy().reshape(-1).view(LANDMARK_REFINED_DTYPE).copy()
+
+
+def _bind_bundle(stream, setter, bd, views, iters, lam, huber_px, inlier_px, min_points, pairs, points):
+    """The one-shot bundle binding of both stream classes; returns what to keep referenced."""
+    if bd is None or not (pairs or points):
+        stream.ctx.check(setter(stream.h, None, None, 0, 0, 0.0, 0.0, 0.0, 0))
+        return None
+    lm, tr = stream._lm_next, stream._tr_next
+    if lm is None or tr is None:
+        raise ValueError("bind_bundle goes after bind_tracks: it is a companion of a pending Tracks")
+    if not isinstance(bd, TrackBundle) or bd.bundle.device != stream.device or bd.points.device != stream.device:
+        raise ValueError("bind_bundle takes a TrackBundle on the stream's device (or None)")
+    if bd.cap != lm.cap or bd.n_pairs < lm.n_pairs:
+        raise ValueError(f"the TrackBundle ({bd.n_pairs} pairs, cap {bd.cap}) must have the bound Landmarks' cap "
+                         f"and pairs ({lm.n_pairs}, cap {lm.cap})")
+    stream._after_torch()  # the buffers' fill ran on torch's stream: order the library's writes after it
+    stream.ctx.check(setter(stream.h, bd.bundle.data_ptr() if pairs else None, bd.points.data_ptr() if points else None,
+                            int(views), int(iters), float(lam), float(huber_px), float(inlier_px), int(min_points)))
+    return bd
+
+
 def _bind_track_poses(stream, setter, tp, iters, huber_px, inlier_px, min_points):
     """The one-shot pose binding of both stream classes; returns what to keep referenced."""
     if tp is None:
@@ -187,24 +232,30 @@ def _bind_track_poses(stream, setter, tp, iters, huber_px, inlier_px, min_points
     return tp
 
 
-def carry_scale(anchor, scales, poses=None) -> np.ndarray:
+def carry_scale(anchor, scales, poses=None, bundle=None) -> np.ndarray:
     """Metric baseline length per pair of one batch: anchor float64 [pairs] holds the marker's scale
     where a marker was seen (the pose tail) and NaN elsewhere; scales is the batch's
     TRACK_SCALE_DTYPE [pairs] (Tracks.scales_numpy).  out[p] = anchor[p] where that is not NaN, else
     out[p - 1] * ratio[p] when n_common[p] >= 1 and out[p - 1] is not NaN, else NaN.  No threshold
     of its own: filter on n_common, q1 and q3 first (set n_common to 0 where the ratio is not trusted).
     poses: the batch's TRACK_POSE_DTYPE [pairs] (TrackPoses.numpy), or None: a pair whose pose has
-    status 0 multiplies by poses["scale"][p] instead of the ratio."""
+    status 0 multiplies by poses["scale"][p] instead of the ratio.  bundle: the batch's
+    TRACK_BUNDLE_DTYPE [pairs] (TrackBundle.numpy), or None: a pair whose bundle has status 0 and a
+    ratio > 0 multiplies by bundle["ratio"][p] instead of either."""
     anchor = np.asarray(anchor, np.float64)
-    if anchor.ndim != 1 or len(scales) != len(anchor) or (poses is not None and len(poses) != len(anchor)):
-        raise ValueError("anchor float64 [pairs], scales [pairs] and poses [pairs] must agree")
+    if (anchor.ndim != 1 or len(scales) != len(anchor) or (poses is not None and len(poses) != len(anchor))
+            or (bundle is not None and len(bundle) != len(anchor))):
+        raise ValueError("anchor float64 [pairs], scales [pairs], poses [pairs] and bundle [pairs] must agree")
     out = np.full(len(anchor), np.nan)
     for p in range(len(anchor)):
         if not np.isnan(anchor[p]):
             out[p] = anchor[p]
         elif p >= 1 and scales["n_common"][p] >= 1 and not np.isnan(out[p - 1]):
             refined = poses is not None and poses["status"][p] == 0
-            out[p] = out[p - 1] * (poses["scale"][p] if refined else scales["ratio"][p])
+            if bundle is not None and bundle["status"][p] == 0 and bundle["ratio"][p] > 0:
+                out[p] = out[p - 1] * bundle["ratio"][p]
+            else:
+                out[p] = out[p - 1] * (poses["scale"][p] if refined else scales["ratio"][p])
     return out
 
 
@@ -250,6 +301,7 @@ class FrameStream:
         self._tr_next = None  # bind_tracks: the Tracks the next batch takes with its Landmarks
         self._tp_next = None  # bind_track_poses: the TrackPoses it takes with them
         self._rf_next = None  # bind_refine: and the RefinedLandmarks
+        self._bd_next = None  # bind_bundle: and the TrackBundle
         self.width, self.height, self.max_frames, self.nfeatures = width, height, max_frames, nfeatures
         self.K = K.reshape(3, 3)
         if ratio:
@@ -277,7 +329,7 @@ class FrameStream:
         after it writes nothing.  None clears a binding no batch has taken yet."""
         self._lm_next = _bind_landmarks(self, self.ctx.lib.dvo_stream_set_landmarks, lm)
         if lm is None:
-            self._tr_next = self._tp_next = self._rf_next = None  # the library clears the companions with it
+            self._tr_next = self._tp_next = self._rf_next = self._bd_next = None  # the library clears the companions with it
 
     def bind_tracks(self, tr: Tracks | None):
         """Have the next batch also write its tracks into `tr` (dvo_stream_set_tracks), after its
@@ -285,7 +337,7 @@ class FrameStream:
         same cap.  One-shot, like the landmark binding; None clears a pending binding.  Only for
         batches of consecutive frames: process_pairs / submit_pairs raise ValueError."""
         self._tr_next = _bind_tracks(self, self.ctx.lib.dvo_stream_set_tracks, tr)
-        self._tp_next = self._rf_next = None  # the library's call cleared pending pose and refine bindings
+        self._tp_next = self._rf_next = self._bd_next = None  # the library's call cleared the later pending bindings
 
     def bind_track_poses(self, tp: TrackPoses | None, iters: int = 10, huber_px: float = 1.0, inlier_px: float = 2.0,
                          min_points: int = 6):
@@ -294,7 +346,7 @@ class FrameStream:
         steps (at most 32); huber_px, inlier_px: the Huber width and the inlier bound in pixels;
         min_points: shared landmarks a pair needs (at least 3).  One-shot; None clears a pending
         binding, as bind_tracks and bind_landmarks(None) do."""
-        self._rf_next = None  # the library's call clears a pending refine binding: bind refine last
+        self._rf_next = self._bd_next = None  # the library's call clears pending refine and bundle bindings
         self._tp_next = _bind_track_poses(self, self.ctx.lib.dvo_stream_set_track_poses, tp, iters, huber_px,
                                           inlier_px, min_points)
 
@@ -306,8 +358,21 @@ class FrameStream:
         to feed the fit.  views: frames of a track a landmark is fitted to (3..8); iters:
         Gauss-Newton steps (at most 16); huber_px, inlier_px as for the poses; ids / refined:
         which of the two outputs to write.  One-shot; None clears a pending binding."""
+        self._bd_next = None  # the library's call clears a pending bundle binding: bind the bundle last
         self._rf_next = _bind_refine(self, self.ctx.lib.dvo_stream_set_track_refine, rf, views, iters, huber_px,
                                      inlier_px, ids, refined)
+
+    def bind_bundle(self, bd: TrackBundle | None, views: int = 6, iters: int = 5, lam: float = 0.0, huber_px: float = 1.0,
+                    inlier_px: float = 2.0, min_points: int = 8, pairs: bool = True, points: bool = True):
+        """Have the next batch also write its track bundle into `bd` (dvo_stream_set_track_bundle),
+        after everything else.  Call it last: after bind_tracks (ValueError otherwise), after
+        bind_track_poses where the refined poses are to start the fit, and after bind_refine where
+        that is bound too (it is not needed).  views: cameras of a pair's window (2..8); iters:
+        Gauss-Newton steps (at most 16); lam: the damping (0: the library's default); huber_px,
+        inlier_px as for the poses; min_points: landmarks a pair needs (at least 6); pairs / points:
+        which of the two outputs to write.  One-shot; None clears a pending binding."""
+        self._bd_next = _bind_bundle(self, self.ctx.lib.dvo_stream_set_track_bundle, bd, views, iters, lam, huber_px,
+                                     inlier_px, min_points, pairs, points)
 
     def _lm_fits(self, pairs: int, shared: bool = True):
         if self._lm_next is not None and self._lm_next.n_pairs < pairs:
@@ -564,15 +629,16 @@ class FrameStream:
         tr, self._tr_next = self._tr_next, None
         tp, self._tp_next = self._tp_next, None
         rf, self._rf_next = self._rf_next, None
+        bd, self._bd_next = self._bd_next, None
         if lm is not None and self._pending:
-            self._lm_pending[next(reversed(self._pending))] = (lm, tr, tp, rf)
+            self._lm_pending[next(reversed(self._pending))] = (lm, tr, tp, rf, bd)
         out, lms = [], []
         for i in range(min(n, cap)):
             t = self._pending.pop(recs[i], None)
             if t is None:
                 raise RuntimeError("retired records that were not submitted through this FrameStream")
             out.append((t, int(pairs[i])))
-            lm, tr, tp, rf = self._lm_pending.pop(recs[i], (None, None, None, None))
+            lm, tr, tp, rf, bd = self._lm_pending.pop(recs[i], (None, None, None, None, None))
             if lm is not None:
                 lms += [lm.entries, lm.counts]
             if tr is not None:
@@ -581,6 +647,8 @@ class FrameStream:
                 lms += [tp.poses]
             if rf is not None:
                 lms += [rf.refined, rf.ids]
+            if bd is not None:
+                lms += [bd.bundle, bd.points]
         if out:
             # the retire kernels (records_kernel, the landmark kernels) writing these buffers are
             # queued on the library's stream by the call that retired them: keep the tensors alive
@@ -721,6 +789,7 @@ class FrameStream:
             self._last = ()
             self._pending = {}
             self._lm_next, self._lm_pending, self._tr_next, self._tp_next, self._rf_next = None, {}, None, None, None
+            self._bd_next = None
 
     def __del__(self):
         try:
@@ -832,6 +901,7 @@ class KnnFrameStream:
         self._tr_next = None  # bind_tracks: the Tracks it takes with them
         self._tp_next = None  # bind_track_poses: and the TrackPoses
         self._rf_next = None  # bind_refine: and the RefinedLandmarks
+        self._bd_next = None  # bind_bundle: and the TrackBundle
         self.width, self.height, self.max_frames = int(width), int(height), int(max_frames)
         self.dim = 64 if cfg.detector == 1 else 128
         self.K = K.reshape(3, 3)
@@ -849,14 +919,14 @@ class KnnFrameStream:
         that batch.  One-shot: the batch after it writes nothing.  None clears a pending binding."""
         self._lm_next = _bind_landmarks(self, self.ctx.lib.dvo_knn_stream_set_landmarks, lm)
         if lm is None:
-            self._tr_next = self._tp_next = self._rf_next = None  # the library clears the companions with it
+            self._tr_next = self._tp_next = self._rf_next = self._bd_next = None  # the library clears the companions with it
 
     def bind_tracks(self, tr: Tracks | None):
         """Have the next batch also write its tracks into `tr` (dvo_knn_stream_set_tracks), after
         its landmarks.  Call it after bind_landmarks (ValueError otherwise), with a Tracks of the
         same cap.  One-shot; None clears a pending binding; detect*() alone does not take it."""
         self._tr_next = _bind_tracks(self, self.ctx.lib.dvo_knn_stream_set_tracks, tr)
-        self._tp_next = self._rf_next = None  # the library's call cleared pending pose and refine bindings
+        self._tp_next = self._rf_next = self._bd_next = None  # the library's call cleared the later pending bindings
 
     def bind_track_poses(self, tp: TrackPoses | None, iters: int = 10, huber_px: float = 1.0, inlier_px: float = 2.0,
                          min_points: int = 6):
@@ -864,7 +934,7 @@ class KnnFrameStream:
         after its tracks.  Call it after bind_tracks (ValueError otherwise); the parameters are
         FrameStream.bind_track_poses's.  One-shot; None clears a pending binding; detect*() alone
         does not take it."""
-        self._rf_next = None  # the library's call clears a pending refine binding: bind refine last
+        self._rf_next = self._bd_next = None  # the library's call clears pending refine and bundle bindings
         self._tp_next = _bind_track_poses(self, self.ctx.lib.dvo_knn_stream_set_track_poses, tp, iters, huber_px,
                                           inlier_px, min_points)
 
@@ -874,8 +944,17 @@ class KnnFrameStream:
         (dvo_knn_stream_set_track_refine), after its tracks and track poses; the parameters are
         FrameStream.bind_refine's.  Call it last.  One-shot; None clears a pending binding;
         detect*() alone does not take it."""
+        self._bd_next = None  # the library's call clears a pending bundle binding: bind the bundle last
         self._rf_next = _bind_refine(self, self.ctx.lib.dvo_knn_stream_set_track_refine, rf, views, iters, huber_px,
                                      inlier_px, ids, refined)
+
+    def bind_bundle(self, bd: TrackBundle | None, views: int = 6, iters: int = 5, lam: float = 0.0, huber_px: float = 1.0,
+                    inlier_px: float = 2.0, min_points: int = 8, pairs: bool = True, points: bool = True):
+        """Have the next batch also write its track bundle into `bd` (dvo_knn_stream_set_track_bundle),
+        after everything else; the parameters are FrameStream.bind_bundle's.  Call it last.
+        One-shot; None clears a pending binding; detect*() alone does not take it."""
+        self._bd_next = _bind_bundle(self, self.ctx.lib.dvo_knn_stream_set_track_bundle, bd, views, iters, lam,
+                                     huber_px, inlier_px, min_points, pairs, points)
 
     def _lm_fits(self, pairs: int):
         if self._lm_next is not None and self._lm_next.n_pairs < pairs:
@@ -887,8 +966,10 @@ class KnnFrameStream:
         tr, self._tr_next = self._tr_next, None
         tp, self._tp_next = self._tp_next, None
         rf, self._rf_next = self._rf_next, None
+        bd, self._bd_next = self._bd_next, None
         return ((() if lm is None else (lm.entries, lm.counts)) + (() if tr is None else (tr.links, tr.scales))
-                + (() if tp is None else (tp.poses,)) + (() if rf is None else (rf.refined, rf.ids)))
+                + (() if tp is None else (tp.poses,)) + (() if rf is None else (rf.refined, rf.ids))
+                + (() if bd is None else (bd.bundle, bd.points)))
 
     def set_detect_group(self, group: int):
         """SIFT frames per detection launch from the next process() on (0: frame by frame).  Waits

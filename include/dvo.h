@@ -1257,6 +1257,142 @@ int dvo_stream_set_track_refine(dvo_stream* s, dvo_landmark_refined* d_refined, 
 int dvo_knn_stream_set_track_refine(dvo_knn_stream* s, dvo_landmark_refined* d_refined, dvo_track_id* d_id, int views,
                                     int iters, double huber_px, double inlier_px);
 
+/* ---------------------------------------------------------------------------
+ * Track bundle: each pair's window cameras and landmarks fitted jointly.  An opt-in companion of a
+ * tracks binding.  The track poses fit a camera to fixed points and the refined landmarks fit a
+ * point to fixed cameras, so each stops at the other's error; here the cameras of pair p's window
+ * and all its landmarks move together, by damped Gauss-Newton steps with the points eliminated
+ * (a Schur complement).  One window per pair: the windows of neighbouring pairs overlap and are
+ * fitted independently, and the fitted cameras of the older frames are not an output.
+ *
+ * Pairs that take part.  Pair p with n landmarks in its full list takes part if n >= 1 and
+ * n >= min_points (a pair whose record failed has none).  Nothing depends on the landmark cap.
+ *
+ * Cameras.  With (R_q, d_q, rho_q) the unit motions and (A_k, b_k), W the window cameras of the
+ * section above computed with this binding's `views` (the poses feed the unit motions where a
+ * track-poses binding was pending when this binding was made): V = W + 2 <= views cameras, each
+ * (A, b) with x' = A x + b.  Camera 0 = (I, 0), frame p, fixed.  Camera 1 = (R_p, d_p), frame
+ * p + 1.  Camera k + 1 = (A_k, b_k), frame p - k, for k = 1..W.  V = 2 where the window is empty
+ * (pair 0 of a batch, a pair after a failed one, views = 2).
+ *
+ * Points.  Landmark o starts at its own X, Y, Z.  Its views are the "Views of landmark (p, o)"
+ * of the section above with V in place of `views`: view v is seen by camera v, so a landmark with
+ * m views sees cameras 0..m-1.  Pixels are normalised as there.
+ *
+ * One step, in double, every operation rounded once, in the written order.  kh = huber_px /
+ * ((fx + fy) / 2).  Per landmark, its views in ascending v, every sum starting at +0.0; per view
+ * with camera (A, b):
+ *   P_i = ((A[i][0] * X0 + A[i][1] * X1) + A[i][2] * X2) + b[i]
+ *   a view with !(P2 > 0) contributes +0.0 to every term below; otherwise
+ *   a = 1 / P2, u = P0 * a, v = P1 * a, ru = u - nu, rv = v - nv, e2 = ru * ru + rv * rv
+ *   w = 1 if e2 <= kh * kh, else kh / sqrt(e2)
+ *   Ju[j] = a * (A[0][j] - u * A[2][j]),  Jv[j] = a * (A[1][j] - v * A[2][j])      (the point, j < 3)
+ *   and for v >= 1, with b = -(u * a), c = -(v * a) (the left perturbation P <- omega x P + dt):
+ *   Cu = (b * P1, a * P2 - b * P0, -(a * P1), a, 0, b)
+ *   Cv = (c * P1 - a * P2, -(c * P0), a * P0, 0, a, c)
+ * The landmark's sums over its views: the 6 terms w * (Ju[i] * Ju[j] + Jv[i] * Jv[j]), i <= j row
+ * by row, of V, and the 3 terms w * (Ju[i] * ru + Jv[i] * rv) of g.  Per camera c >= 1 it sees, one
+ * view's terms each: W_c[r][j] = w * (Cu[r] * Ju[j] + Cv[r] * Jv[j]) (6 x 3), its 21 terms
+ * w * (Cu[r] * Cu[s] + Cv[r] * Cv[s]), r <= s row by row, of U_c and its 6 terms
+ * w * (Cu[r] * ru + Cv[r] * rv) of h_c.
+ *   Damping: V[j][j] = V[j][j] + lambda * V[j][j].
+ *   V = L D L^T by the loops of the track poses with 3 in place of 6.  A landmark with a pivot not
+ *   > 0 contributes nothing to this step and keeps its X.
+ *   V x = q for a right-hand side q: z[i] = q[i], then for k = 0..i-1: z[i] = z[i] - L[i][k] * z[k];
+ *   y[i] = z[i] / D[i];  for i = 2..0: x[i] = y[i], then for k = i+1..2: x[i] = x[i] - L[k][i] * x[k].
+ *   Y_c[r] = the solution for q = W_c[r] (6 rows of 3).
+ * Reduced system of 6 (V - 1) unknowns, camera c's six at 6 (c - 1).  Every scalar below is one
+ * chain: the landmarks' terms in ascending ordinal added onto +0.0 one at a time, a landmark that
+ * failed above or does not see the camera (the later camera of the two) adding nothing:
+ *   T_cc'[r][s] = sum of (Y_c[r][0] * W_c'[s][0] + Y_c[r][1] * W_c'[s][1]) + Y_c[r][2] * W_c'[s][2]
+ *   Tg_c[r]     = sum of (Y_c[r][0] * g[0] + Y_c[r][1] * g[1]) + Y_c[r][2] * g[2]
+ *   U_c[r][s], h_c[r] = the sums of the landmarks' terms
+ * and then, the subtraction made last: for c < c': S_cc'[r][s] = -T_cc'[r][s];  S_cc[r][s] =
+ * U_c[r][s] - T_cc[r][s] for r < s, and (U_c[r][r] + lambda * U_c[r][r]) - T_cc[r][r] on the
+ * diagonal;  r_c[r] = h_c[r] - Tg_c[r].  Only the upper triangle of S is formed.  The order of a
+ * sum depends on no workgroup size and no tiling.
+ *   S delta = -r by the LDL^T of the track poses with 6 (V - 1) in place of 6, the same loops; a
+ *   pivot not > 0 or a non-finite delta ends the pair DEGENERATE on the state before this step.
+ *   Back-substitution per landmark that did not fail: q[j] = -g[j]; then for the cameras c >= 1 it
+ *   sees, in ascending c, with dc = delta's six of camera c:
+ *     t = W_c[0][j] * dc[0], then for r = 1..5: t = t + W_c[r][j] * dc[r];  q[j] = q[j] - t
+ *   dx = the solution of V dx = q as above, X[j] = X[j] + dx[j].
+ *   Cameras c >= 1: A <- C A, b <- C b + dc[3..6) by the Cayley map of the track poses on dc.
+ * Exactly `iters` steps are taken unless one fails: no convergence test, no accept / reject inside
+ * the loop.
+ *
+ * Cost of a state: per landmark, over its views in ascending v onto +0.0, rho = e2 if e2 <= kh *
+ * kh, else (2 * kh) * sqrt(e2) - kh * kh (a view with !(P2 > 0) adds +0.0); the landmarks' values
+ * in ascending ordinal onto +0.0.  cost0 is the cost of the start state, cost that of the state
+ * after the last step taken.
+ *
+ * Guard and gauge.  s = sqrt((b0 * b0 + b1 * b1) + b2 * b2) of camera 1 after the last step.  The
+ * fit is kept if at least one step was taken, s > 0 with 1 / s finite, and cost <= cost0.  A kept
+ * fit is divided by s: every b[i] of the cameras c >= 1 and every X[j] of every landmark becomes
+ * itself / s, so that |t| = 1 and the points stand where the raw ones stand (camera of frame p,
+ * units of baseline p); ratio = 1 / sqrt((b0 * b0 + b1 * b1) + b2 * b2) of camera 2 after that
+ * division (baseline p over baseline p - 1, what scale[p].ratio and pose[p].scale estimate), 0.0
+ * when V = 2.  The scale is left to the damping during the steps: the cost does not change along
+ * it.  A fit that is not kept leaves the start values in every output, byte for byte: R_p, d_p,
+ * the raw X, and ratio = rho_p (0.0 when V = 2); cost still reports the last state's cost.  A
+ * caller never gets a worse state than it put in.
+ *
+ * Final pass on the output state, as in the section above: per landmark n_used, n_inliers, rms
+ * and views; its iters = the steps that moved it, its status DVO_TRACK_REFINE_OK where every step
+ * taken moved it, DVO_TRACK_REFINE_DEGENERATE where its own factorisation failed in one, and
+ * DVO_TRACK_REFINE_NONE with iters 0 where the fit was not kept.  Per pair n_points = n, n_obs =
+ * the sum of the landmarks' views, n_inliers = the sum of theirs, rms = sqrt(the landmarks'
+ * inlier sums of e in ascending ordinal onto +0.0 / n_inliers), 0.0 with none; rms0 is the same
+ * on the start state.
+ *
+ * Status.  DVO_TRACK_BUNDLE_OK.  DVO_TRACK_BUNDLE_NONE: the pair does not take part: R_p, d_p,
+ * and 0 in every other field; its landmarks' slots hold the raw X, views 2, DVO_TRACK_REFINE_NONE.
+ * DVO_TRACK_BUNDLE_DEGENERATE: a step failed (the steps before it count, and are kept if the
+ * guard lets them), or s was not usable.  DVO_TRACK_BUNDLE_NOT_IMPROVED: !(cost <= cost0).
+ * V comes from the window, not from the chains: a window camera that no landmark of the pair sees
+ * (every track shorter than the window) has a zero block in S, the first step fails and the pair
+ * ends DEGENERATE on its start values; where tracks are short, bind fewer views. */
+#define DVO_TRACK_BUNDLE_OK 0
+#define DVO_TRACK_BUNDLE_NONE 1
+#define DVO_TRACK_BUNDLE_DEGENERATE 2
+#define DVO_TRACK_BUNDLE_NOT_IMPROVED 3
+#define DVO_TRACK_BUNDLE_LAMBDA 1e-6 /* the default damping */
+typedef struct {              /* 160 bytes */
+    double R[9], t[3];        /* camera p + 1 from camera p: x' = R x + t, |t| = 1 for a kept fit */
+    double ratio;             /* baseline p over baseline p - 1; 0.0 when n_cams = 2 */
+    double cost0, cost;       /* the Huber cost of the start and of the last state, normalised units squared */
+    double rms0, rms;         /* the inliers' rms in pixels on the start and on the output state */
+    int32_t n_points, n_obs, n_inliers, n_cams, iters, status;
+} dvo_track_bundle;
+#ifdef __cplusplus
+static_assert(sizeof(dvo_track_bundle) == 160, "layout");
+#else
+_Static_assert(sizeof(dvo_track_bundle) == 160, "layout");
+#endif
+/* Binds d_bundle [pairs] and d_points [pairs][the landmark binding's cap] (laid slot for slot
+ * beside the landmarks; slots [0, min(count, cap)) are written, bytes outside them are not
+ * touched) for the NEXT batch only.  Either may be NULL; both NULL clears a pending binding.
+ * DVO_EINVAL unless a tracks binding with non-NULL d_link and d_scale is pending.  A pose binding
+ * is optional and feeds the unit motions when it is pending at the time of this call; a refine
+ * binding is not required.  views 2..8 (default 6), iters 1..16 (default 5), lambda (default
+ * DVO_TRACK_BUNDLE_LAMBDA), huber_px (default 1.0; INFINITY weights every view 1), inlier_px
+ * (default 2.0), min_points >= 6 (default 8): zero or negative means the default; DVO_EINVAL above
+ * the ranges, for views 1, for min_points 1..5, or for a NaN.  Bind the bundle last: clearing the
+ * landmark binding and every dvo_stream_set_tracks, dvo_stream_set_track_poses and
+ * dvo_stream_set_track_refine call clear a pending bundle binding.  It travels with the batch and
+ * is written when it retires, after the refine outputs, on the stream's HIP stream with no
+ * read-back; a *_pairs call refuses it as it refuses tracks.  The first binding allocates 36 B
+ * per slot of the point buffer for every pair set (32 B for a landmark's current X and step
+ * count, 4 B of full links for batches without a refine binding), once; a stream that never
+ * binds it launches and holds what it did before, and the landmark, link, scale, pose, id and
+ * refined bytes of a batch do not depend on the binding. */
+int dvo_stream_set_track_bundle(dvo_stream* s, dvo_track_bundle* d_bundle, dvo_landmark_refined* d_points, int views,
+                                int iters, double lambda, double huber_px, double inlier_px, int min_points);
+/* The same for a k-NN stream; a detect call alone consumes nothing. */
+int dvo_knn_stream_set_track_bundle(dvo_knn_stream* s, dvo_track_bundle* d_bundle, dvo_landmark_refined* d_points,
+                                    int views, int iters, double lambda, double huber_px, double inlier_px,
+                                    int min_points);
+
 /* Test hooks: exercise one device algorithm in isolation. */
 /* KeyPointsFilter::retainBest permutation on `n` float responses (GPU emulation
  * of libstdc++ nth_element + partition); depth < 0 = libstdc++ default. */
@@ -1388,6 +1524,16 @@ int dvo_test_track_refine(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* c
                           int min_points, int32_t* link, dvo_track_scale* scale, dvo_track_pose* pose, int rf_views,
                           int rf_iters, double rf_huber_px, double rf_inlier_px, int use_poses,
                           dvo_landmark_refined* refined, dvo_track_id* id);
+/* dvo_test_track_poses with the bundle kernel (dvo_stream_set_track_bundle) and no refine binding:
+ * each landmark's x1, y1 are read too, the six bd_ parameters are the binding's, defaults
+ * included, and use_poses says whether the poses feed the unit motions.  bundle [pairs] and points
+ * [pairs][cap_out] are copied up whole before the run and back whole after it; either may be NULL. */
+int dvo_test_track_bundle(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* count, const int32_t* mq,
+                          const int32_t* mt, const int32_t* m, const dvo_pair_record* rec, int pairs, int cap, int stride,
+                          int kp_cap, int cap_out, const double* K, int iters, double huber_px, double inlier_px,
+                          int min_points, int32_t* link, dvo_track_scale* scale, dvo_track_pose* pose, int bd_views,
+                          int bd_iters, double bd_lambda, double bd_huber_px, double bd_inlier_px, int bd_min_points,
+                          int use_poses, dvo_track_bundle* bundle, dvo_landmark_refined* points);
 
 #ifdef __cplusplus
 }
