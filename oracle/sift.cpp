@@ -16,8 +16,13 @@
 //   - cos/sin/pow of a float argument = double libm result rounded to float.
 // Parity against OpenCV itself is unpinned (OpenCV is absent).
 // What is pinned: first-principles anchors on Gaussian blobs (blob position, size and orientation:
-// tests/test_detector_anchors.py), and which branches the test images enter (the census below,
-// tests/test_detector_census.py).
+// tests/test_detector_anchors.py); the orientation peaks, the 128 descriptor entries and the refined
+// position, layer byte, size and response of every keypoint as functions of the pixels, against a float64
+// model of the scale space written from Lowe (2004) (tests/sift_reference.py,
+// tests/test_descriptor_anchors.py; the device in tests/test_gpu_descriptor_anchors.py); and which branches
+// the test images enter (the census below, tests/test_detector_census.py).
+// Still not pinned: the extremum search itself (which candidates exist, the contrast and edge tests, the
+// iteration that moves a candidate), and parity with an OpenCV binary.
 #include <algorithm>
 #include <cfloat>
 #include <climits>

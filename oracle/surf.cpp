@@ -19,8 +19,12 @@
 //     ResizeAreaFastVec path), other integer scales cvRound(sum * (1.f/area)).
 // Parity against OpenCV itself is unpinned (OpenCV is absent).
 // What is pinned: first-principles anchors on Gaussian blobs (blob position, sign, size order and orientation:
-// tests/test_detector_anchors.py), and which branches the test images enter (the census below,
-// tests/test_detector_census.py).
+// tests/test_detector_anchors.py); the orientation and the 64 descriptor entries of every keypoint as
+// functions of the pixels, against a float64 model written from Bay et al. (2008) (tests/surf_reference.py,
+// tests/test_descriptor_anchors.py; the device in tests/test_gpu_descriptor_anchors.py); and which branches
+// the test images enter (the census below, tests/test_detector_census.py).
+// Still not pinned: the Hessian response and the interpolation of a maximum (position, size), and parity
+// with an OpenCV binary.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>

@@ -6,6 +6,12 @@ blobs of known centre, width, sign and background slope; the GPU inherits them t
 test_gpu_detector_regimes.py, which compares it with the oracle on the same images (detector_cases.py).
 The tolerances are the algorithms' own grids, none is fitted to the results.  CPU only.
 
+These are the blob-level facts.  The orientation peaks, the 128 and 64 descriptor entries and SIFT's refined
+position, layer, size and response as functions of the pixels are pinned by test_descriptor_anchors.py
+(float64 models: sift_reference.py, surf_reference.py), on the device by test_gpu_descriptor_anchors.py.
+Not pinned anywhere: SURF's Hessian response and interpolation, SIFT's extremum search itself, and parity
+with an OpenCV binary.
+
 Measured on the committed oracle (printed by the tests):
   SIFT position error (after the +0.25 px offset) <= 0.05 px, size ratio 1.001 .. 1.024;
   SURF position error <= 0.12 px; orientation error <= 4.3 deg (SIFT), <= 9.1 deg (SURF, at theta 270)."""
