@@ -1,6 +1,7 @@
 """Float64 model of SIFT's scale space, orientation assignment, descriptor and sub-pixel refinement, written
 from Lowe (2004) and OpenCV's documented definitions of SIFT_create(), NOT from oracle/sift.cpp or sift.hip,
-and the check test_descriptor_anchors.py (oracle) and test_gpu_descriptor_anchors.py (device) share.
+and the check test_descriptor_anchors.py (oracle) and test_gpu_descriptor_anchors.py (device) share.  The
+last part of the module is the detection model (which keypoints exist), described where it begins.
 
 The model takes the 8-bit image and the keypoint records only.  Everything is a function of the pixels:
 
@@ -439,3 +440,173 @@ def check_features(img, kps, desc, label, base_sigma=1.6, max_keypoints=None, re
     assert ref_worst.max() <= 1.0, (label, "refinement", ref_worst.tolist())
     return dict(checked=len(chosen), undecided=undecided, skipped=skipped, entry_err=entry_err, ang_err=ang_err,
                 octaves=octaves, layers=layers, saturated=saturated, by_split=by_split)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Detection: which keypoints exist, as a function of the pixels (Lowe 2004 sections 3 to 4.1, OpenCV's
+# documented SIFT_create(nOctaveLayers=3, contrastThreshold=0.04, edgeThreshold=10)).
+#
+#   search      every octave from -1 upward while rows and columns beyond a border of 5 remain, DoG layers 1 to 3
+#   candidate   |D| (in grey levels) above floor(0.5 * 0.04 / 3 * 255) = 1 and, with D > 0, D >= each of the 26
+#               neighbours of the 3 x 3 x 3 cube (D < 0: <=)
+#   refinement  x = -H^-1 g (refinement() above); accepted when all three |x| < 0.5, otherwise the cell moves by
+#               round(x) and the solve is repeated, five solves at the most; a cell that leaves layers 1 to 3 or
+#               the border is rejected, and so is a fifth solve that still asks for a move
+#   contrast    |D + g.x / 2| * 3 >= 0.04, pixels scaled to [0, 1]
+#   edge        on the 2 x 2 spatial Hessian: det > 0 and tr^2 * 10 < 11^2 * det
+#
+# Every comparison is made with the error its operands carry in a float32 implementation: a DoG sample carries
+# e = 2 PYR_ERR / 255 (PYR_ERR above), a difference of two 2 e, x carries dx = |H^-1|_inf * 7 e, the contrast
+# e + 1.5 (e / 2 + |g|_inf dx), as derived at PYR_ERR; the spatial second differences carry 4 e (dxx, dyy) and e
+# (dxy), so det carries 4 e (|dxx| + |dyy|) + 2 e |dxy| and 121 det - 10 tr^2 carries 121 times that plus
+# 20 |tr| 8 e.  A comparison whose margin exceeds its error is decided; a candidate all of whose comparisons
+# are decided is DECIDED present or absent; any comparison inside its error makes every cell the candidate
+# can still reach UNDECIDED: both outcomes are followed, a move whose rounding can go either way to both
+# cells.  Where dx exceeds 1 (a Hessian too ill conditioned to say where a float32 solve goes) the 3 x 3 x 3
+# cube around the cell is undecided and the path ends.
+#
+# Not from the paper or the documentation: >= rather than > in the extremum test (it differs on exact ties
+# only, which are inside the error and so undecided), five solves rather than five moves, the floor in the
+# pre-threshold, and a singular H giving x = 0 are OpenCV's source, which the oracle restates too.  The last
+# cannot occur unnoticed here: a singular float64 H has dx = infinity and is undecided.
+DET_BORDER = 5
+DET_CONTRAST = 0.04
+DET_EDGE = 10.0
+DET_ACCEPT = 0.5
+DET_STEPS = 5
+DET_E = 2.0 * PYR_ERR / 255.0
+_N26 = [(dl, dr, dc) for dl in (-1, 0, 1) for dr in (-1, 0, 1) for dc in (-1, 0, 1) if (dl, dr, dc) != (0, 0, 0)]
+_N18 = [d for d in _N26 if 0 in d]   # without the cube's eight corners
+assert len(_N18) == 18
+
+
+class DetectionModel:
+    """The keypoint cells (octave, layer, row, column) of one image: present (decided) and undecided.
+    The keyword arguments are the parameters the negative controls of test_detection_anchors.py perturb."""
+
+    def __init__(self, img, border=DET_BORDER, neighbours=26, contrast=DET_CONTRAST, edge=DET_EDGE, accept=DET_ACCEPT,
+                 prethreshold=1.0):
+        self.border, self.contrast, self.edge, self.accept = border, contrast, edge, accept
+        self.offsets = _N26 if neighbours == 26 else _N18
+        self.pre = math.floor(0.5 * DET_CONTRAST / N_LAYERS * 255.0) * prethreshold / 255.0
+        self.ss = ScaleSpace(img)
+        self.present, self.undecided = set(), set()
+        self.candidates = 0
+        h, w = np.asarray(img).shape
+        h, w, octave = 2 * h, 2 * w, -1
+        while h > 2 * border and w > 2 * border:
+            self._octave(octave)
+            h, w, octave = h // 2, w // 2, octave + 1
+        self.octaves = octave + 1   # searched: -1 .. octave - 1
+        self.undecided -= self.present
+
+    def _octave(self, octave):
+        b, e = self.border, DET_E
+        D = np.stack([self.ss.dog(octave, l) for l in range(N_LAYERS + 2)]) / 255.0
+        self.D = D
+        _, h, w = D.shape
+        core = D[1:N_LAYERS + 1, b:h - b, b:w - b]
+        nb = np.stack([D[1 + dl:N_LAYERS + 1 + dl, b + dr:h - b + dr, b + dc:w - b + dc] for dl, dr, dc in self.offsets])
+        hi, lo = nb.max(axis=0), nb.min(axis=0)
+        # possible: no comparison decided against; certain: every comparison decided for
+        pos_p = (core > self.pre - e) & (core > -e) & (core >= hi - 2 * e)
+        neg_p = (core < -self.pre + e) & (core < e) & (core <= lo + 2 * e)
+        pos_c = (core > self.pre + e) & (core >= hi + 2 * e)
+        neg_c = (core < -self.pre - e) & (core <= lo - 2 * e)
+        certain = pos_c | neg_c
+        for l, r, c in np.argwhere(pos_p | neg_p):
+            self.candidates += 1
+            self._refine(octave, int(l) + 1, int(r) + b, int(c) + b, 0, bool(certain[l, r, c]))
+
+    def _at(self, layer, r, c):
+        """(D, g, H) at a cell of self.D (the same differences as refinement())."""
+        p, q, n = self.D[layer - 1], self.D[layer], self.D[layer + 1]
+        g = np.array([(q[r, c + 1] - q[r, c - 1]) / 2.0, (q[r + 1, c] - q[r - 1, c]) / 2.0, (n[r, c] - p[r, c]) / 2.0])
+        v2 = 2.0 * q[r, c]
+        dxx, dyy, dss = q[r, c + 1] + q[r, c - 1] - v2, q[r + 1, c] + q[r - 1, c] - v2, n[r, c] + p[r, c] - v2
+        dxy = (q[r + 1, c + 1] - q[r + 1, c - 1] - q[r - 1, c + 1] + q[r - 1, c - 1]) / 4.0
+        dxs = (n[r, c + 1] - n[r, c - 1] - p[r, c + 1] + p[r, c - 1]) / 4.0
+        dys = (n[r + 1, c] - n[r - 1, c] - p[r + 1, c] + p[r - 1, c]) / 4.0
+        return float(q[r, c]), g, np.array([[dxx, dxy, dxs], [dxy, dyy, dys], [dxs, dys, dss]])
+
+    def _inside(self, layer, r, c):
+        _, h, w = self.D.shape
+        return 1 <= layer <= N_LAYERS and self.border <= r < h - self.border and self.border <= c < w - self.border
+
+    def _refine(self, octave, layer, r, c, step, sure):
+        e = DET_E
+        D, g, H = self._at(layer, r, c)
+        try:
+            Hi = np.linalg.inv(H)
+            x = -Hi @ g
+            dx = float(np.abs(Hi).sum(axis=1).max()) * 7.0 * e
+        except np.linalg.LinAlgError:
+            x, dx = np.zeros(3), np.inf
+        if not np.isfinite(dx) or dx > 1.0 or not np.isfinite(x).all():
+            for dl, dr, dc in _N26 + [(0, 0, 0)]:
+                if self._inside(layer + dl, r + dr, c + dc):
+                    self.undecided.add((octave, layer + dl, r + dr, c + dc))
+            return
+        ax = np.abs(x)
+        may_accept, must_accept = bool((ax < self.accept + dx).all()), bool((ax < self.accept - dx).all())
+        if may_accept:
+            self._tests(octave, layer, r, c, D, g, H, x, dx, sure and must_accept)
+        if must_accept or step + 1 >= DET_STEPS or ax.max() > 1e6:
+            return
+        # the move: each coordinate to round(x), or to either neighbour where x is within dx of a half-integer
+        # (a coordinate that stays while another moves is round(x) = 0 like any other)
+        options = []
+        for v in x:
+            options.append(sorted({int(np.rint(v - dx)), int(np.rint(v)), int(np.rint(v + dx))}))
+        n_opt = len(options[0]) * len(options[1]) * len(options[2])
+        for mc in options[0]:
+            for mr in options[1]:
+                for ml in options[2]:
+                    if (mc, mr, ml) == (0, 0, 0):
+                        continue   # no move is the acceptance, followed above
+                    if self._inside(layer + ml, r + mr, c + mc):
+                        self._refine(octave, layer + ml, r + mr, c + mc, step + 1, sure and not may_accept and n_opt == 1)
+
+    def _tests(self, octave, layer, r, c, D, g, H, x, dx, sure):
+        e = DET_E
+        contr = abs(D + 0.5 * float(g @ x)) * N_LAYERS
+        dcontr = (e + 1.5 * (0.5 * e + float(np.abs(g).max()) * dx)) * N_LAYERS
+        dxx, dyy, dxy = H[0, 0], H[1, 1], H[0, 1]
+        tr, det = dxx + dyy, dxx * dyy - dxy * dxy
+        ddet = 4.0 * e * (abs(dxx) + abs(dyy)) + 2.0 * e * abs(dxy)
+        f = (self.edge + 1.0) ** 2 * det - self.edge * tr * tr
+        df = (self.edge + 1.0) ** 2 * ddet + 2.0 * self.edge * abs(tr) * 8.0 * e
+        margins = (contr - self.contrast, dcontr), (det, ddet), (f, df)
+        if any(m <= -d for m, d in margins):
+            return
+        cell = (octave, layer, r, c)
+        if sure and all(m > d for m, d in margins):
+            self.present.add(cell)
+        else:
+            self.undecided.add(cell)
+
+
+def keypoint_cells(kps):
+    """The cell (octave, layer, row, column) of each returned keypoint: unpack's level position, rounded."""
+    out = []
+    for kp in kps:
+        octave, layer, _, _, px, py, _ = unpack(kp)
+        out.append((octave, layer, int(np.rint(py)), int(np.rint(px))))
+    return out
+
+
+def check_detection(img, kps, label, model=None, **perturb):
+    """The detection anchor on one image's keypoints: every decided-present cell is the cell of a returned
+    keypoint (else missing) and every returned keypoint's cell is decided present or undecided (else
+    unexplained).  Prints and returns the counts; `bad` lists the violations, which the caller asserts empty
+    (the negative controls assert the opposite)."""
+    m = model if model is not None else DetectionModel(img, **perturb)
+    cells = set(keypoint_cells(kps))
+    missing = sorted(m.present - cells)
+    unexplained = sorted(cells - m.present - m.undecided)
+    und = len(cells & m.undecided)
+    print(f"{label}: {len(kps)} keypoints in {len(cells)} cells, octaves -1 .. {m.octaves - 2} searched, {m.candidates} candidates; "
+          f"{len(m.present)} decided present, {len(m.undecided)} undecided cells ({und} of them returned), "
+          f"{len(missing)} missing, {len(unexplained)} unexplained")
+    return dict(keypoints=len(kps), cells=len(cells), present=len(m.present), undecided=len(m.undecided), undecided_returned=und,
+                missing=missing, unexplained=unexplained, bad=missing + unexplained)

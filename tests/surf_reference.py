@@ -1,7 +1,8 @@
 """Float64 model of SURF's orientation assignment and 64-entry descriptor, written from Bay et al. (2008) and
 the documented behaviour of OpenCV's SURF_create(extended=False, upright=False), NOT from oracle/surf.cpp or
 surf.hip, and the check test_descriptor_anchors.py (oracle) and test_gpu_descriptor_anchors.py (device)
-share.  The model takes the 8-bit image and the keypoint records only.
+share.  The model takes the 8-bit image and the keypoint records only.  The last part of the module is the
+fast Hessian (which keypoints exist), described where it begins.
 
 Orientation.  s = size * 1.2 / 9; Haar wavelets of side g = 2 round(2 s): dx = mean of the right half minus
 mean of the left half, dy = mean of the top half minus mean of the bottom half, from an exact integer integral
@@ -283,3 +284,210 @@ def check_features(img, kps, desc, label, smooth=False, max_keypoints=None):
         assert ori_excluded == 0 and clean == m, (label, ori_excluded, clean, m)
     return dict(checked=m, ori_err=ori_err, ori_excluded=ori_excluded, other_window=other_window, clean=clean, clean_err=clean_err,
                 unc_err=unc_err, desc_excluded=desc_excluded)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Detection: the fast Hessian of Bay et al. (2008) section 3 with the documented defaults of SURF_create
+# (nOctaves 4, nOctaveLayers 3): which keypoints exist, where, with what size, sign and response.
+#
+#   layout     octave o has five layers of size (9 + 6 layer) 2^o sampled every 2^o pixels; a window of that size
+#              with its corner at (j, i) 2^o is sample (i + m, j + m) of the layer, m = (size / 2) / 2^o in
+#              integers, so that the samples of an octave's layers with equal index are (nearly) concentric.
+#              A layer larger than the image has no samples.
+#   filters    the 9 x 9 masks of the paper's figure (corner coordinates x0, y0, x1, y1, weight):
+#                Dxx (0, 2, 3, 7, 1) (3, 2, 6, 7, -2) (6, 2, 9, 7, 1), Dyy its transpose,
+#                Dxy (1, 1, 4, 4, 1) (5, 1, 8, 4, -1) (1, 5, 4, 8, -1) (5, 5, 8, 8, 1),
+#              each coordinate c scaled to round(c size / 9).  No product c size / 9 is a half-integer:
+#              2 size c = 9 (2 k + 1) would have an even left and an odd right side, so the rounding mode cannot
+#              matter.  Each lobe is the box sum (exact, from the integer integral image) times weight / area.
+#              det = Dxx Dyy - 0.81 Dxy^2, trace = Dxx + Dyy.
+#   maxima     in the three middle layers: a sample above the threshold and strictly above its 26 neighbours,
+#              at least (size of the next layer / 2) / 2^o + 1 samples from every side of the layer's grid of
+#              (rows / 2^o) x (columns / 2^o).
+#   keypoint   x = -A^-1 b from the central differences of det over (sample column, sample row, layer); kept
+#              when x != 0 and every |x| <= 1; centre = window corner + (size - 1) / 2 + x 2^o, size = round(size +
+#              x[2] (size - size of the layer below)), class_id = sign of the trace, response = det, octave = o.
+#
+# Float32 bound of det, counted.  Box sums are exact integers below 2^24 (255 * 176 * 160 < 2^23 for every
+# image used; asserted).  With U = 2^-24 and A = sum over lobes of |weight / area * box sum|: a lobe's weight is
+# one rounding, its product one, and the (lobes - 1) additions one each of a partial sum that is at most A, so
+# |dDxx| <= 4 U Axx, |dDyy| <= 4 U Ayy, |dDxy| <= 5 U Axy.  Then
+#   d(det) <= |Dyy| dDxx + |Dxx| dDyy + U |Dxx Dyy|            (the product)
+#           + 0.81 (2 |Dxy| dDxy + 3 U Dxy^2)                    (0.81 itself and two products)
+#           + U (|Dxx Dyy| + 0.81 Dxy^2)                         (the subtraction),
+# and d(trace) <= dDxx + dDyy + U |trace|.  An implementation that accumulates in double or fuses a
+# multiply-add makes fewer roundings, none more.
+# Interpolation, to first order as sift_reference.check_refinement: with E the largest d(det) of the 27
+# samples, b carries E per entry and A at most 4 E per entry (row sums 6 E); a float32 LU solve is backward
+# stable with a perturbation of at most 12 U |A|_inf in A's row sums and 2 U |b|_inf in b (3 x 3, partial
+# pivoting), so |dx| <= |A^-1|_inf ((E + 2 U |b|_inf) + (6 E + 12 U |A|_inf) max(|x|_inf, 1)).
+# A comparison whose margin exceeds its error is decided.  A model keypoint is DECIDED when the threshold, all
+# 26 neighbour comparisons, the three |x| <= 1, the rounding of the size and the sign of the trace are; a
+# possible maximum that no decided comparison rejects is UNDECIDED.
+#
+# Not from the paper or the documentation: the masks' integer scaling, the margins, x != 0 and the form of
+# the size interpolation are OpenCV's source, which the oracle restates too.  The negative controls of
+# test_detection_anchors.py show that each of them is observable.
+HESSIAN_OCTAVES, HESSIAN_LAYERS = 4, 5
+DXX = ((0, 2, 3, 7, 1.0), (3, 2, 6, 7, -2.0), (6, 2, 9, 7, 1.0))
+DYY = tuple((y0, x0, y1, x1, wt) for x0, y0, x1, y1, wt in DXX)
+DXY = ((1, 1, 4, 4, 1.0), (5, 1, 8, 4, -1.0), (1, 5, 4, 8, -1.0), (5, 5, 8, 8, 1.0))
+
+
+class FastHessian:
+    """keypoints: list of dicts (octave, x, y, size, class_id, response and the bounds dresp, dpos; cx, cy the
+    sample's own centre; decided).  The keyword arguments are what the negative controls perturb."""
+
+    def __init__(self, img, threshold, weight=0.81, floor_lobes=False, margin_extra=1, layers=HESSIAN_LAYERS,
+                 trace_sign=1, accept=1.0):
+        self.S = integral(img)
+        self.h, self.w = img.shape
+        assert 255 * self.h * self.w < 2 ** 24
+        self.weight, self.floor_lobes, self.accept, self.trace_sign = weight, floor_lobes, accept, trace_sign
+        self.keypoints, self.layers_skipped, self.maxima = [], 0, 0
+        for octave in range(HESSIAN_OCTAVES):
+            step = 2 ** octave
+            sizes = [(9 + 6 * l) * step for l in range(layers)]
+            resp = [self._layer(s, step) for s in sizes]
+            self.layers_skipped += sum(r is None for r in resp)
+            for l in range(1, layers - 1):
+                self._maxima(octave, step, sizes, resp, l, threshold, margin_extra)
+
+    def _pattern(self, mask, size, step, ni, nj):
+        val, mag = np.zeros((ni, nj)), np.zeros((ni, nj))
+        ys, xs = np.arange(ni)[:, None] * step, np.arange(nj)[None, :] * step
+        for x0, y0, x1, y1, wt in mask:
+            if self.floor_lobes:
+                x0, y0, x1, y1 = (c * size // 9 for c in (x0, y0, x1, y1))
+            else:
+                assert all((2 * c * size) % 9 != 0 or (2 * c * size // 9) % 2 == 0 for c in (x0, y0, x1, y1))
+                x0, y0, x1, y1 = (int(np.rint(c * size / 9.0)) for c in (x0, y0, x1, y1))
+            box = (self.S[ys + y1, xs + x1] - self.S[ys + y0, xs + x1] - self.S[ys + y1, xs + x0] + self.S[ys + y0, xs + x0])
+            t = box * (wt / ((x1 - x0) * (y1 - y0)))
+            val += t
+            mag += np.abs(t)
+        return val, mag
+
+    def _layer(self, size, step):
+        """(det, d(det), trace, d(trace)) on the octave's grid, NaN where the layer has no sample."""
+        if size > self.h or size > self.w:
+            return None
+        ni, nj = 1 + (self.h - size) // step, 1 + (self.w - size) // step
+        dxx, axx = self._pattern(DXX, size, step, ni, nj)
+        dyy, ayy = self._pattern(DYY, size, step, ni, nj)
+        dxy, axy = self._pattern(DXY, size, step, ni, nj)
+        k = self.weight
+        det, tr = dxx * dyy - k * dxy * dxy, dxx + dyy
+        ddxx, ddyy, ddxy = 4 * U * axx, 4 * U * ayy, 5 * U * axy
+        ddet = (np.abs(dyy) * ddxx + np.abs(dxx) * ddyy + U * np.abs(dxx * dyy) + k * (2 * np.abs(dxy) * ddxy + 3 * U * dxy * dxy)
+                + U * (np.abs(dxx * dyy) + k * dxy * dxy))
+        dtr = ddxx + ddyy + U * np.abs(tr)
+        m = (size // 2) // step
+        out = []
+        for a in (det, ddet, tr, dtr):
+            g = np.full((self.h // step, self.w // step), np.nan)
+            g[m:m + ni, m:m + nj] = a
+            out.append(g)
+        return out
+
+    def _maxima(self, octave, step, sizes, resp, l, threshold, margin_extra):
+        if resp[l + 1] is None:
+            return  # its margin exceeds half the grid: nothing to search
+        size = sizes[l]
+        rows, cols = self.h // step, self.w // step
+        margin = (sizes[l + 1] // 2) // step + margin_extra
+        if rows - 2 * margin <= 0 or cols - 2 * margin <= 0:
+            return
+        sl = (slice(margin, rows - margin), slice(margin, cols - margin))
+        v, dv = resp[l][0][sl], resp[l][1][sl]
+        possible, certain = v > threshold - dv, v > threshold + dv
+        for dl in (-1, 0, 1):
+            for di in (-1, 0, 1):
+                for dj in (-1, 0, 1):
+                    if (dl, di, dj) == (0, 0, 0):
+                        continue
+                    s2 = (slice(margin + di, rows - margin + di), slice(margin + dj, cols - margin + dj))
+                    n, dn = resp[l + dl][0][s2], resp[l + dl][1][s2]
+                    if margin_extra == 1:
+                        assert not np.isnan(n).any(), (octave, l, "a neighbour outside its layer")
+                    else:   # the control without the + 1 reads where the next layer has no sample: taken as 0
+                        n, dn = np.nan_to_num(n), np.nan_to_num(dn)
+                    possible &= v > n - (dv + dn)
+                    certain &= v > n + (dv + dn)
+        m0 = (size // 2) // step
+        for i, j in np.argwhere(possible):
+            sure = bool(certain[i, j])
+            i, j = int(i) + margin, int(j) + margin
+            self.maxima += 1
+            N = np.nan_to_num(np.stack([resp[l + dl][0][i - 1:i + 2, j - 1:j + 2] for dl in (-1, 0, 1)]))
+            E = float(max(np.nan_to_num(resp[l + dl][1][i - 1:i + 2, j - 1:j + 2]).max() for dl in (-1, 0, 1)))
+            b = -np.array([(N[1, 1, 2] - N[1, 1, 0]) / 2, (N[1, 2, 1] - N[1, 0, 1]) / 2, (N[2, 1, 1] - N[0, 1, 1]) / 2])
+            c2 = 2 * N[1, 1, 1]
+            dxy = (N[1, 2, 2] - N[1, 2, 0] - N[1, 0, 2] + N[1, 0, 0]) / 4
+            dxs = (N[2, 1, 2] - N[2, 1, 0] - N[0, 1, 2] + N[0, 1, 0]) / 4
+            dys = (N[2, 2, 1] - N[2, 0, 1] - N[0, 2, 1] + N[0, 0, 1]) / 4
+            A = np.array([[N[1, 1, 0] + N[1, 1, 2] - c2, dxy, dxs], [dxy, N[1, 0, 1] + N[1, 2, 1] - c2, dys],
+                          [dxs, dys, N[0, 1, 1] + N[2, 1, 1] - c2]])
+            try:
+                Ai = np.linalg.inv(A)
+                x = Ai @ b
+                a_inf = float(np.abs(A).sum(axis=1).max())
+                dx = float(np.abs(Ai).sum(axis=1).max()) * ((E + 2 * U * float(np.abs(b).max())) +
+                                                           (6 * E + 12 * U * a_inf) * max(float(np.abs(x).max()), 1.0))
+            except np.linalg.LinAlgError:
+                x, dx = np.zeros(3), np.inf
+            if not np.isfinite(x).all() or not np.isfinite(dx):
+                x, dx = np.zeros(3), np.inf
+            ax = np.abs(x)
+            if (ax > self.accept + dx).any():
+                continue  # decided absent
+            sure = sure and bool((ax < self.accept - dx).all())
+            ds = size - sizes[l - 1]
+            fsize = size + x[2] * ds
+            sure = sure and abs(fsize - math.floor(fsize) - 0.5) > dx * ds
+            tr, dtr = resp[l][2][i, j], resp[l][3][i, j]
+            sure = sure and abs(tr) > dtr
+            cx, cy = step * (j - m0) + (size - 1) / 2.0, step * (i - m0) + (size - 1) / 2.0
+            px, py = cx + x[0] * step, cy + x[1] * step
+            self.keypoints.append(dict(octave=octave, layer=l, x=px, y=py, cx=cx, cy=cy, step=step, size=int(np.rint(fsize)),
+                                       class_id=self.trace_sign * (1 if tr > 0 else -1), response=float(N[1, 1, 1]),
+                                       dresp=float(resp[l][1][i, j]), dpos=dx * step + 2.0 ** -22 * max(px, py, 1.0), decided=sure))
+
+
+def check_detection(img, kps, threshold, label, **perturb):
+    """The detection anchor on one image's keypoints.  A returned keypoint matches a model keypoint when the
+    octaves are equal, the response lies within d(det) (and one float32 place) and the position within |dx| 2^o
+    per axis; for an undecided model keypoint, whose |dx| may be anything, within (1 + accept) 2^o of the sample's
+    own centre.  Every decided model keypoint has a match of equal size and class_id (else missing); every
+    returned keypoint matches a model keypoint (else unexplained).  Prints and returns the counts; `bad`
+    lists the violations."""
+    m = FastHessian(img, threshold, **perturb)
+    decided = [k for k in m.keypoints if k["decided"]]
+    rx, ry, rr = kps["x"].astype(np.float64), kps["y"].astype(np.float64), kps["response"].astype(np.float64)
+    explained = np.zeros(len(kps), bool)
+    by_undecided = np.zeros(len(kps), bool)
+    missing, worst_pos, worst_resp = [], 0.0, 0.0
+    for k in m.keypoints:
+        near = (kps["octave"] == k["octave"]) & (np.abs(rr - k["response"]) <= k["dresp"] + 2.0 ** -23 * abs(k["response"]))
+        if k["decided"]:
+            near &= (np.abs(rx - k["x"]) <= k["dpos"]) & (np.abs(ry - k["y"]) <= k["dpos"])
+            full = near & (kps["size"] == k["size"]) & (kps["class_id"] == k["class_id"])
+            if not full.any():
+                missing.append((k["octave"], k["layer"], round(k["x"], 3), round(k["y"], 3), k["size"], k["class_id"], k["response"]))
+            for i in np.flatnonzero(full):
+                worst_pos = max(worst_pos, max(abs(rx[i] - k["x"]), abs(ry[i] - k["y"])) / k["dpos"])
+                worst_resp = max(worst_resp, abs(rr[i] - k["response"]) / (k["dresp"] + 2.0 ** -23 * abs(k["response"])))
+            explained |= full
+        else:
+            reach = (1.0 + perturb.get("accept", 1.0)) * k["step"] + min(k["dpos"], k["step"])
+            near &= (np.abs(rx - k["cx"]) <= reach) & (np.abs(ry - k["cy"]) <= reach)
+            by_undecided |= near
+    by_undecided &= ~explained
+    unexplained = [(int(k["octave"]), float(k["x"]), float(k["y"]), float(k["size"]), int(k["class_id"]), float(k["response"]))
+                   for k in kps[~explained & ~by_undecided]]
+    print(f"{label} threshold {threshold:g}: {len(kps)} keypoints, {m.layers_skipped} layers larger than the image, {m.maxima} possible "
+          f"maxima; {len(decided)} decided, {len(m.keypoints) - len(decided)} undecided ({int(by_undecided.sum())} keypoints held to those), "
+          f"{len(missing)} missing, {len(unexplained)} unexplained; position error / bound {worst_pos:.3f}, response error / bound {worst_resp:.3f}")
+    return dict(keypoints=len(kps), decided=len(decided), undecided=len(m.keypoints) - len(decided), by_undecided=int(by_undecided.sum()),
+                layers_skipped=m.layers_skipped, missing=missing, unexplained=unexplained, bad=missing + unexplained,
+                worst_pos=worst_pos, worst_resp=worst_resp)

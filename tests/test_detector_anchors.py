@@ -9,8 +9,9 @@ The tolerances are the algorithms' own grids, none is fitted to the results.  CP
 These are the blob-level facts.  The orientation peaks, the 128 and 64 descriptor entries and SIFT's refined
 position, layer, size and response as functions of the pixels are pinned by test_descriptor_anchors.py
 (float64 models: sift_reference.py, surf_reference.py), on the device by test_gpu_descriptor_anchors.py.
-Not pinned anywhere: SURF's Hessian response and interpolation, SIFT's extremum search itself, and parity
-with an OpenCV binary.
+Which keypoints exist (SIFT's extremum search with its contrast and edge tests, SURF's Hessian response,
+maxima and interpolation) is pinned by test_detection_anchors.py, on the device by
+test_gpu_detection_anchors.py.  Not pinned anywhere: parity with an OpenCV binary.
 
 Measured on the committed oracle (printed by the tests):
   SIFT position error (after the +0.25 px offset) <= 0.05 px, size ratio 1.001 .. 1.024;
