@@ -71,6 +71,12 @@ TRACK_BUNDLE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("ratio",
                                ("n_inliers", "<i4"), ("n_cams", "<i4"), ("iters", "<i4"), ("status", "<i4")])
 assert TRACK_BUNDLE_DTYPE.itemsize == 160
 TRACK_BUNDLE_OK, TRACK_BUNDLE_NONE, TRACK_BUNDLE_DEGENERATE, TRACK_BUNDLE_NOT_IMPROVED = 0, 1, 2, 3
+# dvo_track_pnp: a pair's pose from a P3P RANSAC on the previous pair's landmarks (dvo_stream_set_track_pnp)
+TRACK_PNP_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("scale", "<f8"), ("rms", "<f8"),
+                            ("n_corr", "<i4"), ("n_best", "<i4"), ("n_used", "<i4"), ("n_inliers", "<i4"),
+                            ("sample", "<i4"), ("solution", "<i4"), ("iters", "<i4"), ("status", "<i4")])
+assert TRACK_PNP_DTYPE.itemsize == 144
+TRACK_PNP_OK, TRACK_PNP_NONE, TRACK_PNP_DEGENERATE, TRACK_PNP_NO_MODEL = 0, 1, 2, 3
 
 
 class DVOError(RuntimeError):
@@ -210,6 +216,12 @@ _SIGNATURES = {
     "dvo_knn_stream_set_track_bundle": ([_vp, _vp, _vp, _c, _c, _d, _d, _d, _c], _c),
     "dvo_test_track_bundle": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c, _c, _c, _c, _c, _vp, _c, _d, _d, _c, _vp, _vp,
                                _vp, _c, _c, _d, _d, _d, _c, _c, _vp, _vp], _c),
+    "dvo_stream_set_track_pnp": ([_vp, _vp, _vp, _c, _c, _c, _d, _d, _c, ctypes.c_uint64], _c),
+    "dvo_knn_stream_set_track_pnp": ([_vp, _vp, _vp, _c, _c, _c, _d, _d, _c, ctypes.c_uint64], _c),
+    "dvo_test_track_pnp": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c, _c, _c, _c, _c, _vp, _c, _d, _d, _c, _vp, _vp,
+                            _vp, _vp, _c, _c, _d, _d, _c, ctypes.c_uint64, _vp, _vp, _c], _c),
+    "dvo_track_pnp_samples_host": ([_c, _c, ctypes.c_uint64, _vp], _c),
+    "dvo_p3p_host": ([_vp, _vp, _vp, _vp, _ip], _c),
     "dvo_knn_pair_create": ([_vp, ctypes.POINTER(KnnPairConfig), ctypes.POINTER(_vp)], _c),
     "dvo_knn_pair_destroy": ([_vp], None),
     "dvo_knn_pair_run": ([_vp, _vp, _vp, _c, _c, ctypes.POINTER(ctypes.c_uint64), _vp], _c),

@@ -18,6 +18,7 @@
 #include "dvo_internal.h"
 #include "jpeg_entropy.h"
 #include "jpeg_split.h"
+#include "p3p.h"
 #include "pair_outputs.h"
 
 using namespace dvo;
@@ -1135,6 +1136,35 @@ int dvo_stream_set_track_bundle(dvo_stream* s, dvo_track_bundle* d_bundle, dvo_l
     if (!s) return DVO_EINVAL;
     return bind_status(s->ctx, s->next.set_track_bundle(s->pairs, s->ctx->device, d_bundle, d_points, views, iters, lambda,
                                                         huber_px, inlier_px, min_points));
+}
+
+int dvo_stream_set_track_pnp(dvo_stream* s, dvo_track_pnp* d_pnp, uint8_t* d_mask, int mask_cap, int hyps, int iters,
+                             double huber_px, double inlier_px, int min_points, uint64_t seed) {
+    if (!s) return DVO_EINVAL;
+    return bind_status(s->ctx, s->next.set_track_pnp(s->pairs, s->ctx->device, d_pnp, d_mask, mask_cap, hyps, iters, huber_px,
+                                                     inlier_px, min_points, seed));
+}
+
+int dvo_track_pnp_samples_host(int n, int hyps, uint64_t seed, int32_t* out) {
+    if (n < 1 || hyps < 1 || hyps > kPnpMaxHyps || !out) return DVO_EINVAL;
+    for (int h = 0; h < hyps; ++h) {
+        int idx[3] = {-1, -1, -1};
+        p3p_sample(seed, h, n, idx);
+        for (int j = 0; j < 3; ++j) out[3 * h + j] = idx[j];
+    }
+    return DVO_OK;
+}
+
+int dvo_p3p_host(const double* Y, const double* nunv, double* R, double* t, int* n_solutions) {
+    if (!Y || !nunv || !R || !t || !n_solutions) return DVO_EINVAL;
+    double Rs[4][9], ts[4][3];
+    const int n = p3p_solve(Y, nunv, Rs, ts);
+    for (int s = 0; s < n; ++s) {
+        for (int i = 0; i < 9; ++i) R[9 * s + i] = Rs[s][i];
+        for (int i = 0; i < 3; ++i) t[3 * s + i] = ts[s][i];
+    }
+    *n_solutions = n;
+    return DVO_OK;
 }
 
 int dvo_stream_sync(dvo_stream* s) {
@@ -2968,6 +2998,13 @@ int dvo_knn_stream_set_track_bundle(dvo_knn_stream* s, dvo_track_bundle* d_bundl
                                                         huber_px, inlier_px, min_points));
 }
 
+int dvo_knn_stream_set_track_pnp(dvo_knn_stream* s, dvo_track_pnp* d_pnp, uint8_t* d_mask, int mask_cap, int hyps,
+                                 int iters, double huber_px, double inlier_px, int min_points, uint64_t seed) {
+    if (!s) return DVO_EINVAL;
+    return bind_status(s->ctx, s->next.set_track_pnp(s->pairs, s->ctx->device, d_pnp, d_mask, mask_cap, hyps, iters, huber_px,
+                                                     inlier_px, min_points, seed));
+}
+
 int dvo_knn_stream_sync(dvo_knn_stream* s) {
     if (!s) return DVO_EINVAL;
     dvo_ctx* ctx = s->ctx;
@@ -3641,7 +3678,8 @@ static int test_tracks_run(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* 
                            const TrackPoseBinding* tp, dvo_track_pose* pose, const TrackRefineBinding* rf = nullptr,
                            dvo_landmark_refined* refined = nullptr, dvo_track_id* id = nullptr,
                            const TrackBundleBinding* bd = nullptr, dvo_track_bundle* bundle = nullptr,
-                           dvo_landmark_refined* points = nullptr) {
+                           dvo_landmark_refined* points = nullptr, const TrackPnpBinding* pn = nullptr,
+                           const float* xy2 = nullptr, dvo_track_pnp* pnp = nullptr, uint8_t* mask = nullptr) {
     if (!ctx || !lm || !count || !mq || !mt || !m || !rec || !link || !scale) return DVO_EINVAL;
     if (pairs < 1 || pairs > 65535 || cap < 1 || stride < 1 || kp_cap < 1 || cap_out < 1)
         return fail(ctx, DVO_EINVAL, "bad pair count, cap, stride, kp_cap or cap_out");
@@ -3673,6 +3711,18 @@ static int test_tracks_run(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* 
                 float* q = &pts[((size_t)p * stride + e.match) * 4];
                 q[0] = e.x1, q[1] = e.y1, q[2] = e.x2, q[3] = e.y2;
             }
+        if (pn)  // every match's second-frame pixel
+            for (int p = 0; p < pairs; ++p)
+                for (int i = 0; i < m[p]; ++i) {
+                    float* q = &pts[((size_t)p * stride + i) * 4];
+                    q[2] = xy2[((size_t)p * stride + i) * 2], q[3] = xy2[((size_t)p * stride + i) * 2 + 1];
+                }
+    }
+    std::vector<dvo_pair_record> rec_pn;  // the PnP kernels read the match count from the record
+    if (pn) {
+        rec_pn.assign(rec, rec + pairs);
+        for (int p = 0; p < pairs; ++p) rec_pn[p].n_matches = m[p];
+        rec = rec_pn.data();
     }
     HIP_TRY(hipSetDevice(ctx->device));
     CallMem mem(ctx->call, ctx->stream);
@@ -3697,6 +3747,10 @@ static int test_tracks_run(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* 
     BundlePoint* dbx = bd ? mem.dev<BundlePoint>(P * stride) : nullptr;
     dvo_track_bundle* dbundle = bd && bundle ? mem.dev<dvo_track_bundle>(P) : nullptr;
     dvo_landmark_refined* dpoints = bd && points ? mem.dev<dvo_landmark_refined>(P * cap_out) : nullptr;
+    PnpCorr* dpc = pn ? mem.dev<PnpCorr>(P * stride) : nullptr;
+    int32_t* dpcnt = pn ? mem.dev<int32_t>(P * tiles) : nullptr;
+    dvo_track_pnp* dpnp = pn ? mem.dev<dvo_track_pnp>(P) : nullptr;
+    uint8_t* dmask = pn && mask ? mem.dev<uint8_t>(P * pn->mask_cap) : nullptr;
     HIP_TRY(mem.error());
     // the scratch side by hand (what PairSets::track_args gives a stream), the caller's side as the streams fill it
     a.L.tmp = dtmp;
@@ -3713,12 +3767,15 @@ static int test_tracks_run(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* 
     a.rank = drank;
     a.rank_stride = (int64_t)P * stride;
     a.bd_x = dbx;
+    a.pnp_corr = dpc;
+    a.pnp_cnt = dpcnt;
     PairOutputs o;
     o.lm.cap = cap_out;
     o.tr = TracksBinding{a.link, a.scale};
     if (tp) o.tp = *tp, o.tp.out = dpose;
     if (rf) o.rf = *rf, o.rf.refined = drefined, o.rf.id = did;
     if (bd) o.bd = *bd, o.bd.out = dbundle, o.bd.points = dpoints;
+    if (pn) o.pn = *pn, o.pn.out = dpnp, o.pn.mask = dmask, o.pn.mask_cap = dmask ? pn->mask_cap : 0;
     GeomArgs g{};
     g.pts_f = dpts;
     if (tp) set_camera(g, K);
@@ -3734,7 +3791,11 @@ static int test_tracks_run(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* 
     if (did) HIP_TRY(mem.put(did, id, P * cap_out * sizeof(dvo_track_id)));
     if (dbundle) HIP_TRY(mem.put(dbundle, bundle, P * sizeof(dvo_track_bundle)));
     if (dpoints) HIP_TRY(mem.put(dpoints, points, P * cap_out * sizeof(dvo_landmark_refined)));
+    if (dmask) HIP_TRY(mem.put(dmask, mask, P * pn->mask_cap));
     HIP_TRY(launch_tracks(a, pairs, ctx->stream));
+    uint8_t *hpnp = nullptr, *hmask = nullptr;
+    if (dpnp) HIP_TRY(mem.get(dpnp, P * sizeof(dvo_track_pnp), &hpnp));
+    if (dmask) HIP_TRY(mem.get(dmask, P * pn->mask_cap, &hmask));
     uint8_t *hlink, *hscale, *hpose = nullptr, *hrefined = nullptr, *hid = nullptr, *hbundle = nullptr, *hpoints = nullptr;
     if (dbundle) HIP_TRY(mem.get(dbundle, P * sizeof(dvo_track_bundle), &hbundle));
     if (dpoints) HIP_TRY(mem.get(dpoints, P * cap_out * sizeof(dvo_landmark_refined), &hpoints));
@@ -3751,6 +3812,8 @@ static int test_tracks_run(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* 
     if (hid) std::memcpy(id, hid, P * cap_out * sizeof(dvo_track_id));
     if (hbundle) std::memcpy(bundle, hbundle, P * sizeof(dvo_track_bundle));
     if (hpoints) std::memcpy(points, hpoints, P * cap_out * sizeof(dvo_landmark_refined));
+    if (hpnp) std::memcpy(pnp, hpnp, P * sizeof(dvo_track_pnp));
+    if (hmask) std::memcpy(mask, hmask, P * pn->mask_cap);
     return DVO_OK;
 }
 
@@ -3806,6 +3869,25 @@ int dvo_test_track_bundle(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* c
     d.use_pose = use_poses != 0;
     return test_tracks_run(ctx, lm, count, mq, mt, m, rec, pairs, cap, stride, kp_cap, cap_out, link, scale, K, &b, pose,
                            nullptr, nullptr, nullptr, &d, bundle, points);
+}
+
+int dvo_test_track_pnp(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* count, const int32_t* mq,
+                       const int32_t* mt, const int32_t* m, const dvo_pair_record* rec, int pairs, int cap, int stride,
+                       int kp_cap, int cap_out, const double* K, int iters, double huber_px, double inlier_px,
+                       int min_points, int32_t* link, dvo_track_scale* scale, dvo_track_pose* pose, const float* xy2,
+                       int pnp_hyps, int pnp_iters, double pnp_huber_px, double pnp_inlier_px, int pnp_min_points,
+                       uint64_t pnp_seed, dvo_track_pnp* pnp, uint8_t* mask, int mask_cap) {
+    if (!ctx || !K || !pose || !xy2 || !pnp) return DVO_EINVAL;
+    TrackPoseBinding b;
+    if (!track_pose_params(b, iters, huber_px, inlier_px, min_points))
+        return fail(ctx, DVO_EINVAL, "track poses: iters <= 32, min_points >= 3, no NaN");
+    TrackPnpBinding n;
+    if (!track_pnp_params(n, pnp_hyps, pnp_iters, pnp_huber_px, pnp_inlier_px, pnp_min_points, pnp_seed) ||
+        (mask && mask_cap < 1))
+        return fail(ctx, DVO_EINVAL, "track pnp: hyps <= 512, iters <= 32, min_points >= 4, mask_cap >= 1 with a mask, no NaN");
+    n.mask_cap = mask ? mask_cap : 0;
+    return test_tracks_run(ctx, lm, count, mq, mt, m, rec, pairs, cap, stride, kp_cap, cap_out, link, scale, K, &b, pose,
+                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &n, xy2, pnp, mask);
 }
 
 int dvo_test_five_point(dvo_ctx* ctx, const double* q1, const double* q2, double* models, int* n) {

@@ -259,6 +259,24 @@ struct PairSets {
         tr.blink = reinterpret_cast<int32_t*>(b + n);
         return hipSuccess;
     }
+    // The PnP kernels' correspondences and their per-tile counts (PairOutputs::set_track_pnp): 48 B
+    // per slot and 4 B per tile, one allocation, the counts behind the correspondences.  Allocated
+    // by the first PnP binding (after the track scratch: it needs a pending tracks binding) and
+    // never regrown.
+    DeviceAllocs pn_mem;
+    hipError_t ensure_track_pnp() {
+        if (tr.pc) return hipSuccess;
+        if (!tr.table) return hipErrorInvalidValue;
+        const size_t n = tr_sets * set_slots(), tiles = tr_sets * scratch_pairs() * landmark_tiles(cap);
+        DeviceAllocs fresh;
+        PnpCorr* c = nullptr;
+        const hipError_t e = fresh.alloc(&c, n * sizeof(PnpCorr) + tiles * sizeof(int32_t) + 256);
+        if (e != hipSuccess) return e;
+        pn_mem = std::move(fresh);
+        tr.pc = c;
+        tr.pc_cnt = reinterpret_cast<int32_t*>(c + n);
+        return hipSuccess;
+    }
     // Set k's part of every scratch there is, as the track kernels' arguments: all of a TrackArgs
     // but the records and the caller's side (PairOutputs::fill in pair_outputs.h).  Set k's slots
     // start k set_slots() into each array, its two rank buffers at rank + 2 k set_slots(), one
@@ -279,6 +297,7 @@ struct PairSets {
         if (tr.flink) a.flink = tr.flink + n, a.rank = tr.rank + 2 * n, a.rank_stride = (int64_t)set_slots();
         if (tr.bx) a.bd_x = tr.bx + n;
         if (tr.bx && !a.flink) a.flink = tr.blink + n;
+        if (tr.pc) a.pnp_corr = tr.pc + n, a.pnp_cnt = tr.pc_cnt + k * scratch_pairs() * a.tiles;
         return a;
     }
 

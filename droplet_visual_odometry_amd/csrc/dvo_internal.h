@@ -435,6 +435,20 @@ struct BundlePoint {  // 32 B
     double X[3];
     int32_t steps, pad;
 };
+// Track PnP (dvo_stream_set_track_pnp): with TrackArgs::pnp set, after everything else the
+// correspondence kernel (grid as the link kernel, over the pair's raw matches) looks every match's
+// queryIdx up in pair p - 1's table and compacts the hits of its tile, in match order, into
+// pnp_corr from slot tile * kLandmarkTile on (their number into pnp_cnt), and the PnP kernel (a
+// workgroup per pair) moves the tiles' hits together, draws and solves the samples (p3p.h) in
+// rounds of kPnpRound, a lane per sample, counts every pose's supporters (a wave per sample's
+// poses, ballots), and polishes the winner with the pose kernel's step and final pass.
+constexpr int kPnpRound = 64;      // samples solved per round: their poses take 24 KB of LDS
+constexpr int kPnpMaxHyps = 512;
+struct PnpCorr {  // 48 B
+    double y[3], nu, nv;
+    int32_t match;  // the match index i
+    int32_t sel;    // slot j: the j-th correspondence of the polish set (written by the PnP kernel)
+};
 struct TrackScratch {
     int32_t* table = nullptr;  // [sets][pairs][kp_cap] smallest landmark ordinal per trainIdx
     double* ratio = nullptr;   // [sets][pairs][pts_stride] a tile's linked ratios from its first ordinal on
@@ -446,6 +460,8 @@ struct TrackScratch {
     TrackRank* rank = nullptr;  // [sets][2][pairs][pts_stride] the id kernel's ping-pong buffers (first refine binding)
     BundlePoint* bx = nullptr;  // [sets][pairs][pts_stride] the bundle kernel's points (first bundle binding)
     int32_t* blink = nullptr;   // [sets][pairs][pts_stride] full links of its own, behind bx in the same allocation
+    PnpCorr* pc = nullptr;      // [sets][pairs][pts_stride] the PnP correspondences (first PnP binding)
+    int32_t* pc_cnt = nullptr;  // [sets][pairs][tiles] correspondences per tile, behind pc in the same allocation
 };
 struct TrackArgs {
     LandmarkScratch L;  // the set's full landmark lists
@@ -485,6 +501,15 @@ struct TrackArgs {
     int bd_views, bd_iters;           // 2..kTrackRefineMaxViews, 1..kTrackBundleMaxIters
     int bd_min_points, bd_use_pose;   // >= 6; the unit motions come from `pose` where its status is OK
     double bd_lambda, bd_huber_px, bd_inlier_px;  // > 0
+    // track PnP; all unused while pnp is null (rec's n_matches, pts_f and the camera are read too)
+    dvo_track_pnp* pnp;   // the caller's [pairs], or null
+    uint8_t* pnp_mask;    // the caller's [pairs][pnp_mask_cap], or null
+    int pnp_mask_cap;
+    PnpCorr* pnp_corr;    // [pairs][pts_stride]
+    int32_t* pnp_cnt;     // [pairs][tiles]
+    int pnp_hyps, pnp_iters, pnp_min_points;  // 1..kPnpMaxHyps, 1..kTrackPoseMaxIters, >= 4
+    double pnp_huber_px, pnp_inlier_px;       // > 0
+    uint64_t pnp_seed;                        // 0: the E-RANSAC's
 };
 hipError_t launch_tracks(const TrackArgs& a, int pairs, hipStream_t s);
 // five-point record blocks a merged round can need (sizes the stream's GeomArgs::fprec, dk_list)

@@ -1,5 +1,5 @@
 // Host-side ownership of a stream's pair outputs (api.cpp): the caller's landmark, tracks, pose,
-// refine and bundle bindings of a batch, the rules of setting them, and the one launch of what they ask
+// refine, bundle and PnP bindings of a batch, the rules of setting them, and the one launch of what they ask
 // for when the batch's pair set retires.  Both frame streams use it.  Host code only.
 #pragma once
 
@@ -85,6 +85,29 @@ inline bool track_bundle_params(TrackBundleBinding& b, int views, int iters, dou
     return b.views >= 2 && b.views <= kTrackRefineMaxViews && b.iters <= kTrackBundleMaxIters && b.min_points >= 6;
 }
 
+// The caller's buffers and parameters of a PnP binding (dvo_stream_set_track_pnp), beside a tracks binding.
+struct TrackPnpBinding {
+    dvo_track_pnp* out = nullptr;  // [pairs]; null: no binding
+    uint8_t* mask = nullptr;       // [pairs][mask_cap], or null
+    int mask_cap = 0;
+    int hyps = 0, iters = 0, min_points = 0;
+    double huber_px = 0, inlier_px = 0;
+    uint64_t seed = 0;
+};
+
+// The parameters of a PnP binding with the defaults filled in; false: out of range.
+inline bool track_pnp_params(TrackPnpBinding& b, int hyps, int iters, double huber_px, double inlier_px, int min_points,
+                             uint64_t seed) {
+    if (std::isnan(huber_px) || std::isnan(inlier_px)) return false;
+    b.hyps = hyps > 0 ? hyps : 128;
+    b.iters = iters > 0 ? iters : 10;
+    b.huber_px = huber_px > 0 ? huber_px : 1.0;
+    b.inlier_px = inlier_px > 0 ? inlier_px : 2.0;
+    b.min_points = min_points > 0 ? min_points : 6;
+    b.seed = seed;
+    return b.hyps <= kPnpMaxHyps && b.iters <= kTrackPoseMaxIters && b.min_points >= 4;
+}
+
 // What a setter answers.  DVO_OK; DVO_EINVAL and the message; or DVO_EHIP, the call that failed
 // and its error.
 struct BindResult {
@@ -93,7 +116,7 @@ struct BindResult {
     hipError_t hip = hipSuccess;
 };
 
-// The five bindings of one batch: pending in a stream until its next batch takes them, then the
+// The six bindings of one batch: pending in a stream until its next batch takes them, then the
 // batch's until its pair set retires.  The setters are the dvo_stream_set_* / dvo_knn_stream_set_*
 // entry points after their handle check: a later binding reads an earlier one, so setting an
 // earlier one clears the later ones, and each first binding sizes its scratch in `sets` (on
@@ -104,6 +127,7 @@ struct PairOutputs {
     TrackPoseBinding tp;
     TrackRefineBinding rf;
     TrackBundleBinding bd;
+    TrackPnpBinding pn;
 
     PairOutputs take() { return std::exchange(*this, PairOutputs{}); }
 
@@ -122,6 +146,7 @@ struct PairOutputs {
         tp = TrackPoseBinding{};    // a pose binding goes after the tracks binding it reads
         rf = TrackRefineBinding{};  // and a refine binding after both
         bd = TrackBundleBinding{};  // and a bundle binding last
+        pn = TrackPnpBinding{};     // a PnP binding reads the tracks binding's table
         if (!link && !scale) {
             tr = TracksBinding{};
             return {};
@@ -190,6 +215,26 @@ struct PairOutputs {
         return r;
     }
 
+    // Reads the table of a pending tracks binding only, so the pose, refine and bundle setters leave
+    // it alone, and it clears nothing.
+    BindResult set_track_pnp(PairSets& sets, int device, dvo_track_pnp* pnp, uint8_t* mask, int mask_cap, int hyps,
+                             int iters, double huber_px, double inlier_px, int min_points, uint64_t seed) {
+        if (!pnp) {
+            pn = TrackPnpBinding{};
+            return {};
+        }
+        if (!lm.out || !tr) return {DVO_EINVAL, "track pnp goes with a pending tracks binding"};
+        TrackPnpBinding b;
+        if (!track_pnp_params(b, hyps, iters, huber_px, inlier_px, min_points, seed) || (mask && mask_cap < 1))
+            return {DVO_EINVAL, "track pnp: hyps <= 512, iters <= 32, min_points >= 4, mask_cap >= 1 with a mask, no NaN"};
+        const BindResult r = scratch(sets, device, &PairSets::ensure_track_pnp, "PairSets::ensure_track_pnp");
+        b.out = pnp;
+        b.mask = mask;
+        b.mask_cap = mask ? mask_cap : 0;
+        if (r.code == DVO_OK) pn = b;
+        return r;
+    }
+
     // The caller's side of a retiring set's TrackArgs, over the scratch side (PairSets::track_args,
     // or a test hook's own): the records, the buffers, the parameters, and for a pose or refine
     // binding the points and camera of the set's GeomArgs.  The kernels take corr, id / refined and
@@ -200,7 +245,7 @@ struct PairOutputs {
         a.link = tr.link;
         a.cap = lm.cap;
         a.scale = tr.scale;
-        if (tp.out || rf || bd) {
+        if (tp.out || rf || bd || pn.out) {
             a.pts_f = g.pts_f;
             a.fx = g.fx, a.fy = g.fy, a.cx = g.cx, a.cy = g.cy;
         }
@@ -238,6 +283,20 @@ struct PairOutputs {
             a.bd_inlier_px = bd.inlier_px;
         } else {
             a.bd_x = nullptr;
+        }
+        if (pn.out) {
+            a.pnp = pn.out;
+            a.pnp_mask = pn.mask;
+            a.pnp_mask_cap = pn.mask_cap;
+            a.pnp_hyps = pn.hyps;
+            a.pnp_iters = pn.iters;
+            a.pnp_min_points = pn.min_points;
+            a.pnp_huber_px = pn.huber_px;
+            a.pnp_inlier_px = pn.inlier_px;
+            a.pnp_seed = pn.seed;
+        } else {
+            a.pnp_corr = nullptr;
+            a.pnp_cnt = nullptr;
         }
     }
 

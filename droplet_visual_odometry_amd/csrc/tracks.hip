@@ -41,8 +41,17 @@
 //                        formed again) and the cameras' Cayley updates; the cost before and after,
 //                        the guard, the gauge division and the final pass, lane per landmark with
 //                        the pair's sums added in ordinal order by one lane each.
+// With a PnP binding (dvo.h dvo_stream_set_track_pnp), after all of these:
+//   track_pnp_corr_kernel  per (tile of raw matches, pair): the matches whose queryIdx pair p - 1's
+//                        table holds, compacted in match order with their 3-D point and pixel;
+//   track_pnp_kernel     a workgroup per pair: P3P (p3p.h) on seeded samples, a lane per sample,
+//                        64 samples a round, their poses in LDS; a wave per sample's poses counts
+//                        the supporters with ballots; the best (count, sample, solution) per wave,
+//                        merged by the header's tie rule; then the pose kernel's step over the
+//                        winner's supporters and its final pass over all correspondences.
 // The arithmetic is the header's, one rounding per operation (-ffp-contract=off).
 #include "dvo_internal.h"
+#include "p3p.h"
 
 namespace dvo {
 
@@ -288,6 +297,135 @@ __device__ void pose_update(const double* R, const double* t, const double* d, d
     }
 }
 
+// Correspondence k of a pair: from the LDS copy (y0, y1, y2, nu, nv) where the pair's fit, else from
+// global memory (G: TrackCorr, or the PnP kernel's PnpCorr).
+template <class G>
+__device__ __forceinline__ void pose_corr(const double (*cs)[kTrackPoseLds], const G* g, bool in_lds, int k, double& y0,
+                                          double& y1, double& y2, double& nu, double& nv) {
+    if (in_lds) {
+        y0 = cs[0][k], y1 = cs[1][k], y2 = cs[2][k], nu = cs[3][k], nv = cs[4][k];
+    } else {
+        const G& v = g[k];
+        y0 = v.y[0], y1 = v.y[1], y2 = v.y[2], nu = v.nu, nv = v.nv;
+    }
+}
+
+// The header's "One step" (dvo.h, track poses) over n correspondences, by all 256 threads: 27 sums
+// (lane sums, shuffles inside a wave, the four wave totals through wsum), the LDL^T solve and the
+// Cayley update on lane 0, the new pose and the stop flag broadcast through next / stop.  With kSel
+// the j-th correspondence is g[j].sel (the PnP kernel's polish set), else j itself.  True: R, tv
+// hold the new pose; false: the step failed and they are what they were.  Two barriers, reached by
+// all threads; the next write to *stop lies behind the caller's next barrier.
+template <class G, bool kSel>
+__device__ __forceinline__ bool pose_step(const double (*cs)[kTrackPoseLds], const G* g, bool in_lds, int n, double* R,
+                                          double* tv, double kh, double kh2, double (*wsum)[kPoseTerms], double* next,
+                                          int* stop) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double acc[kPoseTerms];
+#pragma unroll
+    for (int q = 0; q < kPoseTerms; ++q) acc[q] = 0.0;
+    for (int j = tid; j < n; j += kPoseNT) {
+        int k = j;
+        if constexpr (kSel) k = g[j].sel;
+        double y0, y1, y2, nu, nv;
+        pose_corr(cs, g, in_lds, k, y0, y1, y2, nu, nv);
+        const double P0 = ((R[0] * y0 + R[1] * y1) + R[2] * y2) + tv[0];
+        const double P1 = ((R[3] * y0 + R[4] * y1) + R[5] * y2) + tv[1];
+        const double P2 = ((R[6] * y0 + R[7] * y1) + R[8] * y2) + tv[2];
+        const bool ok = P2 > 0;
+        const double ia = 1 / P2, u = P0 * ia, v = P1 * ia;
+        const double ru = u - nu, rv = v - nv, e2 = ru * ru + rv * rv;
+        const double w = e2 <= kh2 ? 1.0 : kh / sqrt(e2);
+        const double b = -(u * ia), c = -(v * ia);
+        const double Ju[6] = {b * P1, ia * P2 - b * P0, -(ia * P1), ia, 0.0, b};
+        const double Jv[6] = {c * P1 - ia * P2, -(c * P0), ia * P0, 0.0, ia, c};
+        int q = 0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int jj = i; jj < 6; ++jj, ++q) {
+                const double term = w * (Ju[i] * Ju[jj] + Jv[i] * Jv[jj]);
+                acc[q] = acc[q] + (ok ? term : 0.0);
+            }
+#pragma unroll
+        for (int i = 0; i < 6; ++i, ++q) {
+            const double term = w * (Ju[i] * ru + Jv[i] * rv);
+            acc[q] = acc[q] + (ok ? term : 0.0);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < kPoseTerms; ++q) {
+        const double v = pose_wave_sum(acc[q]);
+        if (lane == 0) wsum[wave][q] = v;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double S[kPoseTerms], d[6];
+#pragma unroll
+        for (int q = 0; q < kPoseTerms; ++q) S[q] = ((wsum[0][q] + wsum[1][q]) + wsum[2][q]) + wsum[3][q];
+        const bool solved = pose_solve(S, d);
+        if (solved) pose_update(R, tv, d, next);
+        *stop = solved ? 0 : 1;
+    }
+    __syncthreads();
+    if (*stop) return false;  // the same for every thread
+#pragma unroll
+    for (int i = 0; i < 9; ++i) R[i] = next[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) tv[i] = next[9 + i];
+    return true;
+}
+
+// The header's final pass over n correspondences on the pose R, tv, by all 256 threads; mask
+// (PnP only, or null): 1 at the match index of every inlier below mask_cap.  One barrier; after
+// it thread 0 holds the pair's sum of the inliers' e, n_used and n_inliers.  wsum was last read
+// before the caller's last barrier.
+template <class G, bool kMask>
+__device__ __forceinline__ void pose_final(const TrackArgs& a, const double (*cs)[kTrackPoseLds], const G* g, bool in_lds,
+                                           int n, const double* R, const double* tv, double inlier_px,
+                                           double (*wsum)[kPoseTerms], int (*wcnt)[2], uint8_t* mask, int mask_cap,
+                                           double* sum, int* n_used, int* n_inliers) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double se = 0.0;
+    int used = 0, inl = 0;
+    const double in2 = inlier_px * inlier_px;
+    for (int k = tid; k < n; k += kPoseNT) {
+        double y0, y1, y2, nu, nv;
+        pose_corr(cs, g, in_lds, k, y0, y1, y2, nu, nv);
+        const double P0 = ((R[0] * y0 + R[1] * y1) + R[2] * y2) + tv[0];
+        const double P1 = ((R[3] * y0 + R[4] * y1) + R[5] * y2) + tv[1];
+        const double P2 = ((R[6] * y0 + R[7] * y1) + R[8] * y2) + tv[2];
+        const bool ok = P2 > 0;
+        const double ia = 1 / P2, u = P0 * ia, v = P1 * ia;
+        const double ex = a.fx * (u - nu), ey = a.fy * (v - nv);
+        const double e = ex * ex + ey * ey;
+        const bool in = ok && e <= in2;
+        used += ok;
+        inl += in;
+        se = se + (in ? e : 0.0);
+        if constexpr (kMask) {
+            if (mask && in && g[k].match < mask_cap) mask[g[k].match] = 1;
+        }
+    }
+    se = pose_wave_sum(se);
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+        used += __shfl_down(used, s);
+        inl += __shfl_down(inl, s);
+    }
+    if (lane == 0) {
+        wsum[wave][0] = se;
+        wcnt[wave][0] = used;
+        wcnt[wave][1] = inl;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        *sum = ((wsum[0][0] + wsum[1][0]) + wsum[2][0]) + wsum[3][0];
+        *n_used = ((wcnt[0][0] + wcnt[1][0]) + wcnt[2][0]) + wcnt[3][0];
+        *n_inliers = ((wcnt[0][1] + wcnt[1][1]) + wcnt[2][1]) + wcnt[3][1];
+    }
+}
+
 // A workgroup per pair.  Every barrier is reached by all 256 threads: a NONE pair leaves before
 // the first as a whole, and the trip counts (the tiles' lcnt, iters, the stop flag read after a
 // barrier) are the same for every thread.
@@ -298,7 +436,7 @@ __global__ __launch_bounds__(kPoseNT) void track_pose_kernel(TrackArgs a) {
     __shared__ double next[12];
     __shared__ int stop;
     const int p = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int32_t* tc = a.L.tcnt + (int64_t)p * a.tiles;
     const int32_t* lc = a.lcnt + (int64_t)p * a.tiles;
     int n = 0;
@@ -352,106 +490,16 @@ __global__ __launch_bounds__(kPoseNT) void track_pose_kernel(TrackArgs a) {
     }
     const double kh = a.huber_px / ((a.fx + a.fy) / 2), kh2 = kh * kh;
     int status = DVO_TRACK_POSE_OK, it = 0;
-    for (; it < a.pose_iters; ++it) {
-        double acc[kPoseTerms];
-#pragma unroll
-        for (int q = 0; q < kPoseTerms; ++q) acc[q] = 0.0;
-        for (int k = tid; k < n; k += kPoseNT) {
-            double y0, y1, y2, nu, nv;
-            if (in_lds) {
-                y0 = cs[0][k], y1 = cs[1][k], y2 = cs[2][k], nu = cs[3][k], nv = cs[4][k];
-            } else {
-                const TrackCorr v = g[k];
-                y0 = v.y[0], y1 = v.y[1], y2 = v.y[2], nu = v.nu, nv = v.nv;
-            }
-            const double P0 = ((R[0] * y0 + R[1] * y1) + R[2] * y2) + tv[0];
-            const double P1 = ((R[3] * y0 + R[4] * y1) + R[5] * y2) + tv[1];
-            const double P2 = ((R[6] * y0 + R[7] * y1) + R[8] * y2) + tv[2];
-            const bool ok = P2 > 0;
-            const double ia = 1 / P2, u = P0 * ia, v = P1 * ia;
-            const double ru = u - nu, rv = v - nv, e2 = ru * ru + rv * rv;
-            const double w = e2 <= kh2 ? 1.0 : kh / sqrt(e2);
-            const double b = -(u * ia), c = -(v * ia);
-            const double Ju[6] = {b * P1, ia * P2 - b * P0, -(ia * P1), ia, 0.0, b};
-            const double Jv[6] = {c * P1 - ia * P2, -(c * P0), ia * P0, 0.0, ia, c};
-            int q = 0;
-#pragma unroll
-            for (int i = 0; i < 6; ++i)
-#pragma unroll
-                for (int j = i; j < 6; ++j, ++q) {
-                    const double term = w * (Ju[i] * Ju[j] + Jv[i] * Jv[j]);
-                    acc[q] = acc[q] + (ok ? term : 0.0);
-                }
-#pragma unroll
-            for (int i = 0; i < 6; ++i, ++q) {
-                const double term = w * (Ju[i] * ru + Jv[i] * rv);
-                acc[q] = acc[q] + (ok ? term : 0.0);
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < kPoseTerms; ++q) {
-            const double v = pose_wave_sum(acc[q]);
-            if (lane == 0) wsum[wave][q] = v;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            double S[kPoseTerms], d[6];
-#pragma unroll
-            for (int q = 0; q < kPoseTerms; ++q) S[q] = ((wsum[0][q] + wsum[1][q]) + wsum[2][q]) + wsum[3][q];
-            const bool solved = pose_solve(S, d);
-            if (solved) pose_update(R, tv, d, next);
-            stop = solved ? 0 : 1;
-        }
-        __syncthreads();
-        if (stop) {  // the same for every thread; the next write to it lies behind the next barrier
+    for (; it < a.pose_iters; ++it)
+        if (!pose_step<TrackCorr, false>(cs, g, in_lds, n, R, tv, kh, kh2, wsum, next, &stop)) {
             status = DVO_TRACK_POSE_DEGENERATE;
             break;
         }
-#pragma unroll
-        for (int i = 0; i < 9; ++i) R[i] = next[i];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) tv[i] = next[9 + i];
-    }
     // the final pass on the last pose
-    double se = 0.0;
-    int used = 0, inl = 0;
-    const double in2 = a.inlier_px * a.inlier_px;
-    for (int k = tid; k < n; k += kPoseNT) {
-        double y0, y1, y2, nu, nv;
-        if (in_lds) {
-            y0 = cs[0][k], y1 = cs[1][k], y2 = cs[2][k], nu = cs[3][k], nv = cs[4][k];
-        } else {
-            const TrackCorr v = g[k];
-            y0 = v.y[0], y1 = v.y[1], y2 = v.y[2], nu = v.nu, nv = v.nv;
-        }
-        const double P0 = ((R[0] * y0 + R[1] * y1) + R[2] * y2) + tv[0];
-        const double P1 = ((R[3] * y0 + R[4] * y1) + R[5] * y2) + tv[1];
-        const double P2 = ((R[6] * y0 + R[7] * y1) + R[8] * y2) + tv[2];
-        const bool ok = P2 > 0;
-        const double ia = 1 / P2, u = P0 * ia, v = P1 * ia;
-        const double ex = a.fx * (u - nu), ey = a.fy * (v - nv);
-        const double e = ex * ex + ey * ey;
-        const bool in = ok && e <= in2;
-        used += ok;
-        inl += in;
-        se = se + (in ? e : 0.0);
-    }
-    se = pose_wave_sum(se);
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        used += __shfl_down(used, s);
-        inl += __shfl_down(inl, s);
-    }
-    if (lane == 0) {  // wsum was last read before the loop's final barrier
-        wsum[wave][0] = se;
-        wcnt[wave][0] = used;
-        wcnt[wave][1] = inl;
-    }
-    __syncthreads();
+    double sum;
+    pose_final<TrackCorr, false>(a, cs, g, in_lds, n, R, tv, a.inlier_px, wsum, wcnt, nullptr, 0, &sum, &o.n_used,
+                                 &o.n_inliers);
     if (tid == 0) {
-        const double sum = ((wsum[0][0] + wsum[1][0]) + wsum[2][0]) + wsum[3][0];
-        o.n_used = ((wcnt[0][0] + wcnt[1][0]) + wcnt[2][0]) + wcnt[3][0];
-        o.n_inliers = ((wcnt[0][1] + wcnt[1][1]) + wcnt[2][1]) + wcnt[3][1];
         o.rms = o.n_inliers > 0 ? sqrt(sum / (double)o.n_inliers) : 0.0;
 #pragma unroll
         for (int i = 0; i < 9; ++i) o.R[i] = R[i];
@@ -1304,6 +1352,273 @@ __global__ __launch_bounds__(kBundleNT) void track_bundle_kernel(TrackArgs a) {
     }
 }
 
+// ---- track PnP (dvo.h dvo_stream_set_track_pnp) ----------------------------------------------------
+// Per (tile of 256 raw matches, pair): match i is a correspondence iff pair p - 1's table holds a
+// landmark at its queryIdx.  The hits of a tile go, in match order (wave ballots and mbcnt ranks, as
+// the link kernel), to pnp_corr from slot tile * 256 on: hit r of the tile has r <= its place in the
+// tile, so its slot is at most its match index < the pair's matches <= pts_stride.
+__global__ __launch_bounds__(kLandmarkTile) void track_pnp_corr_kernel(TrackArgs a) {
+    __shared__ int wtot[kLandmarkTile / 64];
+    const int p = blockIdx.y, tile = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i = tile * kLandmarkTile + tid;
+    const int nm = p >= 1 ? (int)min((int64_t)max(a.rec[p].n_matches, 0), a.pts_stride) : 0;
+    bool hit = false;
+    PnpCorr c;
+    if (i < nm) {
+        const int q = a.mq[((int64_t)p * a.idx_stride + i) * a.idx_step];
+        if ((unsigned)q < (unsigned)a.kp_cap) {
+            const int v = a.table[(int64_t)(p - 1) * a.kp_cap + q];
+            if (v != kTrackEmpty) {
+                const LandmarkTmp e = track_ordinal(a, p - 1, v);
+                const double* R = a.rec[p - 1].R;
+                const double* tv = a.rec[p - 1].t;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) c.y[k] = ((R[3 * k] * e.X + R[3 * k + 1] * e.Y) + R[3 * k + 2] * e.Z) + tv[k];
+                const double ax = 1. / a.fx, ay = 1. / a.fy, bx = -a.cx * ax, by = -a.cy * ay;
+                const float* px = a.pts_f + ((int64_t)p * a.pts_stride + i) * 4;
+                const double x2 = px[2], y2 = px[3];
+                c.nu = x2 * ax + bx;
+                c.nv = y2 * ay + by;
+                c.match = i;
+                c.sel = 0;
+                hit = true;
+            }
+        }
+    }
+    const unsigned long long bal = __ballot(hit);
+    const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+    if (lane == 0) wtot[wave] = __popcll(bal);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < kLandmarkTile / 64; ++w) {
+        const int n = wtot[w];
+        before += w < wave ? n : 0;
+        total += n;
+    }
+    if (hit) a.pnp_corr[(int64_t)p * a.pts_stride + tile * kLandmarkTile + before + rank] = c;
+    if (tid == 0) a.pnp_cnt[(int64_t)p * a.tiles + tile] = total;
+}
+
+// does correspondence (y, nu, nv) support the pose: the final pass's inlier test
+__device__ __forceinline__ bool pnp_supports(const TrackArgs& a, const double* R, const double* tv, double in2, double y0,
+                                             double y1, double y2, double nu, double nv) {
+    const double P0 = ((R[0] * y0 + R[1] * y1) + R[2] * y2) + tv[0];
+    const double P1 = ((R[3] * y0 + R[4] * y1) + R[5] * y2) + tv[1];
+    const double P2 = ((R[6] * y0 + R[7] * y1) + R[8] * y2) + tv[2];
+    const bool ok = P2 > 0;
+    const double ia = 1 / P2, u = P0 * ia, v = P1 * ia;
+    const double ex = a.fx * (u - nu), ey = a.fy * (v - nv);
+    const double e = ex * ex + ey * ey;
+    return ok && e <= in2;
+}
+
+// is (count, h, solution) a better hypothesis than (bc, bh, bs): more supporters, then the smaller h, then the smaller solution
+__device__ __forceinline__ bool pnp_better(int count, int h, int sol, int bc, int bh, int bs) {
+    return count > bc || (count == bc && (h < bh || (h == bh && sol < bs)));
+}
+
+// A workgroup per pair.  Every barrier is reached by all 256 threads: a NONE or NO_MODEL pair
+// leaves as a whole, and the trip counts (the tiles' counts, hyps, the poses a sample left in LDS,
+// iters, the stop flag read after a barrier) are the same for every thread of the workgroup or,
+// inside the scoring loop where there is no barrier, of the wave.  Nothing is added in an order
+// that lane scheduling could change: the scores are integer counts from ballots.
+__global__ __launch_bounds__(kPoseNT) void track_pnp_kernel(TrackArgs a) {
+    __shared__ double cs[5][kTrackPoseLds];  // y0, y1, y2, nu, nv of the correspondences that fit
+    __shared__ double hyp[kPnpRound * 4][12];  // the round's poses: sample s of the round at hyp[4 s ..]
+    __shared__ int hyp_n[kPnpRound];
+    __shared__ double wpose[kPoseNT / 64][12];  // each wave's best pose
+    __shared__ int wbest[kPoseNT / 64][3];      // its count, sample and solution
+    __shared__ double wsum[kPoseNT / 64][kPoseTerms];
+    __shared__ int wcnt[kPoseNT / 64][2];
+    __shared__ double next[12];
+    __shared__ int stop;
+    const int p = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int32_t* cc = a.pnp_cnt + (int64_t)p * a.tiles;
+    int n = 0;
+    for (int t = 0; t < a.tiles; ++t) n += cc[t];
+    uint8_t* mask = a.pnp_mask ? a.pnp_mask + (int64_t)p * a.pnp_mask_cap : nullptr;
+    if (mask) {  // 0 for every match in range; the final pass sets the inliers after the barriers below
+        const int nm = (int)min((int64_t)max(a.rec[p].n_matches, 0), a.pts_stride);
+        for (int i = tid; i < min(nm, a.pnp_mask_cap); i += kPoseNT) mask[i] = 0;
+    }
+    dvo_track_pnp o;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) o.R[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) o.t[i] = 0.0;
+    o.scale = o.rms = 0.0;
+    o.n_corr = n;
+    o.n_best = o.n_used = o.n_inliers = o.sample = o.solution = o.iters = 0;
+    if (p == 0 || n < a.pnp_min_points) {
+        if (tid == 0) {
+            o.status = DVO_TRACK_PNP_NONE;
+            a.pnp[p] = o;
+        }
+        return;
+    }
+    // the tiles' correspondences together, in match order: moved down in place (a tile's target ends
+    // at or before its source starts), and into LDS as well when they fit
+    PnpCorr* g = a.pnp_corr + (int64_t)p * a.pts_stride;
+    const bool in_lds = n <= kTrackPoseLds;
+    for (int t = 0, off = 0; t < a.tiles; ++t) {
+        const int c = cc[t];
+        if (c == 0) continue;  // the same for every thread
+        PnpCorr v;
+        if (tid < c) v = g[t * kLandmarkTile + tid];
+        __syncthreads();
+        if (tid < c) {
+            g[off + tid] = v;
+            if (in_lds) {
+#pragma unroll
+                for (int i = 0; i < 3; ++i) cs[i][off + tid] = v.y[i];
+                cs[3][off + tid] = v.nu;
+                cs[4][off + tid] = v.nv;
+            }
+        }
+        __syncthreads();
+        off += c;
+    }
+    const double in2 = a.pnp_inlier_px * a.pnp_inlier_px;
+    // the hypotheses, kPnpRound samples at a time: wave 0 solves a sample per lane, then wave w
+    // scores the poses of the round's samples w, w + 4, ... in ascending (sample, solution)
+    int bc = -1, bh = 0, bs = 0;  // the wave's best so far: the same in all its lanes
+    double bR[9], bt[3];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) bR[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) bt[i] = 0.0;
+    for (int base = 0; base < a.pnp_hyps; base += kPnpRound) {
+        if (tid < kPnpRound) {
+            int ns = 0, idx[3];
+            if (base + tid < a.pnp_hyps && p3p_sample(a.pnp_seed, base + tid, n, idx)) {
+                double Y[9], nunv[6], Rs[4][9], ts[4][3];
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+                    pose_corr(cs, g, in_lds, idx[j], Y[3 * j], Y[3 * j + 1], Y[3 * j + 2], nunv[2 * j], nunv[2 * j + 1]);
+                ns = p3p_solve(Y, nunv, Rs, ts);
+                for (int s = 0; s < ns; ++s) {
+#pragma unroll
+                    for (int i = 0; i < 9; ++i) hyp[4 * tid + s][i] = Rs[s][i];
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) hyp[4 * tid + s][9 + i] = ts[s][i];
+                }
+            }
+            hyp_n[tid] = ns;
+        }
+        __syncthreads();
+        for (int s = wave; s < kPnpRound; s += kPoseNT / 64) {
+            const int ns = hyp_n[s];  // 0 past hyps
+            for (int sol = 0; sol < ns; ++sol) {
+                double R[9], tv[3];
+#pragma unroll
+                for (int i = 0; i < 9; ++i) R[i] = hyp[4 * s + sol][i];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) tv[i] = hyp[4 * s + sol][9 + i];
+                int count = 0;
+                for (int k0 = 0; k0 < n; k0 += 64) {  // the same trips for the wave's lanes: the ballot is whole
+                    const int k = k0 + lane;
+                    bool sup = false;
+                    if (k < n) {
+                        double y0, y1, y2, nu, nv;
+                        pose_corr(cs, g, in_lds, k, y0, y1, y2, nu, nv);
+                        sup = pnp_supports(a, R, tv, in2, y0, y1, y2, nu, nv);
+                    }
+                    count += __popcll(__ballot(sup));
+                }
+                if (pnp_better(count, base + s, sol, bc, bh, bs)) {
+                    bc = count, bh = base + s, bs = sol;
+#pragma unroll
+                    for (int i = 0; i < 9; ++i) bR[i] = R[i];
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) bt[i] = tv[i];
+                }
+            }
+        }
+        __syncthreads();  // the round's poses are read; the next round writes them
+    }
+    if (lane == 0) {
+        wbest[wave][0] = bc, wbest[wave][1] = bh, wbest[wave][2] = bs;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) wpose[wave][i] = bR[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) wpose[wave][9 + i] = bt[i];
+    }
+    __syncthreads();
+    int win = 0;
+    bc = wbest[0][0], bh = wbest[0][1], bs = wbest[0][2];
+#pragma unroll
+    for (int w = 1; w < kPoseNT / 64; ++w)
+        if (pnp_better(wbest[w][0], wbest[w][1], wbest[w][2], bc, bh, bs)) bc = wbest[w][0], bh = wbest[w][1], bs = wbest[w][2], win = w;
+    if (bc < a.pnp_min_points) {  // also no kept solution at all: bc is -1
+        if (tid == 0) {
+            o.n_best = bc < 0 ? 0 : bc;
+            o.sample = bc < 0 ? -1 : bh;
+            o.solution = bc < 0 ? -1 : bs;
+            o.status = DVO_TRACK_PNP_NO_MODEL;
+            a.pnp[p] = o;
+        }
+        return;
+    }
+    double R[9], tv[3];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) R[i] = wpose[win][i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) tv[i] = wpose[win][9 + i];
+    // the polish set: the winner's supporters in ascending k, the j-th of them into g[j].sel
+    // (j <= k, and sel is no correspondence's data); hyp_n is free now: the waves' totals
+    int ns = 0;
+    for (int k0 = 0; k0 < n; k0 += kPoseNT) {
+        const int k = k0 + tid;
+        bool sup = false;
+        if (k < n) {
+            double y0, y1, y2, nu, nv;
+            pose_corr(cs, g, in_lds, k, y0, y1, y2, nu, nv);
+            sup = pnp_supports(a, R, tv, in2, y0, y1, y2, nu, nv);
+        }
+        const unsigned long long bal = __ballot(sup);
+        const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+        if (lane == 0) hyp_n[wave] = __popcll(bal);
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < kPoseNT / 64; ++w) {
+            const int c = hyp_n[w];
+            before += w < wave ? c : 0;
+            total += c;
+        }
+        if (sup) g[ns + before + rank].sel = k;
+        ns += total;
+        __syncthreads();
+    }
+    const double kh = a.pnp_huber_px / ((a.fx + a.fy) / 2), kh2 = kh * kh;
+    int status = DVO_TRACK_PNP_OK, it = 0;
+    for (; it < a.pnp_iters; ++it)
+        if (!pose_step<PnpCorr, true>(cs, g, in_lds, ns, R, tv, kh, kh2, wsum, next, &stop)) {
+            status = DVO_TRACK_PNP_DEGENERATE;
+            break;
+        }
+    double sum;
+    pose_final<PnpCorr, true>(a, cs, g, in_lds, n, R, tv, a.pnp_inlier_px, wsum, wcnt, mask, a.pnp_mask_cap, &sum, &o.n_used,
+                              &o.n_inliers);
+    if (tid == 0) {
+        o.rms = o.n_inliers > 0 ? sqrt(sum / (double)o.n_inliers) : 0.0;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) o.R[i] = R[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) o.t[i] = tv[i];
+        o.scale = sqrt((tv[0] * tv[0] + tv[1] * tv[1]) + tv[2] * tv[2]);
+        o.n_best = bc;
+        o.sample = bh;
+        o.solution = bs;
+        o.iters = it;
+        o.status = status;
+        a.pnp[p] = o;
+    }
+}
+
 }  // namespace
 
 hipError_t launch_tracks(const TrackArgs& a, int pairs, hipStream_t s) {
@@ -1326,6 +1641,11 @@ hipError_t launch_tracks(const TrackArgs& a, int pairs, hipStream_t s) {
                    a.bd_iters > kTrackBundleMaxIters || a.bd_min_points < 6 || !(a.bd_lambda > 0) ||
                    !(a.bd_huber_px > 0) || !(a.bd_inlier_px > 0) || (a.bd_use_pose && !a.pose)))
         return hipErrorInvalidValue;
+    if (a.pnp ? !a.pnp_corr || !a.pnp_cnt || !a.pts_f || a.pnp_hyps < 1 || a.pnp_hyps > kPnpMaxHyps || a.pnp_iters < 1 ||
+                    a.pnp_iters > kTrackPoseMaxIters || a.pnp_min_points < 4 || !(a.pnp_huber_px > 0) ||
+                    !(a.pnp_inlier_px > 0) || (a.pnp_mask && a.pnp_mask_cap < 1)
+              : a.pnp_corr != nullptr || a.pnp_mask != nullptr)
+        return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(a.table, 0x7f, (size_t)pairs * a.kp_cap * sizeof(int32_t), s);
     if (e != hipSuccess) return e;
     const dim3 grid((unsigned)a.tiles, (unsigned)pairs);
@@ -1342,6 +1662,10 @@ hipError_t launch_tracks(const TrackArgs& a, int pairs, hipStream_t s) {
     }
     if (a.flink && a.refined) hipLaunchKernelGGL(track_refine_kernel, grid, dim3(kLandmarkTile), 0, s, a);
     if (a.bd_x) hipLaunchKernelGGL(track_bundle_kernel, dim3((unsigned)pairs), dim3(kBundleNT), 0, s, a);
+    if (a.pnp) {
+        hipLaunchKernelGGL(track_pnp_corr_kernel, grid, dim3(kLandmarkTile), 0, s, a);
+        hipLaunchKernelGGL(track_pnp_kernel, dim3((unsigned)pairs), dim3(kPoseNT), 0, s, a);
+    }
     return hipGetLastError();
 }
 

@@ -1205,6 +1205,71 @@ def test_track_poses(lm, count, mq, mt, m, rec, kp_cap, K, iters=10, huber_px=1.
     return link, scale, pose
 
 
+def test_track_pnp(lm, count, mq, mt, m, rec, kp_cap, K, xy2, hyps=128, iters=10, huber_px=1.0, inlier_px=2.0,
+                   min_points=6, seed=0, mask=None, pose_params=(10, 1.0, 2.0, 6), cap_out=None, link=None, ctx=None):
+    """test_track_poses with the PnP kernels after it (stream.TrackPnP): xy2 float32[P, stride, 2] are
+    the second-frame pixels of every match, the record's n_matches is taken as m, and hyps, iters,
+    huber_px, inlier_px, min_points, seed are bind_pnp's (zero or negative: the default; seed 0: the
+    E-RANSAC's).  mask: uint8[P, mask_cap] whose bytes the kernels leave alone outside the written
+    range, or None.  Returns (link, scale, pose, pnp TRACK_PNP_DTYPE[P], mask)."""
+    from ._native import LANDMARK_DTYPE, TRACK_PNP_DTYPE, TRACK_POSE_DTYPE, TRACK_SCALE_DTYPE
+    c = _ctx(ctx)
+    mq = np.ascontiguousarray(mq, np.int32)
+    mt = np.ascontiguousarray(mt, np.int32)
+    count = np.ascontiguousarray(count, np.int32)
+    m = np.ascontiguousarray(m, np.int32)
+    if (lm.dtype != LANDMARK_DTYPE or lm.ndim != 2 or not lm.flags.c_contiguous or mq.ndim != 2 or mq.shape != mt.shape
+            or not (len(lm) == len(mq) == len(count) == len(m) == len(rec))):
+        raise DVOError(-1, "lm LANDMARK_DTYPE[P, cap], mq / mt int32[P, stride], count, m and rec [P] must agree")
+    rec = np.ascontiguousarray(rec, PAIR_RECORD_DTYPE)
+    K = np.ascontiguousarray(K, np.float64).reshape(9)
+    P, cap = lm.shape
+    xy2 = np.ascontiguousarray(xy2, np.float32)
+    if xy2.shape != (P, mq.shape[1], 2):
+        raise DVOError(-1, "xy2 must be float32[P, stride, 2]")
+    cap_out = cap if cap_out is None else int(cap_out)
+    link = np.full((P, cap_out), -1, np.int32) if link is None else link
+    if link.dtype != np.int32 or link.shape != (P, cap_out) or not link.flags.c_contiguous:
+        raise DVOError(-1, "link must be a contiguous int32[P, cap_out] array")
+    if mask is not None and (mask.dtype != np.uint8 or mask.ndim != 2 or len(mask) != P or not mask.flags.c_contiguous):
+        raise DVOError(-1, "mask must be a contiguous uint8[P, mask_cap] array")
+    scale = np.zeros(P, TRACK_SCALE_DTYPE)
+    pose = np.zeros(P, TRACK_POSE_DTYPE)
+    pnp = np.zeros(P, TRACK_PNP_DTYPE)
+    pi, ph, pin, pm = pose_params
+    c.check(c.lib.dvo_test_track_pnp(c.h, ptr(lm), ptr(count), ptr(mq), ptr(mt), ptr(m), ptr(rec), P, cap, mq.shape[1],
+                                     int(kp_cap), cap_out, ptr(K), int(pi), float(ph), float(pin), int(pm), ptr(link),
+                                     ptr(scale), ptr(pose), ptr(xy2), int(hyps), int(iters), float(huber_px),
+                                     float(inlier_px), int(min_points), int(seed), ptr(pnp),
+                                     ptr(mask) if mask is not None else None,
+                                     mask.shape[1] if mask is not None else 0))
+    return link, scale, pose, pnp, mask
+
+
+def track_pnp_samples(n, hyps=128, seed=0):
+    """The PnP sample generator on the host (dvo_track_pnp_samples_host): int32[hyps, 3], a void sample -1."""
+    from ._native import load_library
+    out = np.zeros((int(hyps), 3), np.int32)
+    rc = load_library().dvo_track_pnp_samples_host(int(n), int(hyps), int(seed), ptr(out))
+    if rc != 0:
+        raise DVOError(rc, "dvo_track_pnp_samples_host: n >= 1, hyps 1..512")
+    return out
+
+
+def p3p(Y, nunv):
+    """The P3P solver on the host (dvo_p3p_host): Y [3, 3] points, nunv [3, 2] normalised pixels.
+    Returns (R [n, 3, 3], t [n, 3]) of the n kept solutions."""
+    import ctypes
+    from ._native import load_library
+    Y = np.ascontiguousarray(Y, np.float64).reshape(9)
+    nunv = np.ascontiguousarray(nunv, np.float64).reshape(6)
+    R, t, n = np.zeros((4, 9)), np.zeros((4, 3)), ctypes.c_int(0)
+    rc = load_library().dvo_p3p_host(ptr(Y), ptr(nunv), ptr(R), ptr(t), ctypes.byref(n))
+    if rc != 0:
+        raise DVOError(rc, "dvo_p3p_host")
+    return R[:n.value].reshape(-1, 3, 3), t[:n.value]
+
+
 def test_track_refine(lm, count, mq, mt, m, rec, kp_cap, K, views=6, iters=5, huber_px=1.0, inlier_px=2.0,
                       use_poses=False, pose_params=(10, 1.0, 2.0, 6), cap_out=None, link=None, refined=None, ids=None,
                       want_refined=True, want_ids=True, ctx=None):

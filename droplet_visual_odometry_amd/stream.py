@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from ._native import (DMATCH_DTYPE, KEYPOINT_DTYPE, LANDMARK_DTYPE, LANDMARK_REFINED_DTYPE, PAIR_RECORD_DTYPE,
-                      TRACK_BUNDLE_DTYPE, TRACK_ID_DTYPE, TRACK_POSE_DTYPE, TRACK_SCALE_DTYPE, Context, StreamConfig, _vp, orb_params, ptr)
+                      TRACK_BUNDLE_DTYPE, TRACK_ID_DTYPE, TRACK_PNP_DTYPE, TRACK_POSE_DTYPE, TRACK_SCALE_DTYPE, Context, StreamConfig, _vp, orb_params, ptr)
 
 
 class Landmarks:
@@ -232,7 +232,52 @@ def _bind_track_poses(stream, setter, tp, iters, huber_px, inlier_px, min_points
     return tp
 
 
-def carry_scale(anchor, scales, poses=None, bundle=None) -> np.ndarray:
+class TrackPnP:
+    """Device buffers for one batch's track PnP (dvo_stream_set_track_pnp), the companion of a Tracks:
+    per pair the pose of its second camera from a P3P RANSAC on the previous pair's landmarks and
+    the pair's raw matches, which needs neither the pair's own essential matrix nor its landmarks
+    (see include/dvo.h).  pnp: uint8 [n_pairs, 144] (TRACK_PNP_DTYPE); mask: uint8 [n_pairs, mask_cap]
+    per match 1 for a final inlier (mask_cap 0: none).  Bind it with bind_pnp after bind_tracks;
+    read it after the batch has retired and the stream is synchronised."""
+
+    def __init__(self, n_pairs: int, device, mask_cap: int = 0):
+        if n_pairs < 1 or mask_cap < 0:
+            raise ValueError("TrackPnP needs n_pairs >= 1 and mask_cap >= 0")
+        self.n_pairs, self.mask_cap = int(n_pairs), int(mask_cap)
+        self.pnp = torch.zeros((self.n_pairs, TRACK_PNP_DTYPE.itemsize), dtype=torch.uint8, device=device)
+        self.mask = torch.zeros((self.n_pairs, self.mask_cap), dtype=torch.uint8, device=device) if mask_cap else None
+
+    def numpy(self) -> np.ndarray:
+        """TRACK_PNP_DTYPE [n_pairs]: R, t, scale, rms, the counts, sample, solution, iters, status per pair."""
+        return self.pnp.cpu().numpy().reshape(-1).view(TRACK_PNP_DTYPE).copy()
+
+    def mask_numpy(self) -> np.ndarray:
+        """uint8 [n_pairs, mask_cap]."""
+        return self.mask.cpu().numpy().copy()
+
+    def tensors(self):
+        return (self.pnp,) + (() if self.mask is None else (self.mask,))
+
+
+def _bind_pnp(stream, setter, pn, hyps, iters, huber_px, inlier_px, min_points, seed):
+    """The one-shot PnP binding of both stream classes; returns what to keep referenced."""
+    if pn is None:
+        stream.ctx.check(setter(stream.h, None, None, 0, 0, 0, 0.0, 0.0, 0, 0))
+        return None
+    tr = stream._tr_next
+    if tr is None:
+        raise ValueError("bind_pnp goes after bind_tracks: it is a companion of a pending Tracks")
+    if not isinstance(pn, TrackPnP) or pn.pnp.device != stream.device:
+        raise ValueError("bind_pnp takes a TrackPnP on the stream's device (or None)")
+    if pn.n_pairs < tr.n_pairs:
+        raise ValueError(f"the TrackPnP ({pn.n_pairs} pairs) must have the bound Tracks' pairs ({tr.n_pairs})")
+    stream._after_torch()  # the buffers' fill ran on torch's stream: order the library's writes after it
+    stream.ctx.check(setter(stream.h, pn.pnp.data_ptr(), None if pn.mask is None else pn.mask.data_ptr(), pn.mask_cap,
+                            int(hyps), int(iters), float(huber_px), float(inlier_px), int(min_points), int(seed)))
+    return pn
+
+
+def carry_scale(anchor, scales, poses=None, bundle=None, pnp=None) -> np.ndarray:
     """Metric baseline length per pair of one batch: anchor float64 [pairs] holds the marker's scale
     where a marker was seen (the pose tail) and NaN elsewhere; scales is the batch's
     TRACK_SCALE_DTYPE [pairs] (Tracks.scales_numpy).  out[p] = anchor[p] where that is not NaN, else
@@ -241,11 +286,14 @@ def carry_scale(anchor, scales, poses=None, bundle=None) -> np.ndarray:
     poses: the batch's TRACK_POSE_DTYPE [pairs] (TrackPoses.numpy), or None: a pair whose pose has
     status 0 multiplies by poses["scale"][p] instead of the ratio.  bundle: the batch's
     TRACK_BUNDLE_DTYPE [pairs] (TrackBundle.numpy), or None: a pair whose bundle has status 0 and a
-    ratio > 0 multiplies by bundle["ratio"][p] instead of either."""
+    ratio > 0 multiplies by bundle["ratio"][p] instead of either.  pnp: the batch's TRACK_PNP_DTYPE
+    [pairs] (TrackPnP.numpy), or None: where all of that leaves out[p] NaN, out[p - 1] is not NaN
+    and pnp["status"][p] == 0, out[p] = out[p - 1] * pnp["scale"][p] (a pair whose own essential
+    matrix failed has n_common 0 but may still have a PnP pose)."""
     anchor = np.asarray(anchor, np.float64)
     if (anchor.ndim != 1 or len(scales) != len(anchor) or (poses is not None and len(poses) != len(anchor))
-            or (bundle is not None and len(bundle) != len(anchor))):
-        raise ValueError("anchor float64 [pairs], scales [pairs], poses [pairs] and bundle [pairs] must agree")
+            or (bundle is not None and len(bundle) != len(anchor)) or (pnp is not None and len(pnp) != len(anchor))):
+        raise ValueError("anchor float64 [pairs], scales [pairs], poses [pairs], bundle [pairs] and pnp [pairs] must agree")
     out = np.full(len(anchor), np.nan)
     for p in range(len(anchor)):
         if not np.isnan(anchor[p]):
@@ -256,6 +304,8 @@ def carry_scale(anchor, scales, poses=None, bundle=None) -> np.ndarray:
                 out[p] = out[p - 1] * bundle["ratio"][p]
             else:
                 out[p] = out[p - 1] * (poses["scale"][p] if refined else scales["ratio"][p])
+        if (pnp is not None and np.isnan(out[p]) and p >= 1 and not np.isnan(out[p - 1]) and pnp["status"][p] == 0):
+            out[p] = out[p - 1] * pnp["scale"][p]
     return out
 
 
@@ -302,6 +352,7 @@ class FrameStream:
         self._tp_next = None  # bind_track_poses: the TrackPoses it takes with them
         self._rf_next = None  # bind_refine: and the RefinedLandmarks
         self._bd_next = None  # bind_bundle: and the TrackBundle
+        self._pn_next = None  # bind_pnp: and the TrackPnP
         self.width, self.height, self.max_frames, self.nfeatures = width, height, max_frames, nfeatures
         self.K = K.reshape(3, 3)
         if ratio:
@@ -329,7 +380,7 @@ class FrameStream:
         after it writes nothing.  None clears a binding no batch has taken yet."""
         self._lm_next = _bind_landmarks(self, self.ctx.lib.dvo_stream_set_landmarks, lm)
         if lm is None:
-            self._tr_next = self._tp_next = self._rf_next = self._bd_next = None  # the library clears the companions with it
+            self._tr_next = self._tp_next = self._rf_next = self._bd_next = self._pn_next = None  # the library clears the companions with it
 
     def bind_tracks(self, tr: Tracks | None):
         """Have the next batch also write its tracks into `tr` (dvo_stream_set_tracks), after its
@@ -337,7 +388,7 @@ class FrameStream:
         same cap.  One-shot, like the landmark binding; None clears a pending binding.  Only for
         batches of consecutive frames: process_pairs / submit_pairs raise ValueError."""
         self._tr_next = _bind_tracks(self, self.ctx.lib.dvo_stream_set_tracks, tr)
-        self._tp_next = self._rf_next = self._bd_next = None  # the library's call cleared the later pending bindings
+        self._tp_next = self._rf_next = self._bd_next = self._pn_next = None  # the library's call cleared the later pending bindings
 
     def bind_track_poses(self, tp: TrackPoses | None, iters: int = 10, huber_px: float = 1.0, inlier_px: float = 2.0,
                          min_points: int = 6):
@@ -373,6 +424,17 @@ class FrameStream:
         which of the two outputs to write.  One-shot; None clears a pending binding."""
         self._bd_next = _bind_bundle(self, self.ctx.lib.dvo_stream_set_track_bundle, bd, views, iters, lam, huber_px,
                                      inlier_px, min_points, pairs, points)
+
+    def bind_pnp(self, pn: TrackPnP | None, hyps: int = 128, iters: int = 10, huber_px: float = 1.0,
+                 inlier_px: float = 2.0, min_points: int = 6, seed: int = 0):
+        """Have the next batch also write its track PnP into `pn` (dvo_stream_set_track_pnp), after
+        everything else.  Call it after bind_tracks (ValueError otherwise); the pose, refine and
+        bundle bindings neither need nor clear it.  hyps: P3P samples per pair (at most 512); iters:
+        polish steps (at most 32); huber_px, inlier_px as for the poses; min_points: correspondences
+        and supporters a pair needs (at least 4); seed: of the samples (0: the E-RANSAC's).
+        One-shot; None clears a pending binding, as bind_tracks and bind_landmarks(None) do."""
+        self._pn_next = _bind_pnp(self, self.ctx.lib.dvo_stream_set_track_pnp, pn, hyps, iters, huber_px, inlier_px,
+                                  min_points, seed)
 
     def _lm_fits(self, pairs: int, shared: bool = True):
         if self._lm_next is not None and self._lm_next.n_pairs < pairs:
@@ -630,15 +692,16 @@ class FrameStream:
         tp, self._tp_next = self._tp_next, None
         rf, self._rf_next = self._rf_next, None
         bd, self._bd_next = self._bd_next, None
+        pn, self._pn_next = self._pn_next, None
         if lm is not None and self._pending:
-            self._lm_pending[next(reversed(self._pending))] = (lm, tr, tp, rf, bd)
+            self._lm_pending[next(reversed(self._pending))] = (lm, tr, tp, rf, bd, pn)
         out, lms = [], []
         for i in range(min(n, cap)):
             t = self._pending.pop(recs[i], None)
             if t is None:
                 raise RuntimeError("retired records that were not submitted through this FrameStream")
             out.append((t, int(pairs[i])))
-            lm, tr, tp, rf, bd = self._lm_pending.pop(recs[i], (None, None, None, None, None))
+            lm, tr, tp, rf, bd, pn = self._lm_pending.pop(recs[i], (None, None, None, None, None, None))
             if lm is not None:
                 lms += [lm.entries, lm.counts]
             if tr is not None:
@@ -649,6 +712,8 @@ class FrameStream:
                 lms += [rf.refined, rf.ids]
             if bd is not None:
                 lms += [bd.bundle, bd.points]
+            if pn is not None:
+                lms += list(pn.tensors())
         if out:
             # the retire kernels (records_kernel, the landmark kernels) writing these buffers are
             # queued on the library's stream by the call that retired them: keep the tensors alive
@@ -789,7 +854,7 @@ class FrameStream:
             self._last = ()
             self._pending = {}
             self._lm_next, self._lm_pending, self._tr_next, self._tp_next, self._rf_next = None, {}, None, None, None
-            self._bd_next = None
+            self._bd_next = self._pn_next = None
 
     def __del__(self):
         try:
@@ -902,6 +967,7 @@ class KnnFrameStream:
         self._tp_next = None  # bind_track_poses: and the TrackPoses
         self._rf_next = None  # bind_refine: and the RefinedLandmarks
         self._bd_next = None  # bind_bundle: and the TrackBundle
+        self._pn_next = None  # bind_pnp: and the TrackPnP
         self.width, self.height, self.max_frames = int(width), int(height), int(max_frames)
         self.dim = 64 if cfg.detector == 1 else 128
         self.K = K.reshape(3, 3)
@@ -919,14 +985,14 @@ class KnnFrameStream:
         that batch.  One-shot: the batch after it writes nothing.  None clears a pending binding."""
         self._lm_next = _bind_landmarks(self, self.ctx.lib.dvo_knn_stream_set_landmarks, lm)
         if lm is None:
-            self._tr_next = self._tp_next = self._rf_next = self._bd_next = None  # the library clears the companions with it
+            self._tr_next = self._tp_next = self._rf_next = self._bd_next = self._pn_next = None  # the library clears the companions with it
 
     def bind_tracks(self, tr: Tracks | None):
         """Have the next batch also write its tracks into `tr` (dvo_knn_stream_set_tracks), after
         its landmarks.  Call it after bind_landmarks (ValueError otherwise), with a Tracks of the
         same cap.  One-shot; None clears a pending binding; detect*() alone does not take it."""
         self._tr_next = _bind_tracks(self, self.ctx.lib.dvo_knn_stream_set_tracks, tr)
-        self._tp_next = self._rf_next = self._bd_next = None  # the library's call cleared the later pending bindings
+        self._tp_next = self._rf_next = self._bd_next = self._pn_next = None  # the library's call cleared the later pending bindings
 
     def bind_track_poses(self, tp: TrackPoses | None, iters: int = 10, huber_px: float = 1.0, inlier_px: float = 2.0,
                          min_points: int = 6):
@@ -956,6 +1022,14 @@ class KnnFrameStream:
         self._bd_next = _bind_bundle(self, self.ctx.lib.dvo_knn_stream_set_track_bundle, bd, views, iters, lam,
                                      huber_px, inlier_px, min_points, pairs, points)
 
+    def bind_pnp(self, pn: TrackPnP | None, hyps: int = 128, iters: int = 10, huber_px: float = 1.0,
+                 inlier_px: float = 2.0, min_points: int = 6, seed: int = 0):
+        """Have the next batch also write its track PnP into `pn` (dvo_knn_stream_set_track_pnp), after
+        everything else; the parameters are FrameStream.bind_pnp's.  Call it after bind_tracks.
+        One-shot; None clears a pending binding; detect*() alone does not take it."""
+        self._pn_next = _bind_pnp(self, self.ctx.lib.dvo_knn_stream_set_track_pnp, pn, hyps, iters, huber_px,
+                                  inlier_px, min_points, seed)
+
     def _lm_fits(self, pairs: int):
         if self._lm_next is not None and self._lm_next.n_pairs < pairs:
             raise ValueError(f"the bound Landmarks holds {self._lm_next.n_pairs} pairs, the batch has {pairs}")
@@ -967,9 +1041,10 @@ class KnnFrameStream:
         tp, self._tp_next = self._tp_next, None
         rf, self._rf_next = self._rf_next, None
         bd, self._bd_next = self._bd_next, None
+        pn, self._pn_next = self._pn_next, None
         return ((() if lm is None else (lm.entries, lm.counts)) + (() if tr is None else (tr.links, tr.scales))
                 + (() if tp is None else (tp.poses,)) + (() if rf is None else (rf.refined, rf.ids))
-                + (() if bd is None else (bd.bundle, bd.points)))
+                + (() if bd is None else (bd.bundle, bd.points)) + (() if pn is None else pn.tensors()))
 
     def set_detect_group(self, group: int):
         """SIFT frames per detection launch from the next process() on (0: frame by frame).  Waits

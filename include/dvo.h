@@ -1393,6 +1393,156 @@ int dvo_knn_stream_set_track_bundle(dvo_knn_stream* s, dvo_track_bundle* d_bundl
                                     int views, int iters, double lambda, double huber_px, double inlier_px,
                                     int min_points);
 
+/* ---------------------------------------------------------------------------
+ * Track PnP: each pair's 6-DoF pose from a P3P RANSAC on the previous pair's landmarks.  An
+ * opt-in companion of a tracks binding.  Every output above rests on pair p's own essential
+ * matrix: a pair whose five-point RANSAC or recoverPose fails (a near-pure rotation, a short
+ * baseline, a planar scene) has no landmarks, links nothing, gets DVO_TRACK_POSE_NONE and
+ * breaks the chain of scales.  The previous pair has already put 3-D points into camera j, and
+ * pair p's raw match list says where those keypoints are in frame j + 1: a pose from 3-D to 2-D
+ * correspondences needs neither pair p's E nor its triangulation.  Raw matches are not filtered
+ * by E, hence the minimal-solver RANSAC in front of the track-pose steps.
+ *
+ * Correspondences of pair p >= 1 (frames j, j + 1).  Match i of pair p's match list, in the
+ * order of dvo_stream_get_matches, i < rec[p].n_matches, whatever rec[p].status is, has (q, t)
+ * and second-frame pixels (x2, y2).  It is a correspondence iff pair p - 1's landmarks hold
+ * one whose match has trainIdx == q; the smallest such ordinal if several qualify, as the link
+ * takes it.  Correspondences go in ascending i, k = 0..n-1 with n = n_corr.  Correspondence k has
+ *   Y = (y0, y1, y2)   the y_i of the tracks section from that landmark and pair p - 1's record;
+ *   (nu, nv)           x2, y2 normalised as in the track-pose section;
+ *   f = (nu / l, nv / l, 1 / l) with l = sqrt((nu * nu + nv * nv) + 1), its unit bearing.
+ * Pair 0 of a batch has none, and neither has a pair whose predecessor has no landmarks.
+ *
+ * Samples.  `hyps` samples per pair, h = 0..hyps-1.  With mwc_step the cv::RNG step
+ * s' = (uint32)s * 4164903690 + (s >> 32) and seed' = seed, or (uint64)-1 (the E-RANSAC's) where
+ * seed == 0: the state of sample h is the one 8 h steps after seed'.  A draw is s = mwc_step(s),
+ * idx = (uint32)s % n.  i0 is the first draw, i1 the first later draw != i0, i2 the first later
+ * draw not in {i0, i1}.  A sample takes at most 8 draws; one that has not found three indices by
+ * then is void.  The samples depend on n, h and the seed only.
+ *
+ * P3P, per sample, on (Y_0, f_0), (Y_1, f_1), (Y_2, f_2) in the sample's order.  In double, every
+ * operation one of + - * / sqrt rounded once, in the written order; negation, comparison, |x| and
+ * max select exactly.  Polynomials are listed from the constant term up.
+ *   c01 = (f0x * f1x + f0y * f1y) + f0z * f1z, c02 and c12 alike
+ *   e1 = Y_1 - Y_0, e2 = Y_2 - Y_0, g = Y_2 - Y_1
+ *   a01 = (e1x * e1x + e1y * e1y) + e1z * e1z, a02 from e2 and a12 from g alike
+ * With depths d1 = u d0, d2 = v d0 the three side equations
+ * d_i^2 + d_j^2 - 2 d_i d_j c_ij = a_ij leave two quadratics in u,
+ * p2 u^2 + p1 u + P0(v) = 0 and q2 u^2 + Q1(v) u + Q0(v) = 0:
+ *   p2 = a02, p1 = -((2 * a02) * c01), q2 = a12 - a01
+ *   P0 = (a02 - a01, (2 * a01) * c02, -a01)
+ *   Q1 = (-((2 * a12) * c01), (2 * a01) * c12),  Q0 = (a12, 0, -a01)
+ *   A_k = p2 * Q0_k - P0_k * q2  (k = 0, 1, 2)
+ *   B_0 = p2 * Q1_0 - p1 * q2,  B_1 = p2 * Q1_1
+ *   C_0 = p1 * Q0_0 - P0_0 * Q1_0
+ *   C_1 = p1 * Q0_1 - (P0_0 * Q1_1 + P0_1 * Q1_0)
+ *   C_2 = p1 * Q0_2 - (P0_1 * Q1_1 + P0_2 * Q1_0)
+ *   C_3 = -(P0_2 * Q1_1)
+ * Their resultant G = A^2 - B C is a quartic in v:
+ *   G_0 = A_0 * A_0 - B_0 * C_0
+ *   G_1 = 2 * (A_0 * A_1) - (B_0 * C_1 + B_1 * C_0)
+ *   G_2 = (2 * (A_0 * A_2) + A_1 * A_1) - (B_0 * C_2 + B_1 * C_1)
+ *   G_3 = 2 * (A_1 * A_2) - (B_0 * C_3 + B_1 * C_2)
+ *   G_4 = A_2 * A_2 - B_1 * C_3
+ * Ferrari.  b = G_3 / G_4, c = G_2 / G_4, d = G_1 / G_4, e = G_0 / G_4, b2 = b * b,
+ *   p = c - 0.375 * b2
+ *   q = (d - 0.5 * (b * c)) + 0.125 * (b2 * b)
+ *   r = ((e - 0.25 * (b * d)) + 0.0625 * (b2 * c)) - 0.01171875 * (b2 * b2)
+ * The resolvent g(m) = ((m + k2) * m + k1) * m + k0 with k2 = p, k1 = 0.25 * (p * p) - r,
+ * k0 = -(0.125 * (q * q)) has g(0) <= 0.  From lo = 0, hi = 1 + max(|k2|, |k1|, |k0|), exactly
+ * 100 times: mid = 0.5 * (lo + hi); hi = mid if g(mid) > 0, else lo = mid.  Then m = hi,
+ *   s = sqrt(2 * m), hh = 0.5 * p + m, w = q / (2 * s)
+ *   rt0 = sqrt(s * s - 4 * (hh + w)), rt1 = sqrt(s * s - 4 * (hh - w))
+ *   y = 0.5 * (s + rt0), 0.5 * (s - rt0), 0.5 * (rt1 - s), 0.5 * (-s - rt1)   candidates 0..3
+ * Per candidate: v = y - 0.25 * b, u = -(((A_2 * v + A_1) * v + A_0) / (B_1 * v + B_0)),
+ *   d0 = sqrt(a02 / ((1 + v * v) - (2 * v) * c02)), d1 = u * d0, d2 = v * d0
+ * then exactly 5 Newton steps on the three depths:
+ *   r0 = ((d0 * d0 + d1 * d1) - (2 * (d0 * d1)) * c01) - a01, r1 (d0, d2, c02, a02) and
+ *   r2 (d1, d2, c12, a12) alike
+ *   j00 = 2 * (d0 - d1 * c01), j01 = 2 * (d1 - d0 * c01), j10 = 2 * (d0 - d2 * c02),
+ *   j12 = 2 * (d2 - d0 * c02), j21 = 2 * (d1 - d2 * c12), j22 = 2 * (d2 - d1 * c12)
+ *   det = -(j00 * (j12 * j21) + j01 * (j10 * j22)),  x = r1 * j22 - j12 * r2
+ *   n0 = -(r0 * (j12 * j21)) - j01 * x
+ *   n1 = j00 * x - r0 * (j10 * j22)
+ *   n2 = (r0 * (j10 * j21) - j00 * (r1 * j21)) - j01 * (j10 * r2)
+ *   d_i = d_i - n_i / det
+ * Alignment of the two triangles.  The frame of three points Z_0, Z_1, Z_2:
+ *   z1 = Z_1 - Z_0, z2 = Z_2 - Z_0, F1 = z1 / sqrt((z1x * z1x + z1y * z1y) + z1z * z1z)
+ *   n = F1 x z2 (n0 = F1y * z2z - F1z * z2y, cyclically), F3 = n / sqrt((n0 * n0 + n1 * n1) + n2 * n2)
+ *   F2 = F3 x F1
+ * with E from the Y_i (z1 = e1, z2 = e2, the first norm sqrt(a01)) and F from X_i = d_i * f_i
+ * (X_0 subtracted after the products):
+ *   R[i][j] = (F1_i * E1_j + F2_i * E2_j) + F3_i * E3_j
+ *   t_i = X_0i - ((R[i][0] * Y_0x + R[i][1] * Y_0y) + R[i][2] * Y_0z)
+ * A candidate is kept iff d0, d1, d2 > 0 and every entry of R and t is finite.  The kept
+ * candidates, in candidate order, are the sample's solutions 0, 1, ...: up to 4.
+ *
+ * Score and choice.  A correspondence supports a pose iff it is an inlier of the track-pose
+ * final pass under that pose: P2 > 0 and (fx * ru) * (fx * ru) + (fy * rv) * (fy * rv) <=
+ * inlier_px * inlier_px.  A pose's score is the integer count of its supporters, so no sum order
+ * enters the choice.  The winner has the largest count; ties go to the smaller h, then to the
+ * smaller solution index.  n_best is its count, sample and solution its indices.
+ *
+ * Polish.  The polish set is the winner's supporters, fixed from here on, in ascending k; its
+ * j-th member takes the place of correspondence j in the track-pose section's "One step" (the
+ * same 27 terms, Huber weight, lane, tree and group sum order, LDL^T and Cayley update).  `iters`
+ * steps from the winner's R, t; then the track-pose final pass over all n correspondences gives
+ * n_used, n_inliers, rms and scale = |t|.
+ *
+ * Status.  DVO_TRACK_PNP_NONE: pair 0 of a batch, or n_corr < min_points; the struct is zero
+ * apart from status and n_corr.  DVO_TRACK_PNP_NO_MODEL: no sample has a kept solution (n_best
+ * 0, sample and solution -1), or n_best < min_points (n_best, sample and solution of the best
+ * found); R, t, scale, rms, n_used, n_inliers and iters are zero.  DVO_TRACK_PNP_DEGENERATE: a
+ * polish step failed; the pose of the step before is kept, the final pass runs on it and iters is
+ * the number of steps taken.
+ *
+ * Mask (optional).  d_mask [pairs][mask_cap] bytes: for match index i < min(n_matches, mask_cap)
+ * 1 where match i is a correspondence and a final-pass inlier, 0 otherwise (all 0 for a NONE or
+ * NO_MODEL pair); bytes outside that range are not touched.
+ *
+ * Out of scope: landmarks triangulated from the PnP pose (the pair after a failed pair still has
+ * no correspondences), chains across a batch boundary, the sharded runners, the single-pair calls
+ * and early termination of the hypothesis loop. */
+#define DVO_TRACK_PNP_OK 0
+#define DVO_TRACK_PNP_NONE 1
+#define DVO_TRACK_PNP_DEGENERATE 2
+#define DVO_TRACK_PNP_NO_MODEL 3
+typedef struct {              /* 144 bytes */
+    double R[9], t[3];        /* camera j + 1 from camera j: x' = R x + t, |t| in units of pair p - 1's baseline */
+    double scale, rms;        /* |t|: baseline p over baseline p - 1, as dvo_track_pose; pixels */
+    int32_t n_corr, n_best, n_used, n_inliers, sample, solution, iters, status;
+} dvo_track_pnp;
+#ifdef __cplusplus
+static_assert(sizeof(dvo_track_pnp) == 144, "layout");
+#else
+_Static_assert(sizeof(dvo_track_pnp) == 144, "layout");
+#endif
+/* Binds d_pnp [pairs] and, where d_mask is not NULL, d_mask [pairs][mask_cap] for the NEXT batch
+ * only.  DVO_EINVAL unless a tracks binding is pending (either of its buffers will do: only the
+ * table of landmarks is read), or where d_mask goes with mask_cap < 1.  hyps 1..512 (default 128),
+ * iters 1..32 (default 10), huber_px (default 1.0; INFINITY weights every correspondence 1),
+ * inlier_px (default 2.0), min_points >= 4 (default 6): zero or negative means the default;
+ * DVO_EINVAL above the ranges, for min_points 1..3, or for a NaN.  seed: 0 means (uint64)-1.
+ * d_pnp == NULL clears a pending binding, as clearing the landmark binding and every
+ * dvo_stream_set_tracks call do; the pose, refine and bundle setters leave it alone, and it clears
+ * nothing.  It travels with the batch and is written last when the batch retires, on the stream's
+ * HIP stream with no read-back; a *_pairs call refuses it as it refuses tracks.  The first binding
+ * allocates 48 B per slot of the point buffer (a correspondence's Y, nu, nv, its match index and
+ * the polish set's index) and 4 B per 256 slots for every pair set, once; a stream that never
+ * binds it launches and holds what it did before, and no other output of a batch depends on the
+ * binding. */
+int dvo_stream_set_track_pnp(dvo_stream* s, dvo_track_pnp* d_pnp, uint8_t* d_mask, int mask_cap, int hyps, int iters,
+                             double huber_px, double inlier_px, int min_points, uint64_t seed);
+/* The same for a k-NN stream; a detect call alone consumes nothing. */
+int dvo_knn_stream_set_track_pnp(dvo_knn_stream* s, dvo_track_pnp* d_pnp, uint8_t* d_mask, int mask_cap, int hyps,
+                                 int iters, double huber_px, double inlier_px, int min_points, uint64_t seed);
+/* The samples of n >= 1 correspondences on the host (the kernel's text): out[hyps][3], a void
+ * sample -1, -1, -1.  DVO_EINVAL for n < 1 or hyps outside 1..512. */
+int dvo_track_pnp_samples_host(int n, int hyps, uint64_t seed, int32_t* out);
+/* The P3P solver on the host (the kernel's text): Y the three points, nunv their (nu, nv);
+ * R[4][9], t[4][3] the kept solutions in order, *n_solutions their number. */
+int dvo_p3p_host(const double* Y, const double* nunv, double* R, double* t, int* n_solutions);
+
 /* Test hooks: exercise one device algorithm in isolation. */
 /* KeyPointsFilter::retainBest permutation on `n` float responses (GPU emulation
  * of libstdc++ nth_element + partition); depth < 0 = libstdc++ default. */
@@ -1534,6 +1684,17 @@ int dvo_test_track_bundle(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* c
                           int min_points, int32_t* link, dvo_track_scale* scale, dvo_track_pose* pose, int bd_views,
                           int bd_iters, double bd_lambda, double bd_huber_px, double bd_inlier_px, int bd_min_points,
                           int use_poses, dvo_track_bundle* bundle, dvo_landmark_refined* points);
+/* dvo_test_track_poses with the PnP kernels (dvo_stream_set_track_pnp) after it: xy2 [pairs][stride][2]
+ * are the second-frame pixels of every match (a landmark's x2, y2 is overridden by its match's),
+ * rec[p].n_matches is taken as m[p], and the six pnp_ parameters are the binding's, defaults
+ * included.  pnp [pairs]; mask [pairs][mask_cap] is copied up whole before the run and back whole
+ * after it, or NULL (then mask_cap is ignored). */
+int dvo_test_track_pnp(dvo_ctx* ctx, const dvo_landmark* lm, const int32_t* count, const int32_t* mq,
+                       const int32_t* mt, const int32_t* m, const dvo_pair_record* rec, int pairs, int cap, int stride,
+                       int kp_cap, int cap_out, const double* K, int iters, double huber_px, double inlier_px,
+                       int min_points, int32_t* link, dvo_track_scale* scale, dvo_track_pose* pose, const float* xy2,
+                       int pnp_hyps, int pnp_iters, double pnp_huber_px, double pnp_inlier_px, int pnp_min_points,
+                       uint64_t pnp_seed, dvo_track_pnp* pnp, uint8_t* mask, int mask_cap);
 
 #ifdef __cplusplus
 }
